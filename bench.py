@@ -21,6 +21,10 @@ The JSON line also carries
   roofline     — the limb-transform passes (k_ntt_r16 / k_ntt_r8x3 / k_ntt_pass, the dominant kernel family): algorithmic bytes / HIP-event
                  duration, sampled live on the launch stream; `traffic` from the committed PMC passes of the same command
   cpu_baseline — the CPU oracle ("port") timed on rank 0's host cores on a bounded sample of the same workload.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0) as DIR/<name>.npy: exact float64 [hi32, lo32]
+pairs of the residues, a fixed sample of them when the output is large (dump_outputs).  Inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -58,7 +62,57 @@ def parse():
                     help="--gpus N started plainly: overall deadline in seconds for the ranks this process starts")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launch path only: every rank joins a gloo group, rank 0 prints what it sees (no GPU work; CPU test)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_RESIDUES = 1 << 21   # over all dumped arrays: 2^21 residues x [hi, lo] x 8 bytes = 32 MiB
+
+
+def dump_sample(total, tag, cap):
+    """Flat indices of the residues to dump from an output of `total` residues: all of them when they fit in `cap`, else a
+    fixed stratified sample (one index in each of `cap` equal strata, offsets from a seed fixed per output name)."""
+    import numpy as np
+    if total <= cap:
+        return None
+    stride = total // cap
+    rng = np.random.default_rng([0x5EED, sum(map(ord, tag))])
+    return np.arange(cap, dtype=np.int64) * stride + rng.integers(0, stride, cap)
+
+
+def dump_outputs(dirname, arrays):
+    """Writes {name: residue array} as dirname/<name>.npy.  Residues go up to 61 bits, beyond float64's 53-bit mantissa, so
+    each residue r is stored exactly as the float64 pair [r >> 32, r & 0xffffffff] (a trailing axis of size 2).  An output
+    keeps its shape when it fits its share of DUMP_MAX_RESIDUES; a larger one is reduced to the fixed sample of dump_sample(),
+    shape [share, 2].  Arrays may be numpy (host) or torch (device: gathered on the device first).
+    Returns {name: description} for the result line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    info = {}
+    for name, a in arrays.items():
+        shape = list(a.shape)
+        total = int(np.prod(shape))
+        idx = dump_sample(total, name, DUMP_MAX_RESIDUES // len(arrays))
+        if not isinstance(a, np.ndarray):   # torch tensor
+            import torch
+            flat = a.reshape(-1)
+            if idx is not None:
+                flat = flat[torch.from_numpy(idx).to(a.device)]
+            host = flat.cpu().numpy().view(np.uint64)
+        else:
+            flat = np.ascontiguousarray(a).reshape(-1).view(np.uint64)
+            host = flat[idx] if idx is not None else flat
+        pair = np.stack([(host >> np.uint64(32)).astype(np.float64), (host & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+        if idx is None:
+            pair = pair.reshape(shape + [2])
+        np.save(os.path.join(dirname, name + ".npy"), pair)
+        info[name] = {"of_shape": shape, "saved_shape": list(pair.shape),
+                      "sample": "all" if idx is None else "stratified, %d of %d residues" % (len(idx), total)}
+    return info
 
 
 def visible_gpu_count():
@@ -270,6 +324,7 @@ def run_task_workload(args):
         t.run(ins, outs)
     dt = time.perf_counter() - t0
     st = t.last_run_stats()
+    dumped = dump_outputs(args.dump_outputs, {"zs": np.stack([z.data for z in zs])}) if args.dump_outputs else None
     print(json.dumps({
         "metric": "task_end_to_end_throughput", "value": n_op * args.steps / dt, "unit": "ciphertexts/s", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -278,7 +333,7 @@ def run_task_workload(args):
                    "gpu_nodes": st["gpu_nodes"], "batched_launch_groups": st["gpu_batches"],
                    "keys_last_run": t.last_run_keys(), "direct_copies_last_run": t.last_run_direct(),
                    "caller_buffers": "pinned in place" if args.register_in_place else ("library pinned allocator" if args.pinned_alloc else "pageable (staged)")},
-        "roofline": None, "cpu_baseline": None}), flush=True)
+        "roofline": None, "cpu_baseline": None, **({"dumped_outputs": dumped} if dumped else {})}), flush=True)
 
 
 def run_conv_workload(args):
@@ -324,6 +379,9 @@ def run_conv_workload(args):
         t.run(ins, outs)
     dt = time.perf_counter() - t0
     st = t.last_run_stats()
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {a.id: np.stack([c.data for c in a.objects]) for a in outs})
     print(json.dumps({
         "metric": "conv2d_layer_end_to_end_rate", "value": args.steps / dt, "unit": "layers/s", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -331,7 +389,7 @@ def run_conv_workload(args):
         "config": {"workload": name + " through run_fhe_gpu_task (host buffers, PCIe-inclusive)",
                    "compute_nodes": len(g["compute"]), "gpu_nodes": st["gpu_nodes"],
                    "batched_launch_groups": st["gpu_batches"]},
-        "roofline": None, "cpu_baseline": None}), flush=True)
+        "roofline": None, "cpu_baseline": None, **({"dumped_outputs": dumped} if dumped else {})}), flush=True)
 
 
 def run_bootstrap_workload(args):
@@ -393,11 +451,20 @@ def run_bootstrap_workload(args):
     torch.cuda.synchronize()
     check(L_.lsa_profile_begin(ctx.h, args.prof_stride))
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step().free()
+    last = None
+    for i in range(args.steps):
+        r = step()
+        if args.dump_outputs and i == args.steps - 1:
+            last = r   # kept for --dump-outputs, freed below
+        else:
+            r.free()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     check(L_.lsa_profile_end(ctx.h))
+    dumped = None
+    if last is not None:
+        dumped = dump_outputs(args.dump_outputs, {"out": ctx.download(last, (batch, 2, plan.out_level + 1, n))})
+        last.free()
     kinds = {0: "k_ntt_pass", 1: "k_baseconv", 2: "k_ks_mac", 3: "k_tensor", 4: "elementwise"}
     breakdown = {}
     for kid, name in kinds.items():
@@ -421,7 +488,8 @@ def run_bootstrap_workload(args):
             "2^%d slots" % args.log_slots if plan.sparse else "dense packing", plan.out_level),
                    "batch_per_gpu": batch, "galois_keys": len(glk), "key_bytes_total": sum(t.numel() * 8 for t in keep),
                    "plan_build_s": t_plan, "ms_per_bootstrap": dt / args.steps / batch * 1e3},
-        "roofline": roofline, "cpu_baseline": None, "kernel_breakdown": breakdown}), flush=True)
+        "roofline": roofline, "cpu_baseline": None, "kernel_breakdown": breakdown,
+        **({"dumped_outputs": dumped} if dumped else {})}), flush=True)
 
 
 def main():
@@ -553,6 +621,10 @@ def main():
     if not dual:
         check(L_.lsa_profile_end(ctx.h))
     dt = sharding.max_over_ranks(dt, device=dev)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left for its caller: `out`, or for ntt the batch transformed in place (fwd + inv)
+        dumped = dump_outputs(args.dump_outputs, {"inout": a} if args.workload == "ntt" else {"out": out})
     single = None
     if dual:
         # second measured region: one stream, HIP-event samples around the kernels (roofline, kernel breakdown)
@@ -646,6 +718,8 @@ def main():
             "tile_streams": 2 if dual else 1, "single_stream": single,
             "build_flags": L_.lsa_build_flags().decode(),   # "" = the product library (csrc/build_flags.h)
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
