@@ -15,7 +15,7 @@ Context::Context(int algo_, int n_, const u64* q, int nq_, const u64* p, int np_
     : algo(algo_), n(n_), nq(nq_), np(np_), device(device_), t(t_) {
     LSA_REQUIRE(algo == LSA_ALGO_BFV || algo == LSA_ALGO_CKKS, "unknown algorithm");
     LSA_REQUIRE(n >= 512 && n <= (1 << 17) && (n & (n - 1)) == 0, "ring degree must be a power of two in [2^9, 2^17]");
-    LSA_REQUIRE(nq >= 1 && np >= 0 && np <= LSA_BC_MAX_SRC, "bad modulus chain lengths");
+    LSA_REQUIRE(nq >= 1 && np >= 0 && np <= LSA_BC_NARROW_SRC, "bad modulus chain lengths");
     std::vector<u64> mods(q, q + nq);
     mods.insert(mods.end(), p, p + np);
     nmul = 0;
@@ -216,7 +216,8 @@ const BaseConvPlan* Context::baseconv(const std::vector<int>& src, const std::ve
         for (int v = 0; v <= ns; v++) K->vs[j][v] = mul_mod_host(mul_mod_host((u64)v % pj, all, pj), scale, pj);
         K->half_dst[j] = mul_mod_host(mul_mod_host((all + pj - 1 % pj) % pj, (pj + 1) >> 1, pj), scale, pj);
     }
-    bool small = std::getenv("LSA_BC_NO_SPLIT") == nullptr;
+    // SPLIT is proved for k_baseconv's up to LSA_BC_NARROW_SRC terms; wider conversions take the 128-bit form
+    bool small = std::getenv("LSA_BC_NO_SPLIT") == nullptr && ns <= LSA_BC_NARROW_SRC;
     for (int i = 0; i < ns; i++) small = small && (T.mod[src[i]] >> 58) == 0;
     for (int j = 0; j < nd; j++) small = small && (T.mod[dst[j]] >> 58) == 0;
     K->split29 = small ? 1 : 0;

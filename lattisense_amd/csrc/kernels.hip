@@ -1135,8 +1135,7 @@ static void launch_baseconv_nt(int ns, int nd, bool split, dim3 grid, hipStream_
     else hipLaunchKernelGGL((k_baseconv<NSMAX, false, TGT>), grid, dim3(TPB), 0, s, g);
 }
 // targets per block: the candidate with the least total work ceil(nd/T) * (Y + T*C), Y = y/v phase ~ 2.5 target conversions
-template <int NSMAX>
-static void launch_baseconv_ns(int ns, int nd, bool split, dim3 grid, hipStream_t s, const BaseConvArgs& g) {
+static int baseconv_targets_per_block(int nd) {
     const int cand[3] = {4, 7, 13};
     int best = 4;
     double best_cost = 1e30;
@@ -1147,9 +1146,95 @@ static void launch_baseconv_ns(int ns, int nd, bool split, dim3 grid, hipStream_
             best = T;
         }
     }
+    return best;
+}
+template <int NSMAX>
+static void launch_baseconv_ns(int ns, int nd, bool split, dim3 grid, hipStream_t s, const BaseConvArgs& g) {
+    const int best = baseconv_targets_per_block(nd);
     if (best == 4) launch_baseconv_nt<NSMAX, 4>(ns, nd, split, grid, s, g);
     else if (best == 7) launch_baseconv_nt<NSMAX, 7>(ns, nd, split, grid, s, g);
     else launch_baseconv_nt<NSMAX, 13>(ns, nd, split, grid, s, g);
+}
+
+// ------------------------------------------------------------------------- wide exact base conversion (17..32 sources)
+// The BFV multiply at N = 2^16 converts 24 Q limbs to 24 auxiliary limbs and back.  k_baseconv keeps two points per thread
+// (xin[NSMAX] and y[NSMAX][2]: 4 * NSMAX VGPRs, 128 at 32 sources before any accumulator), so the wide shapes have their own
+// kernel with ONE point per thread: y[NSMAX] is 2 * NSMAX VGPRs.  Same formula, same residues: the loads (and the optional
+// subtrahend) as in k_baseconv, the same y_i and the same float sequence for v, the output correction by the table vs[j][v]
+// (v = 0..ns, ns + 1 entries).  The accumulate is the 128-bit form only, reduced every 8 terms as in k_baseconv (8 products
+// of y_i < 2^61 and shat < p_j stay below p_j * 2^64, the bound of the REDC), which holds for any ns; the 29-bit SPLIT form
+// is proved for at most 16 terms and is never taken here (Context::baseconv clears split29 above 16 sources; every BFV
+// auxiliary prime is 61 bits wide, so the BFV conversions would not qualify anyway).  The 8-term blocks are reduced to
+// [0, p_j) and added mod p_j, so the result is the exact residue whatever the block count.
+template <int NSMAX, bool EXACT, int TGT>
+__global__ __launch_bounds__(TPB) void k_baseconv_wide(BaseConvArgs g) {
+    const LSA_CONST_AS BaseConvConsts& K = *(const LSA_CONST_AS BaseConvConsts*)g.k;
+    const LSA_CONST_AS ModDev* const mods_c = (const LSA_CONST_AS ModDev*)g.mods;
+    const int x = blockIdx.x * TPB + threadIdx.x;
+    const long long b = blockIdx.y;
+    const u64* src = g.src + b * g.ssrc + x;
+    u64* dst = g.dst + b * g.sdst + x;
+    const int ns = EXACT ? NSMAX : K.ns, nd = K.nd;
+    u64 y[NSMAX];
+#pragma unroll
+    for (int i = 0; i < NSMAX; i++)
+        if (EXACT || i < ns) y[i] = src[(long long)g.rows.src_row[i] << g.logn];
+    if (g.sub) {   // block-uniform
+        const u64* sub = g.sub + b * g.ssub + x;
+#pragma unroll
+        for (int i = 0; i < NSMAX; i++)
+            if (EXACT || i < ns) y[i] = sub_mod(y[i], sub[(long long)g.sub_row[i] << g.logn], mods_c[K.src_mod[i]].q);
+    }
+    double vf = 0.0;
+#pragma unroll
+    for (int i = 0; i < NSMAX; i++) {
+        if (EXACT || i < ns) {
+            const ModDev m = ld_mod(mods_c, K.src_mod[i]);
+            u64 v = y[i];
+            if (K.centered) v = add_mod(v, K.half_src[i], m.q);
+            y[i] = mont_mul(v, K.shat_inv_m[i], m.q, m.qinv);
+            const double qf = K.qf[i], rf = K.rf[i];   // the correctly rounded y/q of k_baseconv, summed in source order
+            const double a = (double)y[i];
+            const double e = a * rf;
+            vf += __builtin_fma(__builtin_fma(-e, qf, a), rf, e);
+        }
+    }
+    const int v = (int)(u64)vf;
+    const int j0 = blockIdx.z * TGT;
+#pragma unroll
+    for (int jj = 0; jj < TGT; jj++) {
+        const int j = min(j0 + jj, nd - 1);
+        const ModDev m = ld_mod(mods_c, K.dst_mod[j]);
+        u64 h = 0, l = 0, r = 0;
+#pragma unroll
+        for (int i = 0; i < NSMAX; i++) {
+            if (EXACT || i < ns) {
+                mac128(h, l, y[i], K.shat_m[j][i]);
+                if ((i & 7) == 7) {
+                    r = add_mod(r, csub(mont_redc_lazy(h, l, m.q, m.qinv), m.q), m.q);
+                    h = l = 0;
+                }
+            }
+        }
+        r = add_mod(r, csub(mont_redc_lazy(h, l, m.q, m.qinv), m.q), m.q);
+        r = sub_mod(r, K.vs[j][v], m.q);
+        if (K.centered) r = sub_mod(r, K.half_dst[j], m.q);
+        dst[(long long)g.rows.dst_row[j] << g.logn] = r;
+    }
+}
+
+template <int NSMAX, int TGT>
+static void launch_baseconv_wide_nt(int ns, int nd, dim3 grid, hipStream_t s, const BaseConvArgs& g) {
+    grid.z = (unsigned)((nd + TGT - 1) / TGT);
+    if (ns == NSMAX) hipLaunchKernelGGL((k_baseconv_wide<NSMAX, true, TGT>), grid, dim3(TPB), 0, s, g);
+    else hipLaunchKernelGGL((k_baseconv_wide<NSMAX, false, TGT>), grid, dim3(TPB), 0, s, g);
+}
+template <int NSMAX>
+static void launch_baseconv_wide_ns(int ns, int nd, dim3 grid, hipStream_t s, const BaseConvArgs& g) {
+    const int best = baseconv_targets_per_block(nd);
+    if (best == 4) launch_baseconv_wide_nt<NSMAX, 4>(ns, nd, grid, s, g);
+    else if (best == 7) launch_baseconv_wide_nt<NSMAX, 7>(ns, nd, grid, s, g);
+    else launch_baseconv_wide_nt<NSMAX, 13>(ns, nd, grid, s, g);
 }
 
 void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows, const u64* src, u64* dst, int batch,
@@ -1170,8 +1255,15 @@ void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows
     g.logn = c.logn;
     g.rows = rows;
     ProfScope ps(c, PROF_BASECONV, 8.0 * c.n * batch * (double)(k->ns * (sub ? 2 : 1) + k->nd), s);
-    const dim3 grid((unsigned)(c.n / (2 * TPB)), (unsigned)batch, 1);
     const int ns = k->ns, nd = k->nd;
+    if (ns > LSA_BC_NARROW_SRC) {
+        const dim3 grid((unsigned)(c.n / TPB), (unsigned)batch, 1);   // one point per thread
+        if (ns <= 24) launch_baseconv_wide_ns<24>(ns, nd, grid, s, g);
+        else launch_baseconv_wide_ns<LSA_BC_MAX_SRC>(ns, nd, grid, s, g);
+        LSA_HIP(hipGetLastError());
+        return;
+    }
+    const dim3 grid((unsigned)(c.n / (2 * TPB)), (unsigned)batch, 1);
     if (ns <= 1) launch_baseconv_ns<1>(ns, nd, k->split29, grid, s, g);
     else if (ns <= 2) launch_baseconv_ns<2>(ns, nd, k->split29, grid, s, g);
     else if (ns <= 3) launch_baseconv_ns<3>(ns, nd, k->split29, grid, s, g);
@@ -1179,7 +1271,7 @@ void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows
     else if (ns <= 5) launch_baseconv_ns<5>(ns, nd, k->split29, grid, s, g);
     else if (ns <= 8) launch_baseconv_ns<8>(ns, nd, k->split29, grid, s, g);
     else if (ns <= 12) launch_baseconv_ns<12>(ns, nd, k->split29, grid, s, g);
-    else launch_baseconv_ns<LSA_BC_MAX_SRC>(ns, nd, k->split29, grid, s, g);
+    else launch_baseconv_ns<LSA_BC_NARROW_SRC>(ns, nd, k->split29, grid, s, g);
     LSA_HIP(hipGetLastError());
 }
 

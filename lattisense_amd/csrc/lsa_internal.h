@@ -37,7 +37,11 @@ void set_last_error(const std::string& m);
     } while (0)
 
 // ---------------------------------------------------------------- exact RNS base conversion plan (device constants)
-#define LSA_BC_MAX_SRC 16
+// k_baseconv (two points per thread, optional 29-bit SPLIT accumulate) takes up to LSA_BC_NARROW_SRC sources; wider
+// conversions (the BFV multiply at N = 2^16: 24 Q limbs to 24 auxiliary limbs and back) run k_baseconv_wide, up to
+// LSA_BC_MAX_SRC sources
+#define LSA_BC_NARROW_SRC 16
+#define LSA_BC_MAX_SRC 32
 #define LSA_BC_MAX_DST 64
 
 struct BaseConvConsts {
@@ -49,7 +53,7 @@ struct BaseConvConsts {
     double qf[LSA_BC_MAX_SRC];                      // (double) q_i
     double rf[LSA_BC_MAX_SRC];                      // RN(1 / qf): reciprocal for the 3-operation exact division
     u64 shat_m[LSA_BC_MAX_DST][LSA_BC_MAX_SRC];     // (S/q_i) mod p_j, Montgomery form
-    u64 vs[LSA_BC_MAX_DST][LSA_BC_MAX_SRC + 1];     // v*S mod p_j, v = 0..ns
+    u64 vs[LSA_BC_MAX_DST][LSA_BC_MAX_SRC + 1];     // v*S mod p_j, v = 0..ns (v <= ns: a sum of ns quotients each <= 1)
     u64 half_dst[LSA_BC_MAX_DST];                   // floor(S/2) mod p_j
     // every source and target modulus below 2^58: shat_m split into 29-bit halves for the carry-free accumulate of
     // k_baseconv<.., SPLIT> (shat_m[j][i] = hi * 2^29 + lo)
@@ -57,8 +61,8 @@ struct BaseConvConsts {
     u32 shat_lo[LSA_BC_MAX_DST][LSA_BC_MAX_SRC];
     u32 shat_hi[LSA_BC_MAX_DST][LSA_BC_MAX_SRC];
     u32 shat_sum[LSA_BC_MAX_DST][LSA_BC_MAX_SRC];      // lo + hi: the middle column as ONE product (y0 + y1)(w0 + w1) - y0 w0 - y1 w1
-    // the output corrections -v*S - [centred] floor(S/2), Montgomery form, as ONE addend v * corr_a + corr_b (< 17 * 2^58) of the
-    // 128-bit sum ahead of its single REDC: corr_a = (-S) * 2^64 mod p_j, corr_b = (-floor(S/2)) * 2^64 mod p_j or 0
+    // the output corrections -v*S - [centred] floor(S/2), Montgomery form, as ONE addend v * corr_a + corr_b (< 17 * 2^58: SPLIT
+    // runs only in k_baseconv, ns <= 16, v <= ns) of the 128-bit sum ahead of its single REDC: corr_a = (-S) * 2^64 mod p_j, corr_b = (-floor(S/2)) * 2^64 mod p_j or 0
     u64 corr_a[LSA_BC_MAX_DST], corr_b[LSA_BC_MAX_DST];
 };
 

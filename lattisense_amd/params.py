@@ -67,3 +67,19 @@ def ckks_n17_chain():
     q0 = ntt_primes_below(60, n, 1)
     q = q0 + ntt_primes_below(45, n, 24)
     return {"n": n, "scale": float(1 << 45), "q": q, "p": p}
+
+
+# ---- BFV at N = 2^16 (BASELINE north_star: BFV HMult + relin at N = 2^16).  The reference ships no BFV set above N = 2^15,
+# so this chain is generated the same way: 24 Q primes of 59 bits and 4 special primes of 60 bits, all == 1 mod 2^17.
+def bfv_n16_chain():
+    """BFV chain for N = 2^16: Q = 24 x 59-bit primes (1416 bits), P = 4 x 60-bit primes, log QP = 1656 bits.
+
+    Security: the 128-bit bound used is Lattigo's PN16QP1761 default set (log QP <= 1761 at N = 2^16, ternary secret),
+    itself taken from the HomomorphicEncryption.org security standard tables; it was not re-derived here.
+    t = 786433 = 3 * 2^18 + 1 is prime and == 1 mod 2N, so the plaintext ring batches (65537 does not at N = 2^16).
+    The Q -> QMul extension of a multiply at the top level has 24 source limbs (the wide base conversion).
+    """
+    n = 1 << 16
+    p = ntt_primes_below(60, n, 4)
+    q = ntt_primes_below(59, n, 24, avoid=p)
+    return {"n": n, "t": 786433, "q": q, "p": p}

@@ -246,8 +246,24 @@ def bench_fixtures():
                  (3, 3), 2)
 
 
+def bfv_n16_fixtures():
+    """BFV mult_relin at the top level of the N = 2^16 chain (params.bfv_n16_chain, 24 Q + 4 P limbs), two disjoint
+    subgraphs: both base conversions of each multiply have 24 source limbs."""
+    C = P.bfv_n16_chain()
+    set_fhe_param(BfvParam.create_custom_param(n=C["n"], q=C["q"], p=C["p"], t=C["t"]))
+    lv = len(C["q"]) - 1
+    xs = [BfvCiphertextNode(f"x_{i}", level=lv) for i in range(2)]
+    ys = [BfvCiphertextNode(f"y_{i}", level=lv) for i in range(2)]
+    zs = [mult_relin(xs[i], ys[i], f"z_{i}") for i in range(2)]
+    emit("bfv_n65536_l23_cmc_relin_x2", [Argument("xs", xs), Argument("ys", ys)], [Argument("zs", zs)])
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["bfv_n16"]:   # only the N = 2^16 BFV fixture
+        bfv_n16_fixtures()
+        sys.exit(0)
     main()
+    bfv_n16_fixtures()
     bench_fixtures()
     for d in sorted(os.listdir(OUT)):
         print(d, os.listdir(os.path.join(OUT, d)))
