@@ -135,6 +135,11 @@ int lsa_set_ntt_chunk_mib(lsa_context ctx, int mib);
  * outs[i] = rotate(in, galois_elements[i]), each bit-identical to lsa_ckks_rotate's result. */
 int lsa_ckks_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_rot, const uint64_t* galois_elements,
                          const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream);
+/* The same for BFV (coefficient-domain ciphertexts): outs[i] = rotate(in, galois_elements[i]), each bit-identical to
+ * lsa_bfv_rotate's result.  The input's c1 is transformed and decomposed once; each key then costs its MAC and ModDown only,
+ * the automorphism riding on the ModDown tail.  At most one output may overlap the input. */
+int lsa_bfv_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_rot, const uint64_t* galois_elements,
+                        const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream);
 
 /* ---- CKKS bootstrapping: the `bootstrap` node of a task graph (reference: mega_ag_executors_gpu.cu:410-426 calls HEonGPU's
  * regular_bootstrapping_v2; configuration gpu_wrapper.cu:86-117 / custom_task.py:383-468).  A plan holds the encoded

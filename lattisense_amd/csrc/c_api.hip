@@ -20,6 +20,8 @@ void poly_addsub(Context&, int, int, int, const u64*, const u64*, u64*, int, lon
 void bfv_mult(Context&, int, const u64*, const u64*, u64*, int, long long, long long, long long, hipStream_t);
 void bfv_relin(Context&, int, const u64*, const Key&, u64*, int, long long, long long, hipStream_t);
 void bfv_rotate(Context&, int, const u64*, u64, const Key&, u64*, int, long long, long long, hipStream_t);
+void bfv_rotate_many(Context&, int, const u64*, int, const u64*, const Key* const*, u64* const*, int, long long, long long,
+                     hipStream_t);
 void bfv_rescale(Context&, int, int, const u64*, u64*, int, long long, long long, hipStream_t);
 }  // namespace lsa
 
@@ -383,6 +385,18 @@ int lsa_ckks_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_r
             keys[i] = &K(glk[i]);
         }
         ckks_rotate_many(C(ctx), level, in, n_rot, galois_elements, keys.data(), outs, batch, sin, sout, S(stream));
+    });
+}
+int lsa_bfv_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_rot, const uint64_t* galois_elements,
+                        const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(in != nullptr && n_rot >= 0 && (n_rot == 0 || (galois_elements && glk && outs)), "null argument");
+        std::vector<const Key*> keys(n_rot);
+        for (int i = 0; i < n_rot; i++) {
+            LSA_REQUIRE(glk[i] != nullptr && outs[i] != nullptr, "null key or output");
+            keys[i] = &K(glk[i]);
+        }
+        bfv_rotate_many(C(ctx), level, in, n_rot, galois_elements, keys.data(), outs, batch, sin, sout, S(stream));
     });
 }
 

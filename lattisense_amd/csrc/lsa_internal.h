@@ -281,6 +281,13 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
 void launch_moddown_final(Context& c, int level, const u64* acc, long long sacc, int acc_rows_per_poly, const u64* conv,
                           long long sconv, const u64* base, long long sbase, int base_rows_per_poly, int base_polys,
                           u64* out, long long sout, int batch, hipStream_t s);
+// the same tail (coefficient domain) followed by the automorphism of a rotation, in one pass (k_sub_mul_perm, one limb staged
+// in LDS: N <= 2^LSA_PERM_LDS_MAX_LOGN): out[h][i][x] = sign_x * (base[h][i][pi_x] + (acc[h][i][pi_x] - conv[h][i][pi_x]) * Pinv_i),
+// perm = Context::coeff_perm(g)
+#define LSA_PERM_LDS_MAX_LOGN 14
+void launch_moddown_final_perm(Context& c, int level, const u32* perm, const u64* acc, long long sacc, int acc_rows_per_poly,
+                               const u64* conv, long long sconv, const u64* base, long long sbase, int base_rows_per_poly,
+                               int base_polys, u64* out, long long sout, int batch, hipStream_t s);
 // out[p][i] = base[p][i] + (a[p][i] - b[p][i]) * kvec[i]; row of operand X = p*X_rpp + i; b/base optional
 void launch_sub_mul_general(Context& c, int polys, int limbs, const unsigned char* limb_mod, const u64* kvec,
                             const u64* a, long long sa, int a_rpp, const u64* b, long long sb, int b_rpp,

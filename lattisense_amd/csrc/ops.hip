@@ -155,7 +155,7 @@ static void ks_mac(Context& c, int level, const u64* cx, long long scx, const Ke
 
 static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, u64* p, long long sp, const u64* base,
                        long long sbase, int base_rpp, int base_polys, int nb, hipStream_t s, const KsRescale* rs, bool coeff_out,
-                       const u32* scatter = nullptr);
+                       const u32* scatter = nullptr, const u32* coeff_gather = nullptr);
 
 // steps 4-5 of a key switch on the digits that ks_decompose left in the workspace: they depend on the key, the decomposition
 // does not -- rotations of ONE ciphertext by several Galois elements share it ("hoisting"; with the automorphism applied
@@ -171,11 +171,14 @@ static void ks_finish(Context& c, int level, const u64* cx, long long scx, const
 // step 5, the division by P of a polynomial pair over Q_level u P (acc: [2][L+k][N] per batch item, NTT domain; its P rows --
 // and, for the merged rescale, its last Q row -- are transformed in place), conv: 2L rows of scratch per batch item.
 // scatter (fused tails only): every result row is written through the index map, p[row][scatter[x]] = value(x) -- the
-// NTT-domain automorphism of a rotation applied by the last pass's store instead of a permutation kernel afterwards
+// NTT-domain automorphism of a rotation applied by the last pass's store instead of a permutation kernel afterwards.
+// coeff_gather (coeff_out only): the coefficient-domain automorphism of a BFV rotation, Context::coeff_perm(g), applied by
+// the tail's loads (k_sub_mul_perm): p[row][x] = sign_x * value(pi_x)
 static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, u64* p, long long sp, const u64* base,
                        long long sbase, int base_rpp, int base_polys, int nb, hipStream_t s, const KsRescale* rs, bool coeff_out,
-                       const u32* scatter) {
+                       const u32* scatter, const u32* coeff_gather) {
     LSA_REQUIRE(!scatter || (c.fuse_tails && !rs && !coeff_out), "scattered ModDown store: fused tails, no rescale, NTT-domain output");
+    LSA_REQUIRE(!coeff_gather || (coeff_out && !rs), "gathered ModDown tail: coefficient-domain output, no rescale");
     const long long N = c.n;
     const int L = level + 1, np = c.np, T = L + np;
     const long long s_conv = 2LL * L * N;
@@ -209,7 +212,11 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
             launch_baseconv(c, k, rows, acc + (size_t)h * T * N, conv + (size_t)h * L * N, nb, s_acc, s_conv, s);
     }
     if (coeff_out) {
-        launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, base, sbase, base_rpp, base_polys, p, sp, nb, s);
+        if (coeff_gather)
+            launch_moddown_final_perm(c, level, coeff_gather, acc, s_acc, T, conv, s_conv, base, sbase, base_rpp, base_polys, p, sp,
+                                      nb, s);
+        else
+            launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, base, sbase, base_rpp, base_polys, p, sp, nb, s);
         return;
     }
     if (rs) {
@@ -731,6 +738,65 @@ void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64
         const u64* ct = in + (size_t)b0 * sin;
         bfv_key_switch(c, level, ct + (long long)L * N, sin, glk, p, sp, ct, sin, L, 1, nb, ws, st);   // p0 = c0 + ks0
         launch_permute_coeff(c, perm, p, sp, out + (size_t)b0 * sout, sout, 2 * L, rm_seq(L), nb, st);
+    });
+}
+
+// rotations of the same ciphertexts by several Galois elements with ONE decomposition (hoisting); outs[i] = rotate(in, g[i]),
+// each identical to bfv_rotate's result.  Per tile: c1 into the NTT domain once (the MAC's own-digit operand), the digits'
+// conversions and extension transforms once from the coefficients; then per key the stand-alone MAC (several keys: the
+// fused second pass + MAC does not apply) and the coefficient-domain ModDown, whose tail applies the automorphism by its
+// loads and writes outs[i] directly (k_sub_mul_perm).  Two-step form (tail into the workspace, then k_permute) for an
+// output that overlaps the input, for N > 2^14, with LSA_ROT_SCATTER=0 and with unfused tails.
+void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
+                     int batch, long long sin, long long sout, hipStream_t s) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
+    if (n_rot <= 0) return;
+    if (n_rot == 1) {
+        bfv_rotate(c, level, in, g[0], *glk[0], outs[0], batch, sin, sout, s);
+        return;
+    }
+    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    const long long N = c.n;
+    const int L = level + 1;
+    const size_t ks_rows = ks_ws_rows(c, level) + L;
+    const long long sp = 2LL * L * N;
+    // the one-pass tail stages a limb in LDS (N <= 2^14); larger rings keep the two steps, which measured faster than gathering
+    // from global memory
+    const bool gather_on = rotation_scatter_on() && c.fuse_tails && c.logn <= LSA_PERM_LDS_MAX_LOGN;
+    std::vector<const u32*> perms(n_rot);
+    std::vector<bool> direct(n_rot);
+    std::vector<int> order;   // an output that overlaps the input goes last: every other rotation still reads the intact c0
+    int overlapping = -1;
+    for (int i = 0; i < n_rot; i++) {
+        const bool apart = outs[i] + (size_t)batch * sout <= in || in + (size_t)batch * sin <= outs[i];
+        perms[i] = c.coeff_perm(g[i]);
+        direct[i] = apart && gather_on;
+        if (apart) {
+            order.push_back(i);
+            continue;
+        }
+        LSA_REQUIRE(overlapping < 0, "bfv_rotate_many: at most one output may overlap the input");
+        overlapping = i;
+    }
+    if (overlapping >= 0) order.push_back(overlapping);
+    for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
+        u64* cxn = ws;
+        u64* sub = ws + (size_t)nb * L * N;
+        u64* p = ws + ks_rows * N * tb;
+        const u64* ct = in + (size_t)b0 * sin;
+        const KsWorkspace w = ks_layout(c, level, nb, sub);
+        launch_ntt(c, ct + (long long)L * N, cxn, nb, sin, (long long)L * N, L, rm_seq(L), false, st);
+        ks_decompose(c, level, cxn, (long long)L * N, nb, sub, st, ct + (long long)L * N, sin, true);
+        for (int i : order) {
+            ks_mac(c, level, cxn, (long long)L * N, *glk[i], nb, sub, st, false);
+            if (direct[i]) {   // p0 = c0 + ks0 and the automorphism in one tail, straight into the output
+                ks_moddown(c, level, w.acc, w.s_acc, w.conv, outs[i] + (size_t)b0 * sout, sout, ct, sin, L, 1, nb, st, nullptr, true,
+                           nullptr, perms[i]);
+                continue;
+            }
+            ks_moddown(c, level, w.acc, w.s_acc, w.conv, p, sp, ct, sin, L, 1, nb, st, nullptr, true);
+            launch_permute_coeff(c, perms[i], p, sp, outs[i] + (size_t)b0 * sout, sout, 2 * L, rm_seq(L), nb, st);
+        }
     });
 }
 

@@ -42,6 +42,8 @@ void ckks_mult_relin_rescale(Context&, int, const u64*, const u64*, const Key&, 
 void bfv_mult(Context&, int, const u64*, const u64*, u64*, int, long long, long long, long long, hipStream_t);
 void bfv_relin(Context&, int, const u64*, const Key&, u64*, int, long long, long long, hipStream_t);
 void bfv_rotate(Context&, int, const u64*, u64, const Key&, u64*, int, long long, long long, hipStream_t);
+void bfv_rotate_many(Context&, int, const u64*, int, const u64*, const Key* const*, u64* const*, int, long long, long long,
+                     hipStream_t);
 void bfv_rescale(Context&, int, int, const u64*, u64*, int, long long, long long, hipStream_t);
 }  // namespace lsa
 
@@ -1194,13 +1196,15 @@ struct fhe_task_handle_st {
         pending_free().push_back(out_slab);  // (cheap: shared) keeps frees off the critical path until the level ends
     }
 
-    // Buckets of one level.  CKKS rotations of the SAME ciphertexts by different Galois elements (the frontend's rotate_cols
-    // emits them for convolutions: examples/benchmark_convolution) are hoisted: one decomposition of the inputs, then only
-    // the key MAC + ModDown + permutation per element (ckks_rotate_many; same residues as separate rotations).
+    // Buckets of one level.  Rotations of the SAME ciphertexts by different Galois elements (the frontend's rotate_cols /
+    // advanced_rotate_cols emit them: examples/benchmark_convolution, BFV_4_advanced_rotate_col) are hoisted: one
+    // decomposition of the inputs, then only the key MAC + ModDown + permutation per element (ckks_rotate_many /
+    // bfv_rotate_many; same residues as separate rotations).
     void run_buckets(Context& c, hipStream_t s, std::map<std::string, std::vector<ComputeNode*>>& buckets,
                      const std::vector<std::string>& order, std::unordered_map<NodeIndex, std::any>& avail) {
         std::map<std::vector<NodeIndex>, std::vector<const std::string*>> rot_groups;
-        if (g.algo == ALGO_CKKS)
+        const bool hoist = g.algo == ALGO_CKKS || g.algo == ALGO_BFV;
+        if (hoist)
             for (auto& sg : order) {
                 auto& nodes = buckets[sg];
                 const OperationType op = nodes[0]->op();
@@ -1215,7 +1219,7 @@ struct fhe_task_handle_st {
             auto& nodes = buckets[sg];
             const OperationType op = nodes[0]->op();
             std::vector<const std::string*>* group = nullptr;
-            if (g.algo == ALGO_CKKS && (op == OperationType::ROTATE_COL || op == OperationType::ROTATE_ROW)) {
+            if (hoist && (op == OperationType::ROTATE_COL || op == OperationType::ROTATE_ROW)) {
                 std::vector<NodeIndex> ins;
                 for (auto* n : nodes) ins.push_back(n->input_nodes[0]->index);
                 auto& gr = rot_groups[ins];
@@ -1250,7 +1254,10 @@ struct fhe_task_handle_st {
                 slabs.push_back(dslab(w * m));
                 outs.push_back(slabs.back()->ptr);
             }
-            ckks_rotate_many(c, lvl, a.ptr, (int)els.size(), els.data(), keys.data(), outs.data(), m, a.stride, (long long)w, s);
+            if (g.algo == ALGO_BFV)
+                bfv_rotate_many(c, lvl, a.ptr, (int)els.size(), els.data(), keys.data(), outs.data(), m, a.stride, (long long)w, s);
+            else
+                ckks_rotate_many(c, lvl, a.ptr, (int)els.size(), els.data(), keys.data(), outs.data(), m, a.stride, (long long)w, s);
             for (size_t gi = 0; gi < group->size(); gi++) {
                 auto& mn = buckets[*(*group)[gi]];
                 for (int i = 0; i < m; i++) {

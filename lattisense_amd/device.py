@@ -195,6 +195,18 @@ class DeviceContext:
                                    self.stream))
         return out
 
+    def bfv_rotate_many(self, level, ct, keys, batch):
+        """keys: {galois element: key handle}; returns {element: device buffer}, one decomposition for all (hoisted), each
+        output bit-identical to bfv_rotate's"""
+        L = level + 1
+        outs = {g: self.alloc(batch * 2 * L * self.n) for g in keys}
+        els = (ctypes.c_uint64 * len(keys))(*keys.keys())
+        hk = (ctypes.c_void_p * len(keys))(*[k.value for k in keys.values()])
+        po = (ctypes.c_void_p * len(keys))(*[o.ptr for o in outs.values()])
+        check(lib().lsa_bfv_rotate_many(self.h, level, ct.ptr, len(keys), els, hk, po, batch, 2 * L * self.n, 2 * L * self.n,
+                                        self.stream))
+        return outs
+
     def bfv_rescale(self, level, polys, ct, batch):
         L = level + 1
         out = self.alloc(batch * polys * level * self.n)
