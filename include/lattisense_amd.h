@@ -109,6 +109,17 @@ int lsa_bfv_relin(lsa_context ctx, int level, const uint64_t* d3, lsa_key rlk, u
                   long long stride_d, long long stride_out, void* stream);
 int lsa_bfv_rotate(lsa_context ctx, int level, const uint64_t* in, uint64_t galois_element, lsa_key glk,
                    uint64_t* out, int batch, long long stride_in, long long stride_out, void* stream);
+/* BFV ciphertext x pt_mul plaintext.  A pt_mul plaintext ([level+1][N] words) is the message lifted to Q, in the NTT domain
+ * and in Montgomery form (the frontend's BfvPlaintextMulNode).  Per poly and limb: out = INTT(NTT(ct) . pt . 2^-64 mod q),
+ * Lattigo v4's mulPlaintextMul.  ct / out: [2][level+1][N] per batch item; out may be ct.  LSA_PTMUL_FUSED=0 selects the
+ * unfused form (read per call). */
+int lsa_bfv_mult_plain_mul(lsa_context ctx, int level, const uint64_t* ct, const uint64_t* pt, uint64_t* out, int batch,
+                           long long sct, long long spt, long long sout, void* stream);
+/* out = sum_{i<n} cts[i] x pts[i] (+ partial when not null), n >= 1, the same products as lsa_bfv_mult_plain_mul, summed in
+ * the NTT domain with one inverse transform per output.  out may overlap no input. */
+int lsa_bfv_mac_plain_mul(lsa_context ctx, int level, int n, const uint64_t* const* cts, const long long* scts,
+                          const uint64_t* const* pts, const long long* spts, const uint64_t* partial, long long spartial,
+                          uint64_t* out, int batch, long long sout, void* stream);
 int lsa_bfv_rescale(lsa_context ctx, int level, int polys, const uint64_t* in, uint64_t* out, int batch,
                     long long stride_in, long long stride_out, void* stream);
 int lsa_bfv_mult_relin(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, lsa_key rlk,

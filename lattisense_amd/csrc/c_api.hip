@@ -400,6 +400,23 @@ int lsa_bfv_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_ro
     });
 }
 
+int lsa_bfv_mult_plain_mul(lsa_context ctx, int level, const uint64_t* ct, const uint64_t* pt, uint64_t* out, int batch,
+                           long long sct, long long spt, long long sout, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(ct != nullptr && pt != nullptr && out != nullptr, "null argument");
+        bfv_mult_plain_mul(C(ctx), level, ct, pt, out, batch, sct, spt, sout, S(stream));
+    });
+}
+int lsa_bfv_mac_plain_mul(lsa_context ctx, int level, int n, const uint64_t* const* cts, const long long* scts,
+                          const uint64_t* const* pts, const long long* spts, const uint64_t* partial, long long spartial,
+                          uint64_t* out, int batch, long long sout, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(n >= 1 && cts && scts && pts && spts && out, "null argument");
+        for (int i = 0; i < n; i++) LSA_REQUIRE(cts[i] != nullptr && pts[i] != nullptr, "null ciphertext or plaintext");
+        bfv_mac_plain_mul(C(ctx), level, n, cts, scts, pts, spts, partial, spartial, out, batch, sout, S(stream));
+    });
+}
+
 // ---- CKKS bootstrapping
 struct lsa_bootstrap_st {
     Bootstrap* b;

@@ -61,7 +61,8 @@ __device__ __forceinline__ void ntt_butterfly_phases(const NttPassArgs& a, const
 // TWL: the pass holds global stage 0 (strided first pass of a two-pass plan): its 2^mu twiddles are the same for every tile
 // of the limb and go through LDS -- one fetch per workgroup, issued with the tile loads, instead of one per sub-pass.
 // FZ: 0 plain, 1 fused prologue only (first pass of a two-pass fused transform), 2 fused epilogue only (its last pass), 3 both
-// (single-pass transforms).  Split so that a pass carries only the tail code and registers it can execute.
+// (single-pass transforms), 4 the pt_mul epilogue (fz_epi == 3) only.  Split so that a pass carries only the tail code and
+// registers it can execute.
 template <int FZ, int NT, bool TWL = false>
 __global__ __launch_bounds__(NT, NT > 512 ? 1 : NT > 256 ? 2 : (FZ & 1) ? LSA_NTT_WAVES_FUSED : LSA_NTT_WAVES) void k_ntt_pass(NttPassArgs a) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
@@ -107,11 +108,11 @@ __global__ __launch_bounds__(NT, NT > 512 ? 1 : NT > 256 ? 2 : (FZ & 1) ? LSA_NT
     __syncthreads();
     LSA_STAMP(2);
 #if defined(LSA_NTT_DIAG_COPY_ONLY)   // diagnostic build: data movement of the pass structure without butterflies
-    ntt_phase_store<(FZ & 2) != 0, NT>(a, bc, tid, lds);
+    ntt_phase_store<(FZ & 2) != 0, NT, (FZ & 4) != 0>(a, bc, tid, lds);
     return;
 #endif
     ntt_butterfly_phases<NT, TWL>(a, bc, tid, lds);
-    ntt_phase_store<(FZ & 2) != 0, NT>(a, bc, tid, lds);
+    ntt_phase_store<(FZ & 2) != 0, NT, (FZ & 4) != 0>(a, bc, tid, lds);
     LSA_STAMP(7);
 }
 
@@ -175,6 +176,20 @@ static bool ntt_launch_r16(const NttPassArgs& a, int npass, bool fused, long lon
     const bool pro = fused && a.fz_pro && a.s_lo == 0, epi = fused && a.fz_epi && a.final_reduce;
     const size_t lds_bytes = (size_t)LSA_R16_LDS_WORDS * sizeof(u64);
     const dim3 grid((unsigned)nblocks), block(LSA_R16_THREADS);
+    if (epi && a.fz_epi == 3) {   // the pt_mul epilogue (FZ bit 4): second passes only, it has no prologue
+        if (a.lambda) return false;
+        if (a.mu == 9) {
+            const char* e = getenv("LSA_NTT_R8X3");
+            if (e && e[0] == '0') return false;
+            hipLaunchKernelGGL((k_ntt_r8x3<4>), grid, block, lds_bytes, s, a);
+        } else if (a.mu == 8) {
+            hipLaunchKernelGGL((k_ntt_r16<1, 4, 8>), grid, block, lds_bytes, s, a);
+        } else {
+            hipLaunchKernelGGL((k_ntt_r16<1, 4, 7>), grid, block, lds_bytes, s, a);
+        }
+        LSA_HIP(hipGetLastError());
+        return true;
+    }
     // the two-operand prologue: 394 us per headline launch here against 450 on the staged kernel once the lift's block-uniform
     // cases became branches (628 before: both lifts were evaluated per element, profiles/r03/ab_r16_prologue_epilogue_branches.log);
     // LSA_R16_PRO=0 keeps it on the staged kernel (A/B)
@@ -410,6 +425,10 @@ static void ntt_launch_pass(const NttPassArgs& a, bool fused, long long nblocks,
     // which fused tail this pass can execute: the prologue lives in the pass that holds stage 0, the epilogue in the pass
     // that reduces and stores the final values
     const bool pro = fused && a.fz_pro && a.s_lo == 0, epi = fused && a.fz_epi && a.final_reduce;
+    if (epi && a.fz_epi == 3) {   // the pt_mul epilogue (FZ bit 4, no prologue)
+        ntt_launch_variant<4, NT>(a, nblocks, lds_bytes, s);
+        return;
+    }
     switch ((pro ? 1 : 0) | (epi ? 2 : 0)) {
         case 0: ntt_launch_variant<0, NT>(a, nblocks, lds_bytes, s); break;
         case 1: ntt_launch_variant<1, NT>(a, nblocks, lds_bytes, s); break;
@@ -459,6 +478,7 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
         a.fz_scatter = fz->scatter;
         LSA_REQUIRE(fz->epi != 2 || fz->k2, "merged tail needs its second factor");
         LSA_REQUIRE(!fz->scatter || fz->epi, "a scattered store needs an epilogue");
+        LSA_REQUIRE(fz->epi != 3 || (!fz->pro && !fz->scatter && fz->a && fz->out), "pt_mul epilogue: plaintext and output, nothing else");
     }
     a.period = rm.period;
     a.row0 = rm.row0;
@@ -521,6 +541,11 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
         a.batch = nb;
+        if (fz && fz->epi == 3) {   // the pt_mul epilogue's operands follow the chunk (block batch indices restart at 0)
+            a.fz_a = fz->a + (long long)b0 * fz->a_stride;
+            a.fz_base = fz->base ? fz->base + (long long)b0 * fz->base_stride : nullptr;
+            a.fz_out = fz->out + (long long)b0 * fz->out_stride;
+        }
         for (int step = 0; step < plan.npass; step++) {
             if (plan.npass == 2 && !((passes >> step) & 1)) continue;
             const int k = inverse ? plan.npass - 1 - step : step;
@@ -765,6 +790,61 @@ void launch_mac_plain(Context& c, int terms, const u64* const* ct, const long lo
     fill_rowmap(g.mod_of, period, rm, c.nmod);
     ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * limbs * batch * ((double)terms * (polys + 1) + polys * (partial ? 2 : 1)), s);
     hipLaunchKernelGGL(k_mac_plain, ew_grid(c, polys * limbs, batch), dim3(TPB), 0, s, g);
+    LSA_HIP(hipGetLastError());
+}
+
+// BFV ct x pt_mul, unfused form (the fused one is the forward transform's fz_epi == 3 epilogue):
+// out[p][j] = a[p][j] * pt[j] * 2^-64 mod q (+ acc[p][j]) for every poly p of [batch][polys][limbs][N]; the pt_mul plaintext
+// is in Montgomery form, so one Montgomery product is the whole multiply.  acc and a may be out.
+struct MontMulArgs {
+    const u64* a;
+    const u64* pt;
+    const u64* acc;
+    u64* out;
+    long long sa, spt, sacc, so;
+    const ModDev* mods;
+    int limbs, logn;
+    unsigned char mod_of[LSA_MAX_PERIOD];
+};
+__global__ __launch_bounds__(TPB) void k_mont_muladd(MontMulArgs g) {
+    const int chunks = (1 << g.logn) / (2 * TPB);
+    const int row = blockIdx.x / chunks;             // poly * limbs + limb
+    const int limb = row % g.limbs;
+    const int x = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
+    const ModDev m = g.mods[g.mod_of[limb]];
+    const long long b = blockIdx.y;
+    const long long off = ((long long)row << g.logn) + x;
+    const ulonglong2 va = ld2(g.a + b * g.sa + off);
+    const ulonglong2 w = ld2(g.pt + b * g.spt + ((long long)limb << g.logn) + x);
+    u64 r0 = mont_mul(va.x, w.x, m.q, m.qinv), r1 = mont_mul(va.y, w.y, m.q, m.qinv);
+    if (g.acc) {
+        const ulonglong2 vc = ld2(g.acc + b * g.sacc + off);
+        r0 = add_mod(r0, vc.x, m.q);
+        r1 = add_mod(r1, vc.y, m.q);
+    }
+    st2(g.out + b * g.so + off, r0, r1);
+}
+
+void launch_mont_muladd(Context& c, const u64* a, long long sa, const u64* pt, long long spt, const u64* acc, long long sacc,
+                        u64* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s) {
+    if (batch <= 0) return;
+    LSA_REQUIRE(rm.period == limbs && limbs <= LSA_MAX_PERIOD, "mont_muladd: row map must cover the limbs");
+    MontMulArgs g{};
+    g.a = a;
+    g.pt = pt;
+    g.acc = acc;
+    g.out = out;
+    g.sa = sa;
+    g.spt = spt;
+    g.sacc = sacc;
+    g.so = so;
+    g.mods = c.d_mods;
+    g.limbs = limbs;
+    g.logn = c.logn;
+    int period;
+    fill_rowmap(g.mod_of, period, rm, c.nmod);
+    ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * limbs * batch * (polys * (acc ? 3.0 : 2.0) + 1.0), s);
+    hipLaunchKernelGGL(k_mont_muladd, ew_grid(c, polys * limbs, batch), dim3(TPB), 0, s, g);
     LSA_HIP(hipGetLastError());
 }
 

@@ -251,6 +251,17 @@ void launch_mac_plain(Context& c, int terms, const u64* const* ct, const long lo
                       int polys, int limbs, const RowMap& rm, hipStream_t s);
 void launch_mac_plain_multi(Context& c, int nb, const u64* const* ct, const long long* sct, int ng, const u64* const* pt,
                             u64* const* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s);
+// out[p][j] = a[p][j] * pt[j] * 2^-64 mod q (+ acc[p][j]) over [batch][polys][limbs][N]: BFV ct x pt_mul in the NTT domain,
+// unfused form (k_mont_muladd); acc / a may be out
+void launch_mont_muladd(Context& c, const u64* a, long long sa, const u64* pt, long long spt, const u64* acc, long long sacc,
+                        u64* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s);
+// BFV ct x pt_mul (NTT-domain, Montgomery-form plaintexts [L][N], ops.hip): out = ct . pt per poly; out may be ct
+void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64* out, int batch, long long sct, long long spt,
+                        long long sout, hipStream_t s);
+// out = sum_i cts[i] . pts[i] (+ partial), n >= 1 terms, one inverse transform per output; out overlaps no input
+void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
+                       const long long* spts, const u64* partial, long long spartial, u64* out, int batch, long long sout,
+                       hipStream_t s);
 // ring-t plaintext limb -> [level+1][N] residues: mode 0 centred lift from q_0 (CKKS), 1 direct (BFV multiply),
 // 2 scale-up by Q/t (BFV add/sub)
 void launch_lift_ringt(Context& c, int mode, int level, const u64* pt, long long spt, u64* out, long long sout, int batch,

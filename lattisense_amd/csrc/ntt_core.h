@@ -93,6 +93,8 @@ struct NttPassArgs {
     //   fz_pro = 1:  in = lift = ((fz_last[poly] + h) mod q_l) mod q_limb - (h mod q_limb),  h = (q_l - 1)/2  (rescale head)
     //   fz_pro = 2:  in = src + lift   (merged ModDown + rescale: one transform of conv*P^-1 + lift serves both steps)
     //   fz_epi = 2:  out = (fz_a * fz_k - v + fz_base) * fz_k2   (its tail: (acc*P^-1 - NTT(in) + base) * q_l^-1)
+    //   fz_epi = 3:  out[poly][limb] = v * fz_a[limb] * 2^-64 (+ fz_base[poly][limb] if fz_base)   (BFV ct x pt_mul: the
+    //                Montgomery-form plaintext, shared by both polys; kernels compiled with FZ bit 4, ntt_phase_store_ptm)
     int fz_epi, fz_pro, fz_limbs, fz_base_polys, fz_ql_mod;
     int fz_a_rpp, fz_base_rpp, fz_out_rpp, fz_last_rpp;
     const u64* fz_a;
@@ -550,8 +552,74 @@ LSA_HD NttStoreFix ntt_make_store_fix(const NttPassArgs& a, const NttBlockCtx& b
     }
     return f;
 }
-template <bool FZ, int NT>
+// ---- the pt_mul epilogue (fz_epi == 3): the plain store path reduces the transformed value v to [0, q), then
+// out[poly][limb] = mont_mul(v, pt[limb]) (+ acc[poly][limb]).  fz_a: the plaintexts [batch][fz_limbs][N] (stride fz_a_stride),
+// fz_base: the running sum or null, fz_out: the result; acc may be fz_out (every point is read and written by one thread)
+struct NttPtmFix {
+    const u64* pt;
+    const u64* acc;
+    u64 q, qinv;
+};
+LSA_HD NttPtmFix ntt_make_ptm_fix(const NttPassArgs& a, const NttBlockCtx& bc, u64*& g) {
+    const int poly = bc.row / a.fz_limbs, limb = bc.row % a.fz_limbs;
+    const ModDev md = a.mods[bc.mod];
+    NttPtmFix p;
+    p.q = md.q;
+    p.qinv = md.qinv;
+    p.pt = a.fz_a + (long long)bc.b * a.fz_a_stride + ((long long)limb << a.logn);
+    p.acc = a.fz_base ? a.fz_base + (long long)bc.b * a.fz_base_stride + (((long long)poly * a.fz_base_rpp + limb) << a.logn) : nullptr;
+    g = a.fz_out + (long long)bc.b * a.fz_out_stride + (((long long)poly * a.fz_out_rpp + limb) << a.logn);
+    return p;
+}
+LSA_HD u64 ntt_ptm_fix(const NttPtmFix& p, u64 v, u64 w, u64 acc) {
+    const u64 r = mont_mul(v, w, p.q, p.qinv);
+    return p.acc ? add_mod(r, acc, p.q) : r;
+}
+template <int NT>
+LSA_HD void ntt_phase_store_ptm(const NttPassArgs& a, const NttBlockCtx& bc, int tid, const u64* lds) {
+    u64* g;
+    const u64* pa;
+    const u64* pb;
+    const int half = 1 << (a.tau - 1);
+    const NttStoreFix f = ntt_make_store_fix<false>(a, bc, g, pa, pb);
+    const NttPtmFix pf = ntt_make_ptm_fix(a, bc, g);
+    const NttTileMap tm = ntt_tile_map(a, bc.tile);
+    if (half == LSA_NTT_STAGE_PAIRS * NT) {
+        for (int p0 = 0; p0 < LSA_NTT_STAGE_PAIRS; p0 += LSA_NTT_STORE_CHUNK) {
+            u64 v[2 * LSA_NTT_STORE_CHUNK], w[2 * LSA_NTT_STORE_CHUNK], c[2 * LSA_NTT_STORE_CHUNK];
+            int xs[LSA_NTT_STORE_CHUNK];
+#pragma unroll
+            for (int p = 0; p < LSA_NTT_STORE_CHUNK; p++) {
+                const int l = 2 * (tid + (p0 + p) * NT);
+                const int x = ntt_tile_index(tm, l);
+                xs[p] = x;
+                v[2 * p] = lds[lds_addr(l)];
+                v[2 * p + 1] = lds[lds_addr(l + 1)];
+                ntt_load_data_pair(pf.pt + x, w[2 * p], w[2 * p + 1]);
+                c[2 * p] = c[2 * p + 1] = 0;
+                if (pf.acc) ntt_load_data_pair(pf.acc + x, c[2 * p], c[2 * p + 1]);
+            }
+#pragma unroll
+            for (int p = 0; p < LSA_NTT_STORE_CHUNK; p++)
+                ntt_store_pair(g + xs[p], ntt_ptm_fix(pf, ntt_store_fix(f, v[2 * p], 0, 0), w[2 * p], c[2 * p]),
+                               ntt_ptm_fix(pf, ntt_store_fix(f, v[2 * p + 1], 0, 0), w[2 * p + 1], c[2 * p + 1]));
+        }
+        return;
+    }
+    for (int i = tid; i < half; i += NT) {   // partial tiles (small rings)
+        const int x = ntt_tile_index(tm, 2 * i);
+        const u64 c0 = pf.acc ? pf.acc[x] : 0, c1 = pf.acc ? pf.acc[x + 1] : 0;
+        ntt_store_pair(g + x, ntt_ptm_fix(pf, ntt_store_fix(f, lds[lds_addr(2 * i)], 0, 0), pf.pt[x], c0),
+                       ntt_ptm_fix(pf, ntt_store_fix(f, lds[lds_addr(2 * i + 1)], 0, 0), pf.pt[x + 1], c1));
+    }
+}
+// PM: the pt_mul epilogue instead of the plain store (FZ is false then)
+template <bool FZ, int NT, bool PM = false>
 LSA_HD void ntt_phase_store(const NttPassArgs& a, const NttBlockCtx& bc, int tid, const u64* lds) {
+    if (PM) {
+        ntt_phase_store_ptm<NT>(a, bc, tid, lds);
+        return;
+    }
     u64* g;
     const u64* pa;
     const u64* pb;

@@ -284,8 +284,42 @@ LSA_HD void r16_load_coalesced(const NttPassArgs& a, const NttBlockCtx& bc, int 
     }
 }
 // second pass, forward: LDS -> 16-byte coalesced stores with the store-side conversions and the fused epilogue
-template <bool FZ, int MU>
+// the pt_mul epilogue (fz_epi == 3, ntt_core.h ntt_phase_store_ptm) on the same coalesced positions
+template <int MU>
+LSA_HD void r16_store_coalesced_ptm(const NttPassArgs& a, const NttBlockCtx& bc, int tid, const u64* lds) {
+    u64* g;
+    const u64* pa;
+    const u64* pb;
+    const NttStoreFix f = ntt_make_store_fix<false>(a, bc, g, pa, pb);
+    const NttPtmFix pf = ntt_make_ptm_fix(a, bc, g);
+#pragma unroll
+    for (int m0 = 0; m0 < 8; m0 += LSA_NTT_STORE_CHUNK) {
+        u64 v[2 * LSA_NTT_STORE_CHUNK], w[2 * LSA_NTT_STORE_CHUNK], c[2 * LSA_NTT_STORE_CHUNK];
+        long long xs[LSA_NTT_STORE_CHUNK];
+#pragma unroll
+        for (int m = 0; m < LSA_NTT_STORE_CHUNK; m++) {
+            int k, i;
+            r16_pair_pos<MU>(tid, m0 + m, k, i);
+            xs[m] = r16_x<1, MU>(a, bc.tile, k, i);
+            v[2 * m] = lds[r16_lds<1, MU>(k, i)];
+            v[2 * m + 1] = lds[r16_lds<1, MU>(k, i + 1)];
+            ntt_load_data_pair(pf.pt + xs[m], w[2 * m], w[2 * m + 1]);
+            c[2 * m] = c[2 * m + 1] = 0;
+            if (pf.acc) ntt_load_data_pair(pf.acc + xs[m], c[2 * m], c[2 * m + 1]);
+        }
+#pragma unroll
+        for (int m = 0; m < LSA_NTT_STORE_CHUNK; m++)
+            ntt_store_pair(g + xs[m], ntt_ptm_fix(pf, ntt_store_fix(f, v[2 * m], 0, 0), w[2 * m], c[2 * m]),
+                           ntt_ptm_fix(pf, ntt_store_fix(f, v[2 * m + 1], 0, 0), w[2 * m + 1], c[2 * m + 1]));
+    }
+}
+// PM: the pt_mul epilogue instead (FZ is false then)
+template <bool FZ, int MU, bool PM = false>
 LSA_HD void r16_store_coalesced(const NttPassArgs& a, const NttBlockCtx& bc, int tid, const u64* lds) {
+    if (PM) {
+        r16_store_coalesced_ptm<MU>(a, bc, tid, lds);
+        return;
+    }
     u64* g;
     const u64* pa;
     const u64* pb;
@@ -407,7 +441,7 @@ LSA_HD void r16_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64*
             r16_group<PASS, 1, MU>(v, a, bc, L, G2);
             r16_lds_put<PASS, 1, MU>(tid, lds, v);
         } else {
-            r16_store_coalesced<(FZ & 2) != 0, MU>(a, bc, tid, lds);
+            r16_store_coalesced<(FZ & 2) != 0, MU, (FZ & 4) != 0>(a, bc, tid, lds);
         }
         return;
     }
@@ -423,7 +457,7 @@ LSA_HD void r16_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64*
             if (PASS == 0) r16_store_direct<PASS, (FZ & 2) != 0, 1, MU>(a, bc, tid, v);
             else r16_lds_put<PASS, 1, MU>(tid, lds, v);
         } else if (PASS == 1) {
-            r16_store_coalesced<(FZ & 2) != 0, MU>(a, bc, tid, lds);
+            r16_store_coalesced<(FZ & 2) != 0, MU, (FZ & 4) != 0>(a, bc, tid, lds);
         }
     } else {
         if (phase == 0) {
@@ -517,7 +551,7 @@ LSA_HD void r8x3_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64
             r8x3_group<2>(v, a, bc, L, G1, i);
             r8x3_put<2>(k, i, lds, v);
         } else {
-            r16_store_coalesced<(FZ & 2) != 0, 9>(a, bc, tid, lds);
+            r16_store_coalesced<(FZ & 2) != 0, 9, (FZ & 4) != 0>(a, bc, tid, lds);
         }
     } else {
         if (phase == 0) {

@@ -800,6 +800,87 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
     });
 }
 
+// ---- BFV ct x pt_mul.  A pt_mul plaintext is the message lifted to Q, in the NTT domain and in Montgomery form (the
+// reference frontend's BfvPlaintextMulNode); per poly and limb ct x pt = INTT(NTT(ct) . pt . 2^-64 mod q), Lattigo v4's
+// mulPlaintextMul.  The Montgomery product rides on the store of the forward transform's last pass (fz_epi = 3, FZ bit 4);
+// LSA_PTMUL_FUSED=0 (read per call) runs the forward transform, k_mont_muladd and the inverse transform instead.  A MAC sums
+// its terms in the NTT domain (canonical residues: the same values as a per-term multiply and adds) and runs one inverse
+// transform per output; the partial sum is added after it, in the coefficient domain.
+static bool ptmul_fused_on() {
+    const char* e = std::getenv("LSA_PTMUL_FUSED");
+    return !(e && e[0] == '0');
+}
+static bool spans_apart(const u64* a, long long sa, size_t wa, const u64* b, long long sb, size_t wb, int batch) {
+    const u64* ea = a + (size_t)(batch - 1) * sa + wa;
+    const u64* eb = b + (size_t)(batch - 1) * sb + wb;
+    return ea <= b || eb <= a;
+}
+// out = NTT(ct) . pt . 2^-64 (+ out if acc) for nb ciphertexts; tmp receives the first pass of a two-pass transform (may be
+// out, or ct, when acc is false)
+static void ptmul_term(Context& c, int L, const u64* ct, long long sct, const u64* pt, long long spt, bool acc, u64* out,
+                       long long so, u64* tmp, long long stmp, int nb, hipStream_t s) {
+    const RowMap rm = rm_seq(L);
+    if (ptmul_fused_on()) {
+        NttFusion fz;
+        fz.epi = 3;
+        fz.limbs = L;
+        fz.a = pt;
+        fz.a_stride = spt;
+        fz.base = acc ? out : nullptr;
+        fz.base_stride = so;
+        fz.base_rpp = L;
+        fz.out = out;
+        fz.out_stride = so;
+        fz.out_rpp = L;
+        launch_ntt(c, ct, tmp, nb, sct, stmp, 2 * L, rm, false, s, &fz);
+        return;
+    }
+    launch_ntt(c, ct, tmp, nb, sct, stmp, 2 * L, rm, false, s);
+    launch_mont_muladd(c, tmp, stmp, pt, spt, acc ? out : nullptr, so, out, so, nb, 2, L, rm, s);
+}
+
+void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64* out, int batch, long long sct, long long spt,
+                        long long sout, hipStream_t s) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    if (batch <= 0) return;
+    const int L = level + 1;
+    const size_t wct = 2 * (size_t)L * c.n, wpt = (size_t)L * c.n;
+    LSA_REQUIRE((out == ct && sout == sct) || spans_apart(out, sout, wct, ct, sct, wct, batch),
+                "bfv_mult_plain_mul: out must be ct or not overlap it");
+    LSA_REQUIRE(spans_apart(out, sout, wct, pt, spt, wpt, batch), "bfv_mult_plain_mul: out overlaps the plaintexts");
+    ptmul_term(c, L, ct, sct, pt, spt, false, out, sout, out, sout, batch, s);
+    launch_ntt(c, out, out, batch, sout, 2 * L, rm_seq(L), true, s);
+}
+
+void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
+                       const long long* spts, const u64* partial, long long spartial, u64* out, int batch, long long sout,
+                       hipStream_t s) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    LSA_REQUIRE(n >= 1, "bfv_mac_plain_mul: needs at least one term");
+    if (batch <= 0) return;
+    const long long N = c.n;
+    const int L = level + 1;
+    const size_t wct = 2 * (size_t)L * N, wpt = (size_t)L * N;
+    // out holds the running sum while the terms are read: it may alias none of them
+    for (int i = 0; i < n; i++) {
+        LSA_REQUIRE(spans_apart(out, sout, wct, cts[i], scts[i], wct, batch), "bfv_mac_plain_mul: out overlaps a ciphertext");
+        LSA_REQUIRE(spans_apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_mac_plain_mul: out overlaps a plaintext");
+    }
+    LSA_REQUIRE(!partial || spans_apart(out, sout, wct, partial, spartial, wct, batch), "bfv_mac_plain_mul: out overlaps the partial sum");
+    // workspace: the first pass of terms 1.. (term 0 runs it in out)
+    for_tiles(c, n > 1 ? 2 * (size_t)L : 0, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+        u64* o = out + (size_t)b0 * sout;
+        for (int i = 0; i < n; i++)
+            ptmul_term(c, L, cts[i] + (size_t)b0 * scts[i], scts[i], pts[i] + (size_t)b0 * spts[i], spts[i], i > 0, o, sout,
+                       i == 0 ? o : ws, i == 0 ? sout : 2LL * L * N, nb, st);
+        launch_ntt(c, o, o, nb, sout, 2 * L, rm_seq(L), true, st);
+        if (partial)
+            launch_elementwise(c, EW_ADD, o, partial + (size_t)b0 * spartial, o, nb, sout, spartial, sout, 2 * L, rm_seq(L), st);
+    });
+}
+
 void bfv_rescale(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                  hipStream_t s) {
     for_tiles(c, rescale_ws_rows(level, polys), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {

@@ -253,7 +253,12 @@ void TaskGraph::validate_structure() const {
                 break;
             case OperationType::NEGATE: result(a.level, a.degree); break;
             case OperationType::MULTIPLY:
-                if (n == 2 && is_pt(c.input_nodes[1])) {
+                if (n == 2 && is_pt(c.input_nodes[0]) && is_ct(c.input_nodes[1])) {   // pt * ct: the ciphertext sets the shape
+                    const DatumNode::FheProperty& b = *c.input_nodes[1]->fhe_prop;
+                    if (!ringt(c.input_nodes[0]) && a.level != b.level)
+                        bad(c, "plaintext " + c.input_nodes[0]->id + " is at level " + std::to_string(a.level) + ", the ciphertext at " + std::to_string(b.level));
+                    result(b.level, b.degree);
+                } else if (n == 2 && is_pt(c.input_nodes[1])) {
                     plain_ok(c.input_nodes[1]);
                     result(a.level, a.degree);
                 } else {

@@ -294,6 +294,10 @@ thread_local ExecTls tls_exec;
 
 bool is_plain_node(const DatumNode* d) { return d->datum_type == TYPE_PLAINTEXT; }
 bool is_ringt_node(const DatumNode* d) { return d->fhe_prop && d->fhe_prop->p && d->fhe_prop->p->is_ringt; }
+// pt_mul: the message lifted to Q, NTT domain, Montgomery form (frontend BfvPlaintextMulNode / CkksPlaintextMulNode)
+bool is_ptmul_node(const DatumNode* d) {
+    return is_plain_node(d) && d->fhe_prop && d->fhe_prop->is_ntt && d->fhe_prop->is_mform && !is_ringt_node(d);
+}
 
 }  // namespace
 
@@ -313,9 +317,23 @@ void bind_gpu_executor(ComputeNode& node, Algo algorithm) {
         case OperationType::ADD:
         case OperationType::SUB: break;   // ct+-ct, ct+-pt, ct+-ring-t pt
         case OperationType::MULTIPLY:
+            if (node.input_nodes.size() == 2 && algorithm == ALGO_BFV) {
+                // BFV ct x pt_mul, the plaintext on either side (the reference's find_plaintext_node), at the ciphertext's level
+                const DatumNode *x = node.input_nodes[0], *y = node.input_nodes[1];
+                const DatumNode* pt = is_ptmul_node(y) && !is_plain_node(x) ? y : is_ptmul_node(x) && !is_plain_node(y) ? x : nullptr;
+                if (pt) {
+                    const DatumNode* ct = pt == y ? x : y;
+                    if (pt->fhe_prop->level != ct->fhe_prop->level)
+                        unsupported("pt_mul plaintext at level " + std::to_string(pt->fhe_prop->level) + ", the ciphertext at " +
+                                    std::to_string(ct->fhe_prop->level));
+                    break;
+                }
+            }
             if (node.input_nodes.size() == 2 && is_plain_node(node.input_nodes[1]) && !is_ringt_node(node.input_nodes[1]) &&
                 algorithm == ALGO_BFV)
                 throw std::runtime_error("Multiply with plaintext only supported for CKKS scheme");  // executors_gpu.cu:212
+            if (node.input_nodes.size() == 2 && is_plain_node(node.input_nodes[0]))
+                unsupported("plaintext as the first operand (BFV pt_mul only)");
             break;
         case OperationType::NEGATE:
         case OperationType::RELINEARIZE:
@@ -335,6 +353,18 @@ void bind_gpu_executor(ComputeNode& node, Algo algorithm) {
             const int n = node.fhe_prop->p->sum_cnt;
             const size_t pt0 = (size_t)n + (op == OperationType::MAC_W_PARTIAL_SUM ? 1 : 0);
             if (node.input_nodes.size() != pt0 + (size_t)n) unsupported("compressed plaintext blocks");
+            if (algorithm == ALGO_BFV) {   // pt_mul terms: all of them, at the ciphertexts' level
+                int ptmul = 0;
+                for (int i = 0; i < n; i++) ptmul += is_ptmul_node(node.input_nodes[pt0 + i]) ? 1 : 0;
+                if (ptmul > 0 && ptmul < n) unsupported("pt_mul and other plaintext flavours in one multiply-accumulate");
+                if (ptmul == n) {
+                    for (int i = 0; i < n; i++)
+                        if (node.input_nodes[pt0 + i]->fhe_prop->level != node.input_nodes[0]->fhe_prop->level)
+                            unsupported("pt_mul plaintext at level " + std::to_string(node.input_nodes[pt0 + i]->fhe_prop->level) +
+                                        ", the ciphertexts at " + std::to_string(node.input_nodes[0]->fhe_prop->level));
+                    break;
+                }
+            }
             if (algorithm == ALGO_BFV && !is_ringt_node(node.input_nodes[pt0]))
                 throw std::runtime_error("Multiply with plaintext only supported for CKKS scheme");  // executors_gpu.cu:349,405
             break;
@@ -985,20 +1015,24 @@ struct fhe_task_handle_st {
         const ComputeNode* n0 = nodes[0];
         const OperationType op = n0->op();
         const int m = (int)nodes.size();
-        const DatumNode* in0 = n0->input_nodes[0];
+        // BFV ct x pt_mul may name the plaintext first (bind_gpu_executor): the ciphertext sets the shapes
+        const bool ptmul_first = g.algo == ALGO_BFV && op == OperationType::MULTIPLY && n0->input_nodes.size() == 2 &&
+                                 is_ptmul_node(n0->input_nodes[0]);
+        const DatumNode* in0 = n0->input_nodes[ptmul_first ? 1 : 0];
         const int lvl = in0->fhe_prop->level, L = lvl + 1;
         const int polys_in = in0->fhe_prop->degree + 1;
         const int out_lvl = n0->output_nodes[0]->fhe_prop->level;
         const bool bfv = g.algo == ALGO_BFV;
         const size_t w_in = (size_t)polys_in * L * N;
         int out_polys = polys_in;
-        if (op == OperationType::MULTIPLY && !(n0->input_nodes.size() == 2 && is_plain_node(n0->input_nodes[1]))) out_polys = 3;
+        if (op == OperationType::MULTIPLY && !(n0->input_nodes.size() == 2 && (is_plain_node(n0->input_nodes[1]) || ptmul_first)))
+            out_polys = 3;
         if (op == OperationType::RELINEARIZE || op == OperationType::FUSED_MULT_RELIN_RESCALE) out_polys = 2;
         const size_t w_out = (size_t)out_polys * (out_lvl + 1) * N;
         auto out_slab = dslab(w_out * m);
         u64* out = out_slab->ptr;
         const long long so = (long long)w_out;
-        Operand a = gather(c, s, nodes, 0, avail, w_in);
+        Operand a = gather(c, s, nodes, ptmul_first ? 1 : 0, avail, w_in);
         RowMap rmL;
         rmL.period = L;
         for (int i = 0; i < L; i++) rmL.mod_of[i] = (unsigned char)i;
@@ -1047,6 +1081,11 @@ struct fhe_task_handle_st {
                 launch_elementwise(c, EW_NEG, a.ptr, nullptr, out, m, a.stride, 0, so, polys_in * L, rmL, s);
                 break;
             case OperationType::MULTIPLY: {
+                if (bfv && n0->input_nodes.size() == 2 && (ptmul_first || is_ptmul_node(n0->input_nodes[1]))) {   // ct x pt_mul
+                    Operand b = gather(c, s, nodes, ptmul_first ? 0 : 1, avail, (size_t)L * N);
+                    bfv_mult_plain_mul(c, lvl, a.ptr, b.ptr, out, m, a.stride, b.stride, so, s);
+                    break;
+                }
                 if (n0->input_nodes.size() == 2 && is_plain_node(n0->input_nodes[1])) {
                     if (!bfv) {  // CKKS ct * pt, both NTT domain (ring-t: centred lift + NTT first)
                         Operand b = plain_operand(1, 0, true);
@@ -1156,6 +1195,22 @@ struct fhe_task_handle_st {
                         const u64* acc = i0 == 0 ? part.ptr : out;
                         launch_mac_plain(c, cnt, cp, cs_, pp, ps_, acc, i0 == 0 ? part.stride : so, out, so, m, polys_in, L, rmL, s);
                     }
+                    break;
+                }
+                if (is_ptmul_node(n0->input_nodes[pt0])) {   // BFV pt_mul terms (bind_gpu_executor: all of them)
+                    std::vector<const u64*> cp(n), pp(n);
+                    std::vector<long long> cs_(n), ps_(n);
+                    for (int i = 0; i < n; i++) {
+                        Operand ci = i == 0 ? a : gather(c, s, nodes, i, avail, w_in);
+                        Operand pi = gather(c, s, nodes, pt0 + i, avail, (size_t)L * N);
+                        cp[i] = ci.ptr;
+                        cs_[i] = ci.stride;
+                        pp[i] = pi.ptr;
+                        ps_[i] = pi.stride;
+                    }
+                    Operand part{nullptr, 0, nullptr};
+                    if (with_partial) part = gather(c, s, nodes, n, avail, w_in);
+                    bfv_mac_plain_mul(c, lvl, n, cp.data(), cs_.data(), pp.data(), ps_.data(), part.ptr, part.stride, out, m, so, s);
                     break;
                 }
                 u64* tmp = temp((size_t)m * w_in);

@@ -207,6 +207,30 @@ class DeviceContext:
                                         self.stream))
         return outs
 
+    def bfv_mult_plain_mul(self, level, ct, pt, batch, out=None, spt=None):
+        """ct [batch][2][L][N] x pt_mul plaintexts [batch][L][N] (NTT domain, Montgomery form); out=ct multiplies in place;
+        spt: the plaintexts' batch stride in words (0: one plaintext for the whole batch)"""
+        L = level + 1
+        if out is None:
+            out = self.alloc(batch * 2 * L * self.n)
+        check(lib().lsa_bfv_mult_plain_mul(self.h, level, ct.ptr, pt.ptr, out.ptr, batch, 2 * L * self.n,
+                                           L * self.n if spt is None else spt, 2 * L * self.n, self.stream))
+        return out
+
+    def bfv_mac_plain_mul(self, level, cts, pts, batch, partial=None):
+        """sum_i cts[i] x pts[i] (+ partial): lists of device buffers, [batch][2][L][N] / [batch][L][N]"""
+        L = level + 1
+        n = len(cts)
+        assert n == len(pts) and n >= 1
+        out = self.alloc(batch * 2 * L * self.n)
+        pc = (ctypes.c_void_p * n)(*[c.ptr for c in cts])
+        sc = (ctypes.c_longlong * n)(*([2 * L * self.n] * n))
+        pp = (ctypes.c_void_p * n)(*[p.ptr for p in pts])
+        sp = (ctypes.c_longlong * n)(*([L * self.n] * n))
+        check(lib().lsa_bfv_mac_plain_mul(self.h, level, n, pc, sc, pp, sp, partial.ptr if partial is not None else None,
+                                          2 * L * self.n, out.ptr, batch, 2 * L * self.n, self.stream))
+        return out
+
     def bfv_rescale(self, level, polys, ct, batch):
         L = level + 1
         out = self.alloc(batch * polys * level * self.n)
