@@ -120,6 +120,16 @@ int lsa_bfv_mult_plain_mul(lsa_context ctx, int level, const uint64_t* ct, const
 int lsa_bfv_mac_plain_mul(lsa_context ctx, int level, int n, const uint64_t* const* cts, const long long* scts,
                           const uint64_t* const* pts, const long long* spts, const uint64_t* partial, long long spartial,
                           uint64_t* out, int batch, long long sout, void* stream);
+/* Hoisted rotate-and-MAC, the diagonal (Halevi-Shoup) matrix-vector product:
+ *   out = sum_{i<n} rotate(in, galois_elements[i]) x pts[i] (+ partial when not null),  n >= 1.
+ * galois_elements[i] == 1 is the input itself and takes no key (glk[i] may be null); 2N-1 is the row rotation; every other
+ * element needs its Galois key; elements may repeat.  pts[i]: pt_mul plaintexts as for lsa_bfv_mult_plain_mul, batch stride
+ * spts[i] (0: one plaintext for the whole batch).  Bit-identical to lsa_bfv_rotate_many followed by lsa_bfv_mac_plain_mul
+ * on the same terms.  The input is transformed and decomposed once; the rotations stay in the NTT domain and the rotated
+ * ciphertexts are never written.  out may overlap no input.  LSA_ROTMAC_FUSED=0 (read per call) selects the two-step form. */
+int lsa_bfv_rotate_mac_plain_mul(lsa_context ctx, int level, const uint64_t* in, int n, const uint64_t* galois_elements,
+                                 const lsa_key* glk, const uint64_t* const* pts, const long long* spts, const uint64_t* partial,
+                                 long long spartial, uint64_t* out, int batch, long long sin, long long sout, void* stream);
 int lsa_bfv_rescale(lsa_context ctx, int level, int polys, const uint64_t* in, uint64_t* out, int batch,
                     long long stride_in, long long stride_out, void* stream);
 int lsa_bfv_mult_relin(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, lsa_key rlk,

@@ -86,6 +86,8 @@ SIGNATURES = {
     "lsa_bfv_mult_plain_mul": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_ll, c_vp]),
     "lsa_bfv_mac_plain_mul": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_vp),
                                       ctypes.POINTER(c_ll), c_vp, c_ll, c_vp, c_int, c_ll, c_vp]),
+    "lsa_bfv_rotate_mac_plain_mul": (c_int, [c_vp, c_int, c_vp, c_int, c_u64p, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                             ctypes.POINTER(c_ll), c_vp, c_ll, c_vp, c_int, c_ll, c_ll, c_vp]),
     "lsa_bootstrap_create": (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
                                      c_vp, ctypes.POINTER(c_vp)]),
     "lsa_bootstrap_create_ex": (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,

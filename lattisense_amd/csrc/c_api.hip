@@ -416,6 +416,18 @@ int lsa_bfv_mac_plain_mul(lsa_context ctx, int level, int n, const uint64_t* con
         bfv_mac_plain_mul(C(ctx), level, n, cts, scts, pts, spts, partial, spartial, out, batch, sout, S(stream));
     });
 }
+int lsa_bfv_rotate_mac_plain_mul(lsa_context ctx, int level, const uint64_t* in, int n, const uint64_t* galois_elements,
+                                 const lsa_key* glk, const uint64_t* const* pts, const long long* spts, const uint64_t* partial,
+                                 long long spartial, uint64_t* out, int batch, long long sin, long long sout, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(n >= 1, "bfv_rotate_mac_plain_mul: needs at least one term");
+        LSA_REQUIRE(in && galois_elements && glk && pts && spts && out, "null argument");
+        std::vector<const Key*> keys(n, nullptr);
+        for (int i = 0; i < n; i++) keys[i] = glk[i] ? &K(glk[i]) : nullptr;
+        bfv_rotate_mac_plain_mul(C(ctx), level, in, n, galois_elements, keys.data(), pts, spts, partial, spartial, out, batch, sin,
+                                 sout, S(stream));
+    });
+}
 
 // ---- CKKS bootstrapping
 struct lsa_bootstrap_st {

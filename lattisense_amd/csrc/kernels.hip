@@ -61,8 +61,8 @@ __device__ __forceinline__ void ntt_butterfly_phases(const NttPassArgs& a, const
 // TWL: the pass holds global stage 0 (strided first pass of a two-pass plan): its 2^mu twiddles are the same for every tile
 // of the limb and go through LDS -- one fetch per workgroup, issued with the tile loads, instead of one per sub-pass.
 // FZ: 0 plain, 1 fused prologue only (first pass of a two-pass fused transform), 2 fused epilogue only (its last pass), 3 both
-// (single-pass transforms), 4 the pt_mul epilogue (fz_epi == 3) only.  Split so that a pass carries only the tail code and
-// registers it can execute.
+// (single-pass transforms), 4 the pt_mul epilogue (fz_epi == 3) only, 8 the rotate-and-MAC epilogue (fz_epi == 4) only.  Split
+// so that a pass carries only the tail code and registers it can execute.
 template <int FZ, int NT, bool TWL = false>
 __global__ __launch_bounds__(NT, NT > 512 ? 1 : NT > 256 ? 2 : (FZ & 1) ? LSA_NTT_WAVES_FUSED : LSA_NTT_WAVES) void k_ntt_pass(NttPassArgs a) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
@@ -108,11 +108,11 @@ __global__ __launch_bounds__(NT, NT > 512 ? 1 : NT > 256 ? 2 : (FZ & 1) ? LSA_NT
     __syncthreads();
     LSA_STAMP(2);
 #if defined(LSA_NTT_DIAG_COPY_ONLY)   // diagnostic build: data movement of the pass structure without butterflies
-    ntt_phase_store<(FZ & 2) != 0, NT, (FZ & 4) != 0>(a, bc, tid, lds);
+    ntt_phase_store<(FZ & 2) != 0, NT, (FZ & 4) != 0, (FZ & 8) != 0>(a, bc, tid, lds);
     return;
 #endif
     ntt_butterfly_phases<NT, TWL>(a, bc, tid, lds);
-    ntt_phase_store<(FZ & 2) != 0, NT, (FZ & 4) != 0>(a, bc, tid, lds);
+    ntt_phase_store<(FZ & 2) != 0, NT, (FZ & 4) != 0, (FZ & 8) != 0>(a, bc, tid, lds);
     LSA_STAMP(7);
 }
 
@@ -186,6 +186,20 @@ static bool ntt_launch_r16(const NttPassArgs& a, int npass, bool fused, long lon
             hipLaunchKernelGGL((k_ntt_r16<1, 4, 8>), grid, block, lds_bytes, s, a);
         } else {
             hipLaunchKernelGGL((k_ntt_r16<1, 4, 7>), grid, block, lds_bytes, s, a);
+        }
+        LSA_HIP(hipGetLastError());
+        return true;
+    }
+    if (epi && a.fz_epi == 4) {   // the rotate-and-MAC epilogue (FZ bit 8): likewise second passes only
+        if (a.lambda) return false;
+        if (a.mu == 9) {
+            const char* e = getenv("LSA_NTT_R8X3");
+            if (e && e[0] == '0') return false;
+            hipLaunchKernelGGL((k_ntt_r8x3<8>), grid, block, lds_bytes, s, a);
+        } else if (a.mu == 8) {
+            hipLaunchKernelGGL((k_ntt_r16<1, 8, 8>), grid, block, lds_bytes, s, a);
+        } else {
+            hipLaunchKernelGGL((k_ntt_r16<1, 8, 7>), grid, block, lds_bytes, s, a);
         }
         LSA_HIP(hipGetLastError());
         return true;
@@ -429,6 +443,10 @@ static void ntt_launch_pass(const NttPassArgs& a, bool fused, long long nblocks,
         ntt_launch_variant<4, NT>(a, nblocks, lds_bytes, s);
         return;
     }
+    if (epi && a.fz_epi == 4) {   // the rotate-and-MAC epilogue (FZ bit 8, no prologue)
+        ntt_launch_variant<8, NT>(a, nblocks, lds_bytes, s);
+        return;
+    }
     switch ((pro ? 1 : 0) | (epi ? 2 : 0)) {
         case 0: ntt_launch_variant<0, NT>(a, nblocks, lds_bytes, s); break;
         case 1: ntt_launch_variant<1, NT>(a, nblocks, lds_bytes, s); break;
@@ -479,6 +497,12 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
         LSA_REQUIRE(fz->epi != 2 || fz->k2, "merged tail needs its second factor");
         LSA_REQUIRE(!fz->scatter || fz->epi, "a scattered store needs an epilogue");
         LSA_REQUIRE(fz->epi != 3 || (!fz->pro && !fz->scatter && fz->a && fz->out), "pt_mul epilogue: plaintext and output, nothing else");
+        LSA_REQUIRE(fz->epi != 4 || (!fz->pro && !fz->k2 && fz->scatter && fz->a && fz->k && fz->out && fz->pt),
+                    "rotate-and-MAC epilogue: ModDown operands, index map, plaintext and output");
+        LSA_REQUIRE(fz->epi != 4 || (fz->base_polys <= 1 && fz->limbs == rm.period), "rotate-and-MAC epilogue: base on poly 0, one row per limb");
+        a.fz_pt = fz->pt;
+        a.fz_pt_stride = fz->pt_stride;
+        a.fz_accum = fz->accumulate ? 1 : 0;
     }
     a.period = rm.period;
     a.row0 = rm.row0;
@@ -544,6 +568,12 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
         if (fz && fz->epi == 3) {   // the pt_mul epilogue's operands follow the chunk (block batch indices restart at 0)
             a.fz_a = fz->a + (long long)b0 * fz->a_stride;
             a.fz_base = fz->base ? fz->base + (long long)b0 * fz->base_stride : nullptr;
+            a.fz_out = fz->out + (long long)b0 * fz->out_stride;
+        }
+        if (fz && fz->epi == 4) {   // so do the rotate-and-MAC epilogue's
+            a.fz_a = fz->a + (long long)b0 * fz->a_stride;
+            a.fz_base = fz->base ? fz->base + (long long)b0 * fz->base_stride : nullptr;
+            a.fz_pt = fz->pt + (long long)b0 * fz->pt_stride;
             a.fz_out = fz->out + (long long)b0 * fz->out_stride;
         }
         for (int step = 0; step < plan.npass; step++) {

@@ -231,6 +231,10 @@ struct NttFusion {
     int last_rpp = 1;            // rows between the polynomials' last limbs in `last`
     const u64* k2 = nullptr;     // epi == 2: out = (a*k - v + base) * k2
     const u32* scatter = nullptr;   // epilogue only: out[scatter[x]] = value(x) within each row (the automorphism of a rotation)
+    // epi == 4 (BFV rotate-and-MAC): out[scatter[x]] (+)= ((a - v) * k + base)(x) * pt[scatter[x]] * 2^-64, base on poly 0
+    const u64* pt = nullptr;        // pt_mul plaintexts [batch][limbs][N]
+    long long pt_stride = 0;
+    bool accumulate = false;        // add to out (later terms) instead of writing it (the first)
 };
 // passes: bit 0 = the first executed pass, bit 1 = the second (two-pass plans; a caller that fuses the second pass into
 // another kernel asks for 1 only)
@@ -262,6 +266,11 @@ void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64
 void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
                        const long long* spts, const u64* partial, long long spartial, u64* out, int batch, long long sout,
                        hipStream_t s);
+// out = sum_{i<n} rot_{g[i]}(in) . pts[i] (+ partial), g[i] == 1: the input itself (no key); every output bit-identical to
+// bfv_rotate_many + bfv_mac_plain_mul on the same terms, rotations kept in the NTT domain (fz_epi = 4); out overlaps no input
+void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const u64* g, const Key* const* glk,
+                              const u64* const* pts, const long long* spts, const u64* partial, long long spartial, u64* out,
+                              int batch, long long sin, long long sout, hipStream_t s);
 // ring-t plaintext limb -> [level+1][N] residues: mode 0 centred lift from q_0 (CKKS), 1 direct (BFV multiply),
 // 2 scale-up by Q/t (BFV add/sub)
 void launch_lift_ringt(Context& c, int mode, int level, const u64* pt, long long spt, u64* out, long long sout, int batch,

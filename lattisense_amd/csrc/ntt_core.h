@@ -95,6 +95,9 @@ struct NttPassArgs {
     //   fz_epi = 2:  out = (fz_a * fz_k - v + fz_base) * fz_k2   (its tail: (acc*P^-1 - NTT(in) + base) * q_l^-1)
     //   fz_epi = 3:  out[poly][limb] = v * fz_a[limb] * 2^-64 (+ fz_base[poly][limb] if fz_base)   (BFV ct x pt_mul: the
     //                Montgomery-form plaintext, shared by both polys; kernels compiled with FZ bit 4, ntt_phase_store_ptm)
+    //   fz_epi = 4:  w = the fz_epi = 1 value (the NTT-domain ModDown tail), then through the rotation's index map
+    //                y = fz_scatter[x]: out[poly][limb][y] = (fz_accum ? out[..][y] : 0) + w * fz_pt[limb][y] * 2^-64
+    //                (BFV rotate-and-MAC: one rotated term of sum_i rot_i(ct) . pt_i; FZ bit 8, ntt_phase_store_rmac)
     int fz_epi, fz_pro, fz_limbs, fz_base_polys, fz_ql_mod;
     int fz_a_rpp, fz_base_rpp, fz_out_rpp, fz_last_rpp;
     const u64* fz_a;
@@ -109,6 +112,10 @@ struct NttPassArgs {
     long long fz_a_stride, fz_base_stride, fz_out_stride, fz_last_stride;
     unsigned long long* diag;   // diagnostic builds (LSA_NTT_DIAG_STAMPS): per-workgroup phase time stamps, else unused
     unsigned char mod_of[LSA_MAX_PERIOD];
+    // fz_epi = 4 only (after every other field, so the kernels without it see the layout they always had)
+    const u64* fz_pt;         // the term's pt_mul plaintexts [batch][fz_limbs][N] (batch stride fz_pt_stride)
+    long long fz_pt_stride;
+    int fz_accum;             // 0: the first term writes out, 1: later terms add to it
 };
 
 LSA_HD int lds_addr(int l) { return l + (l >> 4); }
@@ -613,11 +620,95 @@ LSA_HD void ntt_phase_store_ptm(const NttPassArgs& a, const NttBlockCtx& bc, int
                        ntt_ptm_fix(pf, ntt_store_fix(f, lds[lds_addr(2 * i + 1)], 0, 0), pf.pt[x + 1], c1));
     }
 }
-// PM: the pt_mul epilogue instead of the plain store (FZ is false then)
-template <bool FZ, int NT, bool PM = false>
+// ---- the rotate-and-MAC epilogue (fz_epi == 4): the ModDown tail of fz_epi == 1 gives w in [0, q) (ntt_store_fix, both
+// engines), then the term goes through the rotation's index map y = fz_scatter[x]: out[y] = (accum ? out[y] : 0) +
+// mont_mul(w, pt[y]).  The map is a permutation, so within one launch no two threads touch the same y; terms run in order
+// on one stream.  The reads of pt and out follow the map (gathers), the stores scatter as the fz_epi == 1 store does.
+struct NttRmacFix {
+    const u64* pt;
+    u64 q, qinv;
+    bool accum;
+};
+LSA_HD NttRmacFix ntt_make_rmac_fix(const NttPassArgs& a, const NttBlockCtx& bc) {
+    const ModDev md = a.mods[bc.mod];
+    NttRmacFix p;
+    p.q = md.q;
+    p.qinv = md.qinv;
+    p.accum = a.fz_accum != 0;
+    p.pt = a.fz_pt + (long long)bc.b * a.fz_pt_stride + ((long long)(bc.row % a.fz_limbs) << a.logn);
+    return p;
+}
+// the results w[2j], w[2j+1] of the point pairs xs[j], xs[j] + 1 (xs even: one 8-byte load of two map entries): all
+// gathers first, then the products and the scattered stores
+template <int C>
+LSA_HD void ntt_rmac_put(const NttRmacFix& p, const unsigned* scatter, u64* g, const long long (&xs)[C], const u64 (&w)[2 * C]) {
+    unsigned ys[2 * C];
+    u64 pv[2 * C], ov[2 * C];
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+        const unsigned long long yy = *reinterpret_cast<const unsigned long long*>(scatter + xs[j]);
+        ys[2 * j] = (unsigned)yy;
+        ys[2 * j + 1] = (unsigned)(yy >> 32);
+    }
+#pragma unroll
+    for (int j = 0; j < 2 * C; j++) {
+        pv[j] = p.pt[ys[j]];
+        ov[j] = p.accum ? g[ys[j]] : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < 2 * C; j++) {
+        const u64 r = mont_mul(w[j], pv[j], p.q, p.qinv);
+        g[ys[j]] = p.accum ? add_mod(r, ov[j], p.q) : r;
+    }
+}
+template <int NT>
+LSA_HD void ntt_phase_store_rmac(const NttPassArgs& a, const NttBlockCtx& bc, int tid, const u64* lds) {
+    u64* g;
+    const u64* pa;
+    const u64* pb;
+    const int half = 1 << (a.tau - 1);
+    const NttStoreFix f = ntt_make_store_fix<true>(a, bc, g, pa, pb);
+    const NttRmacFix rf = ntt_make_rmac_fix(a, bc);
+    const NttTileMap tm = ntt_tile_map(a, bc.tile);
+    if (half == LSA_NTT_STAGE_PAIRS * NT) {
+        for (int p0 = 0; p0 < LSA_NTT_STAGE_PAIRS; p0 += LSA_NTT_STORE_CHUNK) {
+            u64 v[2 * LSA_NTT_STORE_CHUNK], va[2 * LSA_NTT_STORE_CHUNK], vb[2 * LSA_NTT_STORE_CHUNK];
+            long long xs[LSA_NTT_STORE_CHUNK];
+#pragma unroll
+            for (int p = 0; p < LSA_NTT_STORE_CHUNK; p++) {
+                const int l = 2 * (tid + (p0 + p) * NT);
+                const int x = ntt_tile_index(tm, l);
+                xs[p] = x;
+                v[2 * p] = lds[lds_addr(l)];
+                v[2 * p + 1] = lds[lds_addr(l + 1)];
+                ntt_load_data_pair(pa + x, va[2 * p], va[2 * p + 1]);
+                vb[2 * p] = vb[2 * p + 1] = 0;
+                if (f.with_base) ntt_load_data_pair(pb + x, vb[2 * p], vb[2 * p + 1]);
+            }
+            u64 w[2 * LSA_NTT_STORE_CHUNK];
+#pragma unroll
+            for (int j = 0; j < 2 * LSA_NTT_STORE_CHUNK; j++) w[j] = ntt_store_fix(f, v[j], va[j], vb[j]);
+            ntt_rmac_put(rf, a.fz_scatter, g, xs, w);
+        }
+        return;
+    }
+    for (int i = tid; i < half; i += NT) {   // partial tiles (small rings)
+        const int x = ntt_tile_index(tm, 2 * i);
+        const long long xs[1] = {x};
+        const u64 b0 = f.with_base ? pb[x] : 0, b1 = f.with_base ? pb[x + 1] : 0;
+        const u64 w[2] = {ntt_store_fix(f, lds[lds_addr(2 * i)], pa[x], b0), ntt_store_fix(f, lds[lds_addr(2 * i + 1)], pa[x + 1], b1)};
+        ntt_rmac_put(rf, a.fz_scatter, g, xs, w);
+    }
+}
+// PM: the pt_mul epilogue instead of the plain store, RM: the rotate-and-MAC epilogue (FZ is false with either)
+template <bool FZ, int NT, bool PM = false, bool RM = false>
 LSA_HD void ntt_phase_store(const NttPassArgs& a, const NttBlockCtx& bc, int tid, const u64* lds) {
     if (PM) {
         ntt_phase_store_ptm<NT>(a, bc, tid, lds);
+        return;
+    }
+    if (RM) {
+        ntt_phase_store_rmac<NT>(a, bc, tid, lds);
         return;
     }
     u64* g;

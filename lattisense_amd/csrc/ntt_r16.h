@@ -313,11 +313,45 @@ LSA_HD void r16_store_coalesced_ptm(const NttPassArgs& a, const NttBlockCtx& bc,
                            ntt_ptm_fix(pf, ntt_store_fix(f, v[2 * m + 1], 0, 0), w[2 * m + 1], c[2 * m + 1]));
     }
 }
-// PM: the pt_mul epilogue instead (FZ is false then)
-template <bool FZ, int MU, bool PM = false>
+// the rotate-and-MAC epilogue (fz_epi == 4, ntt_core.h ntt_phase_store_rmac) on the same positions
+template <int MU>
+LSA_HD void r16_store_coalesced_rmac(const NttPassArgs& a, const NttBlockCtx& bc, int tid, const u64* lds) {
+    u64* g;
+    const u64* pa;
+    const u64* pb;
+    const NttStoreFix f = ntt_make_store_fix<true>(a, bc, g, pa, pb);
+    const NttRmacFix rf = ntt_make_rmac_fix(a, bc);
+#pragma unroll
+    for (int m0 = 0; m0 < 8; m0 += LSA_NTT_STORE_CHUNK) {
+        u64 v[2 * LSA_NTT_STORE_CHUNK], va[2 * LSA_NTT_STORE_CHUNK], vb[2 * LSA_NTT_STORE_CHUNK];
+        long long xs[LSA_NTT_STORE_CHUNK];
+#pragma unroll
+        for (int m = 0; m < LSA_NTT_STORE_CHUNK; m++) {
+            int k, i;
+            r16_pair_pos<MU>(tid, m0 + m, k, i);
+            const long long x = r16_x<1, MU>(a, bc.tile, k, i);
+            xs[m] = x;
+            v[2 * m] = lds[r16_lds<1, MU>(k, i)];
+            v[2 * m + 1] = lds[r16_lds<1, MU>(k, i + 1)];
+            ntt_load_data_pair(pa + x, va[2 * m], va[2 * m + 1]);
+            vb[2 * m] = vb[2 * m + 1] = 0;
+            if (f.with_base) ntt_load_data_pair(pb + x, vb[2 * m], vb[2 * m + 1]);
+        }
+        u64 w[2 * LSA_NTT_STORE_CHUNK];
+#pragma unroll
+        for (int j = 0; j < 2 * LSA_NTT_STORE_CHUNK; j++) w[j] = ntt_store_fix(f, v[j], va[j], vb[j]);
+        ntt_rmac_put(rf, a.fz_scatter, g, xs, w);
+    }
+}
+// PM: the pt_mul epilogue instead, RM: the rotate-and-MAC epilogue (FZ is false with either)
+template <bool FZ, int MU, bool PM = false, bool RM = false>
 LSA_HD void r16_store_coalesced(const NttPassArgs& a, const NttBlockCtx& bc, int tid, const u64* lds) {
     if (PM) {
         r16_store_coalesced_ptm<MU>(a, bc, tid, lds);
+        return;
+    }
+    if (RM) {
+        r16_store_coalesced_rmac<MU>(a, bc, tid, lds);
         return;
     }
     u64* g;
@@ -441,7 +475,7 @@ LSA_HD void r16_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64*
             r16_group<PASS, 1, MU>(v, a, bc, L, G2);
             r16_lds_put<PASS, 1, MU>(tid, lds, v);
         } else {
-            r16_store_coalesced<(FZ & 2) != 0, MU, (FZ & 4) != 0>(a, bc, tid, lds);
+            r16_store_coalesced<(FZ & 2) != 0, MU, (FZ & 4) != 0, (FZ & 8) != 0>(a, bc, tid, lds);
         }
         return;
     }
@@ -457,7 +491,7 @@ LSA_HD void r16_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64*
             if (PASS == 0) r16_store_direct<PASS, (FZ & 2) != 0, 1, MU>(a, bc, tid, v);
             else r16_lds_put<PASS, 1, MU>(tid, lds, v);
         } else if (PASS == 1) {
-            r16_store_coalesced<(FZ & 2) != 0, MU, (FZ & 4) != 0>(a, bc, tid, lds);
+            r16_store_coalesced<(FZ & 2) != 0, MU, (FZ & 4) != 0, (FZ & 8) != 0>(a, bc, tid, lds);
         }
     } else {
         if (phase == 0) {
@@ -551,7 +585,7 @@ LSA_HD void r8x3_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64
             r8x3_group<2>(v, a, bc, L, G1, i);
             r8x3_put<2>(k, i, lds, v);
         } else {
-            r16_store_coalesced<(FZ & 2) != 0, 9, (FZ & 4) != 0>(a, bc, tid, lds);
+            r16_store_coalesced<(FZ & 2) != 0, 9, (FZ & 4) != 0, (FZ & 8) != 0>(a, bc, tid, lds);
         }
     } else {
         if (phase == 0) {

@@ -153,9 +153,14 @@ static void ks_mac(Context& c, int level, const u64* cx, long long scx, const Ke
     }
 }
 
+struct RotMacTerm {   // the pt_mul factor of one rotate-and-MAC term (fz_epi = 4): p[scatter[x]] (+)= value(x) * pt[scatter[x]]
+    const u64* pt;
+    long long spt;
+    bool accumulate;
+};
 static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, u64* p, long long sp, const u64* base,
                        long long sbase, int base_rpp, int base_polys, int nb, hipStream_t s, const KsRescale* rs, bool coeff_out,
-                       const u32* scatter = nullptr, const u32* coeff_gather = nullptr);
+                       const u32* scatter = nullptr, const u32* coeff_gather = nullptr, const RotMacTerm* rmac = nullptr);
 
 // steps 4-5 of a key switch on the digits that ks_decompose left in the workspace: they depend on the key, the decomposition
 // does not -- rotations of ONE ciphertext by several Galois elements share it ("hoisting"; with the automorphism applied
@@ -174,10 +179,13 @@ static void ks_finish(Context& c, int level, const u64* cx, long long scx, const
 // NTT-domain automorphism of a rotation applied by the last pass's store instead of a permutation kernel afterwards.
 // coeff_gather (coeff_out only): the coefficient-domain automorphism of a BFV rotation, Context::coeff_perm(g), applied by
 // the tail's loads (k_sub_mul_perm): p[row][x] = sign_x * value(pi_x)
+// rmac (with scatter): the scattered result is multiplied by a pt_mul plaintext and written or added to p instead
+// (p[row][y] (+)= value * pt[limb][y] * 2^-64, y = scatter[x]): one term of a BFV rotate-and-MAC
 static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, u64* p, long long sp, const u64* base,
                        long long sbase, int base_rpp, int base_polys, int nb, hipStream_t s, const KsRescale* rs, bool coeff_out,
-                       const u32* scatter, const u32* coeff_gather) {
+                       const u32* scatter, const u32* coeff_gather, const RotMacTerm* rmac) {
     LSA_REQUIRE(!scatter || (c.fuse_tails && !rs && !coeff_out), "scattered ModDown store: fused tails, no rescale, NTT-domain output");
+    LSA_REQUIRE(!rmac || scatter, "rotate-and-MAC tail: needs the rotation's index map");
     LSA_REQUIRE(!coeff_gather || (coeff_out && !rs), "gathered ModDown tail: coefficient-domain output, no rescale");
     const long long N = c.n;
     const int L = level + 1, np = c.np, T = L + np;
@@ -278,6 +286,12 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
         fz.out_stride = sp;
         fz.out_rpp = L;
         fz.scatter = scatter;
+        if (rmac) {
+            fz.epi = 4;
+            fz.pt = rmac->pt;
+            fz.pt_stride = rmac->spt;
+            fz.accumulate = rmac->accumulate;
+        }
         launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rm_seq(L), false, s, &fz);
     } else {
         launch_ntt(c, conv, conv, nb, s_conv, 2 * L, rm_seq(L), false, s);
@@ -875,6 +889,96 @@ void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, cons
         for (int i = 0; i < n; i++)
             ptmul_term(c, L, cts[i] + (size_t)b0 * scts[i], scts[i], pts[i] + (size_t)b0 * spts[i], spts[i], i > 0, o, sout,
                        i == 0 ? o : ws, i == 0 ? sout : 2LL * L * N, nb, st);
+        launch_ntt(c, o, o, nb, sout, 2 * L, rm_seq(L), true, st);
+        if (partial)
+            launch_elementwise(c, EW_ADD, o, partial + (size_t)b0 * spartial, o, nb, sout, spartial, sout, 2 * L, rm_seq(L), st);
+    });
+}
+
+// ---- BFV rotate-and-MAC: out = sum_i rot_{g_i}(in) . pt_i (+ partial), the diagonal (Halevi-Shoup) matrix-vector product.
+// Every output is bit-identical to bfv_rotate_many followed by bfv_mac_plain_mul on the same terms: the rotations never
+// leave the NTT domain.  NTT(ModDown_coeff(x)) is the NTT-domain ModDown of NTT(x), residue for residue, and the NTT-domain
+// automorphism is the scatter map of the ModDown store, so per rotation term only the 2k P rows of the key-switch
+// accumulator are inverse-transformed and the 2L rows of its conversion forward-transformed (2(L+k) + 2L before); the
+// rotated ciphertext is never written.  Per tile: NTT(c0) and NTT(c1) once, one decomposition; identity terms (g = 1) are
+// a Montgomery product of NTT(ct); a rotation term is its key MAC and a ModDown whose last store applies the automorphism,
+// the pt_mul product and the running sum (fz_epi = 4).  One inverse transform per output, then the partial sum.
+// LSA_ROTMAC_FUSED=0 (read per call), unfused tails and LSA_ROT_SCATTER=0 run each rotation term in two steps instead:
+// the NTT-domain ModDown into the workspace (scattered, or k_permute after it), then k_mont_muladd.
+static bool rotmac_fused_on() {
+    const char* e = std::getenv("LSA_ROTMAC_FUSED");
+    return !(e && e[0] == '0');
+}
+
+void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const u64* g, const Key* const* glk,
+                              const u64* const* pts, const long long* spts, const u64* partial, long long spartial, u64* out,
+                              int batch, long long sin, long long sout, hipStream_t s) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    LSA_REQUIRE(n >= 1, "bfv_rotate_mac_plain_mul: needs at least one term");
+    bool any_rot = false;
+    for (int i = 0; i < n; i++) {
+        LSA_REQUIRE((g[i] & 1) == 1 && g[i] < 2 * (u64)c.n, "bfv_rotate_mac_plain_mul: Galois element must be odd and < 2N");
+        LSA_REQUIRE(pts[i] != nullptr, "bfv_rotate_mac_plain_mul: null plaintext");
+        if (g[i] == 1) continue;
+        LSA_REQUIRE(glk[i] != nullptr, "bfv_rotate_mac_plain_mul: a rotation term needs its key");
+        any_rot = true;
+    }
+    if (batch <= 0) return;
+    const long long N = c.n;
+    const int L = level + 1;
+    const size_t wct = 2 * (size_t)L * N, wpt = (size_t)L * N;
+    // out holds the running sum while the input, the plaintexts and the partial sum are still read: it may alias none of them
+    LSA_REQUIRE(spans_apart(out, sout, wct, in, sin, wct, batch), "bfv_rotate_mac_plain_mul: out overlaps the input");
+    for (int i = 0; i < n; i++)
+        LSA_REQUIRE(spans_apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_rotate_mac_plain_mul: out overlaps a plaintext");
+    LSA_REQUIRE(!partial || spans_apart(out, sout, wct, partial, spartial, wct, batch),
+                "bfv_rotate_mac_plain_mul: out overlaps the partial sum");
+    const bool fused = rotmac_fused_on() && c.fuse_tails && rotation_scatter_on();
+    std::vector<const u32*> scatters(n, nullptr), perms(n, nullptr);
+    for (int i = 0; i < n; i++) {
+        if (g[i] == 1) continue;
+        scatters[i] = rotation_scatter(c, g[i]);
+        if (!scatters[i]) perms[i] = c.ntt_perm(g[i]);
+    }
+    const long long sct = 2LL * L * N;   // NTT(c0) | NTT(c1) per batch item in the workspace
+    const size_t ks_rows = ks_ws_rows(c, level);
+    const size_t rows = 2 * (size_t)L + ks_rows + (fused ? 0 : 2 * (size_t)L);
+    for_tiles(c, rows, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+        u64* ctn = ws;
+        u64* sub = ctn + (size_t)nb * sct;
+        u64* p = sub + (size_t)nb * ks_rows * N;   // two-step form: one rotated term, NTT domain
+        const u64* ct = in + (size_t)b0 * sin;
+        u64* o = out + (size_t)b0 * sout;
+        const KsWorkspace w = ks_layout(c, level, nb, sub);
+        launch_ntt(c, ct, ctn, nb, sin, sct, 2 * L, rm_seq(L), false, st);
+        if (any_rot) ks_decompose(c, level, ctn + L * N, sct, nb, sub, st, ct + (long long)L * N, sin, true);
+        bool first = true;
+        for (int i = 0; i < n; i++) {   // identity terms: no transform at all
+            if (g[i] != 1) continue;
+            launch_mont_muladd(c, ctn, sct, pts[i] + (size_t)b0 * spts[i], spts[i], first ? nullptr : o, sout, o, sout, nb, 2, L,
+                               rm_seq(L), st);
+            first = false;
+        }
+        for (int i = 0; i < n; i++) {
+            if (g[i] == 1) continue;
+            const u64* pt = pts[i] + (size_t)b0 * spts[i];
+            ks_mac(c, level, ctn + L * N, sct, *glk[i], nb, sub, st, false);
+            if (fused) {
+                const RotMacTerm term{pt, spts[i], !first};
+                ks_moddown(c, level, w.acc, w.s_acc, w.conv, o, sout, ctn, sct, L, 1, nb, st, nullptr, false, scatters[i], nullptr,
+                           &term);
+            } else {
+                ks_moddown(c, level, w.acc, w.s_acc, w.conv, p, sct, ctn, sct, L, 1, nb, st, nullptr, false, scatters[i]);
+                const u64* r = p;
+                if (perms[i]) {   // no scattered store: the automorphism as a separate pass (conv is free again)
+                    launch_permute_ntt(c, perms[i], p, sct, w.conv, w.s_conv, 2 * L, nb, st);
+                    r = w.conv;
+                }
+                launch_mont_muladd(c, r, sct, pt, spts[i], first ? nullptr : o, sout, o, sout, nb, 2, L, rm_seq(L), st);
+            }
+            first = false;
+        }
         launch_ntt(c, o, o, nb, sout, 2 * L, rm_seq(L), true, st);
         if (partial)
             launch_elementwise(c, EW_ADD, o, partial + (size_t)b0 * spartial, o, nb, sout, spartial, sout, 2 * L, rm_seq(L), st);

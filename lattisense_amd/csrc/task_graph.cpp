@@ -71,6 +71,7 @@ TaskGraph TaskGraph::load_for_gpu(const std::string& json_path) {
     if (!getenv("LSA_NO_GRAPH_FUSION")) {
         g.fuse_accumulations();
         g.fuse_mult_relin_rescale();
+        g.fuse_rotate_mac();
     }
     g.insert_bridges();
     g.assign_processors();
@@ -375,6 +376,148 @@ void TaskGraph::fuse_mult_relin_rescale() {
         auto it = computes.emplace(c.index, std::move(c)).first;
         for (DatumNode* in : it->second.input_nodes) in->successors.push_back(&it->second);
         for (DatumNode* o : it->second.output_nodes) o->predecessors.push_back(&it->second);
+    }
+}
+
+// Peephole: a BFV multiply-accumulate whose plaintexts are all pt_mul at the ciphertexts' level and whose ciphertext terms
+// are one ciphertext X or private rotations of X (advanced_rotate_cols / rotate_rows followed by ct_pt_mult_accumulate: the
+// diagonal matrix-vector product) becomes one FUSED_ROTATE_MAC node (bfv_rotate_mac_plain_mul: one decomposition of X, the
+// rotations never leave the NTT domain; bit-identical residues).  A partial sum that is the private output of a pt_mul
+// multiply of X or of a private rotation of X is absorbed as one more term; any other partial sum stays.
+void TaskGraph::fuse_rotate_mac() {
+    if (algo != ALGO_BFV) return;
+    auto private_to = [](const DatumNode* d) {
+        return d->predecessors.size() == 1 && d->successors.size() == 1 && !d->is_output && !d->is_input;
+    };
+    auto is_ct = [](const DatumNode* d) { return d->datum_type == TYPE_CIPHERTEXT && d->fhe_prop && d->fhe_prop->degree == 1; };
+    auto is_ptmul = [](const DatumNode* d, int level) {
+        return d->datum_type == TYPE_PLAINTEXT && d->fhe_prop && d->fhe_prop->is_ntt && d->fhe_prop->is_mform &&
+               !(d->fhe_prop->p && d->fhe_prop->p->is_ringt) && d->fhe_prop->level == level;
+    };
+    // a private rotation of a degree-1 ciphertext: its node (inputs [ct, key], one output), else null
+    auto rotation_of = [&](const DatumNode* d) -> ComputeNode* {
+        if (!private_to(d)) return nullptr;
+        ComputeNode* r = d->predecessors[0];
+        const OperationType op = r->op();
+        if ((op != OperationType::ROTATE_COL && op != OperationType::ROTATE_ROW) || r->input_nodes.size() != 2 ||
+            r->output_nodes.size() != 1 || !is_ct(r->input_nodes[0]))
+            return nullptr;
+        if (op == OperationType::ROTATE_COL && !(r->input_nodes[1]->fhe_prop && r->input_nodes[1]->fhe_prop->p &&
+                                                 r->input_nodes[1]->fhe_prop->p->galois_element))
+            return nullptr;
+        return r;
+    };
+    std::vector<NodeIndex> macs;
+    for (auto& kv : computes) {
+        const OperationType op = kv.second.op();
+        if ((op == OperationType::MAC_WO_PARTIAL_SUM || op == OperationType::MAC_W_PARTIAL_SUM) && kv.second.fhe_prop->p)
+            macs.push_back(kv.first);
+    }
+    std::sort(macs.begin(), macs.end());
+    for (NodeIndex mi : macs) {
+        ComputeNode* mac = &computes.at(mi);
+        const int n = mac->fhe_prop->p->sum_cnt;
+        const bool with_partial = mac->op() == OperationType::MAC_W_PARTIAL_SUM;
+        const size_t pt0 = (size_t)n + (with_partial ? 1 : 0);
+        if (n < 1 || mac->input_nodes.size() != pt0 + (size_t)n || mac->output_nodes.size() != 1 || !is_ct(mac->input_nodes[0]))
+            continue;
+        const int level = mac->input_nodes[0]->fhe_prop->level;
+        bool ok = true;
+        for (int i = 0; i < n && ok; i++) ok = is_ptmul(mac->input_nodes[pt0 + i], level) && is_ct(mac->input_nodes[i]);
+        if (!ok) continue;
+        // every term: X, or a private rotation of X
+        DatumNode* X = nullptr;
+        std::vector<ComputeNode*> rot(n, nullptr);
+        auto term_base = [&](DatumNode* d, ComputeNode*& r) -> DatumNode* {
+            r = rotation_of(d);
+            return r ? r->input_nodes[0] : d;
+        };
+        for (int i = 0; i < n && ok; i++) {
+            DatumNode* b = term_base(mac->input_nodes[i], rot[i]);
+            if (!X) X = b;
+            ok = b == X;
+        }
+        if (!ok || X->fhe_prop->level != level) continue;
+        // the partial sum: absorbed when it is a private pt_mul product of X or of a private rotation of X
+        DatumNode* partial = with_partial ? mac->input_nodes[n] : nullptr;
+        ComputeNode* prod = nullptr;
+        ComputeNode* prod_rot = nullptr;
+        DatumNode* prod_pt = nullptr;
+        if (partial && private_to(partial) && partial->fhe_prop && partial->fhe_prop->level == level) {
+            ComputeNode* p = partial->predecessors[0];
+            if (p->op() == OperationType::MULTIPLY && p->input_nodes.size() == 2 && p->output_nodes.size() == 1) {
+                DatumNode *a = p->input_nodes[0], *b = p->input_nodes[1];
+                DatumNode* ct = is_ptmul(b, level) && is_ct(a) ? a : is_ptmul(a, level) && is_ct(b) ? b : nullptr;
+                if (ct) {
+                    ComputeNode* r = nullptr;
+                    if (term_base(ct, r) == X) {
+                        prod = p;
+                        prod_rot = r;
+                        prod_pt = ct == a ? b : a;
+                    }
+                }
+            }
+        }
+        std::vector<ComputeNode*> terms_rot(rot);
+        std::vector<DatumNode*> pts;
+        for (int i = 0; i < n; i++) pts.push_back(mac->input_nodes[pt0 + i]);
+        if (prod) {   // the product becomes the first term
+            terms_rot.insert(terms_rot.begin(), prod_rot);
+            pts.insert(pts.begin(), prod_pt);
+            partial = nullptr;
+        }
+        bool any_rot = false;
+        for (ComputeNode* r : terms_rot) any_rot = any_rot || r;
+        if (!any_rot) continue;
+        // the new node: [X, (partial,) keys of the rotation terms..., pts...]
+        ComputeNode c;
+        c.index = next_compute++;
+        c.id = mac->id + "_rotmac";
+        ComputeNode::FheProperty fp;
+        fp.op_type = OperationType::FUSED_ROTATE_MAC;
+        ComputeNode::FheProperty::ExtraProperty ep;
+        ep.sum_cnt = (int32_t)terms_rot.size();
+        fp.p = ep;
+        c.fhe_prop = fp;
+        c.input_nodes.push_back(X);
+        if (partial) c.input_nodes.push_back(partial);
+        RotMacPlan plan;
+        plan.partial = partial != nullptr;
+        for (ComputeNode* r : terms_rot) {
+            plan.row.push_back(r && r->op() == OperationType::ROTATE_ROW);
+            if (!r) {
+                plan.key_pos.push_back(-1);
+                continue;
+            }
+            plan.key_pos.push_back((int)c.input_nodes.size());
+            c.input_nodes.push_back(r->input_nodes[1]);
+        }
+        for (DatumNode* p : pts) c.input_nodes.push_back(p);
+        c.output_nodes = mac->output_nodes;
+        // detach and drop the MAC, the absorbed product and the rotations with their private outputs
+        std::vector<ComputeNode*> dead{mac};
+        if (prod) dead.push_back(prod);
+        for (ComputeNode* r : terms_rot)
+            if (r) dead.push_back(r);
+        std::vector<NodeIndex> dead_data, dead_compute;
+        for (ComputeNode* old : dead) {
+            for (DatumNode* in : old->input_nodes) {
+                auto& v = in->successors;
+                v.erase(std::remove(v.begin(), v.end(), old), v.end());
+            }
+            for (DatumNode* o : old->output_nodes) {
+                auto& v = o->predecessors;
+                v.erase(std::remove(v.begin(), v.end(), old), v.end());
+            }
+            if (old != mac) dead_data.push_back(old->output_nodes[0]->index);
+            dead_compute.push_back(old->index);
+        }
+        for (NodeIndex d : dead_data) data.erase(d);
+        for (NodeIndex ci : dead_compute) computes.erase(ci);
+        auto it = computes.emplace(c.index, std::move(c)).first;
+        for (DatumNode* in : it->second.input_nodes) in->successors.push_back(&it->second);
+        for (DatumNode* o : it->second.output_nodes) o->predecessors.push_back(&it->second);
+        rotmac_plans[it->first] = std::move(plan);
     }
 }
 

@@ -97,6 +97,16 @@ enum class OperationType {
     // carry them; a custom executor that walks the graph must treat values >= BACKEND_PRIVATE_BEGIN as opaque)
     BACKEND_PRIVATE_BEGIN = 1000,
     FUSED_MULT_RELIN_RESCALE = 1000,  // mult -> relin -> rescale chain merged at load time, inputs [a, (b,) rlk]
+    FUSED_ROTATE_MAC = 1001,          // BFV sum_i rot_i(X) * pt_i (+ partial), inputs [X, (partial,) keys..., pts...]
+};
+
+// The per-term plan of a FUSED_ROTATE_MAC node (TaskGraph::rotmac_plans; the node structs keep the reference's layout):
+// term i is X itself (key_pos[i] < 0) or its rotation with the key at input position key_pos[i], by the row element 2N-1
+// when row[i], else by the key datum's Galois element.  Plaintext i is input 1 + partial + (number of keys) + i.
+struct RotMacPlan {
+    bool partial = false;
+    std::vector<int> key_pos;
+    std::vector<bool> row;
 };
 
 struct DatumNode {
@@ -166,6 +176,7 @@ struct TaskGraph {
     mjson::Value parameter;
     Algo algo = ALGO_BFV;
     int max_top_level = 0;
+    std::unordered_map<NodeIndex, RotMacPlan> rotmac_plans;   // FUSED_ROTATE_MAC nodes' term plans
 
     // parse <path>, insert the ABI bridge nodes for a device backend, compute levels and priorities
     static TaskGraph load_for_gpu(const std::string& json_path);
@@ -178,6 +189,7 @@ private:
     void validate_structure() const;
     void fuse_accumulations();
     void fuse_mult_relin_rescale();
+    void fuse_rotate_mac();
     void insert_bridges();
     void link_bridge(OperationType op, const std::string& id, DatumNode* in, DatumNode* out);
     void assign_processors();

@@ -281,6 +281,7 @@ const char* op_name(OperationType op) {
         case OperationType::MAC_W_PARTIAL_SUM: return "cmpac_sum";
         case OperationType::BOOTSTRAP: return "bootstrap";
         case OperationType::FUSED_MULT_RELIN_RESCALE: return "mult+relin+rescale";
+        case OperationType::FUSED_ROTATE_MAC: return "rotate+cmp_sum";
         default: return "?";
     }
 }
@@ -340,6 +341,10 @@ void bind_gpu_executor(ComputeNode& node, Algo algorithm) {
         case OperationType::RESCALE:
         case OperationType::ROTATE_ROW:
         case OperationType::FUSED_MULT_RELIN_RESCALE:
+            break;
+        case OperationType::FUSED_ROTATE_MAC:   // made by TaskGraph::fuse_rotate_mac, BFV only
+            if (algorithm != ALGO_BFV) unsupported("BFV only");
+            if (!node.fhe_prop->p || node.fhe_prop->p->sum_cnt < 1) throw std::runtime_error("Sum count not found in FHE property");
             break;
         case OperationType::ROTATE_COL:
             if (!node.fhe_prop->p) throw std::runtime_error("Rotation step not found in FHE property");
@@ -991,8 +996,13 @@ struct fhe_task_handle_st {
         return o;
     }
 
-    static std::string signature(const ComputeNode* n) {
+    std::string signature(const ComputeNode* n) const {
         std::string sg = std::to_string((int)n->op());
+        if (n->op() == OperationType::FUSED_ROTATE_MAC) {   // only nodes with the same term plan batch together
+            const RotMacPlan& pl = g.rotmac_plans.at(n->index);
+            sg += pl.partial ? "p" : "-";
+            for (size_t i = 0; i < pl.key_pos.size(); i++) sg += "," + std::to_string(pl.key_pos[i]) + (pl.row[i] ? "r" : "");
+        }
         for (auto* in : n->input_nodes) {
             sg += "|" + std::to_string((int)in->datum_type) + ":" + std::to_string(in->fhe_prop->level) + ":" +
                   std::to_string(in->fhe_prop->degree);
@@ -1027,7 +1037,8 @@ struct fhe_task_handle_st {
         int out_polys = polys_in;
         if (op == OperationType::MULTIPLY && !(n0->input_nodes.size() == 2 && (is_plain_node(n0->input_nodes[1]) || ptmul_first)))
             out_polys = 3;
-        if (op == OperationType::RELINEARIZE || op == OperationType::FUSED_MULT_RELIN_RESCALE) out_polys = 2;
+        if (op == OperationType::RELINEARIZE || op == OperationType::FUSED_MULT_RELIN_RESCALE || op == OperationType::FUSED_ROTATE_MAC)
+            out_polys = 2;
         const size_t w_out = (size_t)out_polys * (out_lvl + 1) * N;
         auto out_slab = dslab(w_out * m);
         u64* out = out_slab->ptr;
@@ -1164,6 +1175,36 @@ struct fhe_task_handle_st {
                 LSA_REQUIRE(gel != 0, "Galois element missing on the key datum");
                 if (bfv) bfv_rotate(c, lvl, a.ptr, gel, key_of(1), out, m, a.stride, so, s);
                 else ckks_rotate(c, lvl, a.ptr, gel, key_of(1), out, m, a.stride, so, s);
+                break;
+            }
+            case OperationType::FUSED_ROTATE_MAC: {   // inputs [X, (partial,) keys..., pts...], TaskGraph::rotmac_plans
+                LSA_REQUIRE(bfv && polys_in == 2, "rotate-and-MAC expects a BFV degree-1 ciphertext");
+                const RotMacPlan& pl = g.rotmac_plans.at(n0->index);
+                const int n = (int)pl.key_pos.size();
+                int nkeys = 0;
+                for (int kp : pl.key_pos) nkeys += kp >= 0 ? 1 : 0;
+                const int pt0 = 1 + (pl.partial ? 1 : 0) + nkeys;
+                LSA_REQUIRE((int)n0->input_nodes.size() == pt0 + n, "rotate-and-MAC node: unexpected number of inputs");
+                std::vector<u64> els(n);
+                std::vector<const Key*> keys(n, nullptr);
+                std::vector<const u64*> pp(n);
+                std::vector<long long> ps_(n);
+                for (int i = 0; i < n; i++) {
+                    els[i] = 1;
+                    if (pl.key_pos[i] >= 0) {
+                        const DatumNode* kd = n0->input_nodes[pl.key_pos[i]];
+                        els[i] = pl.row[i] ? 2 * (u64)c.n - 1 : (kd->fhe_prop->p ? kd->fhe_prop->p->galois_element : 0);
+                        LSA_REQUIRE(els[i] != 0, "Galois element missing on the key datum");
+                        keys[i] = &key_of(pl.key_pos[i]);
+                    }
+                    Operand pi = gather(c, s, nodes, pt0 + i, avail, (size_t)L * N);
+                    pp[i] = pi.ptr;
+                    ps_[i] = pi.stride;
+                }
+                Operand part{nullptr, 0, nullptr};
+                if (pl.partial) part = gather(c, s, nodes, 1, avail, w_in);
+                bfv_rotate_mac_plain_mul(c, lvl, a.ptr, n, els.data(), keys.data(), pp.data(), ps_.data(), part.ptr, part.stride, out,
+                                         m, a.stride, so, s);
                 break;
             }
             case OperationType::MAC_WO_PARTIAL_SUM:

@@ -231,6 +231,23 @@ class DeviceContext:
                                           2 * L * self.n, out.ptr, batch, 2 * L * self.n, self.stream))
         return out
 
+    def bfv_rotate_mac_plain_mul(self, level, ct, terms, batch, partial=None):
+        """sum_i rotate(ct, g_i) x pt_i (+ partial), hoisted, the rotations kept in the NTT domain; terms: a list of
+        (galois element, key handle or None for g = 1, pt_mul plaintexts [batch][L][N]); bit-identical to bfv_rotate_many
+        followed by bfv_mac_plain_mul"""
+        L = level + 1
+        n = len(terms)
+        assert n >= 1
+        out = self.alloc(batch * 2 * L * self.n)
+        els = (ctypes.c_uint64 * n)(*[g for g, _, _ in terms])
+        hk = (ctypes.c_void_p * n)(*[k.value if k is not None else None for _, k, _ in terms])
+        pp = (ctypes.c_void_p * n)(*[p.ptr for _, _, p in terms])
+        sp = (ctypes.c_longlong * n)(*([L * self.n] * n))
+        check(lib().lsa_bfv_rotate_mac_plain_mul(self.h, level, ct.ptr, n, els, hk, pp, sp,
+                                                 partial.ptr if partial is not None else None, 2 * L * self.n, out.ptr, batch,
+                                                 2 * L * self.n, 2 * L * self.n, self.stream))
+        return out
+
     def bfv_rescale(self, level, polys, ct, batch):
         L = level + 1
         out = self.alloc(batch * polys * level * self.n)
