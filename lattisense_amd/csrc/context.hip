@@ -329,6 +329,19 @@ const u64* Context::pmodq_vec(int level) {
     return const_vec("pmodq" + std::to_string(L), mods, pm);
 }
 
+const u64* Context::pfold_vec(int level) {
+    const int L = level + 1;
+    std::vector<u64> v(2 * (size_t)L);
+    for (int j = 0; j < L; j++) {
+        const u64 q = T.mod[j];
+        u64 pr = 1;
+        for (int l = 0; l < np; l++) pr = mul_mod_host(pr, T.mod[p_mod(l)] % q, q);
+        v[j] = to_mont_host(to_mont_host(pr, q), q);   // P * 2^128 mod q
+        v[L + j] = pr;
+    }
+    return raw_vec("pfold" + std::to_string(L), v);
+}
+
 const u64* Context::qlinv_vec(int level) {
     std::vector<int> mods(level);
     std::vector<u64> v(level);

@@ -356,7 +356,7 @@ int ks_fused_engines(const Context& c) {
 }
 
 bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* ext, long long sext, const Key& key, u64* acc,
-                      long long sacc, int batch, hipStream_t s, int engines) {
+                      long long sacc, int batch, hipStream_t s, int engines, const TensorFold* fold) {
     if (batch <= 0) return true;
     if (!ks_fused_enabled(c) || (c.fp64_ntt && !key.fp)) return false;
     LSA_REQUIRE(key.level >= level, "key-switch key exported at a lower level than the ciphertext");
@@ -382,6 +382,15 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
     g.batch = batch;
     g.allow_fp64 = c.fp64_ntt;
     g.fp_raw_in = c.fp_raw;
+    if (fold) {
+        g.fa = fold->a;
+        g.fb = fold->b;
+        g.sfa = fold->sa;
+        g.sfb = fold->sb;
+        g.pfa = fold->pa;
+        g.pfb = fold->pb;
+        g.pf = c.pfold_vec(level);
+    }
     const int T = g.L + c.np, mu = c.plan.pass[1].mu;
     LSA_REQUIRE(T <= 64, "fused key MAC: too many target limbs");
     const size_t lds_bytes = (size_t)LSA_R16_LDS_WORDS * sizeof(u64);
@@ -389,13 +398,14 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
     // (16 N / 2 per limb) + its share of the gadget inner product as launch_ks_mac counts it
     for (int eng = 0; eng < 2; eng++) {
         g.n_tl = 0;
-        int transforms = 0;
+        int transforms = 0, q_targets = 0;
         for (int tl = 0; tl < T; tl++) {
             const int mi = tl < g.L ? tl : c.p_mod(tl - g.L);
             const bool fp = c.fp64_ntt && (c.T.mod[mi] >> LSA_FP64_MAX_BITS) == 0;
             if ((int)fp != eng || !((engines >> eng) & 1)) continue;
             g.tl_list[g.n_tl++] = (unsigned char)tl;
             transforms += g.beta - (tl < g.L ? 1 : 0);
+            q_targets += tl < g.L;
         }
         if (!g.n_tl) continue;
         const long long nblocks = (long long)batch * g.n_tl * (1 << (c.logn - 12));
@@ -404,7 +414,10 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
         const bool xcd = !(xcd_env && xcd_env[0] == '0');
         g.xcd_deal = xcd && ((g.n_tl << (c.logn - 12)) % 8 == 0) ? 1 : 0;
         const double ntt_bytes = 16.0 * c.n * transforms * batch / 2;
-        ProfScope ps(c, PROF_NTT, ntt_bytes + 8.0 * c.n * g.n_tl * (batch * ((double)g.beta + 2.0) + 2.0 * g.beta), s, ntt_bytes);
+        // (tensor fold: the own digit of a Q target reads a0, a1, b0, b1 instead of cx)
+        const double fold_bytes = fold ? 3.0 * 8 * c.n * q_targets * batch : 0.0;
+        ProfScope ps(c, PROF_NTT, ntt_bytes + fold_bytes + 8.0 * c.n * g.n_tl * (batch * ((double)g.beta + 2.0) + 2.0 * g.beta), s,
+                     ntt_bytes);
         const dim3 grid((unsigned)nblocks), block(LSA_R16_THREADS);
         if (mu == 9 && eng) hipLaunchKernelGGL((k_ntt_r16_ksmac<9, true>), grid, block, lds_bytes, s, g);
         else if (mu == 9) hipLaunchKernelGGL((k_ntt_r16_ksmac<9, false>), grid, block, lds_bytes, s, g);
@@ -1048,6 +1061,41 @@ void launch_tensor(Context& c, const u64* a, const u64* b, u64* d, int batch, lo
     LSA_HIP(hipGetLastError());
 }
 
+// d2 = a1 * b1 alone (the tensor-fold HMult: d0 and d1 never leave the key MAC), the same residues as k_tensor's third output
+__global__ __launch_bounds__(TPB) void k_tensor_d2(TensorArgs g) {
+    const int chunks = (1 << g.logn) / (2 * TPB);
+    const int limb = blockIdx.x / chunks;
+    const int x = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
+    const ModDev m = g.mods[limb];
+    const long long b = blockIdx.y;
+    const long long off = ((long long)limb << g.logn) + x;
+    const ulonglong2 a1 = ld2(g.a + b * g.sa + g.pa + off), b1 = ld2(g.b + b * g.sb + g.pb + off);
+    st2(g.d + b * g.sd + off, mont_mul(a1.x, mont_mul_lazy(b1.x, m.r2, m.q, m.qinv), m.q, m.qinv),
+        mont_mul(a1.y, mont_mul_lazy(b1.y, m.r2, m.q, m.qinv), m.q, m.qinv));
+}
+
+void launch_tensor_d2(Context& c, const u64* a, const u64* b, u64* d2, int batch, long long sa, long long sb, long long sd,
+                      int limbs, hipStream_t s, int a_rpp, int b_rpp) {
+    if (batch <= 0) return;
+    TensorArgs g{};
+    LSA_REQUIRE((a_rpp == 0 || a_rpp >= limbs) && (b_rpp == 0 || b_rpp >= limbs), "tensor: rows per polynomial below the limb count");
+    LSA_REQUIRE(limbs <= c.nq, "tensor: Q limbs only");
+    g.pa = (long long)(a_rpp ? a_rpp : limbs) << c.logn;
+    g.pb = (long long)(b_rpp ? b_rpp : limbs) << c.logn;
+    g.a = a;
+    g.b = b;
+    g.d = d2;
+    g.sa = sa;
+    g.sb = sb;
+    g.sd = sd;
+    g.mods = c.d_mods;
+    g.limbs = limbs;
+    g.logn = c.logn;
+    ProfScope ps(c, PROF_TENSOR, 3.0 * 8 * c.n * limbs * batch, s);
+    hipLaunchKernelGGL(k_tensor_d2, ew_grid(c, limbs, batch), dim3(TPB), 0, s, g);
+    LSA_HIP(hipGetLastError());
+}
+
 // ------------------------------------------------------------------------------------------------ exact base conversion
 //  y_i = x_i*(S/q_i)^-1 mod q_i ; v = floor(sum double(y_i)/double(q_i)) ;
 // out_j = sum_i y_i*(S/q_i) - v*S mod p_j   [centered: x+floor(S/2) in, -floor(S/2) out]
@@ -1403,13 +1451,19 @@ struct KsMacArgs {
     const u64* base;
     const u64* pm;                 // [L] P mod q_j, Montgomery form
     long long sbase;
+    // FOLD (k_ks_mac<KB, false, true>, TensorFold): the own digit of a Q target limb is a1 * b1, and P * a0 b0 / P * (a0 b1 +
+    // a1 b0) join the two sums; pf = Context::pfold_vec (its first L entries: mont_mul(x, pf[j]) = x * P in Montgomery form)
+    const u64* fa;
+    const u64* fb;
+    long long sfa, sfb, pfa, pfb;
+    const u64* pf;
 };
 
 // grid: x = T * (N/2/TPB), y = groups of `bpt` batch items.  The key is in Montgomery form, so sum_d ext_d*key_d needs
 // ONE REDC per output.  A thread keeps its 2*beta key words in registers and walks `bpt` ciphertexts with them: the key
 // (68 MiB at the headline shape) is then streamed once per group instead of once per ciphertext.
 // KB = number of digits whose key words are register-resident (0: stream the key per ciphertext)
-template <int KB, bool EXT = false>
+template <int KB, bool EXT = false, bool FOLD = false>
 __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
     const int chunks = (1 << g.logn) / (2 * TPB);
     const int tl = g.n_tl ? g.tl_list[blockIdx.x / chunks] : blockIdx.x / chunks;
@@ -1438,23 +1492,60 @@ __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
     // always has one ciphertext's loads in flight behind its arithmetic and its stores (the kernel is traffic-bound: with the
     // loads issued and consumed in the same iteration it ran at 4.5 TB/s, no faster without its arithmetic)
     ulonglong2 en[KB > 0 ? KB : 1];
+    ulonglong2 fn[FOLD ? 4 : 1];   // FOLD: the next ciphertext's a0, a1, b0, b1 (Q targets)
     auto fetch = [&](long long b) {
         if constexpr (in_regs) {
 #pragma unroll
             for (int d = 0; d < KB; d++)
-                if (d < g.beta)
+                if (d < g.beta && !(FOLD && d == own_d))
                     en[d] = ld2(d == own_d ? g.cx + b * g.scx + tl * N + x : g.ext + b * g.sext + ((long long)d * T + tl) * N + x);
         }
+        if constexpr (FOLD) {
+            if (own_d >= 0) {
+                const u64* pa = g.fa + b * g.sfa + tl * N + x;
+                const u64* pb = g.fb + b * g.sfb + tl * N + x;
+                fn[0] = ld2(pa);
+                fn[1] = ld2(pa + g.pfa);
+                fn[2] = ld2(pb);
+                fn[3] = ld2(pb + g.pfb);
+            }
+        }
+    };
+    // FOLD: the own digit's value d2 = a1 * b1, canonical (k_tensor's residues)
+    auto own_d2 = [&](const ulonglong2& a1, const ulonglong2& b1) {
+        return ulonglong2{mont_mul(a1.x, mont_mul_lazy(b1.x, m.r2, m.q, m.qinv), m.q, m.qinv),
+                          mont_mul(a1.y, mont_mul_lazy(b1.y, m.r2, m.q, m.qinv), m.q, m.qinv)};
     };
     if (b_begin < b_end) fetch(b_begin);
     for (long long b = b_begin; b < b_end; b++) {
         u64 h00 = 0, l00 = 0, h01 = 0, l01 = 0, h10 = 0, l10 = 0, h11 = 0, l11 = 0;
         u64 r00 = 0, r01 = 0, r10 = 0, r11 = 0;
+        ulonglong2 fc[FOLD ? 4 : 1];
+        if constexpr (FOLD) {
+            if constexpr (in_regs) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) fc[i] = fn[i];
+            } else if (own_d >= 0) {
+                const u64* pa = g.fa + b * g.sfa + tl * N + x;
+                const u64* pb = g.fb + b * g.sfb + tl * N + x;
+                fc[0] = ld2(pa);
+                fc[1] = ld2(pa + g.pfa);
+                fc[2] = ld2(pb);
+                fc[3] = ld2(pb + g.pfb);
+            }
+        }
         if constexpr (in_regs) {
             ulonglong2 ec[KB > 0 ? KB : 1];
 #pragma unroll
             for (int d = 0; d < KB; d++) ec[d] = en[d];
             if (b + 1 < b_end) fetch(b + 1);
+            if constexpr (FOLD) {
+                if (own_d >= 0) {
+#pragma unroll
+                    for (int d = 0; d < KB; d++)
+                        if (d == own_d) ec[d] = own_d2(fc[1], fc[3]);
+                }
+            }
 #pragma unroll
             for (int d = 0; d < KB; d++) {
                 if (d < g.beta) {
@@ -1472,7 +1563,7 @@ __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
         } else {
             for (int d = 0; d < g.beta; d++) {
                 const u64* pe = d == own_d ? g.cx + b * g.scx + tl * N + x : g.ext + b * g.sext + ((long long)d * T + tl) * N + x;
-                const ulonglong2 e = ld2(pe);
+                const ulonglong2 e = FOLD && d == own_d ? own_d2(fc[1], fc[3]) : ld2(pe);
                 const u64* pk = g.key + ((long long)(d * 2) * g.kcomp + kj) * N + x;
                 const ulonglong2 kk0 = ld2(pk), kk1 = ld2(pk + (long long)g.kcomp * N);
                 mac128(h00, l00, e.x, kk0.x);
@@ -1496,6 +1587,17 @@ __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
         r10 = add_mod(r10, csub(mont_redc_lazy(h10, l10, m.q, m.qinv), m.q), m.q);
         r11 = add_mod(r11, csub(mont_redc_lazy(h11, l11, m.q, m.qinv), m.q), m.q);
 #endif
+        if constexpr (FOLD) {   // + P * d0, + P * d1 (canonical, like the EXT path's P * c0)
+            if (own_d >= 0) {
+                const u64 pm = g.pf[tl];
+                const u64 p0x = mont_mul(fc[2].x, pm, m.q, m.qinv), p0y = mont_mul(fc[2].y, pm, m.q, m.qinv);   // b0 * P * 2^64
+                const u64 p1x = mont_mul(fc[3].x, pm, m.q, m.qinv), p1y = mont_mul(fc[3].y, pm, m.q, m.qinv);   // b1 * P * 2^64
+                r00 = add_mod(r00, mont_mul(fc[0].x, p0x, m.q, m.qinv), m.q);
+                r01 = add_mod(r01, mont_mul(fc[0].y, p0y, m.q, m.qinv), m.q);
+                r10 = add_mod(r10, add_mod(mont_mul(fc[0].x, p1x, m.q, m.qinv), mont_mul(fc[1].x, p0x, m.q, m.qinv), m.q), m.q);
+                r11 = add_mod(r11, add_mod(mont_mul(fc[0].y, p1y, m.q, m.qinv), mont_mul(fc[1].y, p0y, m.q, m.qinv), m.q), m.q);
+            }
+        }
         if constexpr (EXT) {
             if (tl < g.L) {
                 const ulonglong2 c0 = ld2(g.base + b * g.sbase + tl * N + x);
@@ -1522,25 +1624,36 @@ __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
     }
 }
 
-template <bool EXT>
+template <bool EXT, bool FOLD = false>
 static void launch_ks_mac_kb(int beta, dim3 grid, hipStream_t s, const KsMacArgs& g) {
     // the register-resident key costs 8 VGPRs per digit slot: 5 and 6 digits (the 25Q+5P chains) get their own instantiations
     // instead of the 8-slot one (182 VGPRs, 2 waves per SIMD)
-    if (beta <= 2) hipLaunchKernelGGL((k_ks_mac<2, EXT>), grid, dim3(TPB), 0, s, g);   // low levels: 86 VGPRs, 5 waves per SIMD
-    else if (beta <= 4) hipLaunchKernelGGL((k_ks_mac<4, EXT>), grid, dim3(TPB), 0, s, g);
-    else if (beta <= 5) hipLaunchKernelGGL((k_ks_mac<5, EXT>), grid, dim3(TPB), 0, s, g);
-    else if (beta <= 6) hipLaunchKernelGGL((k_ks_mac<6, EXT>), grid, dim3(TPB), 0, s, g);
-    else if (beta <= 8) hipLaunchKernelGGL((k_ks_mac<8, EXT>), grid, dim3(TPB), 0, s, g);
-    else hipLaunchKernelGGL((k_ks_mac<0, EXT>), grid, dim3(TPB), 0, s, g);
+    if (beta <= 2) hipLaunchKernelGGL((k_ks_mac<2, EXT, FOLD>), grid, dim3(TPB), 0, s, g);   // low levels: 86 VGPRs, 5 waves per SIMD
+    else if (beta <= 4) hipLaunchKernelGGL((k_ks_mac<4, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
+    else if (beta <= 5) hipLaunchKernelGGL((k_ks_mac<5, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
+    else if (beta <= 6) hipLaunchKernelGGL((k_ks_mac<6, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
+    else if (beta <= 8) hipLaunchKernelGGL((k_ks_mac<8, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
+    else hipLaunchKernelGGL((k_ks_mac<0, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
 }
 
 // scatter (with engine < 0): the result is written as the rotated extended ciphertext perm(acc + P * c0) -- scatter = the index
 // map of the rotation's inverse element, base = the ciphertext whose c0 enters (see KsMacArgs)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, const Key& key,
-                   u64* acc, long long sacc, int batch, hipStream_t s, int engine, const u32* scatter, const u64* base, long long sbase) {
+                   u64* acc, long long sacc, int batch, hipStream_t s, int engine, const u32* scatter, const u64* base, long long sbase,
+                   const TensorFold* fold) {
     if (batch <= 0) return;
     KsMacArgs g{};
     LSA_REQUIRE(!scatter || (engine < 0 && base), "key MAC: the extended output covers every target limb and needs the ciphertext");
+    LSA_REQUIRE(!(scatter && fold), "key MAC: the tensor fold has no extended output");
+    if (fold) {
+        g.fa = fold->a;
+        g.fb = fold->b;
+        g.sfa = fold->sa;
+        g.sfb = fold->sb;
+        g.pfa = fold->pa;
+        g.pfb = fold->pb;
+        g.pf = c.pfold_vec(level);
+    }
     if (scatter) {
         g.pm = c.pmodq_vec(level);
         g.scatter = scatter;
@@ -1575,7 +1688,10 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
         targets = g.n_tl;
     }
     const double T = targets;
-    ProfScope ps(c, PROF_KSMAC, 8.0 * c.n * (batch * (g.beta * T + 2 * T + (scatter ? g.L : 0)) + 2.0 * g.beta * T), s);
+    int q_targets = 0;   // (tensor fold: the own digit of a Q target reads a0, a1, b0, b1 instead of cx)
+    for (int i = 0; i < targets; i++) q_targets += (g.n_tl ? g.tl_list[i] : i) < g.L;
+    ProfScope ps(c, PROF_KSMAC, 8.0 * c.n * (batch * (g.beta * T + 2 * T + (scatter ? g.L : 0) + (fold ? 3.0 * q_targets : 0.0)) +
+                                             2.0 * g.beta * T), s);
     // enough workgroups to fill the chip, as few key re-reads as possible
     const dim3 grid1 = ew_grid(c, targets, 1);
     const int groups = std::max(1, std::min(batch, (int)((2048 + grid1.x - 1) / grid1.x)));
@@ -1583,6 +1699,7 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
     g.bpt = (batch + groups - 1) / groups;
     const dim3 grid(grid1.x, (unsigned)((batch + g.bpt - 1) / g.bpt));
     if (scatter) launch_ks_mac_kb<true>(g.beta, grid, s, g);
+    else if (fold) launch_ks_mac_kb<false, true>(g.beta, grid, s, g);
     else launch_ks_mac_kb<false>(g.beta, grid, s, g);
     LSA_HIP(hipGetLastError());
 }

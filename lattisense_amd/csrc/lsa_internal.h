@@ -159,6 +159,9 @@ struct Context {
                                  bool pinv_scaled = false, const BaseConvFold* fold = nullptr);
     const u64* pinv_vec(int level);
     const u64* pmodq_vec(int level);   // [level+1] P mod q_j, Montgomery form (extended ciphertexts: c0 * P)
+    // [2][level+1] the P factors of the tensor-fold key MAC (TensorFold): row 0 the Montgomery form of P * 2^64 mod q_j
+    // (mont_mul(x, .) = x * P in Montgomery form), row 1 P mod q_j as a plain residue (the FP64 engine's double)
+    const u64* pfold_vec(int level);
     const u64* qlinv_vec(int level);
     const u32* ntt_perm(u64 g);
     const u32* coeff_perm(u64 g);
@@ -280,6 +283,19 @@ void launch_lift_ringt(Context& c, int mode, int level, const u64* pt, long long
 // `limbs` rows of each polynomial are the operand at this level -- no copy needed to "drop" it)
 void launch_tensor(Context& c, const u64* a, const u64* b, u64* d, int batch, long long sa, long long sb, long long sd,
                    int limbs, const RowMap& rm, hipStream_t s, int a_rpp = 0, int b_rpp = 0);
+// d2 = a1 * b1 only (limbs 0..limbs-1, [limbs][N] per item), the residues k_tensor writes to its third polynomial: the input
+// of the tensor-fold key switch's ModUp (the key MAC takes d0 / d1 / the own digit from a and b themselves, TensorFold)
+void launch_tensor_d2(Context& c, const u64* a, const u64* b, u64* d2, int batch, long long sa, long long sb, long long sd,
+                      int limbs, hipStream_t s, int a_rpp = 0, int b_rpp = 0);
+// the tensor product folded into the relinearisation's key MAC (CKKS HMult+relin+rescale): for a Q target limb j the MAC
+// takes its own digit as d2_j = a1_j * b1_j and adds P * d0_j to the first and P * d1_j to the second running sum
+// (d0 = a0 b0, d1 = a0 b1 + a1 b0): acc'_j = acc_j + P * d_j.  a / b point at the tile's first item, [2][rpp][N] each.
+struct TensorFold {
+    const u64* a;
+    const u64* b;
+    long long sa, sb;   // batch strides
+    long long pa, pb;   // elements between the two polynomials of a / b
+};
 // exact base conversion: src limbs at rows src_row[i] of the source item, dst limbs at rows dst_row[j] of the dest item
 struct BaseConvRows {
     int src_row[LSA_BC_MAX_SRC];
@@ -296,7 +312,8 @@ void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows
 // P * base[tl][x]) -- gadget product, c0 * P and the automorphism of a baby-step rotation in one pass
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext,
                    const Key& key, u64* acc, long long sacc, int batch, hipStream_t s, int engine = -1,
-                   const u32* scatter = nullptr, const u64* base = nullptr, long long sbase = 0);
+                   const u32* scatter = nullptr, const u64* base = nullptr, long long sbase = 0,
+                   const TensorFold* fold = nullptr);
 // out[h][i] = base[h][i] + (acc[h][i] - conv[h][i]) * Pinv_i       (base may be null)
 void launch_moddown_final(Context& c, int level, const u64* acc, long long sacc, int acc_rows_per_poly, const u64* conv,
                           long long sconv, const u64* base, long long sbase, int base_rows_per_poly, int base_polys,
@@ -336,7 +353,7 @@ bool ks_fused_enabled(const Context& c);   // the fused second-pass + key-MAC ke
 // second pass of the extension transform + gadget inner product in one launch (see k_ntt_r16_ksmac); false = shape not covered
 // engines: bit 0 integer-engine target limbs, bit 1 FP64-engine target limbs
 bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* ext, long long sext, const Key& key, u64* acc,
-                      long long sacc, int batch, hipStream_t s, int engines = 3);
+                      long long sacc, int batch, hipStream_t s, int engines = 3, const TensorFold* fold = nullptr);
 int ks_fused_engines(const Context& c);   // which engines' target limbs take the fused kernel (LSA_KS_FUSED_ENGINES, default FP64 only)
 // out = (a - b) * k_i  with per-row constant (Montgomery form) ; out = a * k_i
 void launch_sub_mul_const(Context& c, const u64* a, long long sa, const u64* b, long long sb, const u64* kvec, u64* out,

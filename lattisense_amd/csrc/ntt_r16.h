@@ -631,6 +631,12 @@ struct KsFusedArgs {
     int xcd_deal;                  // 1: the workgroups of one (tile, limb) -- one key tile -- are dealt to one XCD: one key fetch instead of eight (LSA_KSMAC_XCD=0 off)
     int n_tl;                      // target limbs of this launch (one launch per butterfly engine: each has its own register budget)
     unsigned char tl_list[64];
+    // tensor fold (fa != null, TensorFold in lsa_internal.h): the own digit of a Q target limb is a1 * b1 and the sums gain
+    // P * a0 b0 / P * (a0 b1 + a1 b0); cx is not read.  pf = Context::pfold_vec: [0, L) Montgomery form of P * 2^64, [L, 2L) P
+    const u64* fa;
+    const u64* fb;
+    long long sfa, sfb, pfa, pfb;
+    const u64* pf;
 };
 
 // the MAC of one digit on the pair image: vin = the operand pair values (FP: doubles' bits), acc0/acc1 the two halves' sums
@@ -650,6 +656,60 @@ LSA_HD void r16_mac_digit(const KsFusedArgs& g, const NttPassArgs& a, const NttB
 #define LSA_KSMAC_CHUNK 4   // 16-byte pairs whose operand and key loads are in flight together
 #endif
     constexpr int CH = LSA_KSMAC_CHUNK;
+    if (own && g.fa) {
+        // tensor fold: four operand pairs per position instead of one, taken one position at a time in a loop that is not
+        // unrolled -- with chunks of two or four positions, or the loop unrolled, the compiler hoists loads across positions
+        // and the FP64 instantiations spill (MU = 8: 232 -> 256 VGPRs, 48 spilled); this way they stay at 2 workgroups per
+        // CU without scratch (profiles/r07/hmult_fold_resources.txt).
+        // FP64 sums: every term is an integer-valued double in (-1.1q, 1.1q) (fp_modmul); a sum holds beta + 1 (first half)
+        // or beta + 2 (second half) of them, below 9 * 1.1 * 2^47 < 2^51 for beta <= 7: exact (2^53), and fp_reduce's range.
+        // Integer sums: every Montgomery product is below 2q (operands below 2q and q), the sums stay below 2q as below.
+        const u64* pa0 = g.fa + b * g.sfa + (long long)tl * N;
+        const u64* pb0 = g.fb + b * g.sfb + (long long)tl * N;
+        const u64 pm = g.pf[tl];                    // integer: P * 2^128 mod q (mont_mul_lazy(x, pm) = x * P * 2^64)
+        const double pd = (double)g.pf[g.L + tl];   // FP64: P mod q (< 2^47, exact)
+#pragma unroll 1
+        for (int m = 0; m < 8; m++) {
+            int k, i;
+            r16_pair_pos<MU>(tid, m, k, i);
+            const long long x = r16_x<1, MU>(a, bc.tile, k, i);
+            u64 va0[2], va1[2], vb0[2], vb1[2], ka[2], kb[2];
+            ntt_load_data_pair(pa0 + x, va0[0], va0[1]);
+            ntt_load_data_pair(pa0 + g.pfa + x, va1[0], va1[1]);
+            ntt_load_data_pair(pb0 + x, vb0[0], vb0[1]);
+            ntt_load_data_pair(pb0 + g.pfb + x, vb1[0], vb1[1]);
+            if (FP) {
+                ntt_load_pair(reinterpret_cast<const u64*>(k0d + x), ka[0], ka[1]);
+                ntt_load_pair(reinterpret_cast<const u64*>(k1d + x), kb[0], kb[1]);
+            } else {
+                ntt_load_pair(k0 + x, ka[0], ka[1]);
+                ntt_load_pair(k1 + x, kb[0], kb[1]);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int e = 2 * m + j;
+                if (FP) {   // canonical operands (< q < 2^47) as doubles; P * b first: fp_modmul wants its second factor in [0, q)
+                    const double a0 = u52_to_double(va0[j]), a1 = u52_to_double(va1[j]);
+                    const double b0 = u52_to_double(vb0[j]), b1 = u52_to_double(vb1[j]);
+                    const double d2 = fp_modmul(a1, b1, L.q, L.qinv);
+                    const double p0 = fp_modmul(b0, pd, L.q, L.qinv), p1 = fp_modmul(b1, pd, L.q, L.qinv);
+                    acc0[e] = d_to_bits(d_from_bits(acc0[e]) + fp_modmul(d2, d_from_bits(ka[j]), L.q, L.qinv) +
+                                        fp_modmul(p0, a0, L.q, L.qinv));
+                    acc1[e] = d_to_bits(d_from_bits(acc1[e]) + fp_modmul(d2, d_from_bits(kb[j]), L.q, L.qinv) +
+                                        fp_modmul(p1, a0, L.q, L.qinv) + fp_modmul(p0, a1, L.q, L.qinv));
+                } else {
+                    const u64 d2 = mont_mul_lazy(va1[j], mont_mul_lazy(vb1[j], L.md.r2, q, qinv), q, qinv);   // a1 b1, [0, 2q)
+                    const u64 p0 = mont_mul_lazy(vb0[j], pm, q, qinv), p1 = mont_mul_lazy(vb1[j], pm, q, qinv);   // b P 2^64
+                    u64 s0 = csub_sign(acc0[e] + mont_mul_lazy(d2, ka[j], q, qinv), 0 - 2 * q);
+                    u64 s1 = csub_sign(acc1[e] + mont_mul_lazy(d2, kb[j], q, qinv), 0 - 2 * q);
+                    s1 = csub_sign(s1 + mont_mul_lazy(va0[j], p1, q, qinv), 0 - 2 * q);
+                    acc0[e] = csub_sign(s0 + mont_mul_lazy(va0[j], p0, q, qinv), 0 - 2 * q);
+                    acc1[e] = csub_sign(s1 + mont_mul_lazy(va1[j], p0, q, qinv), 0 - 2 * q);
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int m0 = 0; m0 < 8; m0 += CH) {
         u64 v[2 * CH], ka[2 * CH], kb[2 * CH];

@@ -140,16 +140,18 @@ static KsWorkspace ks_layout(const Context& c, int level, int nb, u64* ws) {
 // step 4 of a key switch on the digits that ks_decompose left in the workspace: the gadget inner product with the key (both
 // halves) -> w.acc, [2][L+k][N] over Q_level u P, NTT domain; fused with the extension transform's second pass when
 // ks_decompose stopped after the first one
+// fold: the tensor product folded into the MAC (TensorFold; cx is then d2 and only the decomposition reads it)
 static void ks_mac(Context& c, int level, const u64* cx, long long scx, const Key& key, int nb, u64* ws, hipStream_t s,
-                   bool ext_first_pass_only) {
+                   bool ext_first_pass_only, const TensorFold* fold = nullptr) {
     const KsWorkspace w = ks_layout(c, level, nb, ws);
     if (ext_first_pass_only) {
         const int eng = ks_fused_engines(c);
-        LSA_REQUIRE(launch_ntt_ksmac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s, eng), "fused key MAC: shape not covered");
+        LSA_REQUIRE(launch_ntt_ksmac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s, eng, fold),
+                    "fused key MAC: shape not covered");
         for (int e = 0; e < 2; e++)
-            if (!((eng >> e) & 1)) launch_ks_mac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s, e);
+            if (!((eng >> e) & 1)) launch_ks_mac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s, e, nullptr, nullptr, 0, fold);
     } else {
-        launch_ks_mac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s);
+        launch_ks_mac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s, -1, nullptr, nullptr, 0, fold);
     }
 }
 
@@ -228,20 +230,26 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
         return;
     }
     if (rs) {
-        LSA_REQUIRE(c.fuse_tails && level >= 1 && base && base_polys == 2, "merged ModDown+rescale: unsupported shape");
+        // base_polys == 0: the tensor fold -- P * base is already in acc's Q rows (TensorFold), so INTT(acc_l) * P^-1 carries
+        // INTT(base_l) and the tails below run without base
+        LSA_REQUIRE(c.fuse_tails && level >= 1 && ((base && base_polys == 2) || (!base && base_polys == 0)),
+                    "merged ModDown+rescale: unsupported shape");
         const int l = level;
         // t[h] = (INTT(acc[h][l]) - conv[h][l]) * P^-1 + INTT(base[h][l]) -> p[h][l].  base is the caller's scratch here
         // (the tensor output): its last limbs are transformed in place, nothing reads them in NTT form afterwards.
-        u64* base_rw = const_cast<u64*>(base);
-        RowMap rb;
-        rb.period = 1;
-        rb.mod_of[0] = (unsigned char)l;
-        rb.row0 = l;
-        rb.row_step = base_rpp;
-        launch_ntt(c, base_rw, base_rw, nb, sbase, sbase, 2, rb, true, s);
+        if (base) {
+            u64* base_rw = const_cast<u64*>(base);
+            RowMap rb;
+            rb.period = 1;
+            rb.mod_of[0] = (unsigned char)l;
+            rb.row0 = l;
+            rb.row_step = base_rpp;
+            launch_ntt(c, base_rw, base_rw, nb, sbase, sbase, 2, rb, true, s);
+        }
         const unsigned char lm[1] = {(unsigned char)l};
         launch_sub_mul_general(c, 2, 1, lm, c.pinv_vec(level) + l, acc + (long long)l * N, s_acc, T, conv + (long long)l * N,
-                               s_conv, L, base + (long long)l * N, sbase, base_rpp, 2, p + (long long)l * N, sp, L, nb, s);
+                               s_conv, L, base ? base + (long long)l * N : nullptr, sbase, base_rpp, base_polys,
+                               p + (long long)l * N, sp, L, nb, s);
         // every other limb: in = conv_j*P^-1 + lift_j(t), out = (acc_j*P^-1 - NTT(in) + base_j) * q_l^-1
         RowMap rmo;
         rmo.period = 2 * L;
@@ -573,6 +581,18 @@ void ckks_mult_relin_rescale(Context& c, int level, const u64* a, const u64* b, 
                              long long sa, long long sb, long long so, hipStream_t s) {
     ckks_mult_relin_rescale_rpp(c, level, a, b, rlk, out, batch, sa, sb, so, s, 0, 0);
 }
+// Tensor fold (fused tails; LSA_HMULT_FOLD=0 keeps the three steps apart, read per call: the parity tests flip it inside one
+// process).  d0, d1 and d2 = k_tensor's outputs are each read again by one consumer only, and each consumer can take them
+// from a and b itself, residue for residue:
+//   ModUp input  d2 = a1 b1                   (k_tensor_d2: L rows written instead of 3L, 2 operand polynomials read instead of 4)
+//   MAC          own digit of Q target j: d2_j = a1_j b1_j, and acc'_j = acc_j + P * d_j  (d = (d0, d1), TensorFold)
+//   ModDown      (acc'_j * P^-1 - NTT(in)) * q_l^-1 = (acc_j * P^-1 - NTT(in) + d_j) * q_l^-1;
+//                INTT(acc'_l) * P^-1 = INTT(acc_l) * P^-1 + INTT(d_l)       (the merged tail with base_polys = 0)
+static bool hmult_fold_on() {
+    const char* e = std::getenv("LSA_HMULT_FOLD");
+    return !(e && e[0] == '0');
+}
+
 // a_rpp / b_rpp: rows per polynomial of a / b when an operand sits at a higher level than `level` (0: level + 1) -- its leading
 // rows ARE the operand at this level, so callers with operands at mixed levels (polynomial evaluation) need no copies
 void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch,
@@ -580,13 +600,27 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
     LSA_REQUIRE(level >= 1, "mult+relin+rescale needs level >= 1");
     const long long N = c.n;
     const int L = level + 1;
-    const size_t r_d3 = 3 * (size_t)L, r_r2 = 2 * (size_t)L;
+    const bool fold = c.fuse_tails && hmult_fold_on();
+    const size_t r_d3 = (fold ? 1 : 3) * (size_t)L, r_r2 = 2 * (size_t)L;
     const size_t r_shared = std::max(ks_ws_rows(c, level), rescale_ws_rows(level, 2));
-    const long long sd = 3LL * L * N, sr = 2LL * L * N;
+    const long long sd = (long long)r_d3 * N, sr = 2LL * L * N;
     for_tiles(c, r_d3 + r_r2 + r_shared, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* d3 = ws;
         u64* r2 = d3 + r_d3 * N * tb;
         u64* sub = r2 + r_r2 * N * tb;
+        if (fold) {
+            const u64* ta = a + (size_t)b0 * sa;
+            const u64* bt = b + (size_t)b0 * sb;
+            launch_tensor_d2(c, ta, bt, d3, nb, sa, sb, sd, L, st, a_rpp, b_rpp);
+            const TensorFold tf{ta, bt, sa, sb, (long long)(a_rpp ? a_rpp : L) * N, (long long)(b_rpp ? b_rpp : L) * N};
+            const bool fuse = ks_fuse_mac(c, level, rlk);
+            ks_decompose(c, level, d3, sd, nb, sub, st, nullptr, 0, !fuse);
+            ks_mac(c, level, d3, sd, rlk, nb, sub, st, fuse, &tf);
+            const KsWorkspace w = ks_layout(c, level, nb, sub);
+            const KsRescale rs{out + (size_t)b0 * so, so};
+            ks_moddown(c, level, w.acc, w.s_acc, w.conv, r2, sr, nullptr, 0, 0, 0, nb, st, &rs, false);
+            return;
+        }
         launch_tensor(c, a + (size_t)b0 * sa, b + (size_t)b0 * sb, d3, nb, sa, sb, sd, L, rm_seq(L), st, a_rpp, b_rpp);
         if (c.fuse_tails) {
             const KsRescale rs{out + (size_t)b0 * so, so};
