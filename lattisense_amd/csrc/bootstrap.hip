@@ -23,21 +23,6 @@
 
 namespace lsa {
 
-void ckks_rescale(Context&, int, int, const u64*, u64*, int, long long, long long, hipStream_t);
-void ckks_rotate(Context&, int, const u64*, u64, const Key&, u64*, int, long long, long long, hipStream_t);
-void ckks_switch_key(Context&, int, const u64*, const Key&, u64*, int, long long, long long, hipStream_t);
-void ckks_rotate_many(Context&, int, const u64*, int, const u64*, const Key* const*, u64* const*, int, long long, long long,
-                      hipStream_t);
-void ckks_mult_relin_rescale(Context&, int, const u64*, const u64*, const Key&, u64*, int, long long, long long, long long,
-                             hipStream_t);
-void ckks_mult_relin_rescale_rpp(Context&, int, const u64*, const u64*, const Key&, u64*, int, long long, long long, long long,
-                                 hipStream_t, int, int);
-void ckks_lift_ext(Context&, int, const u64*, u64*, int, long long, long long, hipStream_t);
-void ckks_rotate_many_ext(Context&, int, const u64*, int, const u64*, const Key* const*, u64* const*, int, long long, long long,
-                          hipStream_t);
-void ckks_rotate_ext(Context&, int, const u64*, u64, const Key&, u64*, bool, int, long long, long long, hipStream_t);
-void ckks_moddown_ext(Context&, int, u64*, u64*, int, long long, long long, hipStream_t);
-
 using cplx = std::complex<double>;
 using Diags = std::map<int, std::vector<cplx>>;   // diagonal k: d[t] multiplies x[(t + k) mod n]
 

@@ -6,23 +6,6 @@
 namespace lsa {
 const char* kernels_build_flags();   // kernels.hip / context.hip: what THOSE translation units were compiled with
 const char* context_build_flags();
-void ckks_mult(Context&, int, const u64*, const u64*, u64*, int, long long, long long, long long, hipStream_t);
-void ckks_relin(Context&, int, const u64*, const Key&, u64*, int, long long, long long, hipStream_t);
-void ckks_rescale(Context&, int, int, const u64*, u64*, int, long long, long long, hipStream_t);
-void ckks_rotate(Context&, int, const u64*, u64, const Key&, u64*, int, long long, long long, hipStream_t);
-void ckks_rotate_many(Context&, int, const u64*, int, const u64*, const Key* const*, u64* const*, int, long long, long long,
-                      hipStream_t);
-void ckks_mult_relin_rescale(Context&, int, const u64*, const u64*, const Key&, u64*, int, long long, long long,
-                             long long, hipStream_t);
-void drop_level(Context&, int, int, const u64*, u64*, int, long long, long long, hipStream_t);
-void poly_addsub(Context&, int, int, int, const u64*, const u64*, u64*, int, long long, long long, long long,
-                 hipStream_t);
-void bfv_mult(Context&, int, const u64*, const u64*, u64*, int, long long, long long, long long, hipStream_t);
-void bfv_relin(Context&, int, const u64*, const Key&, u64*, int, long long, long long, hipStream_t);
-void bfv_rotate(Context&, int, const u64*, u64, const Key&, u64*, int, long long, long long, hipStream_t);
-void bfv_rotate_many(Context&, int, const u64*, int, const u64*, const Key* const*, u64* const*, int, long long, long long,
-                     hipStream_t);
-void bfv_rescale(Context&, int, int, const u64*, u64*, int, long long, long long, hipStream_t);
 }  // namespace lsa
 
 using namespace lsa;
@@ -180,11 +163,7 @@ int lsa_event_destroy(lsa_context ctx, void* ev) {
 
 // ---- keys
 size_t lsa_key_bytes(lsa_context ctx, int key_level) {
-    if (!ctx) return 0;
-    const Context& c = ctx->ctx;
-    if (c.np < 1 || key_level < 0 || key_level >= c.nq) return 0;
-    const size_t beta = (key_level + 1 + c.np - 1) / c.np;
-    return beta * 2 * (size_t)(key_level + 1 + c.np) * c.n * sizeof(u64);
+    return ctx ? key_layout(ctx->ctx, key_level).words * sizeof(u64) : 0;
 }
 
 struct lsa_key_fp_owner;   // (see lsa_key_st::fp_owned)
@@ -193,17 +172,13 @@ int lsa_key_upload(lsa_context ctx, const uint64_t* compact_host, int key_level,
     return guard([&] {
         Context& c = C(ctx);
         LSA_REQUIRE(out != nullptr && compact_host != nullptr, "null argument");
-        const size_t bytes = lsa_key_bytes(ctx, key_level);
-        LSA_REQUIRE(bytes > 0, "bad key level (or context has no special primes)");
+        const KeyLayout kl = key_layout(c, key_level);
+        LSA_REQUIRE(kl.words > 0, "bad key level (or context has no special primes)");
         auto k = std::make_unique<lsa_key_st>();
-        k->key.level = key_level;
         k->key.owned = true;
-        const bool with_fp = ks_fused_enabled(c);   // the double copy sits behind the key in the same allocation
-        LSA_HIP(hipMalloc((void**)&k->key.data, with_fp ? 2 * bytes : bytes));
-        LSA_HIP(hipMemcpyAsync(k->key.data, compact_host, bytes, hipMemcpyHostToDevice, S(stream)));
-        double* fp = with_fp ? reinterpret_cast<double*>(k->key.data + bytes / sizeof(u64)) : nullptr;
-        launch_key_prepare(c, k->key.data, fp, key_level, S(stream));
-        k->key.fp = fp;
+        LSA_HIP(hipMalloc((void**)&k->key.data, kl.alloc_words() * sizeof(u64)));   // the double copy, if any, behind the key
+        LSA_HIP(hipMemcpyAsync(k->key.data, compact_host, kl.words * sizeof(u64), hipMemcpyHostToDevice, S(stream)));
+        key_prepare(c, k->key, k->key.data, key_level, kl.fp_of(k->key.data), S(stream));
         LSA_HIP(hipStreamSynchronize(S(stream)));  // host buffer may be released by the caller on return
         *out = k.release();
     });
@@ -212,17 +187,13 @@ int lsa_key_adopt_device(lsa_context ctx, uint64_t* compact_dev, int key_level, 
     return guard([&] {
         Context& c = C(ctx);
         LSA_REQUIRE(out != nullptr && compact_dev != nullptr, "null argument");
-        const size_t bytes = lsa_key_bytes(ctx, key_level);
-        LSA_REQUIRE(bytes > 0, "bad key level (or context has no special primes)");
+        const KeyLayout kl = key_layout(c, key_level);
+        LSA_REQUIRE(kl.words > 0, "bad key level (or context has no special primes)");
         auto k = std::make_unique<lsa_key_st>();
-        k->key.level = key_level;
         k->key.owned = false;
-        k->key.data = compact_dev;
-        if (ks_fused_enabled(c)) {   // the caller's buffer has no room: the double copy is this handle's own allocation
-            LSA_HIP(hipMalloc((void**)&k->fp_owned, bytes));
-            k->key.fp = k->fp_owned;
-        }
-        launch_key_prepare(c, k->key.data, k->fp_owned, key_level, S(stream));
+        if (kl.fp)   // the caller's buffer has no room: the double copy is this handle's own allocation
+            LSA_HIP(hipMalloc((void**)&k->fp_owned, kl.words * sizeof(double)));
+        key_prepare(c, k->key, compact_dev, key_level, k->fp_owned, S(stream));
         *out = k.release();
     });
 }

@@ -355,8 +355,10 @@ int ks_fused_engines(const Context& c) {
     return c.fp64_ntt ? e : 0;
 }
 
+bool ks_fused_limb(const Context& c, int L, int tl) { return (ks_fused_engines(c) >> (c.fp_engine(c.qp_mod(L, tl)) ? 1 : 0)) & 1; }
+
 bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* ext, long long sext, const Key& key, u64* acc,
-                      long long sacc, int batch, hipStream_t s, int engines, const TensorFold* fold) {
+                      long long sacc, int batch, hipStream_t s, const TensorFold* fold) {
     if (batch <= 0) return true;
     if (!ks_fused_enabled(c) || (c.fp64_ntt && !key.fp)) return false;
     LSA_REQUIRE(key.level >= level, "key-switch key exported at a lower level than the ciphertext");
@@ -400,9 +402,7 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
         g.n_tl = 0;
         int transforms = 0, q_targets = 0;
         for (int tl = 0; tl < T; tl++) {
-            const int mi = tl < g.L ? tl : c.p_mod(tl - g.L);
-            const bool fp = c.fp64_ntt && (c.T.mod[mi] >> LSA_FP64_MAX_BITS) == 0;
-            if ((int)fp != eng || !((engines >> eng) & 1)) continue;
+            if (!ks_fused_limb(c, g.L, tl) || (int)c.fp_engine(c.qp_mod(g.L, tl)) != eng) continue;
             g.tl_list[g.n_tl++] = (unsigned char)tl;
             transforms += g.beta - (tl < g.L ? 1 : 0);
             q_targets += tl < g.L;
@@ -564,7 +564,7 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
         for (int r = 0; r < rows; r++) {
             const unsigned char m = rm.mod_of[(rm.row0 + r * rm.row_step) % rm.period];
             if (m == LSA_ROW_SKIP) continue;
-            const bool fp = c.fp64_ntt && (c.T.mods[m].q >> LSA_FP64_MAX_BITS) == 0;
+            const bool fp = c.fp_engine(m);
             any_fp |= fp;
             any_int |= !fp;
         }
@@ -1639,11 +1639,11 @@ static void launch_ks_mac_kb(int beta, dim3 grid, hipStream_t s, const KsMacArgs
 // scatter (with engine < 0): the result is written as the rotated extended ciphertext perm(acc + P * c0) -- scatter = the index
 // map of the rotation's inverse element, base = the ciphertext whose c0 enters (see KsMacArgs)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, const Key& key,
-                   u64* acc, long long sacc, int batch, hipStream_t s, int engine, const u32* scatter, const u64* base, long long sbase,
+                   u64* acc, long long sacc, int batch, hipStream_t s, bool unfused_only, const u32* scatter, const u64* base, long long sbase,
                    const TensorFold* fold) {
     if (batch <= 0) return;
     KsMacArgs g{};
-    LSA_REQUIRE(!scatter || (engine < 0 && base), "key MAC: the extended output covers every target limb and needs the ciphertext");
+    LSA_REQUIRE(!scatter || (!unfused_only && base), "key MAC: the extended output covers every target limb and needs the ciphertext");
     LSA_REQUIRE(!(scatter && fold), "key MAC: the tensor fold has no extended output");
     if (fold) {
         g.fa = fold->a;
@@ -1677,13 +1677,10 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
     g.kcomp = key.level + 1 + c.np;
     LSA_REQUIRE(key.level >= level, "key-switch key exported at a lower level than the ciphertext");
     int targets = g.L + c.np;
-    if (engine >= 0) {   // only the target limbs of one butterfly engine (the others went through the fused kernel)
+    if (unfused_only) {   // the others went through the fused kernel
         LSA_REQUIRE(targets <= 64, "key MAC: too many target limbs for a subset launch");
-        for (int tl = 0; tl < targets; tl++) {
-            const int mi = tl < g.L ? tl : c.p_mod(tl - g.L);
-            const bool fp = c.fp64_ntt && (c.T.mod[mi] >> LSA_FP64_MAX_BITS) == 0;
-            if ((int)fp == engine) g.tl_list[g.n_tl++] = (unsigned char)tl;
-        }
+        for (int tl = 0; tl < targets; tl++)
+            if (!ks_fused_limb(c, g.L, tl)) g.tl_list[g.n_tl++] = (unsigned char)tl;
         if (!g.n_tl) return;
         targets = g.n_tl;
     }
@@ -2081,7 +2078,7 @@ void launch_permute_ext(Context& c, int level, const u32* perm, const u64* acc, 
     g.accumulate = accumulate ? 1 : 0;
     g.base_polys = base_polys;
     g.pm = c.pmodq_vec(level);
-    for (int tl = 0; tl < T; tl++) g.mod_of[tl] = (unsigned char)(tl < L ? tl : c.p_mod(tl - L));
+    for (int tl = 0; tl < T; tl++) g.mod_of[tl] = (unsigned char)c.qp_mod(L, tl);
     const double streams = (acc ? 1.0 : 0.0) * 2 * T + (double)base_polys * L + (accumulate ? 2.0 : 1.0) * 2 * T;
     ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * streams * batch, s);
     hipLaunchKernelGGL(k_permute_ext, ew_grid(c, 2 * T, batch), dim3(TPB), 0, s, g);
@@ -2171,12 +2168,12 @@ void launch_to_mont(Context& c, u64* data, int rows, const RowMap& rm, hipStream
 }
 
 // a freshly loaded key: plain residues -> Montgomery form in place, and (fp != null) the same values as doubles for the limbs
-// the FP64 engine serves
+// the FP64 engine can serve -- whether it is switched on or not (lsa_set_fp64_ntt may turn it on after the upload)
 struct KeyPrepArgs {
     u64* data;
     double* fp;
     const ModDev* mods;
-    int logn, period, allow_fp64;
+    int logn, period;
     unsigned char mod_of[LSA_MAX_PERIOD];
 };
 __global__ __launch_bounds__(TPB) void k_key_prepare(KeyPrepArgs g) {
@@ -2188,15 +2185,23 @@ __global__ __launch_bounds__(TPB) void k_key_prepare(KeyPrepArgs g) {
     const ulonglong2 v = ld2(g.data + off);
     st2(g.data + off, mont_mul(v.x, m.r2, m.q, m.qinv), mont_mul(v.y, m.r2, m.q, m.qinv));
     if (g.fp) {
-        const bool fp = g.allow_fp64 && (m.q >> LSA_FP64_MAX_BITS) == 0;
+        const bool fp = (m.q >> LSA_FP64_MAX_BITS) == 0;
         double2 d;
         d.x = fp ? (double)v.x : 0.0;
         d.y = fp ? (double)v.y : 0.0;
         *reinterpret_cast<double2*>(g.fp + off) = d;
     }
 }
-void launch_key_prepare(Context& c, u64* data, double* fp, int key_level, hipStream_t s) {
+KeyLayout key_layout(const Context& c, int key_level) {
+    KeyLayout k;
+    if (c.np < 1 || key_level < 0 || key_level >= c.nq) return k;
     const int comp = key_level + 1 + c.np, beta = (key_level + 1 + c.np - 1) / c.np;
+    k.words = (size_t)beta * 2 * comp * c.n;
+    k.fp = ks_fused_enabled(c);
+    return k;
+}
+void key_prepare(Context& c, Key& key, u64* data, int key_level, double* fp, hipStream_t s) {
+    const int comp = key_level + 1 + c.np;
     LSA_REQUIRE(comp <= LSA_MAX_PERIOD, "key has too many limbs");
     KeyPrepArgs g{};
     g.data = data;
@@ -2204,10 +2209,12 @@ void launch_key_prepare(Context& c, u64* data, double* fp, int key_level, hipStr
     g.mods = c.d_mods;
     g.logn = c.logn;
     g.period = comp;
-    g.allow_fp64 = c.fp64_ntt;
-    for (int j = 0; j < comp; j++) g.mod_of[j] = (unsigned char)(j <= key_level ? j : c.p_mod(j - key_level - 1));
-    hipLaunchKernelGGL(k_key_prepare, ew_grid(c, beta * 2 * comp, 1), dim3(TPB), 0, s, g);
+    for (int j = 0; j < comp; j++) g.mod_of[j] = (unsigned char)c.qp_mod(key_level + 1, j);
+    hipLaunchKernelGGL(k_key_prepare, ew_grid(c, (int)(key_layout(c, key_level).words >> c.logn), 1), dim3(TPB), 0, s, g);   // [beta][2][comp] rows
     LSA_HIP(hipGetLastError());
+    key.data = data;
+    key.level = key_level;
+    key.fp = fp;
 }
 
 // ------------------------------------------------------------------------------------------------ ring-t plaintext lifts (K11)

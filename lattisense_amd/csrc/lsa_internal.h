@@ -147,6 +147,8 @@ struct Context {
     u64* workspace2(size_t words, hipStream_t s);
     int p_mod(int i) const { return nq + i; }
     int aux_mod(int i) const { return nq + np + i; }
+    int qp_mod(int L, int tl) const { return tl < L ? tl : p_mod(tl - L); }   // row tl of Q_level u P (L = level + 1) -> modulus
+    bool fp_engine(int mod) const { return fp64_ntt && (T.mod[mod] >> LSA_FP64_MAX_BITS) == 0; }   // FP64 butterflies serve it
     // pinv_scaled: the outputs of every target but the last are multiplied by P^-1 mod p_j (merged ModDown + rescale)
     // fold: element-wise steps on either side of a conversion folded into its constants (both linear, so the residues are the
     // ones the separate steps give): src_pre[i] multiplies source limb i BEFORE the conversion (the centring offset and
@@ -262,18 +264,6 @@ void launch_mac_plain_multi(Context& c, int nb, const u64* const* ct, const long
 // unfused form (k_mont_muladd); acc / a may be out
 void launch_mont_muladd(Context& c, const u64* a, long long sa, const u64* pt, long long spt, const u64* acc, long long sacc,
                         u64* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s);
-// BFV ct x pt_mul (NTT-domain, Montgomery-form plaintexts [L][N], ops.hip): out = ct . pt per poly; out may be ct
-void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64* out, int batch, long long sct, long long spt,
-                        long long sout, hipStream_t s);
-// out = sum_i cts[i] . pts[i] (+ partial), n >= 1 terms, one inverse transform per output; out overlaps no input
-void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
-                       const long long* spts, const u64* partial, long long spartial, u64* out, int batch, long long sout,
-                       hipStream_t s);
-// out = sum_{i<n} rot_{g[i]}(in) . pts[i] (+ partial), g[i] == 1: the input itself (no key); every output bit-identical to
-// bfv_rotate_many + bfv_mac_plain_mul on the same terms, rotations kept in the NTT domain (fz_epi = 4); out overlaps no input
-void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const u64* g, const Key* const* glk,
-                              const u64* const* pts, const long long* spts, const u64* partial, long long spartial, u64* out,
-                              int batch, long long sin, long long sout, hipStream_t s);
 // ring-t plaintext limb -> [level+1][N] residues: mode 0 centred lift from q_0 (CKKS), 1 direct (BFV multiply),
 // 2 scale-up by Q/t (BFV add/sub)
 void launch_lift_ringt(Context& c, int mode, int level, const u64* pt, long long spt, u64* out, long long sout, int batch,
@@ -307,11 +297,11 @@ void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows
                      long long ssrc, long long sdst, hipStream_t s, const u64* sub = nullptr, long long ssub = 0,
                      const int* sub_row = nullptr);
 // key-switch inner product: acc[h][tl] = sum_d ext(d,tl) * key[d][h][tl];  ext(d,tl) = cx[tl] when tl is in digit d
-// engine: -1 every target limb; 0 / 1 only the target limbs of the integer / FP64 butterfly engine
-// scatter (engine -1 only): the result leaves as the ROTATED EXTENDED ciphertext acc[h][tl][scatter[x]] = sum(x) + (h == 0, tl < L:
+// unfused_only: only the target limbs that do not take the fused kernel (ks_fused_limb; k_ntt_r16_ksmac did the others)
+// scatter (every target limb only): the result leaves as the ROTATED EXTENDED ciphertext acc[h][tl][scatter[x]] = sum(x) + (h == 0, tl < L:
 // P * base[tl][x]) -- gadget product, c0 * P and the automorphism of a baby-step rotation in one pass
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext,
-                   const Key& key, u64* acc, long long sacc, int batch, hipStream_t s, int engine = -1,
+                   const Key& key, u64* acc, long long sacc, int batch, hipStream_t s, bool unfused_only = false,
                    const u32* scatter = nullptr, const u64* base = nullptr, long long sbase = 0,
                    const TensorFold* fold = nullptr);
 // out[h][i] = base[h][i] + (acc[h][i] - conv[h][i]) * Pinv_i       (base may be null)
@@ -347,14 +337,24 @@ void launch_permute_ext(Context& c, int level, const u32* perm, const u64* acc, 
 void launch_copy_rows(Context& c, const u64* in, long long sin, u64* out, long long sout, int rows, const int* src_row,
                       int batch, hipStream_t s);
 void launch_to_mont(Context& c, u64* data, int rows, const RowMap& rm, hipStream_t s);
-// a freshly loaded key (plain residues, compact order) -> Montgomery form in place (+ the double copy when fp != nullptr)
-void launch_key_prepare(Context& c, u64* data, double* fp, int key_level, hipStream_t s);
 bool ks_fused_enabled(const Context& c);   // the fused second-pass + key-MAC kernel applies to this context (and is not switched off)
-// second pass of the extension transform + gadget inner product in one launch (see k_ntt_r16_ksmac); false = shape not covered
-// engines: bit 0 integer-engine target limbs, bit 1 FP64-engine target limbs
+// a key-switch key on the device: `words` u64 in compact order [beta][2][key_level+1+np][N]; where the fused key MAC applies
+// (ks_fused_enabled) the key's double copy follows in the same allocation, `words` doubles more (words = 0: no such key)
+struct KeyLayout {
+    size_t words = 0;
+    bool fp = false;
+    size_t alloc_words() const { return fp ? 2 * words : words; }
+    double* fp_of(u64* data) const { return fp ? reinterpret_cast<double*>(data + words) : nullptr; }
+};
+KeyLayout key_layout(const Context& c, int key_level);
+// a freshly loaded key at `data` (plain residues) -> key: Montgomery form in place, its double copy written to `fp` (null: none)
+void key_prepare(Context& c, Key& key, u64* data, int key_level, double* fp, hipStream_t s);
+// second pass of the extension transform + gadget inner product in one launch (see k_ntt_r16_ksmac) for the target limbs that
+// take it (ks_fused_limb); false = shape not covered
 bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* ext, long long sext, const Key& key, u64* acc,
-                      long long sacc, int batch, hipStream_t s, int engines = 3, const TensorFold* fold = nullptr);
+                      long long sacc, int batch, hipStream_t s, const TensorFold* fold = nullptr);
 int ks_fused_engines(const Context& c);   // which engines' target limbs take the fused kernel (LSA_KS_FUSED_ENGINES, default FP64 only)
+bool ks_fused_limb(const Context& c, int L, int tl);   // target limb tl of Q_level u P takes it (by its engine)
 // out = (a - b) * k_i  with per-row constant (Montgomery form) ; out = a * k_i
 void launch_sub_mul_const(Context& c, const u64* a, long long sa, const u64* b, long long sb, const u64* kvec, u64* out,
                           long long so, int rows, const RowMap& rm, int batch, hipStream_t s);
@@ -386,5 +386,53 @@ void bootstrap_run(Bootstrap& bt, const u64* in, long long sin, u64* out, long l
 
 // ---------------------------------------------------------------- operator pipelines (ops.hip)
 const std::string& last_error();
+void ckks_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int batch, long long sa, long long sb, long long sd,
+               hipStream_t s);
+void ckks_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, int batch, long long sd, long long so,
+                hipStream_t s);
+void ckks_rescale(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
+                  hipStream_t s);
+void ckks_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, int batch, long long sin,
+                 long long sout, hipStream_t s);
+void ckks_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
+                      int batch, long long sin, long long sout, hipStream_t s);
+void ckks_switch_key(Context& c, int level, const u64* in, const Key& swk, u64* out, int batch, long long sin, long long sout,
+                     hipStream_t s);
+void ckks_mult_relin_rescale(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch,
+                             long long sa, long long sb, long long so, hipStream_t s);
+void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch,
+                                 long long sa, long long sb, long long so, hipStream_t s, int a_rpp, int b_rpp);
+void ckks_lift_ext(Context& c, int level, const u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
+void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
+                          int batch, long long sin, long long sout, hipStream_t s);
+void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, bool accumulate, int batch,
+                     long long sin, long long sout, hipStream_t s);
+void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
+void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
+                hipStream_t s);
+void poly_addsub(Context& c, int op, int level, int polys, const u64* a, const u64* b, u64* out, int batch, long long sa,
+                 long long sb, long long so, hipStream_t s);
+void bfv_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int batch, long long sa, long long sb, long long sd,
+              hipStream_t s);
+void bfv_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, int batch, long long sd, long long so,
+               hipStream_t s);
+void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, int batch, long long sin,
+                long long sout, hipStream_t s);
+void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
+                     int batch, long long sin, long long sout, hipStream_t s);
+void bfv_rescale(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
+                 hipStream_t s);
+// BFV ct x pt_mul (NTT-domain, Montgomery-form plaintexts [L][N]): out = ct . pt per poly; out may be ct
+void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64* out, int batch, long long sct, long long spt,
+                        long long sout, hipStream_t s);
+// out = sum_i cts[i] . pts[i] (+ partial), n >= 1 terms, one inverse transform per output; out overlaps no input
+void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
+                       const long long* spts, const u64* partial, long long spartial, u64* out, int batch, long long sout,
+                       hipStream_t s);
+// out = sum_{i<n} rot_{g[i]}(in) . pts[i] (+ partial), g[i] == 1: the input itself (no key); every output bit-identical to
+// bfv_rotate_many + bfv_mac_plain_mul on the same terms, rotations kept in the NTT domain (fz_epi = 4); out overlaps no input
+void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const u64* g, const Key* const* glk,
+                              const u64* const* pts, const long long* spts, const u64* partial, long long spartial, u64* out,
+                              int batch, long long sin, long long sout, hipStream_t s);
 
 }  // namespace lsa

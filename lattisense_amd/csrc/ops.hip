@@ -21,11 +21,6 @@ static RowMap rm_seq(int count, int first = 0) {
 static int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // ------------------------------------------------------------------------------------------------ key switch
-static size_t ks_ws_rows(const Context& c, int level) {
-    const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
-    return (size_t)L + (size_t)beta * T + 2 * (size_t)T + 2 * (size_t)L;
-}
-
 // Merged tail: the key-switch result is rescaled straight away (CKKS HMult+relin+rescale).  ModDown ends with
 // c_j = (acc_j - NTT(conv_j)) * P^-1 + base_j and the rescale continues with (c_j - NTT(lift_j(t))) * q_l^-1, t = INTT(c_l).
 // Modular arithmetic being exact and the transforms linear, residue for residue
@@ -38,157 +33,43 @@ struct KsRescale {
     long long sout;
 };
 
-// p[h][i] = (h < base_polys ? base[h][i] : 0) + ModDown( sum_d ModUp_d(cx) * key_d[h] )[i]   (all NTT domain)
-// With `rs` (needs fused tails): p is scratch of the same shape and rs->out receives rescale(p).
-static void ks_finish(Context& c, int level, const u64* cx, long long scx, const Key& key, u64* p, long long sp,
-                      const u64* base, long long sbase, int base_rpp, int base_polys, int nb, u64* ws, hipStream_t s,
-                      const KsRescale* rs, bool coeff_out = false, bool ext_first_pass_only = false, const u32* scatter = nullptr);
-
-// steps 1-3: cx out of the NTT domain, every digit converted to the other limbs of Q u P, extended limbs back into the
-// NTT domain (workspace layout: cxi | ext | acc | conv).  cx_coef: the same polynomial in the coefficient domain if the
-// caller has it (BFV): the inverse transform is skipped.
-// second_pass = false: the extended limbs are left in first-pass form for the fused second pass + key MAC (ks_finish)
-static void ks_decompose(Context& c, int level, const u64* cx, long long scx, int nb, u64* ws, hipStream_t s,
-                         const u64* cx_coef = nullptr, long long s_coef = 0, bool second_pass = true) {
-    LSA_REQUIRE(c.np >= 1, "key switching needs at least one special prime");
-    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
-    const long long N = c.n;
-    const int L = level + 1, np = c.np, T = L + np, beta = ceil_div(L, np);
-    u64* cxi = ws;
-    u64* ext = cxi + (size_t)nb * L * N;
-    const long long s_cxi = (long long)L * N, s_ext = (long long)beta * T * N;
-
-    // 1. cx out of the NTT domain
-    const u64* conv_src = cxi;
-    long long s_src = s_cxi;
-    if (cx_coef) {
-        conv_src = cx_coef;
-        s_src = s_coef;
-    } else {
-        launch_ntt(c, cx, cxi, nb, scx, s_cxi, L, rm_seq(L), true, s);
-    }
-    // 2. per digit: exact conversion of the digit's limbs to every other limb of Q u P
-    auto tl_mod = [&](int tl) { return tl < L ? tl : c.p_mod(tl - L); };
-    for (int d = 0; d < beta; d++) {
-        const int d0 = d * np, d1 = std::min(d0 + np, L);
-        std::vector<int> src, dst;
-        BaseConvRows rows{};
-        for (int i = d0; i < d1; i++) {
-            rows.src_row[i - d0] = i;
-            src.push_back(i);
-        }
-        for (int tl = 0; tl < T; tl++) {
-            if (tl >= d0 && tl < d1) continue;
-            rows.dst_row[dst.size()] = d * T + tl;
-            dst.push_back(tl_mod(tl));
-        }
-        launch_baseconv(c, c.baseconv(src, dst, false), rows, conv_src, ext, nb, s_src, s_ext, s);
-    }
-    // 3. extended limbs into the NTT domain (the digit's own limbs are taken from cx directly by the MAC)
-    if (beta * T <= LSA_MAX_PERIOD) {
-        RowMap rm;
-        rm.period = beta * T;
-        for (int d = 0; d < beta; d++)
-            for (int tl = 0; tl < T; tl++) {
-                const bool own = tl >= d * np && tl < std::min((d + 1) * np, L);
-                rm.mod_of[d * T + tl] = own ? LSA_ROW_SKIP : (unsigned char)tl_mod(tl);
-            }
-        launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, second_pass ? 3 : 1);
-        if (!second_pass && ks_fused_engines(c) != 3) {
-            // the target limbs whose engine does not take the fused kernel get their second pass here (stand-alone MAC later)
-            RowMap r2 = rm;
-            bool any = false;
-            for (int i = 0; i < beta * T; i++) {
-                if (r2.mod_of[i] == LSA_ROW_SKIP) continue;
-                const bool fp = c.fp64_ntt && (c.T.mod[r2.mod_of[i]] >> LSA_FP64_MAX_BITS) == 0;
-                if ((ks_fused_engines(c) >> (fp ? 1 : 0)) & 1) r2.mod_of[i] = LSA_ROW_SKIP;
-                else any = true;
-            }
-            if (any) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, r2, false, s, nullptr, 2);
-        }
-    } else {
-        for (int d = 0; d < beta; d++) {
-            RowMap rm;
-            rm.period = T;
-            for (int tl = 0; tl < T; tl++) {
-                const bool own = tl >= d * np && tl < std::min((d + 1) * np, L);
-                rm.mod_of[tl] = own ? LSA_ROW_SKIP : (unsigned char)tl_mod(tl);
-            }
-            launch_ntt(c, ext + (size_t)d * T * N, ext + (size_t)d * T * N, nb, s_ext, s_ext, T, rm, false, s, nullptr, second_pass ? 3 : 1);
-        }
-    }
-}
-
-struct KsWorkspace {   // where ks_decompose / ks_mac / ks_moddown keep their intermediates inside one tile's workspace
-    u64 *cxi, *ext, *acc, *conv;
-    long long s_ext, s_acc, s_conv;
-};
-static KsWorkspace ks_layout(const Context& c, int level, int nb, u64* ws) {
-    const long long N = c.n;
-    const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
-    KsWorkspace w;
-    w.cxi = ws;
-    w.ext = w.cxi + (size_t)nb * L * N;
-    w.acc = w.ext + (size_t)nb * beta * T * N;
-    w.conv = w.acc + (size_t)nb * 2 * T * N;
-    w.s_ext = (long long)beta * T * N;
-    w.s_acc = 2LL * T * N;
-    w.s_conv = 2LL * L * N;
-    return w;
-}
-
-// step 4 of a key switch on the digits that ks_decompose left in the workspace: the gadget inner product with the key (both
-// halves) -> w.acc, [2][L+k][N] over Q_level u P, NTT domain; fused with the extension transform's second pass when
-// ks_decompose stopped after the first one
-// fold: the tensor product folded into the MAC (TensorFold; cx is then d2 and only the decomposition reads it)
-static void ks_mac(Context& c, int level, const u64* cx, long long scx, const Key& key, int nb, u64* ws, hipStream_t s,
-                   bool ext_first_pass_only, const TensorFold* fold = nullptr) {
-    const KsWorkspace w = ks_layout(c, level, nb, ws);
-    if (ext_first_pass_only) {
-        const int eng = ks_fused_engines(c);
-        LSA_REQUIRE(launch_ntt_ksmac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s, eng, fold),
-                    "fused key MAC: shape not covered");
-        for (int e = 0; e < 2; e++)
-            if (!((eng >> e) & 1)) launch_ks_mac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s, e, nullptr, nullptr, 0, fold);
-    } else {
-        launch_ks_mac(c, level, cx, scx, w.ext, w.s_ext, key, w.acc, w.s_acc, nb, s, -1, nullptr, nullptr, 0, fold);
-    }
-}
-
 struct RotMacTerm {   // the pt_mul factor of one rotate-and-MAC term (fz_epi = 4): p[scatter[x]] (+)= value(x) * pt[scatter[x]]
     const u64* pt;
     long long spt;
     bool accumulate;
 };
-static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, u64* p, long long sp, const u64* base,
-                       long long sbase, int base_rpp, int base_polys, int nb, hipStream_t s, const KsRescale* rs, bool coeff_out,
-                       const u32* scatter = nullptr, const u32* coeff_gather = nullptr, const RotMacTerm* rmac = nullptr);
 
-// steps 4-5 of a key switch on the digits that ks_decompose left in the workspace: they depend on the key, the decomposition
-// does not -- rotations of ONE ciphertext by several Galois elements share it ("hoisting"; with the automorphism applied
-// after the switch, as here, every rotation's residues are the same as if it had been computed on its own)
-static void ks_finish(Context& c, int level, const u64* cx, long long scx, const Key& key, u64* p, long long sp,
-                      const u64* base, long long sbase, int base_rpp, int base_polys, int nb, u64* ws, hipStream_t s,
-                      const KsRescale* rs, bool coeff_out, bool ext_first_pass_only, const u32* scatter) {
-    const KsWorkspace w = ks_layout(c, level, nb, ws);
-    ks_mac(c, level, cx, scx, key, nb, ws, s, ext_first_pass_only);
-    ks_moddown(c, level, w.acc, w.s_acc, w.conv, p, sp, base, sbase, base_rpp, base_polys, nb, s, rs, coeff_out, scatter);
-}
+// What ModDown writes: p[h][i] = (h < base_polys ? base[h][i] : 0) + ModDown(acc)[h][i], base row h * base_rpp + i.
+//   NTT      NTT domain.  scatter (fused tails only): every result row is written through the index map, p[row][scatter[x]] =
+//            value(x) -- the NTT-domain automorphism of a rotation applied by the last pass's store instead of a permutation
+//            kernel afterwards.  rmac (with scatter): the scattered result is multiplied by a pt_mul plaintext and written or
+//            added to p instead (p[row][y] (+)= value * pt[limb][y] * 2^-64, y = scatter[x]): one term of a BFV rotate-and-MAC
+//   RESCALE  NTT domain, fused tails: p is scratch of the same shape and rs.out receives rescale(p)
+//   COEFF    coefficient domain, `base` given there (BFV).  coeff_gather: the coefficient-domain automorphism of a BFV rotation,
+//            Context::coeff_perm(g), applied by the tail's loads (k_sub_mul_perm): p[row][x] = sign_x * value(pi_x)
+struct KsOut {
+    enum Form { NTT, RESCALE, COEFF };
+    u64* p;
+    long long sp;
+    const u64* base = nullptr;
+    long long sbase = 0;
+    int base_rpp = 0, base_polys = 0;
+    Form form = NTT;
+    KsRescale rs = {nullptr, 0};
+    const u32* scatter = nullptr;
+    const u32* coeff_gather = nullptr;
+    const RotMacTerm* rmac = nullptr;
+};
 
 // step 5, the division by P of a polynomial pair over Q_level u P (acc: [2][L+k][N] per batch item, NTT domain; its P rows --
-// and, for the merged rescale, its last Q row -- are transformed in place), conv: 2L rows of scratch per batch item.
-// scatter (fused tails only): every result row is written through the index map, p[row][scatter[x]] = value(x) -- the
-// NTT-domain automorphism of a rotation applied by the last pass's store instead of a permutation kernel afterwards.
-// coeff_gather (coeff_out only): the coefficient-domain automorphism of a BFV rotation, Context::coeff_perm(g), applied by
-// the tail's loads (k_sub_mul_perm): p[row][x] = sign_x * value(pi_x)
-// rmac (with scatter): the scattered result is multiplied by a pt_mul plaintext and written or added to p instead
-// (p[row][y] (+)= value * pt[limb][y] * 2^-64, y = scatter[x]): one term of a BFV rotate-and-MAC
-static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, u64* p, long long sp, const u64* base,
-                       long long sbase, int base_rpp, int base_polys, int nb, hipStream_t s, const KsRescale* rs, bool coeff_out,
-                       const u32* scatter, const u32* coeff_gather, const RotMacTerm* rmac) {
-    LSA_REQUIRE(!scatter || (c.fuse_tails && !rs && !coeff_out), "scattered ModDown store: fused tails, no rescale, NTT-domain output");
-    LSA_REQUIRE(!rmac || scatter, "rotate-and-MAC tail: needs the rotation's index map");
-    LSA_REQUIRE(!coeff_gather || (coeff_out && !rs), "gathered ModDown tail: coefficient-domain output, no rescale");
+// and, for the merged rescale, its last Q row -- are transformed in place), conv: 2L rows of scratch per batch item
+static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
+    LSA_REQUIRE(!o.scatter || (c.fuse_tails && o.form == KsOut::NTT), "scattered ModDown store: fused tails, NTT-domain output");
+    LSA_REQUIRE(!o.rmac || o.scatter, "rotate-and-MAC tail: needs the rotation's index map");
+    LSA_REQUIRE(!o.coeff_gather || o.form == KsOut::COEFF, "gathered ModDown tail: coefficient-domain output");
+    LSA_REQUIRE(o.form != KsOut::RESCALE || (c.fuse_tails && level >= 1 && ((o.base && o.base_polys == 2) || (!o.base && o.base_polys == 0))),
+                "merged ModDown+rescale: unsupported shape");
+    const bool coeff_out = o.form == KsOut::COEFF, rs = o.form == KsOut::RESCALE;
     const long long N = c.n;
     const int L = level + 1, np = c.np, T = L + np;
     const long long s_conv = 2LL * L * N;
@@ -217,39 +98,37 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
             rows.dst_row[j] = j;
             dst.push_back(j);
         }
-        const BaseConvPlan* k = c.baseconv(src, dst, true, rs != nullptr);
+        const BaseConvPlan* k = c.baseconv(src, dst, true, rs);
         for (int h = 0; h < 2; h++)
             launch_baseconv(c, k, rows, acc + (size_t)h * T * N, conv + (size_t)h * L * N, nb, s_acc, s_conv, s);
     }
     if (coeff_out) {
-        if (coeff_gather)
-            launch_moddown_final_perm(c, level, coeff_gather, acc, s_acc, T, conv, s_conv, base, sbase, base_rpp, base_polys, p, sp,
-                                      nb, s);
+        if (o.coeff_gather)
+            launch_moddown_final_perm(c, level, o.coeff_gather, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp,
+                                      o.base_polys, o.p, o.sp, nb, s);
         else
-            launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, base, sbase, base_rpp, base_polys, p, sp, nb, s);
+            launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp, o.base_polys, o.p, o.sp, nb, s);
         return;
     }
     if (rs) {
         // base_polys == 0: the tensor fold -- P * base is already in acc's Q rows (TensorFold), so INTT(acc_l) * P^-1 carries
         // INTT(base_l) and the tails below run without base
-        LSA_REQUIRE(c.fuse_tails && level >= 1 && ((base && base_polys == 2) || (!base && base_polys == 0)),
-                    "merged ModDown+rescale: unsupported shape");
         const int l = level;
         // t[h] = (INTT(acc[h][l]) - conv[h][l]) * P^-1 + INTT(base[h][l]) -> p[h][l].  base is the caller's scratch here
         // (the tensor output): its last limbs are transformed in place, nothing reads them in NTT form afterwards.
-        if (base) {
-            u64* base_rw = const_cast<u64*>(base);
+        if (o.base) {
+            u64* base_rw = const_cast<u64*>(o.base);
             RowMap rb;
             rb.period = 1;
             rb.mod_of[0] = (unsigned char)l;
             rb.row0 = l;
-            rb.row_step = base_rpp;
-            launch_ntt(c, base_rw, base_rw, nb, sbase, sbase, 2, rb, true, s);
+            rb.row_step = o.base_rpp;
+            launch_ntt(c, base_rw, base_rw, nb, o.sbase, o.sbase, 2, rb, true, s);
         }
         const unsigned char lm[1] = {(unsigned char)l};
         launch_sub_mul_general(c, 2, 1, lm, c.pinv_vec(level) + l, acc + (long long)l * N, s_acc, T, conv + (long long)l * N,
-                               s_conv, L, base ? base + (long long)l * N : nullptr, sbase, base_rpp, base_polys,
-                               p + (long long)l * N, sp, L, nb, s);
+                               s_conv, L, o.base ? o.base + (long long)l * N : nullptr, o.sbase, o.base_rpp, o.base_polys,
+                               o.p + (long long)l * N, o.sp, L, nb, s);
         // every other limb: in = conv_j*P^-1 + lift_j(t), out = (acc_j*P^-1 - NTT(in) + base_j) * q_l^-1
         RowMap rmo;
         rmo.period = 2 * L;
@@ -260,20 +139,20 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
         fb.epi = 2;
         fb.limbs = L;
         fb.ql_mod = l;
-        fb.last = p + (long long)l * N;
-        fb.last_stride = sp;
+        fb.last = o.p + (long long)l * N;
+        fb.last_stride = o.sp;
         fb.last_rpp = L;
         fb.a = acc;
         fb.a_stride = s_acc;
         fb.a_rpp = T;
-        fb.base = base;
-        fb.base_stride = sbase;
-        fb.base_rpp = base_rpp;
-        fb.base_polys = base_polys;
+        fb.base = o.base;
+        fb.base_stride = o.sbase;
+        fb.base_rpp = o.base_rpp;
+        fb.base_polys = o.base_polys;
         fb.k = c.pinv_vec(level);
         fb.k2 = c.qlinv_vec(level);
-        fb.out = rs->out;
-        fb.out_stride = rs->sout;
+        fb.out = o.rs.out;
+        fb.out_stride = o.rs.sout;
         fb.out_rpp = level;
         launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rmo, false, s, &fb);
     } else if (c.fuse_tails) {
@@ -285,47 +164,152 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
         fz.a = acc;
         fz.a_stride = s_acc;
         fz.a_rpp = T;
-        fz.base = base;
-        fz.base_stride = sbase;
-        fz.base_rpp = base_rpp;
-        fz.base_polys = base_polys;
+        fz.base = o.base;
+        fz.base_stride = o.sbase;
+        fz.base_rpp = o.base_rpp;
+        fz.base_polys = o.base_polys;
         fz.k = c.pinv_vec(level);
-        fz.out = p;
-        fz.out_stride = sp;
+        fz.out = o.p;
+        fz.out_stride = o.sp;
         fz.out_rpp = L;
-        fz.scatter = scatter;
-        if (rmac) {
+        fz.scatter = o.scatter;
+        if (o.rmac) {
             fz.epi = 4;
-            fz.pt = rmac->pt;
-            fz.pt_stride = rmac->spt;
-            fz.accumulate = rmac->accumulate;
+            fz.pt = o.rmac->pt;
+            fz.pt_stride = o.rmac->spt;
+            fz.accumulate = o.rmac->accumulate;
         }
         launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rm_seq(L), false, s, &fz);
     } else {
         launch_ntt(c, conv, conv, nb, s_conv, 2 * L, rm_seq(L), false, s);
-        launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, base, sbase, base_rpp, base_polys, p, sp, nb, s);
+        launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp, o.base_polys, o.p, o.sp, nb, s);
     }
 }
 
 // one key per decomposition (relinearisation, a single rotation, a generic switch): the extension transform's second pass
-// and the key MAC run as one kernel where the shape allows (k_ntt_r16_ksmac); hoisted rotations (several keys on one
-// decomposition) keep the two steps apart
+// and the key MAC run as one kernel where the shape allows (k_ntt_r16_ksmac) and some target limb takes it
 static bool ks_fuse_mac(const Context& c, int level, const Key& key) {
-    const int T = level + 1 + c.np, beta = ceil_div(level + 1, c.np);
+    const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
     if (!ks_fused_enabled(c) || !ks_fused_engines(c) || (c.fp64_ntt && !key.fp) || beta * T > LSA_MAX_PERIOD || T > 64) return false;
-    for (int tl = 0; tl < T; tl++) {   // worth it only if some target limb takes the fused kernel
-        const u64 q = c.T.mod[tl <= level ? tl : c.p_mod(tl - level - 1)];
-        const bool fp = c.fp64_ntt && (q >> LSA_FP64_MAX_BITS) == 0;
-        if ((ks_fused_engines(c) >> (fp ? 1 : 0)) & 1) return true;
-    }
+    for (int tl = 0; tl < T; tl++)
+        if (ks_fused_limb(c, L, tl)) return true;
     return false;
 }
-static void key_switch(Context& c, int level, const u64* cx, long long scx, const Key& key, u64* p, long long sp,
-                       const u64* base, long long sbase, int base_rpp, int base_polys, int nb, u64* ws, hipStream_t s,
-                       const KsRescale* rs = nullptr, const u32* scatter = nullptr) {
-    const bool fuse = ks_fuse_mac(c, level, key);
-    ks_decompose(c, level, cx, scx, nb, ws, s, nullptr, 0, !fuse);
-    ks_finish(c, level, cx, scx, key, p, sp, base, sbase, base_rpp, base_polys, nb, ws, s, rs, false, fuse, scatter);
+
+// One tile of a key switch: nb batch items on stream s, with the workspace laid out per batch item as
+// cxi [L] | ext [beta][L+k] | acc [2][L+k] | conv [2][L] rows.  Whether the extension transform's second pass runs fused with
+// the key MAC is decided here, once, so decompose() leaves the extended limbs in the state mac() reads them in.  Only a switch
+// with one key per decomposition fuses (single_key); hoisted rotations -- several keys on one decomposition, whose
+// residues are the same as if each rotation had been computed on its own -- pass none and keep the two steps apart.
+struct KsTile {
+    Context& c;
+    int level, L, T, beta, nb;
+    hipStream_t s;
+    const Key* key;   // fused: the one key mac() accepts
+    bool fused;
+    u64 *cxi, *ext, *acc, *conv;
+    long long s_cxi, s_ext, s_acc, s_conv;
+
+    static size_t rows(const Context& c, int level) {   // workspace rows per batch item
+        LSA_REQUIRE(c.np >= 1, "key switching needs at least one special prime");
+        const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
+        return (size_t)L + (size_t)beta * T + 2 * (size_t)T + 2 * (size_t)L;
+    }
+    KsTile(Context& c_, int level_, int nb_, u64* ws, hipStream_t s_, const Key* single_key = nullptr)
+        : c(c_), level(level_), nb(nb_), s(s_), key(single_key) {
+        LSA_REQUIRE(c.np >= 1, "key switching needs at least one special prime");
+        LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+        const long long N = c.n;
+        L = level + 1;
+        T = L + c.np;
+        beta = ceil_div(L, c.np);
+        fused = key && ks_fuse_mac(c, level, *key);
+        s_cxi = (long long)L * N;
+        s_ext = (long long)beta * T * N;
+        s_acc = 2LL * T * N;
+        s_conv = 2LL * L * N;
+        cxi = ws;
+        ext = cxi + (size_t)nb * s_cxi;
+        acc = ext + (size_t)nb * s_ext;
+        conv = acc + (size_t)nb * s_acc;
+    }
+
+    // steps 1-3: cx out of the NTT domain, every digit converted to the other limbs of Q u P, extended limbs back into the NTT
+    // domain.  cx_coef: the same polynomial in the coefficient domain if the caller has it (BFV): the inverse transform is
+    // skipped.  Fused: the limbs that take the fused kernel are left after the first pass (mac() runs the second).
+    void decompose(const u64* cx, long long scx, const u64* cx_coef = nullptr, long long s_coef = 0) {
+        const long long N = c.n;
+        const int np = c.np;
+        // 1. cx out of the NTT domain
+        if (!cx_coef) launch_ntt(c, cx, cxi, nb, scx, s_cxi, L, rm_seq(L), true, s);
+        const u64* conv_src = cx_coef ? cx_coef : cxi;
+        const long long s_src = cx_coef ? s_coef : s_cxi;
+        // 2. per digit: exact conversion of the digit's limbs to every other limb of Q u P
+        for (int d = 0; d < beta; d++) {
+            const int d0 = d * np, d1 = std::min(d0 + np, L);
+            std::vector<int> src, dst;
+            BaseConvRows rows{};
+            for (int i = d0; i < d1; i++) {
+                rows.src_row[i - d0] = i;
+                src.push_back(i);
+            }
+            for (int tl = 0; tl < T; tl++) {
+                if (tl >= d0 && tl < d1) continue;
+                rows.dst_row[dst.size()] = d * T + tl;
+                dst.push_back(c.qp_mod(L, tl));
+            }
+            launch_baseconv(c, c.baseconv(src, dst, false), rows, conv_src, ext, nb, s_src, s_ext, s);
+        }
+        // 3. extended limbs into the NTT domain (the digit's own limbs are taken from cx directly by the MAC)
+        auto own = [&](int d, int tl) { return tl >= d * np && tl < std::min((d + 1) * np, L); };
+        if (beta * T <= LSA_MAX_PERIOD) {
+            RowMap rm;
+            rm.period = beta * T;
+            for (int d = 0; d < beta; d++)
+                for (int tl = 0; tl < T; tl++) rm.mod_of[d * T + tl] = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
+            launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, fused ? 1 : 3);
+            if (!fused) return;
+            // the target limbs that do not take the fused kernel get their second pass here (stand-alone MAC later)
+            bool any = false;
+            for (int i = 0; i < beta * T; i++) {
+                if (rm.mod_of[i] == LSA_ROW_SKIP) continue;
+                if (ks_fused_limb(c, L, i % T)) rm.mod_of[i] = LSA_ROW_SKIP;
+                else any = true;
+            }
+            if (any) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, 2);
+            return;
+        }
+        for (int d = 0; d < beta; d++) {   // (never fused: ks_fuse_mac needs beta * T <= LSA_MAX_PERIOD)
+            RowMap rm;
+            rm.period = T;
+            for (int tl = 0; tl < T; tl++) rm.mod_of[tl] = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
+            launch_ntt(c, ext + (size_t)d * T * N, ext + (size_t)d * T * N, nb, s_ext, s_ext, T, rm, false, s);
+        }
+    }
+
+    // step 4: the gadget inner product of the digits with key k (both halves) -> acc, [2][L+k][N] over Q_level u P, NTT
+    // domain; fused with the extension transform's second pass where decompose() stopped after the first one.
+    // fold: the tensor product folded into the MAC (TensorFold; cx is then d2 and only the decomposition reads it)
+    void mac(const u64* cx, long long scx, const Key& k, const TensorFold* fold = nullptr) {
+        if (!fused) {
+            launch_ks_mac(c, level, cx, scx, ext, s_ext, k, acc, s_acc, nb, s, false, nullptr, nullptr, 0, fold);
+            return;
+        }
+        LSA_REQUIRE(&k == key, "fused key MAC: the tile was planned for another key");
+        LSA_REQUIRE(launch_ntt_ksmac(c, level, cx, scx, ext, s_ext, k, acc, s_acc, nb, s, fold), "fused key MAC: shape not covered");
+        launch_ks_mac(c, level, cx, scx, ext, s_ext, k, acc, s_acc, nb, s, true, nullptr, nullptr, 0, fold);
+    }
+
+    void moddown(const KsOut& o) { ks_moddown(c, level, acc, s_acc, conv, o, nb, s); }   // step 5
+};
+
+// a key switch of cx (NTT domain) with one key
+static void key_switch(Context& c, int level, const u64* cx, long long scx, const Key& key, const KsOut& o, int nb, u64* ws,
+                       hipStream_t s) {
+    KsTile t(c, level, nb, ws, s, &key);
+    t.decompose(cx, scx);
+    t.mac(cx, scx, key);
+    t.moddown(o);
 }
 
 // the automorphism X -> X^g of a rotation as the SCATTER map of the key switch's last store: out[i] = in[perm_g[i]] is
@@ -437,9 +421,10 @@ void ckks_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, 
                 hipStream_t s) {
     const long long N = c.n;
     const int L = level + 1;
-    for_tiles(c, ks_ws_rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+    for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* d = d3 + (size_t)b0 * sd;
-        key_switch(c, level, d + 2LL * L * N, sd, rlk, out + (size_t)b0 * so, so, d, sd, L, 2, nb, ws, st);
+        key_switch(c, level, d + 2LL * L * N, sd, rlk, {.p = out + (size_t)b0 * so, .sp = so, .base = d, .sbase = sd, .base_rpp = L, .base_polys = 2},
+                   nb, ws, st);
     });
 }
 
@@ -454,7 +439,7 @@ void ckks_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u6
                  long long sout, hipStream_t s) {
     const long long N = c.n;
     const int L = level + 1;
-    const size_t ks_rows = ks_ws_rows(c, level);
+    const size_t ks_rows = KsTile::rows(c, level);
     const long long sp = 2LL * L * N;
     // (an in-place rotation keeps the two-step form: the tail reads c0 from `in` while other workgroups already store)
     const bool apart = out + (size_t)batch * sout <= in || in + (size_t)batch * sin <= out;
@@ -462,7 +447,9 @@ void ckks_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u6
         // the permutation rides on the ModDown tail's store: no intermediate, no permutation kernel (2L reads + 2L writes less)
         for_tiles(c, ks_rows, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
             const u64* ct = in + (size_t)b0 * sin;
-            key_switch(c, level, ct + (long long)L * N, sin, glk, out + (size_t)b0 * sout, sout, ct, sin, L, 1, nb, ws, st, nullptr, scatter);
+            key_switch(c, level, ct + (long long)L * N, sin, glk,
+                       {.p = out + (size_t)b0 * sout, .sp = sout, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1, .scatter = scatter},
+                       nb, ws, st);
         });
         return;
     }
@@ -470,7 +457,8 @@ void ckks_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u6
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
-        key_switch(c, level, ct + (long long)L * N, sin, glk, p, sp, ct, sin, L, 1, nb, ws, st);
+        key_switch(c, level, ct + (long long)L * N, sin, glk, {.p = p, .sp = sp, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1},
+                   nb, ws, st);
         launch_permute_ntt(c, perm, p, sp, out + (size_t)b0 * sout, sout, 2 * L, nb, st);
     });
 }
@@ -482,7 +470,7 @@ void ckks_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64
     if (n_rot <= 0) return;
     const long long N = c.n;
     const int L = level + 1;
-    const size_t ks_rows = ks_ws_rows(c, level);
+    const size_t ks_rows = KsTile::rows(c, level);
     const long long sp = 2LL * L * N;
     std::vector<const u32*> perms(n_rot), scatters(n_rot);
     for (int i = 0; i < n_rot; i++) {
@@ -493,14 +481,16 @@ void ckks_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
-        ks_decompose(c, level, ct + (long long)L * N, sin, nb, ws, st);
+        KsTile t(c, level, nb, ws, st);
+        t.decompose(ct + (long long)L * N, sin);
         for (int i = 0; i < n_rot; i++) {
+            t.mac(ct + (long long)L * N, sin, *glk[i]);
             if (scatters[i]) {   // the permutation rides on the ModDown tail's store
-                ks_finish(c, level, ct + (long long)L * N, sin, *glk[i], outs[i] + (size_t)b0 * sout, sout, ct, sin, L, 1, nb, ws, st, nullptr,
-                          false, false, scatters[i]);
+                t.moddown({.p = outs[i] + (size_t)b0 * sout, .sp = sout, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1,
+                           .scatter = scatters[i]});
                 continue;
             }
-            ks_finish(c, level, ct + (long long)L * N, sin, *glk[i], p, sp, ct, sin, L, 1, nb, ws, st, nullptr);
+            t.moddown({.p = p, .sp = sp, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1});
             launch_permute_ntt(c, perms[i], p, sp, outs[i] + (size_t)b0 * sout, sout, 2 * L, nb, st);
         }
     });
@@ -523,18 +513,18 @@ void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const
     const bool one_pass = rotation_scatter_on();   // the MAC writes the rotated extended ciphertext itself (LSA_ROT_SCATTER=0: MAC, then k_permute_ext)
     std::vector<const u32*> perms(n_rot);
     for (int i = 0; i < n_rot; i++) perms[i] = one_pass ? inverse_perm(c, g[i]) : c.ntt_perm(g[i]);
-    for_tiles(c, ks_ws_rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+    for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* ct = in + (size_t)b0 * sin;
-        const KsWorkspace w = ks_layout(c, level, nb, ws);
-        ks_decompose(c, level, ct + (long long)L * N, sin, nb, ws, st);
+        KsTile t(c, level, nb, ws, st);
+        t.decompose(ct + (long long)L * N, sin);
         for (int i = 0; i < n_rot; i++) {
             if (one_pass) {
-                launch_ks_mac(c, level, ct + (long long)L * N, sin, w.ext, w.s_ext, *glk[i], outs[i] + (size_t)b0 * sout, sout, nb, st, -1,
-                              perms[i], ct, sin);
+                launch_ks_mac(c, level, ct + (long long)L * N, sin, t.ext, t.s_ext, *glk[i], outs[i] + (size_t)b0 * sout, sout, nb, st,
+                              false, perms[i], ct, sin);
                 continue;
             }
-            ks_mac(c, level, ct + (long long)L * N, sin, *glk[i], nb, ws, st, false);
-            launch_permute_ext(c, level, perms[i], w.acc, w.s_acc, ct, sin, 1, outs[i] + (size_t)b0 * sout, sout, false, nb, st);
+            t.mac(ct + (long long)L * N, sin, *glk[i]);
+            launch_permute_ext(c, level, perms[i], t.acc, t.s_acc, ct, sin, 1, outs[i] + (size_t)b0 * sout, sout, false, nb, st);
         }
     });
 }
@@ -545,13 +535,12 @@ void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk
     const long long N = c.n;
     const int L = level + 1;
     const u32* perm = c.ntt_perm(g);
-    const bool fuse = ks_fuse_mac(c, level, glk);
-    for_tiles(c, ks_ws_rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+    for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* ct = in + (size_t)b0 * sin;
-        const KsWorkspace w = ks_layout(c, level, nb, ws);
-        ks_decompose(c, level, ct + (long long)L * N, sin, nb, ws, st, nullptr, 0, !fuse);
-        ks_mac(c, level, ct + (long long)L * N, sin, glk, nb, ws, st, fuse);
-        launch_permute_ext(c, level, perm, w.acc, w.s_acc, ct, sin, 1, out + (size_t)b0 * sout, sout, accumulate, nb, st);
+        KsTile t(c, level, nb, ws, st, &glk);
+        t.decompose(ct + (long long)L * N, sin);
+        t.mac(ct + (long long)L * N, sin, glk);
+        launch_permute_ext(c, level, perm, t.acc, t.s_acc, ct, sin, 1, out + (size_t)b0 * sout, sout, accumulate, nb, st);
     });
 }
 
@@ -559,7 +548,7 @@ void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk
 void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s) {
     const int L = level + 1;
     for_tiles(c, 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
-        ks_moddown(c, level, in + (size_t)b0 * sin, sin, ws, out + (size_t)b0 * sout, sout, nullptr, 0, 0, 0, nb, st, nullptr, false);
+        ks_moddown(c, level, in + (size_t)b0 * sin, sin, ws, {.p = out + (size_t)b0 * sout, .sp = sout}, nb, st);
     });
 }
 
@@ -569,14 +558,13 @@ void ckks_switch_key(Context& c, int level, const u64* in, const Key& swk, u64* 
                      hipStream_t s) {
     const long long N = c.n;
     const int L = level + 1;
-    for_tiles(c, ks_ws_rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+    for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* ct = in + (size_t)b0 * sin;
-        key_switch(c, level, ct + (long long)L * N, sin, swk, out + (size_t)b0 * sout, sout, ct, sin, L, 1, nb, ws, st);
+        key_switch(c, level, ct + (long long)L * N, sin, swk,
+                   {.p = out + (size_t)b0 * sout, .sp = sout, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1}, nb, ws, st);
     });
 }
 
-void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch,
-                                 long long sa, long long sb, long long so, hipStream_t s, int a_rpp, int b_rpp);
 void ckks_mult_relin_rescale(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch,
                              long long sa, long long sb, long long so, hipStream_t s) {
     ckks_mult_relin_rescale_rpp(c, level, a, b, rlk, out, batch, sa, sb, so, s, 0, 0);
@@ -602,7 +590,7 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
     const int L = level + 1;
     const bool fold = c.fuse_tails && hmult_fold_on();
     const size_t r_d3 = (fold ? 1 : 3) * (size_t)L, r_r2 = 2 * (size_t)L;
-    const size_t r_shared = std::max(ks_ws_rows(c, level), rescale_ws_rows(level, 2));
+    const size_t r_shared = std::max(KsTile::rows(c, level), rescale_ws_rows(level, 2));
     const long long sd = (long long)r_d3 * N, sr = 2LL * L * N;
     for_tiles(c, r_d3 + r_r2 + r_shared, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* d3 = ws;
@@ -613,21 +601,21 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
             const u64* bt = b + (size_t)b0 * sb;
             launch_tensor_d2(c, ta, bt, d3, nb, sa, sb, sd, L, st, a_rpp, b_rpp);
             const TensorFold tf{ta, bt, sa, sb, (long long)(a_rpp ? a_rpp : L) * N, (long long)(b_rpp ? b_rpp : L) * N};
-            const bool fuse = ks_fuse_mac(c, level, rlk);
-            ks_decompose(c, level, d3, sd, nb, sub, st, nullptr, 0, !fuse);
-            ks_mac(c, level, d3, sd, rlk, nb, sub, st, fuse, &tf);
-            const KsWorkspace w = ks_layout(c, level, nb, sub);
-            const KsRescale rs{out + (size_t)b0 * so, so};
-            ks_moddown(c, level, w.acc, w.s_acc, w.conv, r2, sr, nullptr, 0, 0, 0, nb, st, &rs, false);
+            KsTile t(c, level, nb, sub, st, &rlk);
+            t.decompose(d3, sd);
+            t.mac(d3, sd, rlk, &tf);
+            t.moddown({.p = r2, .sp = sr, .form = KsOut::RESCALE, .rs = {out + (size_t)b0 * so, so}});
             return;
         }
         launch_tensor(c, a + (size_t)b0 * sa, b + (size_t)b0 * sb, d3, nb, sa, sb, sd, L, rm_seq(L), st, a_rpp, b_rpp);
+        KsOut o{.p = r2, .sp = sr, .base = d3, .sbase = sd, .base_rpp = L, .base_polys = 2};
         if (c.fuse_tails) {
-            const KsRescale rs{out + (size_t)b0 * so, so};
-            key_switch(c, level, d3 + 2LL * L * N, sd, rlk, r2, sr, d3, sd, L, 2, nb, sub, st, &rs);
+            o.form = KsOut::RESCALE;
+            o.rs = {out + (size_t)b0 * so, so};
+            key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
             return;
         }
-        key_switch(c, level, d3 + 2LL * L * N, sd, rlk, r2, sr, d3, sd, L, 2, nb, sub, st);
+        key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
         rescale(c, level, 2, r2, sr, out + (size_t)b0 * so, so, nb, true, sub, st);
     });
 }
@@ -750,27 +738,26 @@ void bfv_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int ba
 // key switch of a coefficient-domain polynomial: NTT in, INTT out
 // cx in the coefficient domain; p[h] = (h < base_polys ? base[h] : 0) + KeySwitch(cx)[h], all in the coefficient domain.
 // Only the MAC's own-digit operand needs cx in the NTT domain; the decomposition starts from the coefficients the caller
-// already has and the ModDown tail runs on coefficients (ks_finish, coeff_out).
-static void bfv_key_switch(Context& c, int level, const u64* cx, long long scx, const Key& key, u64* p, long long sp,
-                           const u64* base, long long sbase, int base_rpp, int base_polys, int nb, u64* ws, hipStream_t s) {
-    const long long N = c.n;
-    const int L = level + 1;
-    u64* cxn = ws;
-    u64* sub = ws + (size_t)nb * L * N;
-    launch_ntt(c, cx, cxn, nb, scx, (long long)L * N, L, rm_seq(L), false, s);
-    const bool fuse = ks_fuse_mac(c, level, key);
-    ks_decompose(c, level, cxn, (long long)L * N, nb, sub, s, cx, scx, !fuse);
-    ks_finish(c, level, cxn, (long long)L * N, key, p, sp, base, sbase, base_rpp, base_polys, nb, sub, s, nullptr, true, fuse);
+// already has and the ModDown tail runs on coefficients (KsOut::COEFF).  Workspace: NTT(cx) [L] rows, then the tile's.
+static void bfv_key_switch(Context& c, int level, const u64* cx, long long scx, const Key& key, const KsOut& o, int nb, u64* ws,
+                           hipStream_t s) {
+    const long long scxn = (long long)(level + 1) * c.n;
+    KsTile t(c, level, nb, ws + (size_t)nb * scxn, s, &key);
+    launch_ntt(c, cx, ws, nb, scx, scxn, level + 1, rm_seq(level + 1), false, s);
+    t.decompose(ws, scxn, cx, scx);
+    t.mac(ws, scxn, key);
+    t.moddown(o);
 }
 
 void bfv_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, int batch, long long sd, long long so,
                hipStream_t s) {
     const long long N = c.n;
     const int L = level + 1;
-    const size_t ks_rows = ks_ws_rows(c, level) + L;
-    for_tiles(c, ks_rows, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+    for_tiles(c, KsTile::rows(c, level) + L, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* d = d3 + (size_t)b0 * sd;
-        bfv_key_switch(c, level, d + 2LL * L * N, sd, rlk, out + (size_t)b0 * so, so, d, sd, L, 2, nb, ws, st);
+        bfv_key_switch(c, level, d + 2LL * L * N, sd, rlk,
+                       {.p = out + (size_t)b0 * so, .sp = so, .base = d, .sbase = sd, .base_rpp = L, .base_polys = 2, .form = KsOut::COEFF},
+                       nb, ws, st);
     });
 }
 
@@ -779,12 +766,13 @@ void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64
     const long long N = c.n;
     const int L = level + 1;
     const u32* perm = c.coeff_perm(g);
-    const size_t ks_rows = ks_ws_rows(c, level) + L;
+    const size_t ks_rows = KsTile::rows(c, level) + L;
     const long long sp = 2LL * L * N;
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
-        bfv_key_switch(c, level, ct + (long long)L * N, sin, glk, p, sp, ct, sin, L, 1, nb, ws, st);   // p0 = c0 + ks0
+        bfv_key_switch(c, level, ct + (long long)L * N, sin, glk,   // p0 = c0 + ks0
+                       {.p = p, .sp = sp, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1, .form = KsOut::COEFF}, nb, ws, st);
         launch_permute_coeff(c, perm, p, sp, out + (size_t)b0 * sout, sout, 2 * L, rm_seq(L), nb, st);
     });
 }
@@ -806,7 +794,7 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
     LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
     const long long N = c.n;
     const int L = level + 1;
-    const size_t ks_rows = ks_ws_rows(c, level) + L;
+    const size_t ks_rows = KsTile::rows(c, level) + L;
     const long long sp = 2LL * L * N;
     // the one-pass tail stages a limb in LDS (N <= 2^14); larger rings keep the two steps, which measured faster than gathering
     // from global memory
@@ -829,20 +817,22 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
     if (overlapping >= 0) order.push_back(overlapping);
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* cxn = ws;
-        u64* sub = ws + (size_t)nb * L * N;
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
-        const KsWorkspace w = ks_layout(c, level, nb, sub);
+        KsTile t(c, level, nb, ws + (size_t)nb * L * N, st);
         launch_ntt(c, ct + (long long)L * N, cxn, nb, sin, (long long)L * N, L, rm_seq(L), false, st);
-        ks_decompose(c, level, cxn, (long long)L * N, nb, sub, st, ct + (long long)L * N, sin, true);
+        t.decompose(cxn, (long long)L * N, ct + (long long)L * N, sin);
         for (int i : order) {
-            ks_mac(c, level, cxn, (long long)L * N, *glk[i], nb, sub, st, false);
+            t.mac(cxn, (long long)L * N, *glk[i]);
+            KsOut o{.p = p, .sp = sp, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1, .form = KsOut::COEFF};
             if (direct[i]) {   // p0 = c0 + ks0 and the automorphism in one tail, straight into the output
-                ks_moddown(c, level, w.acc, w.s_acc, w.conv, outs[i] + (size_t)b0 * sout, sout, ct, sin, L, 1, nb, st, nullptr, true,
-                           nullptr, perms[i]);
+                o.p = outs[i] + (size_t)b0 * sout;
+                o.sp = sout;
+                o.coeff_gather = perms[i];
+                t.moddown(o);
                 continue;
             }
-            ks_moddown(c, level, w.acc, w.s_acc, w.conv, p, sp, ct, sin, L, 1, nb, st, nullptr, true);
+            t.moddown(o);
             launch_permute_coeff(c, perms[i], p, sp, outs[i] + (size_t)b0 * sout, sout, 2 * L, rm_seq(L), nb, st);
         }
     });
@@ -976,7 +966,7 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
         if (!scatters[i]) perms[i] = c.ntt_perm(g[i]);
     }
     const long long sct = 2LL * L * N;   // NTT(c0) | NTT(c1) per batch item in the workspace
-    const size_t ks_rows = ks_ws_rows(c, level);
+    const size_t ks_rows = KsTile::rows(c, level);
     const size_t rows = 2 * (size_t)L + ks_rows + (fused ? 0 : 2 * (size_t)L);
     for_tiles(c, rows, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         u64* ctn = ws;
@@ -984,9 +974,9 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
         u64* p = sub + (size_t)nb * ks_rows * N;   // two-step form: one rotated term, NTT domain
         const u64* ct = in + (size_t)b0 * sin;
         u64* o = out + (size_t)b0 * sout;
-        const KsWorkspace w = ks_layout(c, level, nb, sub);
+        KsTile t(c, level, nb, sub, st);
         launch_ntt(c, ct, ctn, nb, sin, sct, 2 * L, rm_seq(L), false, st);
-        if (any_rot) ks_decompose(c, level, ctn + L * N, sct, nb, sub, st, ct + (long long)L * N, sin, true);
+        if (any_rot) t.decompose(ctn + L * N, sct, ct + (long long)L * N, sin);
         bool first = true;
         for (int i = 0; i < n; i++) {   // identity terms: no transform at all
             if (g[i] != 1) continue;
@@ -997,17 +987,17 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
         for (int i = 0; i < n; i++) {
             if (g[i] == 1) continue;
             const u64* pt = pts[i] + (size_t)b0 * spts[i];
-            ks_mac(c, level, ctn + L * N, sct, *glk[i], nb, sub, st, false);
+            t.mac(ctn + L * N, sct, *glk[i]);
             if (fused) {
                 const RotMacTerm term{pt, spts[i], !first};
-                ks_moddown(c, level, w.acc, w.s_acc, w.conv, o, sout, ctn, sct, L, 1, nb, st, nullptr, false, scatters[i], nullptr,
-                           &term);
+                t.moddown({.p = o, .sp = sout, .base = ctn, .sbase = sct, .base_rpp = L, .base_polys = 1, .scatter = scatters[i],
+                           .rmac = &term});
             } else {
-                ks_moddown(c, level, w.acc, w.s_acc, w.conv, p, sct, ctn, sct, L, 1, nb, st, nullptr, false, scatters[i]);
+                t.moddown({.p = p, .sp = sct, .base = ctn, .sbase = sct, .base_rpp = L, .base_polys = 1, .scatter = scatters[i]});
                 const u64* r = p;
                 if (perms[i]) {   // no scattered store: the automorphism as a separate pass (conv is free again)
-                    launch_permute_ntt(c, perms[i], p, sct, w.conv, w.s_conv, 2 * L, nb, st);
-                    r = w.conv;
+                    launch_permute_ntt(c, perms[i], p, sct, t.conv, t.s_conv, 2 * L, nb, st);
+                    r = t.conv;
                 }
                 launch_mont_muladd(c, r, sct, pt, spts[i], first ? nullptr : o, sout, o, sout, nb, 2, L, rm_seq(L), st);
             }

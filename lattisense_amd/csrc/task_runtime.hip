@@ -31,22 +31,6 @@
 #include "shard_plan.h"
 #include "task_graph.h"
 
-namespace lsa {
-void ckks_relin(Context&, int, const u64*, const Key&, u64*, int, long long, long long, hipStream_t);
-void ckks_rescale(Context&, int, int, const u64*, u64*, int, long long, long long, hipStream_t);
-void ckks_rotate(Context&, int, const u64*, u64, const Key&, u64*, int, long long, long long, hipStream_t);
-void ckks_rotate_many(Context&, int, const u64*, int, const u64*, const Key* const*, u64* const*, int, long long, long long,
-                      hipStream_t);
-void ckks_mult_relin_rescale(Context&, int, const u64*, const u64*, const Key&, u64*, int, long long, long long, long long,
-                             hipStream_t);
-void bfv_mult(Context&, int, const u64*, const u64*, u64*, int, long long, long long, long long, hipStream_t);
-void bfv_relin(Context&, int, const u64*, const Key&, u64*, int, long long, long long, hipStream_t);
-void bfv_rotate(Context&, int, const u64*, u64, const Key&, u64*, int, long long, long long, hipStream_t);
-void bfv_rotate_many(Context&, int, const u64*, int, const u64*, const Key* const*, u64* const*, int, long long, long long,
-                     hipStream_t);
-void bfv_rescale(Context&, int, int, const u64*, u64*, int, long long, long long, hipStream_t);
-}  // namespace lsa
-
 using namespace lsa;
 
 // ------------------------------------------------------------------------------------------------ C-struct helpers
@@ -758,7 +742,7 @@ struct fhe_task_handle_st {
                 }
             }
             k.off = total;
-            total += (size_t)k.beta * 2 * k.comp * N;
+            total += key_layout(c, k.level).words;
             keys.push_back(std::move(k));
         }
         // 1b. direct groups: device slab + one copy per item straight from the caller's pinned buffer
@@ -833,10 +817,10 @@ struct fhe_task_handle_st {
         }
         std::vector<std::shared_ptr<DevKey>> dkeys;
         for (auto& k : keys) {
-            const size_t words = (size_t)k.beta * 2 * k.comp * N;
+            const KeyLayout kl = key_layout(c, k.level);
             auto dk = std::make_shared<DevKey>();
-            dk->slab = dslab(ks_fused_enabled(c) ? 2 * words : words);   // (+ the key as doubles behind it, launch_key_prepare)
-            segs.push_back({k.off, words, dk->slab->ptr});
+            dk->slab = dslab(kl.alloc_words());
+            segs.push_back({k.off, kl.words, dk->slab->ptr});
             dkeys.push_back(dk);
         }
         // gather and copy in chunks: while the DMA engine moves chunk k, the host threads gather chunk k+1 (the staging
@@ -855,12 +839,8 @@ struct fhe_task_handle_st {
         for (size_t i = 0; i < keys.size(); i++) {
             auto& k = keys[i];
             auto& dk = dkeys[i];
-            dk->key.data = dk->slab->ptr;
-            dk->key.level = k.level;
             dk->key.owned = false;
-            double* fp = ks_fused_enabled(c) ? reinterpret_cast<double*>(dk->slab->ptr + (size_t)k.beta * 2 * k.comp * N) : nullptr;
-            launch_key_prepare(c, dk->key.data, fp, k.level, s);
-            dk->key.fp = fp;
+            key_prepare(c, dk->key, dk->slab->ptr, k.level, key_layout(c, k.level).fp_of(dk->slab->ptr), s);
             avail[k.node->output_nodes[0]->index] = dk;
             last_key_uploads++;
             if (keep_keys) key_cache[{c.device, k.node->output_nodes[0]->index}] = CachedKey{k.handle, k.fingerprint, dk};
@@ -1657,7 +1637,7 @@ struct fhe_task_handle_st {
                         dk->key.data = (u64*)table.at(d)[j];
                         dk->key.owned = false;
                         if (key_src[k]->key.fp)   // the double copy travelled in the same slab
-                            dk->key.fp = reinterpret_cast<const double*>(dk->key.data + (reinterpret_cast<const u64*>(key_src[k]->key.fp) - key_src[k]->key.data));
+                            dk->key.fp = reinterpret_cast<const double*>(dk->key.data + key_layout(c, dk->key.level).words);
                         av[key_idx[k]] = dk;
                         if (keep_keys) {
                             auto up = key_cache.find({up_dev, key_idx[k]});

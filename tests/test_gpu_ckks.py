@@ -239,6 +239,36 @@ def test_engine_and_stream_variants_agree():
         assert np.array_equal(got, ref), (fp64, dual, tile)
 
 
+def test_key_uploaded_on_integer_engine_serves_fp64_engine():
+    """a key uploaded while the FP64 butterfly engine is off, used after it is switched on: the fused second pass + key MAC
+    (N = 2^16) reads the key's double copy, which must hold the key whatever the engine setting was at upload"""
+    need_gpu()
+    from lattisense_amd.device import DeviceContext, ALGO_CKKS
+    from oracle.pyoracle import Oracle
+    C = params.CKKS_DEFAULT[65536]
+    n, q, p = 1 << 16, C["q"][:6], C["p"][:2]
+    lvl, klvl, batch = 4, 5, 2
+    rng = np.random.default_rng(16)
+    o = Oracle(n, q, p, 0)
+    A, Bc = rand_ct(rng, q[: lvl + 1], 2, n, batch), rand_ct(rng, q[: lvl + 1], 2, n, batch)
+    beta = (klvl + 1 + len(p) - 1) // len(p)
+    key = np.empty((beta, 2, klvl + 1 + len(p), n), dtype=np.uint64)
+    for j, m in enumerate(q[: klvl + 1] + p):
+        key[:, :, j, :] = rng.integers(0, m, size=(beta, 2, n), dtype=np.uint64)
+    g = int(pow(5, 77, 2 * n))
+    ctx = DeviceContext(ALGO_CKKS, n, q, p)
+    ctx.set_fp64_ntt(0)
+    k = ctx.upload_key(key, klvl)
+    ctx.set_fp64_ntt(1)
+    da, db = ctx.upload(A), ctx.upload(Bc)
+    got_mul = ctx.download(ctx.ckks_mult_relin_rescale(lvl, da, db, k, batch), (batch, 2, lvl, n))
+    got_rot = ctx.download(ctx.ckks_rotate(lvl, da, g, k, batch), (batch, 2, lvl + 1, n))
+    for b in range(batch):
+        assert np.array_equal(got_mul[b], o.ckks_mult_relin_rescale(lvl, A[b], Bc[b], key, klvl)), ("hmult", b)
+        assert np.array_equal(got_rot[b], o.ckks_rotate(lvl, A[b], g, key, klvl)), ("rotate", b)
+    ctx.close()
+
+
 def test_headline_shape_full_size():
     """BASELINE configs[2] at full size (N=2^16, 13 Q + 4 P limbs): the fused operator against the oracle on one ciphertext,
     against the three separate operators, across butterfly engines / fused tails / operator tiles, and independent of the
