@@ -1,5 +1,5 @@
 // emu_ntt.cpp — CPU replay of the NTT kernel's phase functions, one simulated thread at a time
-// (g++ -DLSA_EMULATE).  Debugging aid for the kernel's indexing; used only by tests/test_emulate_ntt.py.
+// (g++ -DLSA_EMULATE).  Debugging aid for the kernel's indexing; used only by the tests/test_emulate_ntt*.py replays.
 #define LSA_EMULATE 1
 #include <cstddef>
 #include <vector>
@@ -10,7 +10,7 @@
 
 template <int NT>
 static void emu_block(const NttPassArgs& a, const NttBlockCtx& bc, u64* lds) {
-    for (int t = 0; t < NT; t++) ntt_phase_load<true, NT>(a, bc, t, lds);
+    for (int t = 0; t < NT; t++) ntt_phase_load<true, NT, true>(a, bc, t, lds);
     int rho[4];
     const int np = ntt_split(a.mu, rho);
     if (!a.inverse) {
@@ -36,7 +36,7 @@ static void emu_block_r16(const NttPassArgs& a, const NttBlockCtx& bc, u64* lds)
     for (int phase = 0; phase < 3; phase++)
         for (int t = 0; t < LSA_R16_THREADS; t++) {
             u64(&v)[16] = *reinterpret_cast<u64(*)[16]>(regs[t].data());
-            r16_phase<PASS, 3, MU>(a, bc, t, lds, phase, v);
+            r16_phase<PASS, 3 | 16, MU>(a, bc, t, lds, phase, v);
         }
 }
 
@@ -46,12 +46,14 @@ static void emu_block_r8x3(const NttPassArgs& a, const NttBlockCtx& bc, u64* lds
     for (int phase = 0; phase < 4; phase++)
         for (int t = 0; t < LSA_R16_THREADS; t++) {
             u64(&v)[16] = *reinterpret_cast<u64(*)[16]>(regs[t].data());
-            r8x3_phase<3>(a, bc, t, lds, phase, v);
+            r8x3_phase<3 | 16>(a, bc, t, lds, phase, v);
         }
 }
 
-extern "C" int lsa_emu_ntt(int n, const u64* moduli, int nmod, u64* data, int batch, long long batch_stride, int rows,
-                           const unsigned char* mod_of, int period, int inverse, int tau_max, int allow_fp64) {
+// pa / pb (inverse only): the product prologue, the transform's input is pa * pb (both [batch][rows][N], batch stride
+// batch_stride, as launch_ntt runs it for the tensor-fold key switch); data is then output only
+static int emu_ntt(int n, const u64* moduli, int nmod, u64* data, int batch, long long batch_stride, int rows,
+                   const unsigned char* mod_of, int period, int inverse, int tau_max, int allow_fp64, const u64* pa, const u64* pb) {
     const int row_inner = (allow_fp64 >> 1) & 1;   // bit 1: the (tile, row, batch) workgroup order
     const bool r16 = (allow_fp64 >> 2) & 1;        // bit 2: 8-stage passes through the radix-16-squared kernel
     allow_fp64 &= 1;
@@ -84,6 +86,14 @@ extern "C" int lsa_emu_ntt(int n, const u64* moduli, int nmod, u64* data, int ba
     a.row_step = 1;
     a.row_inner = row_inner;
     for (int i = 0; i < period; i++) a.mod_of[i] = mod_of[i];
+    if (pa) {
+        a.fz_pro = 3;
+        a.fz_limbs = rows;
+        a.fz_a = pa;
+        a.fz_b = pb;
+        a.fz_a_stride = a.fz_b_stride = batch_stride;
+        a.fz_a_rpp = a.fz_b_rpp = rows;
+    }
     // as launch_ntt: the grid covers the active rows only
     int launch_rows = 0;
     for (int r = 0; r < rows; r++)
@@ -93,7 +103,8 @@ extern "C" int lsa_emu_ntt(int n, const u64* moduli, int nmod, u64* data, int ba
     for (int step = 0; step < plan.npass; step++) {
         int k = inverse ? plan.npass - 1 - step : step;
         ntt_fill_pass(a, plan, T.logn, k, inverse);
-        a.fp_raw_out = plan.npass == 2 && step == 0;   // as launch_ntt sets them
+        a.fz_first = step == 0;   // as launch_ntt sets them
+        a.fp_raw_out = plan.npass == 2 && step == 0;
         a.fp_raw_in = plan.npass == 2 && step == 1;
         std::vector<u64> lds(lds_words(a.tau));
         long long nblocks = (long long)batch * launch_rows * (1 << (a.logn - a.tau));
@@ -112,4 +123,16 @@ extern "C" int lsa_emu_ntt(int n, const u64* moduli, int nmod, u64* data, int ba
         }
     }
     return 0;
+}
+
+extern "C" int lsa_emu_ntt(int n, const u64* moduli, int nmod, u64* data, int batch, long long batch_stride, int rows,
+                           const unsigned char* mod_of, int period, int inverse, int tau_max, int allow_fp64) {
+    return emu_ntt(n, moduli, nmod, data, batch, batch_stride, rows, mod_of, period, inverse, tau_max, allow_fp64, nullptr, nullptr);
+}
+
+extern "C" int lsa_emu_intt_prod(int n, const u64* moduli, int nmod, const u64* pa, const u64* pb, u64* out, int batch,
+                                 long long batch_stride, int rows, const unsigned char* mod_of, int period, int tau_max,
+                                 int allow_fp64) {
+    if (!pa || !pb) return -1;
+    return emu_ntt(n, moduli, nmod, out, batch, batch_stride, rows, mod_of, period, 1, tau_max, allow_fp64, pa, pb);
 }

@@ -61,8 +61,9 @@ __device__ __forceinline__ void ntt_butterfly_phases(const NttPassArgs& a, const
 // TWL: the pass holds global stage 0 (strided first pass of a two-pass plan): its 2^mu twiddles are the same for every tile
 // of the limb and go through LDS -- one fetch per workgroup, issued with the tile loads, instead of one per sub-pass.
 // FZ: 0 plain, 1 fused prologue only (first pass of a two-pass fused transform), 2 fused epilogue only (its last pass), 3 both
-// (single-pass transforms), 4 the pt_mul epilogue (fz_epi == 3) only, 8 the rotate-and-MAC epilogue (fz_epi == 4) only.  Split
-// so that a pass carries only the tail code and registers it can execute.
+// (single-pass transforms), 4 the pt_mul epilogue (fz_epi == 3) only, 8 the rotate-and-MAC epilogue (fz_epi == 4) only, 16 the
+// product prologue (fz_pro == 3, the first executed pass of an inverse transform) only.  Split so that a pass carries only the
+// tail code and registers it can execute.
 template <int FZ, int NT, bool TWL = false>
 __global__ __launch_bounds__(NT, NT > 512 ? 1 : NT > 256 ? 2 : (FZ & 1) ? LSA_NTT_WAVES_FUSED : LSA_NTT_WAVES) void k_ntt_pass(NttPassArgs a) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(NT, NT > 512 ? 1 : NT > 256 ? 2 : (FZ & 1) ? LSA_NT
     return;
 #endif
     LSA_STAMP(0);
-    ntt_phase_load<(FZ & 1) != 0, NT>(a, bc, tid, lds);
+    ntt_phase_load<(FZ & 1) != 0, NT, (FZ & 16) != 0>(a, bc, tid, lds);
     if (TWL && tid < (1 << a.mu)) {
         u64* tw_l = lds + lds_words(a.tau);
         if (bc.fp) tw_l[tid] = twp.x;
@@ -173,9 +174,23 @@ static bool ntt_launch_r16(const NttPassArgs& a, int npass, bool fused, long lon
         return !(e && e[0] == '0');
     }();
     if (!enabled || !ntt_r16_shape_ok(a, npass)) return false;
-    const bool pro = fused && a.fz_pro && a.s_lo == 0, epi = fused && a.fz_epi && a.final_reduce;
+    const bool pro = fused && a.fz_pro && a.fz_first, epi = fused && a.fz_epi && a.final_reduce;
     const size_t lds_bytes = (size_t)LSA_R16_LDS_WORDS * sizeof(u64);
     const dim3 grid((unsigned)nblocks), block(LSA_R16_THREADS);
+    if (pro && a.fz_pro == 3) {   // the product prologue (FZ bit 16): the first executed pass of an inverse transform = a second pass
+        if (a.lambda || !a.inverse) return false;
+        if (a.mu == 9) {
+            const char* e = getenv("LSA_NTT_R8X3");
+            if (e && e[0] == '0') return false;
+            hipLaunchKernelGGL((k_ntt_r8x3<16>), grid, block, lds_bytes, s, a);
+        } else if (a.mu == 8) {
+            hipLaunchKernelGGL((k_ntt_r16<1, 16, 8>), grid, block, lds_bytes, s, a);
+        } else {
+            hipLaunchKernelGGL((k_ntt_r16<1, 16, 7>), grid, block, lds_bytes, s, a);
+        }
+        LSA_HIP(hipGetLastError());
+        return true;
+    }
     if (epi && a.fz_epi == 3) {   // the pt_mul epilogue (FZ bit 4): second passes only, it has no prologue
         if (a.lambda) return false;
         if (a.mu == 9) {
@@ -285,6 +300,7 @@ __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMA
     a.scaled = nullptr;
     a.src = g.ext;
     a.fz_pro = a.fz_epi = 0;
+    a.fz_first = 0;
     NttBlockCtx bc;
     bc.tile = tile;
     bc.mod = tl < g.L ? tl : g.nq + (tl - g.L);
@@ -451,7 +467,12 @@ static void ntt_launch_pass(const NttPassArgs& a, bool fused, long long nblocks,
     LSA_REQUIRE((1 << a.tau) <= 2 * LSA_NTT_STAGE_PAIRS * NT, "ntt: tile larger than the staging registers");
     // which fused tail this pass can execute: the prologue lives in the pass that holds stage 0, the epilogue in the pass
     // that reduces and stores the final values
-    const bool pro = fused && a.fz_pro && a.s_lo == 0, epi = fused && a.fz_epi && a.final_reduce;
+    const bool pro = fused && a.fz_pro && a.fz_first, epi = fused && a.fz_epi && a.final_reduce;
+    if (pro && a.fz_pro == 3) {   // the product prologue (FZ bit 16, no epilogue): only tiles of the two-pass shape take it
+        if constexpr (NT == LSA_NTT_THREADS) ntt_launch_variant<16, NT>(a, nblocks, lds_bytes, s);
+        else LSA_REQUIRE(false, "ntt: the product prologue needs a tile of at most 4096 points");
+        return;
+    }
     if (epi && a.fz_epi == 3) {   // the pt_mul epilogue (FZ bit 4, no prologue)
         ntt_launch_variant<4, NT>(a, nblocks, lds_bytes, s);
         return;
@@ -486,7 +507,10 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
     a.scaled = c.d_scale_d;
     a.allow_fp64 = c.fp64_ntt;
     if (fz) {
-        LSA_REQUIRE(!inverse, "fused tails exist for forward transforms only");
+        // inverse transforms take the product prologue and nothing else; it forms its input in the first executed pass
+        LSA_REQUIRE(!inverse || (fz->pro == 3 && !fz->epi), "inverse transforms take the product prologue only");
+        LSA_REQUIRE(fz->pro != 3 || (inverse && !fz->epi && fz->a && fz->b && fz->limbs >= 1 && (passes & 1)),
+                    "product prologue: an inverse transform from its first pass, two operands, no epilogue");
         a.fz_epi = fz->epi;
         a.fz_pro = fz->pro;
         a.fz_limbs = fz->limbs;
@@ -516,6 +540,9 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
         a.fz_pt = fz->pt;
         a.fz_pt_stride = fz->pt_stride;
         a.fz_accum = fz->accumulate ? 1 : 0;
+        a.fz_b = fz->b;
+        a.fz_b_stride = fz->b_stride;
+        a.fz_b_rpp = fz->b_rpp;
     }
     a.period = rm.period;
     a.row0 = rm.row0;
@@ -556,6 +583,7 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
         wide = !fz && (c.logn == 13 ? limbs >= 1024 : (all_fp && limbs >= 512));
     }
     if (passes != 3) wide = false;   // a caller that runs the passes separately means the two-pass plan
+    if (fz && fz->pro == 3) wide = false;   // (the product prologue has no whole-limb kernel)
     const NttPlan& plan = wide ? c.plan_wide : c.plan;
     a.tw = wide ? (inverse ? c.d_psiinv_w : c.d_psi_w) : (inverse ? c.d_psiinv : c.d_psi);
     a.twd = wide ? (inverse ? c.d_psiinv_d_w : c.d_psi_d_w) : (inverse ? c.d_psiinv_d : c.d_psi_d);
@@ -589,12 +617,20 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
             a.fz_pt = fz->pt + (long long)b0 * fz->pt_stride;
             a.fz_out = fz->out + (long long)b0 * fz->out_stride;
         }
+        if (fz && fz->pro == 3) {   // and the product prologue's
+            a.fz_a = fz->a + (long long)b0 * fz->a_stride;
+            a.fz_b = fz->b + (long long)b0 * fz->b_stride;
+        }
+        bool first = true;
         for (int step = 0; step < plan.npass; step++) {
             if (plan.npass == 2 && !((passes >> step) & 1)) continue;
+            a.fz_first = first ? 1 : 0;   // the prologue's pass: the transform's first EXECUTED pass, forward or inverse
+            first = false;
             const int k = inverse ? plan.npass - 1 - step : step;
             ntt_fill_pass(a, plan, c.logn, k, inverse ? 1 : 0);
             a.fp_raw_out = plan.npass == 2 && step == 0 && c.fp_raw;
             a.fp_raw_in = plan.npass == 2 && step == 1 && c.fp_raw;
+            LSA_REQUIRE(!(a.fz_first && a.fz_pro && a.fp_raw_in), "ntt: a fused prologue reads canonical inputs, never a raw hand-off");
             a.src = (step == 0 ? src + (long long)b0 * src_stride : dst + (long long)b0 * dst_stride);
             a.src_stride = step == 0 ? src_stride : dst_stride;
             a.dst = dst + (long long)b0 * dst_stride;
@@ -604,7 +640,9 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
             LSA_REQUIRE(nblocks < (1LL << 31), "ntt: grid too large");
             const size_t lds_bytes = (size_t)lds_words(a.tau) * sizeof(u64);
             // one launch = one pass = 1/npass of the limb transforms it touches (algorithmic 16*N bytes per transform)
-            ProfScope ps(c, PROF_NTT, 16.0 * c.n * active_rows * nb / plan.npass, s);
+            // (+ the product prologue's second operand: two 8 N reads in place of one)
+            const double pro_bytes = fz && fz->pro == 3 && a.fz_first ? 8.0 * c.n * active_rows * nb : 0.0;
+            ProfScope ps(c, PROF_NTT, 16.0 * c.n * active_rows * nb / plan.npass + pro_bytes, s);
             if (ntt_launch_r16(a, plan.npass, fz != nullptr, nblocks, s)) continue;
             if (a.tau <= 12) ntt_launch_pass<LSA_NTT_THREADS>(a, fz != nullptr, nblocks, lds_bytes, s);
             else if (a.tau == 13) ntt_launch_pass<512>(a, fz != nullptr, nblocks, lds_bytes, s);
@@ -1058,41 +1096,6 @@ void launch_tensor(Context& c, const u64* a, const u64* b, u64* d, int batch, lo
     fill_rowmap(g.mod_of, period, rm, c.nmod);
     ProfScope ps(c, PROF_TENSOR, 7.0 * 8 * c.n * limbs * batch, s);
     hipLaunchKernelGGL(k_tensor, ew_grid(c, limbs, batch), dim3(TPB), 0, s, g);
-    LSA_HIP(hipGetLastError());
-}
-
-// d2 = a1 * b1 alone (the tensor-fold HMult: d0 and d1 never leave the key MAC), the same residues as k_tensor's third output
-__global__ __launch_bounds__(TPB) void k_tensor_d2(TensorArgs g) {
-    const int chunks = (1 << g.logn) / (2 * TPB);
-    const int limb = blockIdx.x / chunks;
-    const int x = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
-    const ModDev m = g.mods[limb];
-    const long long b = blockIdx.y;
-    const long long off = ((long long)limb << g.logn) + x;
-    const ulonglong2 a1 = ld2(g.a + b * g.sa + g.pa + off), b1 = ld2(g.b + b * g.sb + g.pb + off);
-    st2(g.d + b * g.sd + off, mont_mul(a1.x, mont_mul_lazy(b1.x, m.r2, m.q, m.qinv), m.q, m.qinv),
-        mont_mul(a1.y, mont_mul_lazy(b1.y, m.r2, m.q, m.qinv), m.q, m.qinv));
-}
-
-void launch_tensor_d2(Context& c, const u64* a, const u64* b, u64* d2, int batch, long long sa, long long sb, long long sd,
-                      int limbs, hipStream_t s, int a_rpp, int b_rpp) {
-    if (batch <= 0) return;
-    TensorArgs g{};
-    LSA_REQUIRE((a_rpp == 0 || a_rpp >= limbs) && (b_rpp == 0 || b_rpp >= limbs), "tensor: rows per polynomial below the limb count");
-    LSA_REQUIRE(limbs <= c.nq, "tensor: Q limbs only");
-    g.pa = (long long)(a_rpp ? a_rpp : limbs) << c.logn;
-    g.pb = (long long)(b_rpp ? b_rpp : limbs) << c.logn;
-    g.a = a;
-    g.b = b;
-    g.d = d2;
-    g.sa = sa;
-    g.sb = sb;
-    g.sd = sd;
-    g.mods = c.d_mods;
-    g.limbs = limbs;
-    g.logn = c.logn;
-    ProfScope ps(c, PROF_TENSOR, 3.0 * 8 * c.n * limbs * batch, s);
-    hipLaunchKernelGGL(k_tensor_d2, ew_grid(c, limbs, batch), dim3(TPB), 0, s, g);
     LSA_HIP(hipGetLastError());
 }
 

@@ -218,7 +218,9 @@ struct RowMap {   // rows of a batch item -> modulus index (0xFF = skip)
 
 void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long batch_stride, int rows, const RowMap& rm,
                 bool inverse, hipStream_t s);
-// element-wise work fused into a forward transform's first-pass load / last-pass store (see NttPassArgs::fz_*)
+// element-wise work fused into a forward transform's first-pass load / last-pass store (see NttPassArgs::fz_*), or (pro == 3,
+// the only fusion an inverse transform takes) into the load of its first executed pass: in = a * b, a and b canonical
+// NTT-domain residues, row r of the transform = limb r % limbs of polynomial r / limbs of each operand
 struct NttFusion {
     int epi = 0, pro = 0, limbs = 1, base_polys = 0, ql_mod = 0;
     const u64* a = nullptr;
@@ -240,6 +242,10 @@ struct NttFusion {
     const u64* pt = nullptr;        // pt_mul plaintexts [batch][limbs][N]
     long long pt_stride = 0;
     bool accumulate = false;        // add to out (later terms) instead of writing it (the first)
+    // pro == 3: the second operand (the first is a / a_stride / a_rpp)
+    const u64* b = nullptr;
+    long long b_stride = 0;
+    int b_rpp = 0;
 };
 // passes: bit 0 = the first executed pass, bit 1 = the second (two-pass plans; a caller that fuses the second pass into
 // another kernel asks for 1 only)
@@ -273,10 +279,6 @@ void launch_lift_ringt(Context& c, int mode, int level, const u64* pt, long long
 // `limbs` rows of each polynomial are the operand at this level -- no copy needed to "drop" it)
 void launch_tensor(Context& c, const u64* a, const u64* b, u64* d, int batch, long long sa, long long sb, long long sd,
                    int limbs, const RowMap& rm, hipStream_t s, int a_rpp = 0, int b_rpp = 0);
-// d2 = a1 * b1 only (limbs 0..limbs-1, [limbs][N] per item), the residues k_tensor writes to its third polynomial: the input
-// of the tensor-fold key switch's ModUp (the key MAC takes d0 / d1 / the own digit from a and b themselves, TensorFold)
-void launch_tensor_d2(Context& c, const u64* a, const u64* b, u64* d2, int batch, long long sa, long long sb, long long sd,
-                      int limbs, hipStream_t s, int a_rpp = 0, int b_rpp = 0);
 // the tensor product folded into the relinearisation's key MAC (CKKS HMult+relin+rescale): for a Q target limb j the MAC
 // takes its own digit as d2_j = a1_j * b1_j and adds P * d0_j to the first and P * d1_j to the second running sum
 // (d0 = a0 b0, d1 = a0 b1 + a1 b0): acc'_j = acc_j + P * d_j.  a / b point at the tile's first item, [2][rpp][N] each.

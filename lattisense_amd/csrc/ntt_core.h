@@ -89,9 +89,12 @@ struct NttPassArgs {
     // epilogue of the LAST pass of a forward transform, replaces the plain store of the transformed value v:
     //   fz_epi = 1:  out[poly][limb] = (fz_a[poly][limb] - v) * fz_k[limb]  (+ fz_base[poly][limb] if poly < fz_base_polys)
     //                (ModDown tail: (acc_Q - conv) * P^-1 + d;   rescale tail: (c - t) * q_l^-1)
-    // prologue of the FIRST pass, replaces the plain load:
+    // prologue of the FIRST EXECUTED pass (fz_first; the last plan pass of an inverse transform), replaces the plain load:
     //   fz_pro = 1:  in = lift = ((fz_last[poly] + h) mod q_l) mod q_limb - (h mod q_limb),  h = (q_l - 1)/2  (rescale head)
     //   fz_pro = 2:  in = src + lift   (merged ModDown + rescale: one transform of conv*P^-1 + lift serves both steps)
+    //   fz_pro = 3:  in = fz_a[poly][limb] * fz_b[poly][limb] mod q   (NTT-domain canonical operands, rows per polynomial
+    //                fz_a_rpp / fz_b_rpp; FZ bit 16, ntt_make_prod_fix): the tensor-fold HMult's ModUp input d2 = a1 b1, formed
+    //                by the load of its inverse transform instead of being stored and read back
     //   fz_epi = 2:  out = (fz_a * fz_k - v + fz_base) * fz_k2   (its tail: (acc*P^-1 - NTT(in) + base) * q_l^-1)
     //   fz_epi = 3:  out[poly][limb] = v * fz_a[limb] * 2^-64 (+ fz_base[poly][limb] if fz_base)   (BFV ct x pt_mul: the
     //                Montgomery-form plaintext, shared by both polys; kernels compiled with FZ bit 4, ntt_phase_store_ptm)
@@ -116,6 +119,11 @@ struct NttPassArgs {
     const u64* fz_pt;         // the term's pt_mul plaintexts [batch][fz_limbs][N] (batch stride fz_pt_stride)
     long long fz_pt_stride;
     int fz_accum;             // 0: the first term writes out, 1: later terms add to it
+    // fz_pro = 3 only: the second operand
+    const u64* fz_b;
+    long long fz_b_stride;
+    int fz_b_rpp;
+    int fz_first;             // 1: this launch runs the transform's first executed pass (set by launch_ntt): the prologue's pass
 };
 
 LSA_HD int lds_addr(int l) { return l + (l >> 4); }
@@ -373,10 +381,12 @@ LSA_HD NttLoadFix ntt_make_load_fix(const NttPassArgs& a, const NttBlockCtx& bc,
     g = a.src + bc.base_src;
     gl = g;   // last-limb source of the head modes
     NttLoadFix f;
-    f.head = FZ && a.fz_pro && a.s_lo == 0;   // fused rescale head: the tile is derived from the (coefficient-domain) last limb
+    // fused rescale head: the tile is derived from the (coefficient-domain) last limb
+    f.head = FZ && (a.fz_pro == 1 || a.fz_pro == 2) && a.fz_first;
     f.add = f.head && a.fz_pro == 2;
     f.fp = bc.fp != 0;
     f.raw = f.fp && a.fp_raw_in;   // (never together with a fused prologue: that belongs to the first pass)
+    LSA_EMU_CHECK(!(a.fz_pro && a.fz_first && a.fp_raw_in));
     f.mi = a.mods[bc.mod];
     f.ql = f.h = f.hq = 0;
     f.hd = f.qld = 0.0;
@@ -394,11 +404,70 @@ LSA_HD NttLoadFix ntt_make_load_fix(const NttPassArgs& a, const NttBlockCtx& bc,
     }
     return f;
 }
-template <bool FZ, int NT>
+// ---- the product prologue (fz_pro == 3): in = a * b mod q for canonical a, b.  Integer limbs: two Montgomery products
+// (k_tensor's for d2), canonical.  FP64-engine limbs: fp_modmul gives (-1.1q, 1.1q), one fp_reduce takes it to |.| <= q/2 + 1 --
+// the range of a raw hand-off between passes, which every pass of either direction takes (a forward stage adds < 1.1q, an
+// inverse sub-pass of 2^rho points sums at most 2^rho of them and reduces after itself).
+struct NttProdFix {
+    const u64* pa;
+    const u64* pb;
+    ModDev mi;
+    double qd, qinvd;
+    bool fp;
+};
+LSA_HD NttProdFix ntt_make_prod_fix(const NttPassArgs& a, const NttBlockCtx& bc) {
+    const int poly = bc.row / a.fz_limbs, limb = bc.row % a.fz_limbs;
+    NttProdFix p;
+    p.pa = a.fz_a + (long long)bc.b * a.fz_a_stride + (((long long)poly * a.fz_a_rpp + limb) << a.logn);
+    p.pb = a.fz_b + (long long)bc.b * a.fz_b_stride + (((long long)poly * a.fz_b_rpp + limb) << a.logn);
+    p.mi = a.mods[bc.mod];
+    p.fp = bc.fp != 0;
+    p.qd = (double)p.mi.q;
+    p.qinvd = 1.0 / p.qd;
+    LSA_EMU_CHECK(!a.fp_raw_in);
+    return p;
+}
+LSA_HD u64 ntt_prod_fix(const NttProdFix& p, u64 x, u64 y) {
+    LSA_EMU_CHECK(x < p.mi.q && y < p.mi.q);
+    if (p.fp) return d_to_bits(fp_reduce(fp_modmul(u52_to_double(x), u52_to_double(y), p.qd, p.qinvd), p.qd, p.qinvd));
+    return mont_mul(x, mont_mul_lazy(y, p.mi.r2, p.mi.q, p.mi.qinv), p.mi.q, p.mi.qinv);
+}
+// PR: the kernel carries the product prologue (FZ bit 16); it runs where the launch asks for it (fz_pro == 3, first executed pass)
+template <bool FZ, int NT, bool PR = false>
 LSA_HD void ntt_phase_load(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64* lds) {
     const u64* g;
     const u64* gl;
     const int half = 1 << (a.tau - 1);
+    if (PR && a.fz_pro == 3 && a.fz_first) {
+        const NttProdFix pf = ntt_make_prod_fix(a, bc);
+        const NttTileMap tm = ntt_tile_map(a, bc.tile);
+        if (half == LSA_NTT_STAGE_PAIRS * NT) {   // two operands per element: half the pairs per round, as the head modes
+            constexpr int CH = LSA_NTT_STAGE_PAIRS / LSA_NTT_HEAD_ROUNDS;
+#pragma unroll 1
+            for (int p0 = 0; p0 < LSA_NTT_STAGE_PAIRS; p0 += CH) {
+                u64 sa[2 * CH], sb[2 * CH];
+#pragma unroll
+                for (int p = 0; p < CH; p++) {
+                    const int x = ntt_tile_index(tm, 2 * (tid + (p0 + p) * NT));
+                    ntt_load_data_pair(pf.pa + x, sa[2 * p], sa[2 * p + 1]);
+                    ntt_load_data_pair(pf.pb + x, sb[2 * p], sb[2 * p + 1]);
+                }
+#pragma unroll
+                for (int p = 0; p < CH; p++) {
+                    const int l = 2 * (tid + (p0 + p) * NT);
+                    lds[lds_addr(l)] = ntt_prod_fix(pf, sa[2 * p], sb[2 * p]);
+                    lds[lds_addr(l + 1)] = ntt_prod_fix(pf, sa[2 * p + 1], sb[2 * p + 1]);
+                }
+            }
+            return;
+        }
+        for (int i = tid; i < half; i += NT) {   // partial tiles (small rings)
+            const int x = ntt_tile_index(tm, 2 * i);
+            lds[lds_addr(2 * i)] = ntt_prod_fix(pf, pf.pa[x], pf.pb[x]);
+            lds[lds_addr(2 * i + 1)] = ntt_prod_fix(pf, pf.pa[x + 1], pf.pb[x + 1]);
+        }
+        return;
+    }
     const NttLoadFix f = ntt_make_load_fix<FZ>(a, bc, g, gl);
     const NttTileMap tm = ntt_tile_map(a, bc.tile);
     if (half == LSA_NTT_STAGE_PAIRS * NT && !f.add) {

@@ -261,9 +261,39 @@ LSA_HD void r16_pair_pos(int tid, int m, int& k, int& i) {
     k = (wave << (10 - MU)) + (c >> MU);
     i = c & ((1 << MU) - 1);
 }
-// second pass, inverse: 16-byte coalesced loads -> LDS (contiguous image is read back from there)
-template <bool FZ, int MU>
+// second pass, inverse: 16-byte coalesced loads -> LDS (contiguous image is read back from there).  PR: the product prologue
+// (fz_pro == 3, FZ bit 16: the inverse transform's first executed pass forms a * b as it loads, ntt_core.h ntt_prod_fix)
+template <bool FZ, int MU, bool PR = false>
 LSA_HD void r16_load_coalesced(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64* lds) {
+    if (PR && a.fz_pro == 3 && a.fz_first) {
+        const NttProdFix pf = ntt_make_prod_fix(a, bc);
+        u64 sa[16], sb[16];   // all 16 operand pairs in flight (64 VGPRs: nothing else is live yet)
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            int k, i;
+            r16_pair_pos<MU>(tid, m, k, i);
+            const long long x = r16_x<1, MU>(a, bc.tile, k, i);
+            ntt_load_data_pair(pf.pa + x, sa[2 * m], sa[2 * m + 1]);
+            ntt_load_data_pair(pf.pb + x, sb[2 * m], sb[2 * m + 1]);
+        }
+        // (block-uniform engine: a branch around each loop instead of both products per element and a select)
+        if (pf.fp) {
+#pragma unroll
+            for (int j = 0; j < 16; j++)
+                sa[j] = d_to_bits(fp_reduce(fp_modmul(u52_to_double(sa[j]), u52_to_double(sb[j]), pf.qd, pf.qinvd), pf.qd, pf.qinvd));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; j++) sa[j] = ntt_prod_fix(pf, sa[j], sb[j]);
+        }
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            int k, i;
+            r16_pair_pos<MU>(tid, m, k, i);
+            lds[r16_lds<1, MU>(k, i)] = sa[2 * m];
+            lds[r16_lds<1, MU>(k, i + 1)] = sa[2 * m + 1];
+        }
+        return;
+    }
     const u64* g;
     const u64* gl;
     NttLoadFix f = ntt_make_load_fix<FZ>(a, bc, g, gl);
@@ -496,7 +526,7 @@ LSA_HD void r16_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64*
     } else {
         if (phase == 0) {
             if (PASS == 0) r16_load_direct<PASS, false, 1, MU>(a, bc, tid, v);
-            else r16_load_coalesced<false, MU>(a, bc, tid, lds);
+            else r16_load_coalesced<false, MU, (FZ & 16) != 0>(a, bc, tid, lds);
         } else if (phase == 1) {
             if (PASS == 1) r16_lds_get<PASS, 1, MU>(tid, lds, v);
             r16_group<PASS, 1, MU>(v, a, bc, L, G2);
@@ -589,7 +619,7 @@ LSA_HD void r8x3_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64
         }
     } else {
         if (phase == 0) {
-            r16_load_coalesced<false, 9>(a, bc, tid, lds);
+            r16_load_coalesced<false, 9, (FZ & 16) != 0>(a, bc, tid, lds);
         } else if (phase == 1) {
             r8x3_get<2>(k, i, lds, v);
             r8x3_group<2>(v, a, bc, L, G1, i);

@@ -236,12 +236,27 @@ struct KsTile {
 
     // steps 1-3: cx out of the NTT domain, every digit converted to the other limbs of Q u P, extended limbs back into the NTT
     // domain.  cx_coef: the same polynomial in the coefficient domain if the caller has it (BFV): the inverse transform is
-    // skipped.  Fused: the limbs that take the fused kernel are left after the first pass (mac() runs the second).
-    void decompose(const u64* cx, long long scx, const u64* cx_coef = nullptr, long long s_coef = 0) {
+    // skipped.  prod (tensor fold, cx unused): cx = a1 * b1 is never stored, the inverse transform forms it as it loads (the
+    // product prologue).  Fused: the limbs that take the fused kernel are left after the first pass (mac() runs the second).
+    void decompose(const u64* cx, long long scx, const u64* cx_coef = nullptr, long long s_coef = 0, const TensorFold* prod = nullptr) {
         const long long N = c.n;
         const int np = c.np;
         // 1. cx out of the NTT domain
-        if (!cx_coef) launch_ntt(c, cx, cxi, nb, scx, s_cxi, L, rm_seq(L), true, s);
+        if (prod) {
+            LSA_REQUIRE(!cx_coef, "key switch: a product source has no coefficient-domain copy");
+            NttFusion fz;
+            fz.pro = 3;
+            fz.limbs = L;
+            fz.a = prod->a + prod->pa;   // the second polynomials a1, b1
+            fz.a_stride = prod->sa;
+            fz.a_rpp = (int)(prod->pa >> c.logn);
+            fz.b = prod->b + prod->pb;
+            fz.b_stride = prod->sb;
+            fz.b_rpp = (int)(prod->pb >> c.logn);
+            launch_ntt(c, cxi, cxi, nb, s_cxi, s_cxi, L, rm_seq(L), true, s, &fz);
+        } else if (!cx_coef) {
+            launch_ntt(c, cx, cxi, nb, scx, s_cxi, L, rm_seq(L), true, s);
+        }
         const u64* conv_src = cx_coef ? cx_coef : cxi;
         const long long s_src = cx_coef ? s_coef : s_cxi;
         // 2. per digit: exact conversion of the digit's limbs to every other limb of Q u P
@@ -289,7 +304,7 @@ struct KsTile {
 
     // step 4: the gadget inner product of the digits with key k (both halves) -> acc, [2][L+k][N] over Q_level u P, NTT
     // domain; fused with the extension transform's second pass where decompose() stopped after the first one.
-    // fold: the tensor product folded into the MAC (TensorFold; cx is then d2 and only the decomposition reads it)
+    // fold: the tensor product folded into the MAC (TensorFold; the own digits come from its operands, cx is not read)
     void mac(const u64* cx, long long scx, const Key& k, const TensorFold* fold = nullptr) {
         if (!fused) {
             launch_ks_mac(c, level, cx, scx, ext, s_ext, k, acc, s_acc, nb, s, false, nullptr, nullptr, 0, fold);
@@ -572,7 +587,7 @@ void ckks_mult_relin_rescale(Context& c, int level, const u64* a, const u64* b, 
 // Tensor fold (fused tails; LSA_HMULT_FOLD=0 keeps the three steps apart, read per call: the parity tests flip it inside one
 // process).  d0, d1 and d2 = k_tensor's outputs are each read again by one consumer only, and each consumer can take them
 // from a and b itself, residue for residue:
-//   ModUp input  d2 = a1 b1                   (k_tensor_d2: L rows written instead of 3L, 2 operand polynomials read instead of 4)
+//   ModUp input  d2 = a1 b1                   (formed by the load of the decomposition's inverse transform, never stored)
 //   MAC          own digit of Q target j: d2_j = a1_j b1_j, and acc'_j = acc_j + P * d_j  (d = (d0, d1), TensorFold)
 //   ModDown      (acc'_j * P^-1 - NTT(in)) * q_l^-1 = (acc_j * P^-1 - NTT(in) + d_j) * q_l^-1;
 //                INTT(acc'_l) * P^-1 = INTT(acc_l) * P^-1 + INTT(d_l)       (the merged tail with base_polys = 0)
@@ -589,7 +604,7 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
     const long long N = c.n;
     const int L = level + 1;
     const bool fold = c.fuse_tails && hmult_fold_on();
-    const size_t r_d3 = (fold ? 1 : 3) * (size_t)L, r_r2 = 2 * (size_t)L;
+    const size_t r_d3 = (fold ? 0 : 3) * (size_t)L, r_r2 = 2 * (size_t)L;
     const size_t r_shared = std::max(KsTile::rows(c, level), rescale_ws_rows(level, 2));
     const long long sd = (long long)r_d3 * N, sr = 2LL * L * N;
     for_tiles(c, r_d3 + r_r2 + r_shared, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
@@ -599,11 +614,11 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
         if (fold) {
             const u64* ta = a + (size_t)b0 * sa;
             const u64* bt = b + (size_t)b0 * sb;
-            launch_tensor_d2(c, ta, bt, d3, nb, sa, sb, sd, L, st, a_rpp, b_rpp);
+            LSA_REQUIRE((a_rpp == 0 || a_rpp >= L) && (b_rpp == 0 || b_rpp >= L), "tensor: rows per polynomial below the limb count");
             const TensorFold tf{ta, bt, sa, sb, (long long)(a_rpp ? a_rpp : L) * N, (long long)(b_rpp ? b_rpp : L) * N};
             KsTile t(c, level, nb, sub, st, &rlk);
-            t.decompose(d3, sd);
-            t.mac(d3, sd, rlk, &tf);
+            t.decompose(nullptr, 0, nullptr, 0, &tf);
+            t.mac(t.cxi, t.s_cxi, rlk, &tf);   // (the MAC takes the own digit from a and b: its cx is not read)
             t.moddown({.p = r2, .sp = sr, .form = KsOut::RESCALE, .rs = {out + (size_t)b0 * so, so}});
             return;
         }
