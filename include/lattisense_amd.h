@@ -205,6 +205,13 @@ int lsa_ckks_bootstrap(lsa_context ctx, lsa_bootstrap b, const uint64_t* in, uin
 /* diagnostic builds only (-DLSA_NTT_DIAG_STAMPS): device buffer of 8192*8 u64 receiving per-workgroup phase time stamps
  * of every following NTT launch; NULL turns it off.  Ignored by the normal build. */
 int lsa_debug_set_ntt_stamps(lsa_context ctx, void* device_buffer);
+/* Read-only views of decisions the context has taken, for tests.  The base-conversion plans built so far (one per distinct
+ * source / destination list and flavour, in a fixed order): source and destination limb counts and whether the plan runs
+ * the narrow kernel's 29-bit split accumulate.  count receives the number of plans; at most `capacity` are written. */
+int lsa_debug_baseconv_plans(lsa_context ctx, int capacity, int* count, int* ns, int* nd, int* split);
+/* Whether a key switch with this one key at this level runs the extension transform's second pass fused with the key MAC
+ * (under the settings and environment switches in force at the call). */
+int lsa_debug_key_switch_fused(lsa_context ctx, int level, lsa_key key, int* fused);
 /* Sampled HIP-event timing of the library's own kernel launches, recorded on the stream they are launched on (every
  * `stride`-th launch of each kind gets an event pair).  kind: 0 NTT pass, 1 base conversion, 2 key-switch MAC,
  * 3 tensor, 4 other element-wise.  total_bytes = ALGORITHMIC bytes of the sampled launches. */

@@ -79,6 +79,9 @@ SIGNATURES = {
     "lsa_set_fuse_tails": (c_int, [c_vp, c_int]),
     "lsa_set_ntt_chunk_mib": (c_int, [c_vp, c_int]),
     "lsa_debug_set_ntt_stamps": (c_int, [c_vp, c_vp]),
+    "lsa_debug_baseconv_plans": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                         ctypes.POINTER(c_int)]),
+    "lsa_debug_key_switch_fused": (c_int, [c_vp, c_int, c_vp, ctypes.POINTER(c_int)]),
     "lsa_ckks_rotate_many": (c_int, [c_vp, c_int, c_vp, c_int, c_u64p, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_int,
                                      ctypes.c_longlong, ctypes.c_longlong, c_vp]),
     "lsa_bfv_rotate_many": (c_int, [c_vp, c_int, c_vp, c_int, c_u64p, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_int,

@@ -345,6 +345,29 @@ int lsa_set_dual_stream(lsa_context ctx, int enable) {
 int lsa_debug_set_ntt_stamps(lsa_context ctx, void* device_buffer) {
     return guard([&] { C(ctx).ntt_diag = static_cast<unsigned long long*>(device_buffer); });
 }
+int lsa_debug_baseconv_plans(lsa_context ctx, int capacity, int* count, int* ns, int* nd, int* split) {
+    return guard([&] {
+        Context& c = C(ctx);
+        LSA_REQUIRE(count != nullptr && (capacity == 0 || (ns && nd && split)), "null argument");
+        std::lock_guard<std::mutex> lk(c.mu);
+        *count = (int)c.bconv.size();
+        int i = 0;
+        for (auto& kv : c.bconv) {
+            if (i >= capacity) break;
+            ns[i] = kv.second.ns;
+            nd[i] = kv.second.nd;
+            split[i] = kv.second.split29 ? 1 : 0;
+            i++;
+        }
+    });
+}
+int lsa_debug_key_switch_fused(lsa_context ctx, int level, lsa_key key, int* fused) {
+    return guard([&] {
+        Context& c = C(ctx);
+        LSA_REQUIRE(fused != nullptr && level >= 0 && level < c.nq, "bad argument");
+        *fused = ks_fuse_mac(c, level, K(key)) ? 1 : 0;
+    });
+}
 
 int lsa_ckks_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_rot, const uint64_t* galois_elements,
                          const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream) {

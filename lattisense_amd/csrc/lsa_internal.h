@@ -356,6 +356,7 @@ void key_prepare(Context& c, Key& key, u64* data, int key_level, double* fp, hip
 bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* ext, long long sext, const Key& key, u64* acc,
                       long long sacc, int batch, hipStream_t s, const TensorFold* fold = nullptr);
 int ks_fused_engines(const Context& c);   // which engines' target limbs take the fused kernel (LSA_KS_FUSED_ENGINES, default FP64 only)
+bool ks_fuse_mac(const Context& c, int level, const Key& key);   // a single-key switch at this level runs k_ntt_r16_ksmac (ops.hip)
 bool ks_fused_limb(const Context& c, int L, int tl);   // target limb tl of Q_level u P takes it (by its engine)
 // out = (a - b) * k_i  with per-row constant (Montgomery form) ; out = a * k_i
 void launch_sub_mul_const(Context& c, const u64* a, long long sa, const u64* b, long long sb, const u64* kvec, u64* out,

@@ -692,7 +692,10 @@ LSA_HD void r16_mac_digit(const KsFusedArgs& g, const NttPassArgs& a, const NttB
         // and the FP64 instantiations spill (MU = 8: 232 -> 256 VGPRs, 48 spilled); this way they stay at 2 workgroups per
         // CU without scratch (profiles/r07/hmult_fold_resources.txt).
         // FP64 sums: every term is an integer-valued double in (-1.1q, 1.1q) (fp_modmul); a sum holds beta + 1 (first half)
-        // or beta + 2 (second half) of them, below 9 * 1.1 * 2^47 < 2^51 for beta <= 7: exact (2^53), and fp_reduce's range.
+        // or beta + 2 (second half) of them.  The fused kernel runs beta <= 13 (beta * T <= LSA_MAX_PERIOD with T >= beta + 1):
+        // at most 15 terms, below 15 * 1.1 * 2^47 < 2^51.1 -- past 2^51 from beta = 13 on, which is fine: the sums are only
+        // added and then reduced, never multiplied, and sums of integers below 2^53 are exact, as is fp_reduce for |x| < 2^53
+        // (tests/cpp/test_ntt_fix.cpp checks fp_reduce over that whole range).
         // Integer sums: every Montgomery product is below 2q (operands below 2q and q), the sums stay below 2q as below.
         const u64* pa0 = g.fa + b * g.sfa + (long long)tl * N;
         const u64* pb0 = g.fb + b * g.sfb + (long long)tl * N;

@@ -188,7 +188,7 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
 
 // one key per decomposition (relinearisation, a single rotation, a generic switch): the extension transform's second pass
 // and the key MAC run as one kernel where the shape allows (k_ntt_r16_ksmac) and some target limb takes it
-static bool ks_fuse_mac(const Context& c, int level, const Key& key) {
+bool ks_fuse_mac(const Context& c, int level, const Key& key) {
     const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
     if (!ks_fused_enabled(c) || !ks_fused_engines(c) || (c.fp64_ntt && !key.fp) || beta * T > LSA_MAX_PERIOD || T > 64) return false;
     for (int tl = 0; tl < T; tl++)

@@ -84,6 +84,21 @@ class DeviceContext:
     def set_tile_batch(self, tb):
         check(lib().lsa_set_tile_batch(self.h, tb))
 
+    def baseconv_plans(self):
+        """the base-conversion plans built so far: a list of (source limbs, destination limbs, runs the 29-bit split)"""
+        cnt = ctypes.c_int()
+        check(lib().lsa_debug_baseconv_plans(self.h, 0, ctypes.byref(cnt), None, None, None))
+        n = cnt.value
+        ns, nd, sp = (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))()
+        check(lib().lsa_debug_baseconv_plans(self.h, n, ctypes.byref(cnt), ns, nd, sp))
+        return [(ns[i], nd[i], bool(sp[i])) for i in range(min(n, cnt.value))]
+
+    def key_switch_fused(self, level, key):
+        """whether a switch with this one key at this level runs the fused second pass + key MAC kernel"""
+        out = ctypes.c_int()
+        check(lib().lsa_debug_key_switch_fused(self.h, level, key, ctypes.byref(out)))
+        return bool(out.value)
+
     def set_fp64_ntt(self, enable):
         check(lib().lsa_set_fp64_ntt(self.h, int(enable)))
 

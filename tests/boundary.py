@@ -1,0 +1,115 @@
+"""Test helpers for the modulus-size thresholds: chains whose primes sit on both sides of every bit length at which a kernel
+switches its arithmetic (46, 47, 48, 57, 58 bits, and the 61-bit ceiling), and worst-case residue patterns for operands
+and keys.  Used by tests/test_gpu_boundary.py and the CPU replay tests."""
+import numpy as np
+
+from lattisense_amd import params
+
+THRESHOLD_BITS = (46, 47, 48, 57, 58)
+ORDERS = ("ascending", "descending", "interleaved")
+PATTERNS = ("zero", "max", "one", "half", "alt", "alt1", "delta", "top", "uniform")
+
+
+def primes_above(bits, n, count, avoid=()):
+    """the `count` smallest primes p > 2^bits with p == 1 (mod 2n), skipping `avoid`"""
+    out, step = [], 2 * n
+    x = (1 << bits) + 1
+    while len(out) < count:
+        x += step
+        if x not in avoid and params._is_prime(x):
+            out.append(x)
+    return out
+
+
+def fp_engine(q):
+    """the FP64-FMA butterfly engine takes the limb (LSA_FP64_MAX_BITS = 47)"""
+    return q >> 47 == 0
+
+
+def head_flags(ql, qi):
+    """(near, fp_lift) of the rescale / ModDown head for target prime qi and dropped prime ql (ntt_make_load_fix)"""
+    return ql <= 2 * qi, fp_engine(qi) and ql >> 48 == 0
+
+
+def straddle_chain(n, np_, order="ascending"):
+    """Q: for every bit length in THRESHOLD_BITS the largest NTT prime below 2^bits and the smallest above it, plus the largest
+    60-bit prime, one 30-bit and one 40-bit prime (13 primes); P: the np_ largest primes below 2^61.
+    order: ascending / descending by size, or interleaved (small and large alternate), so that over the levels every size
+    class is dropped onto both smaller and larger targets."""
+    q = []
+    for b in THRESHOLD_BITS:
+        q += params.ntt_primes_below(b, n, 1) + primes_above(b, n, 1)
+    q += params.ntt_primes_below(60, n, 1) + params.ntt_primes_below(30, n, 1) + params.ntt_primes_below(40, n, 1)
+    q = sorted(q)
+    assert len(set(q)) == 13
+    if order == "descending":
+        q = q[::-1]
+    elif order == "interleaved":
+        lo, hi = q[:7], q[7:][::-1]
+        q = [x for pair in zip(lo, hi + [None]) for x in pair if x is not None]
+    else:
+        assert order == "ascending", order
+    p = params.ntt_primes_below(61, n, np_)
+    assert all((m - 1) % (2 * n) == 0 and params._is_prime(m) for m in q + p) and not set(q) & set(p)
+    # every size class present
+    for lo, hi in ((46, 47), (47, 48), (48, 49), (57, 58)):
+        assert any((1 << lo) < m < (1 << hi) for m in q), (lo, hi)
+    assert any(m > (1 << 58) for m in q)
+    assert any(m < (1 << 46) and m.bit_length() == 46 for m in q)
+    # both values of both head selectors over the levels, on both engines where the engine can take it
+    seen = {head_flags(q[l], q[i]) + (fp_engine(q[i]),) for l in range(1, len(q)) for i in range(l)}
+    if order == "descending":   # every dropped limb is the smallest: only near, and fp_lift wherever the target is FP64
+        assert seen == {(True, True, True), (True, False, False)}
+        return {"n": n, "q": q, "p": p}
+    assert {s[0] for s in seen} == {True, False}, "near"
+    assert {s[1] for s in seen} == {True, False}, "fp_lift"
+    assert {s[1] for s in seen if s[2]} == {True, False}, "fp_lift on and off for FP64-engine targets"
+    if order == "ascending":
+        assert {(s[0], s[2]) for s in seen} == {(a, b) for a in (True, False) for b in (True, False)}, "near x engine"
+    return {"n": n, "q": q, "p": p}
+
+
+def pattern(name, q, n, rng):
+    """one limb-polynomial of n residues modulo q"""
+    q = int(q)
+    h = q // 2
+    v = np.zeros(n, dtype=np.uint64)
+    if name == "zero":
+        pass
+    elif name == "max":
+        v[:] = q - 1
+    elif name == "one":
+        v[:] = 1
+    elif name == "half":          # floor(q/2), floor(q/2) + 1 interleaved: the centred-remainder compare of the rescale head
+        v[0::2] = h
+        v[1::2] = h + 1
+    elif name == "alt":
+        v[0::2] = q - 1
+    elif name == "alt1":          # the shifted variant
+        v[1::2] = q - 1
+    elif name == "delta":
+        v[[0, 1, n // 2, n - 1]] = q - 1
+    elif name == "top":
+        v[:] = np.uint64(q - 1) - rng.integers(0, 4, size=n, dtype=np.uint64)
+    elif name == "uniform":
+        v[:] = rng.integers(0, q, size=n, dtype=np.uint64)
+    else:
+        raise ValueError(name)
+    return v
+
+
+def pattern_ct(names, mods, polys, n, rng, oracle=None):
+    """[len(names)][polys][len(mods)][n]: batch slot b carries pattern names[b] in every limb.  With `oracle`, the pattern
+    is the coefficient-domain content and the words returned are its forward transform (limb i is oracle modulus i)."""
+    out = np.empty((len(names), polys, len(mods), n), dtype=np.uint64)
+    for b, name in enumerate(names):
+        for pl in range(polys):
+            for i, m in enumerate(mods):
+                v = pattern(name, m, n, rng)
+                out[b, pl, i] = oracle.ntt(i, v) if oracle is not None else v
+    return out
+
+
+def pattern_key(name, mods, beta, n, rng):
+    """a switching key [beta][2][len(mods)][n] whose every limb carries the pattern"""
+    return pattern_ct([name] * beta, mods, 2, n, rng)

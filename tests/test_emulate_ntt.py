@@ -11,6 +11,7 @@ import pytest
 
 from lattisense_amd import params
 from oracle.pyoracle import Oracle
+from tests.boundary import PATTERNS, pattern_ct, primes_above
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lattisense_amd", "csrc")
 
@@ -67,10 +68,41 @@ def test_fp64_engine_matches_oracle(emu, logn, tau):
     D = params.CKKS_DEFAULT[65536]
     B = params.CKKS_BOOTSTRAP_65536
     mods = [D["q"][1], D["q"][3], B["q"][1], B["q"][10], B["q"][0]]
-    assert max(m.bit_length() for m in mods[:4]) <= 46
+    assert max(m.bit_length() for m in mods[:4]) <= 46   # (the 47-bit sizes: test_threshold_primes_and_worst_case_patterns)
     _check(emu, logn, tau, mods, fp64=1)
     _check(emu, logn, tau, mods, fp64=0)
     _check(emu, logn, tau, mods, fp64=3)   # the interleaved workgroup order of mixed-engine launches
+
+
+def _threshold_primes(n):
+    """the largest NTT primes below 2^46 (raw hand-off stored unreduced), 2^47 (last FP64-engine size), 2^48, 2^57 (last lazy
+    integer size), 2^58 and 2^61, and the smallest above 2^46 (FP64 engine, hand-off reduced: the other side of skip_reduce)"""
+    mods = [params.ntt_primes_below(b, n, 1)[0] for b in (46, 47, 48, 57, 58, 61)] + primes_above(46, n, 1)
+    assert [m.bit_length() for m in mods] == [46, 47, 48, 57, 58, 61, 47]
+    return mods
+
+
+@pytest.mark.parametrize("logn", range(10, 18))
+def test_threshold_primes_and_worst_case_patterns(emu, logn):
+    """every pattern of tests/boundary.py on a prime next to every size threshold of the transform, forward and inverse, both
+    engines, the staged kernel and (N >= 2^14) the radix-16-squared / nine-stage passes; the replay aborts on any violated
+    range invariant (LSA_EMU_CHECK)"""
+    n = 1 << logn
+    mods = _threshold_primes(n)
+    o = Oracle(n, mods, [], 0)
+    data = pattern_ct(PATTERNS, mods, 1, n, np.random.default_rng(logn))[:, 0]   # [9][7][N]
+    rows = len(mods)
+    want = np.stack([np.stack([o.ntt(r, data[b, r]) for r in range(rows)]) for b in range(len(PATTERNS))])
+    want_inv = np.stack([np.stack([o.intt(r, data[b, r]) for r in range(rows)]) for b in range(len(PATTERNS))])
+    for flags in (1, 0, 3) + ((4 | 1, 4, 4 | 3) if logn >= 14 else ()):
+        got = data.copy()
+        run(emu, n, mods, got, rows, list(range(rows)), 0, 12, flags)
+        assert np.array_equal(got, want), (flags, np.argwhere((got != want).any(axis=-1)))
+        run(emu, n, mods, got, rows, list(range(rows)), 1, 12, flags)
+        assert np.array_equal(got, data), flags
+        got = data.copy()
+        run(emu, n, mods, got, rows, list(range(rows)), 1, 12, flags)
+        assert np.array_equal(got, want_inv), (flags, "inverse", np.argwhere((got != want_inv).any(axis=-1)))
 
 
 @pytest.mark.parametrize("logn", [14, 15, 16, 17, 18])

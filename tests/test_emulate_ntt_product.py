@@ -9,6 +9,7 @@ import pytest
 
 from lattisense_amd import params
 from oracle.pyoracle import Oracle
+from tests.boundary import pattern, primes_above
 from tests.test_emulate_ntt import emu  # noqa: F401  (the replay library fixture)
 
 
@@ -68,3 +69,30 @@ def test_product_prologue_staged_kernel(emu, logn, tau):
     small tiles, LSA_NTT_R16=0)"""
     _check(emu, logn, 1, tau)
     _check(emu, logn, 0, tau)
+
+
+def _edge_mods(n):
+    """47-bit FP64-engine primes on both ends of their range (just above 2^46, just below 2^47) and the integer-engine primes on
+    either side of the lazy-butterfly limit 2^57"""
+    return primes_above(46, n, 1) + params.ntt_primes_below(47, n, 1) + params.ntt_primes_below(57, n, 1) + primes_above(57, n, 1)
+
+
+@pytest.mark.parametrize("logn", [12, 13, 14, 15, 16, 17])
+def test_product_prologue_threshold_primes_and_extreme_pairs(emu, logn):
+    """(q-1)^2, half . half and max . one operand pairs (and the half points against the maximum) on the edge primes"""
+    n = 1 << logn
+    mods = _edge_mods(n)
+    assert [m.bit_length() for m in mods] == [47, 47, 57, 58]
+    o = Oracle(n, mods, [], 0)
+    rng = np.random.default_rng(logn)
+    pairs = (("max", "max"), ("half", "half"), ("max", "one"), ("half", "max"), ("top", "top"), ("alt", "alt1"))
+    A = np.stack([np.stack([pattern(a, m, n, rng) for m in mods]) for a, _ in pairs])
+    B = np.stack([np.stack([pattern(b, m, n, rng) for m in mods]) for _, b in pairs])
+    want = np.empty_like(A)
+    for b in range(len(pairs)):
+        for r, m in enumerate(mods):
+            d2 = np.array([(int(x) * int(y)) % m for x, y in zip(A[b, r], B[b, r])], dtype=np.uint64)
+            want[b, r] = o.intt(r, d2)
+    for flags in (1, 0) + ((4 | 1, 4, 4 | 3) if logn >= 14 else ()):
+        got = _run(emu, n, mods, A, B, flags)
+        assert np.array_equal(got, want), (logn, flags, np.argwhere((got != want).any(axis=-1)))
