@@ -202,6 +202,50 @@ int lsa_ckks_bootstrap(lsa_context ctx, lsa_bootstrap b, const uint64_t* in, uin
                        lsa_key rlk, int n_glk, const uint64_t* glk_elements, const lsa_key* glk, lsa_key swk_dts, lsa_key swk_std,
                        void* stream);
 
+/* ---- CKKS linear transform: plaintext matrix x encrypted vector, the matrix in diagonal form (matrix-vector products,
+ * convolutions, CoeffsToSlots / SlotsToCoeffs steps).  The evaluator is the one bootstrapping runs on its own matrices; the CPU
+ * oracle of both is oracle/ckks_bootstrap.py linear_transform, whose semantics these are exactly:
+ *   fewer than three diagonals: one rotation per diagonal, no baby-step / giant-step split;
+ *   otherwise n1 = the reference planner's split at bsgs_ratio (frontend/bootstrap_params.py:193-207), diagonal k = giant + baby
+ *   with giant = floor(k / n1) * n1, M x = sum_giant rot_giant( sum_baby rot_{-giant}(d_k) . rot_baby(x) ), giant step 0 first.
+ * M in diagonal form: diagonal k (index taken mod period, period = 2^log_slots; negative indices allowed) holds `period`
+ * complex values, d_k[t] multiplies x[(t + k) mod period].  values: [n_diag][period][2] doubles (re, im).  level: the level of
+ * the ciphertexts the plan will be applied to.  pt_scale: encoding scale of the diagonals, 0 = q_level (then the rescale leaves
+ * the ciphertext's scale unchanged); in general the result decrypts at in_scale * pt_scale (/ q_level after the rescale).
+ * bsgs_ratio: 0 = 2.0, the reference planner's ratio.  double_hoist: 1 = the baby-step rotations and the inner sums stay over
+ * Q_level u P and are divided by P once per giant step and once at the end (giant steps + 1 divisions: Lattigo v4
+ * MultiplyByDiagMatrixBSGS); 0 = one division per rotation.  The plaintext of diagonal k is the encoding of rot_{-giant}(d_k)
+ * tiled over the N/2 slots, over Q_level (no double hoisting, or fewer than three diagonals) or Q_level u P.
+ * Errors (LSA_ERR_ARG): level out of range, a BFV context, log_slots > log2(N) - 1, two indices equal modulo the period, a value
+ * that encodes beyond 2^62.  The plan keeps its plaintexts and the temporaries of its runs on the device until destroyed; it
+ * belongs to its context and runs on one stream at a time. */
+typedef struct lsa_linear_transform_st* lsa_linear_transform;
+int lsa_lt_create(lsa_context ctx, int level, int log_slots, int n_diag, const int* diag_index, const double* values,
+                  double pt_scale, double bsgs_ratio, int double_hoist, void* stream, lsa_linear_transform* out);
+void lsa_lt_destroy(lsa_linear_transform lt);
+/* n1: the baby-step count, 0 = no split (fewer than three diagonals); rows: rows of each plaintext, level + 1 or level + 1 + k;
+ * any output pointer may be null */
+int lsa_lt_info(lsa_linear_transform lt, int* level, int* period, int* n_diag, int* n1, int* rows, int* n_galois,
+                int* double_hoist, double* pt_scale);
+int lsa_lt_diagonals(lsa_linear_transform lt, int* index_out, int capacity); /* ascending, reduced mod period */
+/* Galois elements of the rotations a run needs a key for (ascending) */
+int lsa_lt_galois_elements(lsa_linear_transform lt, uint64_t* out, int capacity);
+/* the encoded diagonal at position diag_pos of lsa_lt_diagonals' order: rows * N words, NTT domain */
+int lsa_lt_plaintext(lsa_linear_transform lt, int diag_pos, uint64_t* host_out, long long capacity_words);
+/* in [batch][2][level+1][N] (NTT domain) -> out [batch][2][level (rescale) | level+1 (no rescale)][N], batch strides sin / sout in
+ * words; out may not overlap in (LSA_ERR_ARG); batch <= 0 is a no-op.  glk_elements / glk: n_glk Galois keys, in any order and
+ * possibly more than needed; a missing one fails with LSA_ERR_ARG (the message names the element) before any work is queued.
+ * Switches read per call: LSA_LT_BLOCKED_MAC=0 (matrices beyond 8 x 8 baby / giant steps: one multiply-accumulate launch per
+ * giant step instead of 8 x 8 blocks), LSA_ROT_SCATTER=0 (rotations as MAC + permutation kernel), LSA_LT_GIANT_SCATTER=0 / 1
+ * (giant-step rotations alone).  Every combination produces the same words. */
+int lsa_ckks_linear_transform(lsa_context ctx, lsa_linear_transform lt, const uint64_t* in, uint64_t* out, int batch,
+                              long long sin, long long sout, int rescale, int n_glk, const uint64_t* glk_elements,
+                              const lsa_key* glk, void* stream);
+/* host only, needs no device: the split (n1, 0 = none) and the non-zero rotations (ascending, reduced mod period) that a
+ * diagonal index set gets -- what lsa_lt_create will pick.  count receives their number; LSA_ERR_ARG if capacity is less. */
+int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double bsgs_ratio, int* n1, int* rotations,
+                          int capacity, int* count);
+
 /* diagnostic builds only (-DLSA_NTT_DIAG_STAMPS): device buffer of 8192*8 u64 receiving per-workgroup phase time stamps
  * of every following NTT launch; NULL turns it off.  Ignored by the normal build. */
 int lsa_debug_set_ntt_stamps(lsa_context ctx, void* device_buffer);

@@ -109,6 +109,18 @@ SIGNATURES = {
     "lsa_bootstrap_plaintext_ext": (c_int, [c_vp, c_int, c_int, c_u64p, ctypes.c_longlong]),
     "lsa_ckks_bootstrap": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_int, c_u64p,
                                    ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
+    "lsa_lt_create": (c_int, [c_vp, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double), ctypes.c_double,
+                              ctypes.c_double, c_int, c_vp, ctypes.POINTER(c_vp)]),
+    "lsa_lt_destroy": (None, [c_vp]),
+    "lsa_lt_info": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                            ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double)]),
+    "lsa_lt_diagonals": (c_int, [c_vp, ctypes.POINTER(c_int), c_int]),
+    "lsa_lt_galois_elements": (c_int, [c_vp, c_u64p, c_int]),
+    "lsa_lt_plaintext": (c_int, [c_vp, c_int, c_u64p, c_ll]),
+    "lsa_ckks_linear_transform": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_int, c_int, c_u64p, ctypes.POINTER(c_vp),
+                                          c_vp]),
+    "lsa_lt_plan_rotations": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.c_double, ctypes.POINTER(c_int),
+                                      ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int)]),
     "lsa_profile_begin": (c_int, [c_vp, c_int]),
     "lsa_profile_end": (c_int, [c_vp]),
     "lsa_profile_read": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),

@@ -19,27 +19,13 @@
 #include <map>
 #include <memory>
 
-#include "lsa_internal.h"
+#include "linear_transform.h"
 
 namespace lsa {
-
-using cplx = std::complex<double>;
-using Diags = std::map<int, std::vector<cplx>>;   // diagonal k: d[t] multiplies x[(t + k) mod n]
 
 namespace {
 
 const double kPi = 3.14159265358979323846;
-
-std::vector<int> rot_group(int n_slots) {
-    std::vector<int> g(n_slots);
-    long long v = 1;
-    const long long m = 4LL * n_slots;
-    for (int i = 0; i < n_slots; i++) {
-        g[i] = (int)v;
-        v = v * 5 % m;
-    }
-    return g;
-}
 
 // one radix-2 layer of the special FFT (forward: slots <- coefficients) or of its inverse, as three diagonals
 Diags layer_diagonals(int n, int length, bool inverse, const std::vector<int>& rg) {
@@ -148,80 +134,9 @@ std::vector<cplx> tiled(const std::vector<cplx>& v, int n) {
     return out;
 }
 
-void bsgs_sets(const std::vector<int>& ks, int n, int n1, std::vector<int>& giants, std::vector<int>& babies) {
-    std::map<int, bool> g, b;
-    for (int k : ks) {
-        g[((k % n) / n1) * n1 % n] = true;
-        b[(k % n) % n1] = true;
-    }
-    giants.clear();
-    babies.clear();
-    for (auto& kv : g) giants.push_back(kv.first);
-    for (auto& kv : b) babies.push_back(kv.first);
-}
-
-// the planner's baby-step count (frontend/bootstrap_params.py:193-207): the caller's Galois keys exist for this choice
-int bsgs_split(const std::vector<int>& ks, int n, double ratio) {
-    int n1 = 1;
-    std::vector<int> g, b;
-    while (n1 < n) {
-        bsgs_sets(ks, n, n1, g, b);
-        const int nb_g = (int)g.size() - 1, nb_b = (int)b.size() - 1;
-        if (nb_g == 0 || (double)nb_b / nb_g == ratio) return n1;
-        if ((double)nb_b / nb_g > ratio) return n1 / 2;
-        n1 <<= 1;
-    }
-    return 1;
-}
-
-// slots -> coefficients: t = U^-1 z (inverse special FFT), m_k = Re t_k, m_{k+n} = Im t_k
-std::vector<double> slots_to_coeffs(std::vector<cplx> v, const std::vector<int>& rg) {
-    const int n = (int)v.size();
-    const long long m = 4LL * n;
-    for (int len = n; len >= 2; len >>= 1) {
-        const int lenh = len >> 1;
-        const long long lenq = 4LL * len;
-        for (int i = 0; i < n; i += len)
-            for (int j = 0; j < lenh; j++) {
-                const long long idx = (lenq - (rg[j] % lenq)) * (m / lenq);
-                const cplx w = std::polar(1.0, 2.0 * kPi * (double)idx / (double)m);
-                const cplx a = v[i + j], b = v[i + j + lenh];
-                v[i + j] = a + b;
-                v[i + j + lenh] = (a - b) * w;
-            }
-    }
-    int lg = 0;
-    while ((1 << lg) < n) lg++;
-    std::vector<double> out(2 * (size_t)n);
-    for (int i = 0; i < n; i++) {
-        int r = 0;
-        for (int b = 0; b < lg; b++) r |= ((i >> b) & 1) << (lg - 1 - b);
-        out[i] = v[r].real() / n;
-        out[i + n] = v[r].imag() / n;
-    }
-    return out;
-}
-
-// Python's round(): ties to even.  A constant beyond 2^62 means the modulus chain does not fit the level plan (e.g. EvalMod
-// running on primes much smaller than its scale): refuse instead of computing garbage.
-long long round_even(double v) {
-    LSA_REQUIRE(std::fabs(v) < 4.6e18, "bootstrap: encoded constant out of range -- the modulus chain does not match the "
-                                       "bootstrap level plan (depths / scales)");
-    return (long long)std::nearbyint(v);
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ plan
-struct BtMatrix {
-    int level = 0, n1 = 1;
-    int period = 0;                      // period of the diagonals (index arithmetic mod period); N/2 for dense packing
-    bool naive = false;
-    std::vector<int> ks;                 // diagonal indices, ascending
-    std::vector<u64*> plains;            // per diagonal: NTT-domain plaintext [rows][N] of rot_{-giant}(diag)
-    int rows = 0;                        // level + 1, or level + 1 + k (the special primes too) for a double-hoisted matrix
-};
-
 struct Bootstrap {
     Context& c;
     int cts_depth, stc_depth, K, r, top_level;
@@ -245,48 +160,18 @@ struct Bootstrap {
     std::vector<u64*> owned;
     // temporaries of a run, kept across runs (hipMalloc / hipFree of GiB-sized buffers cost more than the kernels); a plan
     // belongs to one context and is run on one in-order stream at a time, so reuse is ordered
-    std::multimap<size_t, u64*> pool;
-    std::vector<u64*> pool_all;
+    DevPool pool;
 
     explicit Bootstrap(Context& ctx) : c(ctx) {}
     ~Bootstrap() {
         (void)hipSetDevice(c.device);
         (void)hipDeviceSynchronize();
         for (u64* p : owned) (void)hipFree(p);
-        for (u64* p : pool_all) (void)hipFree(p);
+        pool.release();
     }
 
-    RowMap rm_limbs(int L) const {
-        RowMap rm;
-        rm.period = L;
-        for (int j = 0; j < L; j++) rm.mod_of[j] = (unsigned char)j;
-        return rm;
-    }
-
-    // real polynomial coefficients * scale -> NTT-domain plaintext on the device
-    // ext: the same integer polynomial at the special primes too, rows level+1 .. level+k (operand of extended ciphertexts)
-    u64* upload_plain(const std::vector<double>& coef, double scale, int level, hipStream_t s, bool ext = false) {
-        const int L = level + 1 + (ext ? c.np : 0);
-        const size_t N = (size_t)c.n;
-        std::vector<u64> host((size_t)L * N);
-        RowMap rm = rm_limbs(L);
-        for (int j = level + 1; j < L; j++) rm.mod_of[j] = (unsigned char)c.p_mod(j - level - 1);
-        for (size_t x = 0; x < N; x++) {
-            const long long v = round_even(coef[x] * scale);
-            for (int j = 0; j < L; j++) {
-                const long long q = (long long)c.T.mod[rm.mod_of[j]];
-                long long r = v % q;
-                if (r < 0) r += q;
-                host[(size_t)j * N + x] = (u64)r;
-            }
-        }
-        u64* d = nullptr;
-        LSA_HIP(hipMalloc((void**)&d, host.size() * sizeof(u64)));
-        owned.push_back(d);
-        LSA_HIP(hipMemcpyAsync(d, host.data(), host.size() * sizeof(u64), hipMemcpyHostToDevice, s));
-        launch_ntt(c, d, d, 1, (long long)L * N, L, rm, false, s);
-        LSA_HIP(hipStreamSynchronize(s));   // `host` goes out of scope
-        return d;
+    u64* upload_plain(const std::vector<double>& coef, double scale, int level, hipStream_t s) {
+        return lt_upload_plain(c, coef, scale, level, s, false, owned, "bootstrap");
     }
 
     double evalmod_out_scale(int level_in) const {
@@ -317,7 +202,7 @@ struct Bootstrap {
         LSA_REQUIRE(top_level - cts_depth - evalmod_depth() - stc_depth >= 0, "bootstrap: modulus chain too short");
         const std::vector<int> rg = rot_group(n);
         const double q0 = (double)c.T.mod[0];
-        mul_c = std::max<long long>(1, round_even(q0 / (mr * in_scale)));
+        mul_c = std::max<long long>(1, round_even(q0 / (mr * in_scale), "bootstrap"));
         d1 = in_scale * (double)mul_c;
         const int evalmod_level = top_level - cts_depth;
         const int stc_level = evalmod_level - evalmod_depth();
@@ -407,26 +292,7 @@ struct Bootstrap {
         };
         // one matrix -> plaintexts (diagonals of period `period`, tiled over the N/2 slots) + the rotations it needs
         auto make_one = [&](const Diags& mat, int level, int period) {
-            BtMatrix bm;
-            bm.level = level;
-            bm.period = period;
-            for (auto& kv : mat) bm.ks.push_back(kv.first);
-            bm.naive = bm.ks.size() < 3;
-            bm.n1 = bm.naive ? 1 : bsgs_split(bm.ks, period, 2.0);
-            const double pt_scale = (double)c.T.mod[bm.level];
-            const bool ext = double_hoist && !bm.naive;
-            bm.rows = bm.level + 1 + (ext ? c.np : 0);
-            for (int k : bm.ks) {
-                const int giant = bm.naive ? 0 : (k / bm.n1) * bm.n1;
-                const std::vector<cplx>& d = mat.at(k);
-                std::vector<cplx> rolled(n);
-                for (int t = 0; t < n; t++) rolled[t] = d[(((t - giant) % period) + period) % period];   // rot_{-giant}(diag), tiled
-                bm.plains.push_back(upload_plain(slots_to_coeffs(rolled, rg), pt_scale, bm.level, s, ext));
-                const int baby = bm.naive ? k : k - giant;
-                if (baby) gal[gel(baby)] = true;
-                if (giant) gal[gel(giant)] = true;
-            }
-            return bm;
+            return lt_make_matrix(c, mat, level, period, (double)c.T.mod[level], 2.0, double_hoist, s, owned, gal, "bootstrap");
         };
         for (size_t i = 0; i < mc.size(); i++) cts.push_back(make_one(mc[i], top_level - (int)i, ns));
         if (sparse) {
@@ -476,90 +342,13 @@ struct Bootstrap {
 // ------------------------------------------------------------------------------------------------ device evaluator
 namespace {
 
-struct DBuf {
-    u64* p = nullptr;
-    size_t words = 0;
-    std::multimap<size_t, u64*>* pool;
-    ~DBuf() { pool->emplace(words, p); }
-};
-struct DCt {
-    std::shared_ptr<DBuf> buf;
-    int level = 0;
-    double scale = 0;
-    u64* data() const { return buf->p; }
-};
-
-struct Eval {
-    Context& c;
+// the linear transforms and the ciphertext bookkeeping come from LtEval (linear_transform.h); what is added here is EvalMod
+struct Eval : LtEval {
     Bootstrap& bt;
-    hipStream_t s;
-    int m;   // batch
     const Key& rlk;
-    const std::map<u64, const Key*>& glk;
-    std::multimap<size_t, u64*>& pool;   // released device buffers (single in-order stream: reuse is ordered)
-    long long N;
 
     Eval(Context& c_, Bootstrap& b, hipStream_t s_, int m_, const Key& rlk_, const std::map<u64, const Key*>& g)
-        : c(c_), bt(b), s(s_), m(m_), rlk(rlk_), glk(g), pool(b.pool), N(c_.n) {}
-    long long stride(int level) const { return 2LL * (level + 1) * N; }
-    DCt alloc(int level, double scale) {
-        DCt o = alloc_words((size_t)m * stride(level));
-        o.level = level;
-        o.scale = scale;
-        return o;
-    }
-    DCt alloc_words(size_t words) {
-        auto b = std::make_shared<DBuf>();
-        b->words = words;
-        b->pool = &pool;
-        auto it = pool.find(words);
-        if (it != pool.end()) {
-            b->p = it->second;
-            pool.erase(it);
-        } else {
-            LSA_HIP(hipMalloc((void**)&b->p, words * sizeof(u64)));
-            bt.pool_all.push_back(b->p);
-        }
-        return DCt{b, 0, 0.0};
-    }
-    // extended ciphertext [2][level+1+k][N] over Q_level u P (ops.hip, ckks_rotate_many_ext); `level` and `scale` as for the
-    // ciphertext it will be divided down to
-    long long stride_ext(int level) const { return 2LL * (level + 1 + c.np) * N; }
-    DCt alloc_ext(int level, double scale) {
-        DCt o = alloc_words((size_t)m * stride_ext(level));
-        o.level = level;
-        o.scale = scale;
-        return o;
-    }
-    RowMap rm_ext(int level) const {   // both polynomials' rows of an extended ciphertext
-        RowMap rm;
-        rm.period = level + 1 + c.np;
-        for (int j = 0; j <= level; j++) rm.mod_of[j] = (unsigned char)j;
-        for (int i = 0; i < c.np; i++) rm.mod_of[level + 1 + i] = (unsigned char)c.p_mod(i);
-        return rm;
-    }
-    RowMap rm2(int level) const {   // both polynomials' limbs
-        RowMap rm;
-        rm.period = level + 1;
-        for (int j = 0; j <= level; j++) rm.mod_of[j] = (unsigned char)j;
-        return rm;
-    }
-    double q(int level) const { return (double)c.T.mod[level]; }
-
-    DCt addsub(const DCt& a, const DCt& b, EwOp op) {
-        LSA_REQUIRE(a.level == b.level && std::fabs(a.scale / b.scale - 1) < 1e-9, "bootstrap: operands of add/sub differ in level or scale");
-        DCt o = alloc(a.level, a.scale);
-        launch_elementwise(c, op, a.data(), b.data(), o.data(), m, stride(a.level), stride(a.level), stride(a.level),
-                           2 * (a.level + 1), rm2(a.level), s);
-        return o;
-    }
-    DCt add(const DCt& a, const DCt& b) { return addsub(a, b, EW_ADD); }
-    DCt sub(const DCt& a, const DCt& b) { return addsub(a, b, EW_SUB); }
-    DCt rescale(const DCt& a) {
-        DCt o = alloc(a.level - 1, a.scale / q(a.level));
-        ckks_rescale(c, a.level, 2, a.data(), o.data(), m, stride(a.level), stride(a.level - 1), s);
-        return o;
-    }
+        : LtEval(c_, b.pool, s_, m_, g, "bootstrap"), bt(b), rlk(rlk_) {}
     DCt mul(const DCt& a0, const DCt& b0) {
         // operands at different levels: the leading rows of each polynomial of the higher one ARE it at the lower level, the
         // tensor kernel takes the rows per polynomial -- no copy (k_copy_rows was 2 % of a bootstrap)
@@ -567,82 +356,6 @@ struct Eval {
         DCt o = alloc(lvl - 1, a0.scale * b0.scale / q(lvl));
         ckks_mult_relin_rescale_rpp(c, lvl, a0.data(), b0.data(), rlk, o.data(), m, stride(a0.level), stride(b0.level), stride(lvl - 1), s,
                                     a0.level + 1, b0.level + 1);
-        return o;
-    }
-    const Key& gkey(u64 e) const {
-        auto it = glk.find(e);
-        LSA_REQUIRE(it != glk.end(), "bootstrap: Galois key for element " + std::to_string(e) + " missing");
-        return *it->second;
-    }
-    DCt rotate(const DCt& a, int r) {
-        const int n = c.n / 2;
-        r = ((r % n) + n) % n;
-        if (r == 0) return a;
-        u64 e = 1;
-        for (int i = 0; i < r; i++) e = e * 5 % (2ULL * c.n);
-        DCt o = alloc(a.level, a.scale);
-        ckks_rotate(c, a.level, a.data(), e, gkey(e), o.data(), m, stride(a.level), stride(a.level), s);
-        return o;
-    }
-    // rotations of one ciphertext by several steps with a single decomposition (hoisted); same residues as rotate()
-    std::map<int, DCt> rotate_many(const DCt& a, const std::vector<int>& steps) {
-        const int n = c.n / 2;
-        std::map<int, DCt> out;
-        std::vector<u64> els;
-        std::vector<const Key*> keys;
-        std::vector<u64*> ptrs;
-        for (int r0 : steps) {
-            const int r = ((r0 % n) + n) % n;
-            if (out.count(r)) continue;
-            if (r == 0) {
-                out[0] = a;
-                continue;
-            }
-            u64 e = 1;
-            for (int i = 0; i < r; i++) e = e * 5 % (2ULL * c.n);
-            DCt o = alloc(a.level, a.scale);
-            els.push_back(e);
-            keys.push_back(&gkey(e));
-            ptrs.push_back(o.data());
-            out[r] = o;
-        }
-        ckks_rotate_many(c, a.level, a.data(), (int)els.size(), els.data(), keys.data(), ptrs.data(), m, stride(a.level),
-                         stride(a.level), s);
-        return out;
-    }
-    u64 galois_of(int r) const {
-        u64 e = 1;
-        for (int i = 0; i < r; i++) e = e * 5 % (2ULL * c.n);
-        return e;
-    }
-    // the same rotations WITHOUT their division by P: extended ciphertexts (step 0: the ciphertext times P)
-    std::map<int, DCt> rotate_many_ext(const DCt& a, const std::vector<int>& steps) {
-        const int n = c.n / 2;
-        std::map<int, DCt> out;
-        std::vector<u64> els;
-        std::vector<const Key*> keys;
-        std::vector<u64*> ptrs;
-        for (int r0 : steps) {
-            const int r = ((r0 % n) + n) % n;
-            if (out.count(r)) continue;
-            DCt o = alloc_ext(a.level, a.scale);
-            out[r] = o;
-            if (r == 0) {
-                ckks_lift_ext(c, a.level, a.data(), o.data(), m, stride(a.level), stride_ext(a.level), s);
-                continue;
-            }
-            const u64 e = galois_of(r);
-            els.push_back(e);
-            keys.push_back(&gkey(e));
-            ptrs.push_back(o.data());
-        }
-        ckks_rotate_many_ext(c, a.level, a.data(), (int)els.size(), els.data(), keys.data(), ptrs.data(), m, stride(a.level),
-                             stride_ext(a.level), s);
-        return out;
-    }
-    DCt moddown(const DCt& a) {   // extended -> ciphertext; `a` is consumed
-        DCt o = alloc(a.level, a.scale);
-        ckks_moddown_ext(c, a.level, a.data(), o.data(), m, stride_ext(a.level), stride(a.level), s);
         return o;
     }
     DCt conj(const DCt& a) {
@@ -677,7 +390,7 @@ struct Eval {
     }
     DCt mul_int(const DCt& a, long long k) { return mul_int_raw(a, k, a.scale); }
     DCt mul_const(const DCt& a, double cst, double const_scale, int level = -1) {
-        return mul_int_raw(a, round_even(cst * const_scale), a.scale * const_scale, level);
+        return mul_int_raw(a, round_even(cst * const_scale, "bootstrap"), a.scale * const_scale, level);
     }
     // per-row vectors over BOTH polynomials: [value for the L limbs of c0 | `second` for the L limbs of c1]
     const u64* kvec2(long long k0, long long k1, int level, bool montgomery) {
@@ -704,7 +417,7 @@ struct Eval {
     }
     // a * factor + cst in every slot, one pass (factor 1: plain add_const)
     DCt mul_int_add_const(const DCt& a, long long factor, double cst) {
-        const long long k = round_even(cst * a.scale);
+        const long long k = round_even(cst * a.scale, "bootstrap");
         DCt o = alloc(a.level, a.scale);
         launch_add_const(c, a.data(), stride(a.level), kvec2(k, 0, a.level, false), o.data(), stride(a.level), 2 * (a.level + 1),
                          rm_both(a.level), m, s, factor == 1 ? nullptr : kvec2(factor, factor, a.level, true));
@@ -725,173 +438,6 @@ struct Eval {
         DCt o = mul_plain(a, pt, 1.0);
         o.scale = a.scale;
         return o;
-    }
-
-    // Baby-step / giant-step with the sums kept over Q u P ("double hoisting", Lattigo v4 ckks/linear_transform.go
-    // MultiplyByDiagMatrixBSGS; oracle twin: oracle/ckks_bootstrap.py linear_transform, double_hoist): the baby-step rotations
-    // are gadget products without their division by P, the plaintexts carry the special primes' residues, each giant step's
-    // inner sum is divided once, rotated without division into the running sum, and that sum is divided once:
-    // (giant steps + 1) ModDowns instead of (baby steps + giant steps).
-    DCt linear_transform_dh(const DCt& ct, const BtMatrix& mt, bool do_rescale) {
-        const double pt_scale = q(ct.level);
-        const int T = ct.level + 1 + c.np;
-        std::vector<int> steps;
-        for (int k : mt.ks) steps.push_back(k % mt.n1);
-        std::map<int, DCt> babies = rotate_many_ext(ct, steps);
-        std::map<int, std::vector<size_t>> by_giant;
-        for (size_t i = 0; i < mt.ks.size(); i++) by_giant[(mt.ks[i] / mt.n1) * mt.n1].push_back(i);
-        std::vector<int> bsteps, gsteps;
-        std::vector<const u64*> cp;
-        std::vector<long long> cs;
-        for (auto& kv : babies) {
-            bsteps.push_back(kv.first);
-            cp.push_back(kv.second.data());
-            cs.push_back(stride_ext(ct.level));
-        }
-        const int nb = (int)bsteps.size(), ng = (int)by_giant.size();
-        std::vector<const u64*> pp((size_t)ng * nb, nullptr);
-        std::vector<DCt> inner;
-        std::vector<u64*> op;
-        int gi = 0;
-        for (auto& kv : by_giant) {
-            for (size_t i : kv.second) {
-                const int bi = (int)(std::find(bsteps.begin(), bsteps.end(), mt.ks[i] - kv.first) - bsteps.begin());
-                LSA_REQUIRE(bi < nb, "bootstrap: baby step without its rotation");
-                pp[(size_t)gi * nb + bi] = mt.plains[i];
-            }
-            inner.push_back(alloc_ext(ct.level, ct.scale * pt_scale));
-            op.push_back(inner.back().data());
-            gsteps.push_back(kv.first);
-            gi++;
-        }
-        if (nb <= LSA_MACM_MAX && ng <= LSA_MACM_MAX) {
-            launch_mac_plain_multi(c, nb, cp.data(), cs.data(), ng, pp.data(), op.data(), stride_ext(ct.level), m, 2, T, rm_ext(ct.level), s);
-        } else {
-            for (int g2 = 0; g2 < ng; g2++) {   // wide matrices: one giant step per launch, LSA_MAC_MAX_TERMS products each
-                std::vector<int> bi;
-                for (int b = 0; b < nb; b++)
-                    if (pp[(size_t)g2 * nb + b]) bi.push_back(b);
-                for (size_t i0 = 0; i0 < bi.size(); i0 += LSA_MAC_MAX_TERMS) {
-                    const int cnt = (int)std::min<size_t>(LSA_MAC_MAX_TERMS, bi.size() - i0);
-                    const u64* tc[LSA_MAC_MAX_TERMS];
-                    const u64* tp[LSA_MAC_MAX_TERMS];
-                    long long ts[LSA_MAC_MAX_TERMS], tz[LSA_MAC_MAX_TERMS];
-                    for (int i = 0; i < cnt; i++) {
-                        tc[i] = cp[bi[i0 + i]];
-                        ts[i] = stride_ext(ct.level);
-                        tp[i] = pp[(size_t)g2 * nb + bi[i0 + i]];
-                        tz[i] = 0;
-                    }
-                    launch_mac_plain(c, cnt, tc, ts, tp, tz, i0 ? op[g2] : nullptr, stride_ext(ct.level), op[g2], stride_ext(ct.level), m, 2, T,
-                                     rm_ext(ct.level), s);
-                }
-            }
-        }
-        babies.clear();
-        DCt acc;
-        bool have = false;
-        const int n = c.n / 2;
-        for (int g2 = 0; g2 < ng; g2++) {
-            const int r = ((gsteps[g2] % n) + n) % n;
-            if (r == 0) {
-                LSA_REQUIRE(!have, "bootstrap: giant step 0 must come first");
-                acc = inner[g2];
-                have = true;
-                continue;
-            }
-            DCt iq = moddown(inner[g2]);
-            if (!have) acc = alloc_ext(ct.level, ct.scale * pt_scale);
-            const u64 e = galois_of(r);
-            ckks_rotate_ext(c, ct.level, iq.data(), e, gkey(e), acc.data(), have, m, stride(ct.level), stride_ext(ct.level), s);
-            have = true;
-        }
-        DCt res = moddown(acc);
-        return do_rescale ? rescale(res) : res;
-    }
-
-    DCt linear_transform(const DCt& ct, const BtMatrix& mt, bool do_rescale = true) {
-        LSA_REQUIRE(ct.level == mt.level, "bootstrap: linear transform applied at an unexpected level");
-        if (!mt.naive && mt.rows > ct.level + 1) return linear_transform_dh(ct, mt, do_rescale);
-        const double pt_scale = q(ct.level);
-        const int L = ct.level + 1;
-        // every baby step is a rotation of the SAME ciphertext: one decomposition serves them all
-        std::vector<int> steps;
-        for (int k : mt.ks) steps.push_back(mt.naive ? k : k % mt.n1);
-        std::map<int, DCt> babies = rotate_many(ct, steps);
-        auto baby = [&](int b) -> const DCt& { return babies.at(b); };
-        // sum of (shared plaintext) x (rotated ciphertext) terms, LSA_MAC_MAX_TERMS per launch
-        auto mac = [&](const std::vector<std::pair<const u64*, const DCt*>>& terms) {
-            DCt o = alloc(ct.level, ct.scale * pt_scale);
-            for (size_t i0 = 0; i0 < terms.size(); i0 += LSA_MAC_MAX_TERMS) {
-                const int cnt = (int)std::min<size_t>(LSA_MAC_MAX_TERMS, terms.size() - i0);
-                const u64* cp[LSA_MAC_MAX_TERMS];
-                const u64* pp[LSA_MAC_MAX_TERMS];
-                long long cs[LSA_MAC_MAX_TERMS], ps[LSA_MAC_MAX_TERMS];
-                for (int i = 0; i < cnt; i++) {
-                    cp[i] = terms[i0 + i].second->data();
-                    cs[i] = stride(ct.level);
-                    pp[i] = terms[i0 + i].first;
-                    ps[i] = 0;
-                }
-                launch_mac_plain(c, cnt, cp, cs, pp, ps, i0 ? o.data() : nullptr, stride(ct.level), o.data(), stride(ct.level), m, 2,
-                                 L, rm2(ct.level), s);
-            }
-            return o;
-        };
-        DCt acc;
-        bool have = false;
-        if (mt.naive) {
-            std::vector<std::pair<const u64*, const DCt*>> terms;
-            for (size_t i = 0; i < mt.ks.size(); i++) terms.push_back({mt.plains[i], &baby(mt.ks[i])});
-            acc = mac(terms);
-            return do_rescale ? rescale(acc) : acc;
-        }
-        std::map<int, std::vector<size_t>> by_giant;
-        for (size_t i = 0; i < mt.ks.size(); i++) by_giant[(mt.ks[i] / mt.n1) * mt.n1].push_back(i);
-        if (babies.size() <= 8 && by_giant.size() <= 8 && by_giant.size() > 1 && !std::getenv("LSA_BT_NO_MULTI_MAC")) {
-            // all inner sums in one launch: every baby-step ciphertext is read once, not once per giant step (same sums)
-            std::vector<int> bsteps;
-            std::vector<const u64*> cp;
-            std::vector<long long> cs;
-            for (auto& kv : babies) {
-                bsteps.push_back(kv.first);
-                cp.push_back(kv.second.data());
-                cs.push_back(stride(ct.level));
-            }
-            const int nb = (int)bsteps.size(), ng = (int)by_giant.size();
-            std::vector<const u64*> pp((size_t)ng * nb, nullptr);
-            std::vector<DCt> inner;
-            std::vector<u64*> op;
-            std::vector<int> gsteps;
-            int gi = 0;
-            for (auto& kv : by_giant) {
-                for (size_t i : kv.second) {
-                    const int bs = mt.ks[i] - kv.first;
-                    const int bi = (int)(std::find(bsteps.begin(), bsteps.end(), bs) - bsteps.begin());
-                    LSA_REQUIRE(bi < nb, "bootstrap: baby step without its rotation");
-                    pp[(size_t)gi * nb + bi] = mt.plains[i];
-                }
-                inner.push_back(alloc(ct.level, ct.scale * pt_scale));
-                op.push_back(inner.back().data());
-                gsteps.push_back(kv.first);
-                gi++;
-            }
-            launch_mac_plain_multi(c, nb, cp.data(), cs.data(), ng, pp.data(), op.data(), stride(ct.level), m, 2, L, rm2(ct.level), s);
-            for (int g2 = 0; g2 < ng; g2++) {
-                DCt r = rotate(inner[g2], gsteps[g2]);
-                acc = have ? add(acc, r) : r;
-                have = true;
-            }
-            return do_rescale ? rescale(acc) : acc;
-        }
-        for (auto& kv : by_giant) {
-            std::vector<std::pair<const u64*, const DCt*>> terms;
-            for (size_t i : kv.second) terms.push_back({mt.plains[i], &baby(mt.ks[i] - kv.first)});
-            DCt inner = rotate(mac(terms), kv.first);
-            acc = have ? add(acc, inner) : inner;
-            have = true;
-        }
-        return do_rescale ? rescale(acc) : acc;
     }
 
     DCt eval_chebyshev(const DCt& u, const std::vector<double>& coeffs) {

@@ -1,6 +1,7 @@
 // c_api.hip — extern "C" operator layer (include/lattisense_amd.h).  Every entry point converts C++ exceptions into
 // error codes: nothing throws across the C boundary (the reference does, SURVEY §8b "Errors").
 #include "build_flags.h"
+#include "linear_transform.h"
 #include "lsa_internal.h"
 
 namespace lsa {
@@ -555,6 +556,101 @@ int lsa_ckks_bootstrap(lsa_context ctx, lsa_bootstrap b, const uint64_t* in, uin
         for (int i = 0; i < n_glk; i++) g[glk_elements[i]] = &K(glk[i]);
         bootstrap_run(*b->b, in, sin, out, sout, batch, K(rlk), g, swk_dts ? &K(swk_dts) : nullptr,
                       swk_std ? &K(swk_std) : nullptr, S(stream));
+    });
+}
+
+// ---- CKKS linear transform (linear_transform.hip)
+struct lsa_linear_transform_st {
+    LinearTransform* lt;
+    Context* c;
+};
+int lsa_lt_create(lsa_context ctx, int level, int log_slots, int n_diag, const int* diag_index, const double* values,
+                  double pt_scale, double bsgs_ratio, int double_hoist, void* stream, lsa_linear_transform* out) {
+    return guard([&] {
+        LSA_REQUIRE(out != nullptr, "null argument");
+        auto h = std::make_unique<lsa_linear_transform_st>();
+        h->c = &C(ctx);
+        h->lt = lt_create(*h->c, level, log_slots, n_diag, diag_index, values, pt_scale, bsgs_ratio, double_hoist != 0, S(stream));
+        *out = h.release();
+    });
+}
+void lsa_lt_destroy(lsa_linear_transform lt) {
+    if (!lt) return;
+    delete lt->lt;
+    delete lt;
+}
+int lsa_lt_info(lsa_linear_transform lt, int* level, int* period, int* n_diag, int* n1, int* rows, int* n_galois,
+                int* double_hoist, double* pt_scale) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr, "null linear-transform handle");
+        const BtMatrix& m = lt->lt->m;
+        if (level) *level = m.level;
+        if (period) *period = m.period;
+        if (n_diag) *n_diag = (int)m.ks.size();
+        if (n1) *n1 = m.naive ? 0 : m.n1;
+        if (rows) *rows = m.rows;
+        if (n_galois) *n_galois = (int)lt->lt->galois.size();
+        if (double_hoist) *double_hoist = lt->lt->double_hoist ? 1 : 0;
+        if (pt_scale) *pt_scale = m.pt_scale;
+    });
+}
+int lsa_lt_diagonals(lsa_linear_transform lt, int* index_out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr && index_out != nullptr, "null argument");
+        const auto& ks = lt->lt->m.ks;
+        LSA_REQUIRE((int)ks.size() <= capacity, "buffer too small");
+        std::copy(ks.begin(), ks.end(), index_out);
+    });
+}
+int lsa_lt_galois_elements(lsa_linear_transform lt, uint64_t* out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr && out != nullptr, "null argument");
+        const auto& g = lt->lt->galois;
+        LSA_REQUIRE((int)g.size() <= capacity, "buffer too small");
+        std::copy(g.begin(), g.end(), out);
+    });
+}
+int lsa_lt_plaintext(lsa_linear_transform lt, int diag_pos, uint64_t* host_out, long long capacity_words) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr && host_out != nullptr, "null argument");
+        const BtMatrix& m = lt->lt->m;
+        LSA_REQUIRE(diag_pos >= 0 && diag_pos < (int)m.plains.size(), "diagonal position out of range");
+        LSA_REQUIRE(capacity_words >= (long long)m.rows * lt->c->n, "buffer too small for the plaintext's rows (lsa_lt_info)");
+        lt->c->use_device();
+        LSA_HIP(hipMemcpy(host_out, m.plains[diag_pos], (size_t)m.rows * lt->c->n * sizeof(u64), hipMemcpyDeviceToHost));
+    });
+}
+int lsa_ckks_linear_transform(lsa_context ctx, lsa_linear_transform lt, const uint64_t* in, uint64_t* out, int batch,
+                              long long sin, long long sout, int rescale, int n_glk, const uint64_t* glk_elements,
+                              const lsa_key* glk, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr, "null linear-transform handle");
+        LSA_REQUIRE(lt->c == &C(ctx), "linear-transform plan belongs to another context");
+        if (batch <= 0) return;
+        LSA_REQUIRE(in != nullptr && out != nullptr && n_glk >= 0 && (n_glk == 0 || (glk_elements && glk)), "null argument");
+        std::map<u64, const Key*> g;
+        for (int i = 0; i < n_glk; i++) g[glk_elements[i]] = &K(glk[i]);
+        lt_run(*lt->lt, in, sin, out, sout, batch, rescale != 0, g, S(stream));
+    });
+}
+int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double bsgs_ratio, int* n1, int* rotations,
+                          int capacity, int* count) {
+    return guard([&] {
+        LSA_REQUIRE(period >= 1 && (period & (period - 1)) == 0, "period must be a power of two");
+        LSA_REQUIRE(n_diag >= 1 && diag_index != nullptr && bsgs_ratio >= 0, "bad argument");
+        std::map<int, bool> seen;
+        for (int i = 0; i < n_diag; i++) {
+            const int k = ((diag_index[i] % period) + period) % period;
+            LSA_REQUIRE(!seen.count(k), "diagonal index " + std::to_string(diag_index[i]) + " repeats another modulo the period");
+            seen[k] = true;
+        }
+        std::vector<int> ks, rot;
+        for (auto& kv : seen) ks.push_back(kv.first);
+        const int split = lt_plan(ks, period, bsgs_ratio > 0 ? bsgs_ratio : 2.0, rot);
+        if (n1) *n1 = split;
+        if (count) *count = (int)rot.size();
+        LSA_REQUIRE(rotations == nullptr || (int)rot.size() <= capacity, "buffer too small");
+        if (rotations) std::copy(rot.begin(), rot.end(), rotations);
     });
 }
 

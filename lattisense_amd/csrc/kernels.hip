@@ -932,6 +932,9 @@ void launch_mont_muladd(Context& c, const u64* a, long long sa, const u64* pt, l
 // The inner sums of a baby-step / giant-step linear transform in ONE launch: out[g] = sum_b ct[b] * pt[g][b] for every giant
 // step g.  Each baby-step ciphertext is read once for all giant steps (k_mac_plain, one launch per giant step, re-reads all of
 // them every time): nb*polys + terms + ng*polys limb streams instead of terms*(polys + 1) + ng*polys.
+// ACC (k_mac_plain_multi<POLYS, true>): out[g] += the same sums -- the launch is one 8 x 8 block of a wider matrix and adds to
+// what the previous baby-step block left (LtEval::inner_sums): nb baby and ng giant steps then cost ceil(nb/8) * ceil(ng/8)
+// launches, every baby-step ciphertext read ceil(ng/8) times instead of ng times, every plaintext once.
 struct MacPlainMultiArgs {
     const u64* ct[LSA_MACM_MAX];
     long long sct[LSA_MACM_MAX];
@@ -948,7 +951,7 @@ struct MacPlainMultiArgs {
 // shared by the whole batch: the batch index varies fastest and, where the piece count allows, the workgroups of one piece
 // are dealt to ONE XCD (consecutive workgroup ids go round-robin over the 8 XCDs, each with its own L2), so a piece is
 // fetched from HBM once instead of once per batch item (LSA_MACM_NO_XCD=1: batch-fastest order only).
-template <int POLYS>
+template <int POLYS, bool ACC>
 __global__ __launch_bounds__(TPB) void k_mac_plain_multi(MacPlainMultiArgs g) {
     const int chunks = (1 << g.logn) / (2 * TPB);
     int piece, b;
@@ -972,7 +975,10 @@ __global__ __launch_bounds__(TPB) void k_mac_plain_multi(MacPlainMultiArgs g) {
             for (int p = 0; p < POLYS; p++) c[p][i] = ld2(g.ct[i] + (long long)b * g.sct[i] + p * pstep + poff);
         }
     for (int gi = 0; gi < g.ng; gi++) {
-        u64 h[POLYS][2], l[POLYS][2];   // at most 8 products of < q^2, q < 2^61: below q * 2^64
+        // at most 8 products of < q^2, q < 2^61: the 128-bit sum stays below q * 2^64, which is what the lazy REDC takes.  The
+        // running sum of an ACC launch does not enter it: it is a fully reduced residue, added (mod q) to the reduced block sum
+        // after the reduction, so the bound is the same 8 products with or without it and the stored sum is again < q.
+        u64 h[POLYS][2], l[POLYS][2];
 #pragma unroll
         for (int p = 0; p < POLYS; p++) h[p][0] = h[p][1] = l[p][0] = l[p][1] = 0;
 #pragma unroll
@@ -991,13 +997,20 @@ __global__ __launch_bounds__(TPB) void k_mac_plain_multi(MacPlainMultiArgs g) {
             u64 r0 = csub(mont_redc_lazy(h[p][0], l[p][0], m.q, m.qinv), m.q), r1 = csub(mont_redc_lazy(h[p][1], l[p][1], m.q, m.qinv), m.q);
             r0 = mont_mul(r0, m.r2, m.q, m.qinv);            // sum * R^-1 -> sum
             r1 = mont_mul(r1, m.r2, m.q, m.qinv);
-            st2(g.out[gi] + (long long)b * g.so + p * pstep + poff, r0, r1);
+            u64* po = g.out[gi] + (long long)b * g.so + p * pstep + poff;
+            if constexpr (ACC) {
+                const ulonglong2 v = ld2(po);
+                r0 = add_mod(r0, v.x, m.q);
+                r1 = add_mod(r1, v.y, m.q);
+            }
+            st2(po, r0, r1);
         }
     }
 }
 
 void launch_mac_plain_multi(Context& c, int nb, const u64* const* ct, const long long* sct, int ng, const u64* const* pt /*[ng*nb]*/,
-                            u64* const* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s) {
+                            u64* const* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s,
+                            bool accumulate) {
     if (batch <= 0 || nb <= 0 || ng <= 0) return;
     LSA_REQUIRE(nb <= LSA_MACM_MAX && ng <= LSA_MACM_MAX, "too many baby or giant steps for one multiply-accumulate launch");
     LSA_REQUIRE(rm.period == limbs && limbs <= LSA_MAX_PERIOD, "mac: row map must cover the limbs");
@@ -1024,15 +1037,17 @@ void launch_mac_plain_multi(Context& c, int nb, const u64* const* ct, const long
     int period;
     fill_rowmap(g.mod_of, period, rm, c.nmod);
     // algorithmic bytes: every ciphertext piece read once, every plaintext ONCE per launch (shared by the batch), the sums written
-    ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * limbs * ((double)batch * polys * (nb + ng) + (double)terms), s);
+    ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * limbs * ((double)batch * polys * (nb + ng * (accumulate ? 2 : 1)) + (double)terms), s);
     LSA_REQUIRE(polys == 1 || polys == 2, "mac: one or two polynomials per ciphertext");
     const int pieces = limbs * (c.n / (2 * TPB));
     g.batch = batch;
     g.xcd_map = (pieces % 8 == 0 && !std::getenv("LSA_MACM_NO_XCD")) ? 1 : 0;
     LSA_REQUIRE(c.n >= 2 * TPB, "ring degree too small for the elementwise kernels (need N >= 512)");
     const dim3 grid((unsigned)(pieces * batch));
-    if (polys == 2) hipLaunchKernelGGL(k_mac_plain_multi<2>, grid, dim3(TPB), 0, s, g);
-    else hipLaunchKernelGGL(k_mac_plain_multi<1>, grid, dim3(TPB), 0, s, g);
+    if (polys == 2 && accumulate) hipLaunchKernelGGL((k_mac_plain_multi<2, true>), grid, dim3(TPB), 0, s, g);
+    else if (polys == 2) hipLaunchKernelGGL((k_mac_plain_multi<2, false>), grid, dim3(TPB), 0, s, g);
+    else if (accumulate) hipLaunchKernelGGL((k_mac_plain_multi<1, true>), grid, dim3(TPB), 0, s, g);
+    else hipLaunchKernelGGL((k_mac_plain_multi<1, false>), grid, dim3(TPB), 0, s, g);
     LSA_HIP(hipGetLastError());
 }
 
@@ -1450,6 +1465,9 @@ struct KsMacArgs {
     // EXT (k_ks_mac<KB, true>): the product leaves as a ROTATED EXTENDED ciphertext instead of the plain accumulator --
     // acc[b][h][tl][scatter[x]] = sum(x) + (h == 0 and tl < L ? P * base[b][tl][x] : 0): the gadget product, the c0 * P term and
     // the automorphism of a baby-step rotation in one pass (otherwise k_permute_ext re-reads and re-writes 2(L+k) limbs)
+    // EXT_ACC (k_ks_mac<KB, true, false, true>): the same values are ADDED to what acc holds at the scattered positions -- a
+    // giant-step rotation joining the running sum of a double-hoisted linear transform without a permutation kernel.  scatter
+    // is a permutation of the row and every thread owns its two points, so each word is read and written by one thread only.
     const unsigned* scatter;
     const u64* base;
     const u64* pm;                 // [L] P mod q_j, Montgomery form
@@ -1466,7 +1484,7 @@ struct KsMacArgs {
 // ONE REDC per output.  A thread keeps its 2*beta key words in registers and walks `bpt` ciphertexts with them: the key
 // (68 MiB at the headline shape) is then streamed once per group instead of once per ciphertext.
 // KB = number of digits whose key words are register-resident (0: stream the key per ciphertext)
-template <int KB, bool EXT = false, bool FOLD = false>
+template <int KB, bool EXT = false, bool FOLD = false, bool EXT_ACC = false>
 __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
     const int chunks = (1 << g.logn) / (2 * TPB);
     const int tl = g.n_tl ? g.tl_list[blockIdx.x / chunks] : blockIdx.x / chunks;
@@ -1610,6 +1628,12 @@ __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
             }
             const uint2 sx = *reinterpret_cast<const uint2*>(g.scatter + x);
             u64* po = g.acc + b * g.sacc + tl * N;
+            if constexpr (EXT_ACC) {
+                r00 = add_mod(r00, po[sx.x], m.q);
+                r01 = add_mod(r01, po[sx.y], m.q);
+                r10 = add_mod(r10, po[(long long)T * N + sx.x], m.q);
+                r11 = add_mod(r11, po[(long long)T * N + sx.y], m.q);
+            }
             po[sx.x] = r00;
             po[sx.y] = r01;
             po[(long long)T * N + sx.x] = r10;
@@ -1627,25 +1651,26 @@ __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
     }
 }
 
-template <bool EXT, bool FOLD = false>
+template <bool EXT, bool FOLD = false, bool EXT_ACC = false>
 static void launch_ks_mac_kb(int beta, dim3 grid, hipStream_t s, const KsMacArgs& g) {
     // the register-resident key costs 8 VGPRs per digit slot: 5 and 6 digits (the 25Q+5P chains) get their own instantiations
     // instead of the 8-slot one (182 VGPRs, 2 waves per SIMD)
-    if (beta <= 2) hipLaunchKernelGGL((k_ks_mac<2, EXT, FOLD>), grid, dim3(TPB), 0, s, g);   // low levels: 86 VGPRs, 5 waves per SIMD
-    else if (beta <= 4) hipLaunchKernelGGL((k_ks_mac<4, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
-    else if (beta <= 5) hipLaunchKernelGGL((k_ks_mac<5, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
-    else if (beta <= 6) hipLaunchKernelGGL((k_ks_mac<6, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
-    else if (beta <= 8) hipLaunchKernelGGL((k_ks_mac<8, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
-    else hipLaunchKernelGGL((k_ks_mac<0, EXT, FOLD>), grid, dim3(TPB), 0, s, g);
+    if (beta <= 2) hipLaunchKernelGGL((k_ks_mac<2, EXT, FOLD, EXT_ACC>), grid, dim3(TPB), 0, s, g);   // low levels: 86 VGPRs, 5 waves per SIMD
+    else if (beta <= 4) hipLaunchKernelGGL((k_ks_mac<4, EXT, FOLD, EXT_ACC>), grid, dim3(TPB), 0, s, g);
+    else if (beta <= 5) hipLaunchKernelGGL((k_ks_mac<5, EXT, FOLD, EXT_ACC>), grid, dim3(TPB), 0, s, g);
+    else if (beta <= 6) hipLaunchKernelGGL((k_ks_mac<6, EXT, FOLD, EXT_ACC>), grid, dim3(TPB), 0, s, g);
+    else if (beta <= 8) hipLaunchKernelGGL((k_ks_mac<8, EXT, FOLD, EXT_ACC>), grid, dim3(TPB), 0, s, g);
+    else hipLaunchKernelGGL((k_ks_mac<0, EXT, FOLD, EXT_ACC>), grid, dim3(TPB), 0, s, g);
 }
 
 // scatter (with engine < 0): the result is written as the rotated extended ciphertext perm(acc + P * c0) -- scatter = the index
 // map of the rotation's inverse element, base = the ciphertext whose c0 enters (see KsMacArgs)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, const Key& key,
                    u64* acc, long long sacc, int batch, hipStream_t s, bool unfused_only, const u32* scatter, const u64* base, long long sbase,
-                   const TensorFold* fold) {
+                   const TensorFold* fold, bool accumulate) {
     if (batch <= 0) return;
     KsMacArgs g{};
+    LSA_REQUIRE(!accumulate || scatter, "key MAC: only the extended output accumulates");
     LSA_REQUIRE(!scatter || (!unfused_only && base), "key MAC: the extended output covers every target limb and needs the ciphertext");
     LSA_REQUIRE(!(scatter && fold), "key MAC: the tensor fold has no extended output");
     if (fold) {
@@ -1690,7 +1715,7 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
     const double T = targets;
     int q_targets = 0;   // (tensor fold: the own digit of a Q target reads a0, a1, b0, b1 instead of cx)
     for (int i = 0; i < targets; i++) q_targets += (g.n_tl ? g.tl_list[i] : i) < g.L;
-    ProfScope ps(c, PROF_KSMAC, 8.0 * c.n * (batch * (g.beta * T + 2 * T + (scatter ? g.L : 0) + (fold ? 3.0 * q_targets : 0.0)) +
+    ProfScope ps(c, PROF_KSMAC, 8.0 * c.n * (batch * (g.beta * T + 2 * T * (accumulate ? 2 : 1) + (scatter ? g.L : 0) + (fold ? 3.0 * q_targets : 0.0)) +
                                              2.0 * g.beta * T), s);
     // enough workgroups to fill the chip, as few key re-reads as possible
     const dim3 grid1 = ew_grid(c, targets, 1);
@@ -1698,7 +1723,8 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
     g.batch = batch;
     g.bpt = (batch + groups - 1) / groups;
     const dim3 grid(grid1.x, (unsigned)((batch + g.bpt - 1) / g.bpt));
-    if (scatter) launch_ks_mac_kb<true>(g.beta, grid, s, g);
+    if (scatter && accumulate) launch_ks_mac_kb<true, false, true>(g.beta, grid, s, g);
+    else if (scatter) launch_ks_mac_kb<true>(g.beta, grid, s, g);
     else if (fold) launch_ks_mac_kb<false, true>(g.beta, grid, s, g);
     else launch_ks_mac_kb<false>(g.beta, grid, s, g);
     LSA_HIP(hipGetLastError());

@@ -1,0 +1,173 @@
+// linear_transform.h — CKKS plaintext-matrix x encrypted-vector products in diagonal form: the matrix type, the diagonal
+// encoder, the baby-step / giant-step planner and the device evaluator.  Shared by bootstrapping (bootstrap.hip: the
+// CoeffsToSlots / SlotsToCoeffs matrices) and by the public operator (lsa_lt_* / lsa_ckks_linear_transform); the code is in
+// linear_transform.hip.  Oracle twin: oracle/ckks_bootstrap.py linear_transform.
+#pragma once
+#include <cmath>
+#include <complex>
+#include <map>
+#include <memory>
+
+#include "lsa_internal.h"
+
+namespace lsa {
+
+using cplx = std::complex<double>;
+using Diags = std::map<int, std::vector<cplx>>;   // diagonal k: d[t] multiplies x[(t + k) mod n]
+
+// ------------------------------------------------------------------------------------------------ planner (host only)
+std::vector<int> rot_group(int n_slots);   // 5^i mod 4 n_slots
+void bsgs_sets(const std::vector<int>& ks, int n, int n1, std::vector<int>& giants, std::vector<int>& babies);
+// the planner's baby-step count (frontend/bootstrap_params.py:193-207): the caller's Galois keys exist for this choice
+int bsgs_split(const std::vector<int>& ks, int n, double ratio);
+// the split (0: fewer than three diagonals, one rotation each) and the non-zero rotations of a reduced, ascending index set
+int lt_plan(const std::vector<int>& ks, int period, double ratio, std::vector<int>& rotations);
+// Python's round(): ties to even; a constant beyond 2^62 is refused (`who` prefixes the message)
+long long round_even(double v, const char* who);
+
+// ------------------------------------------------------------------------------------------------ matrix
+struct BtMatrix {
+    int level = 0, n1 = 1;
+    int period = 0;                      // period of the diagonals (index arithmetic mod period); N/2 for dense packing
+    bool naive = false;
+    std::vector<int> ks;                 // diagonal indices, ascending
+    std::vector<u64*> plains;            // per diagonal: NTT-domain plaintext [rows][N] of rot_{-giant}(diag)
+    int rows = 0;                        // level + 1, or level + 1 + k (the special primes too) for a double-hoisted matrix
+    double pt_scale = 0;                 // encoding scale of the diagonals
+};
+
+// real polynomial coefficients * scale -> NTT-domain plaintext on the device (appended to `owned`)
+// ext: the same integer polynomial at the special primes too, rows level+1 .. level+k (operand of extended ciphertexts)
+u64* lt_upload_plain(Context& c, const std::vector<double>& coef, double scale, int level, hipStream_t s, bool ext,
+                     std::vector<u64*>& owned, const char* who);
+// one matrix -> plaintexts (diagonals of period `period`, tiled over the N/2 slots) + the Galois elements of its rotations
+// (added to `gal`).  Keys of `mat` are reduced mod period.
+BtMatrix lt_make_matrix(Context& c, const Diags& mat, int level, int period, double pt_scale, double ratio, bool double_hoist,
+                        hipStream_t s, std::vector<u64*>& owned, std::map<u64, bool>& gal, const char* who);
+
+// ------------------------------------------------------------------------------------------------ device evaluator
+// temporaries of a run, kept across runs (hipMalloc / hipFree of GiB-sized buffers cost more than the kernels); a pool
+// belongs to one plan, which is run on one in-order stream at a time, so reuse is ordered
+struct DevPool {
+    std::multimap<size_t, u64*> free;
+    std::vector<u64*> all;
+    void release();   // hipFree of everything (the owner has synchronised)
+};
+struct DBuf {
+    u64* p = nullptr;
+    size_t words = 0;
+    DevPool* pool = nullptr;   // null: the caller's memory, wrapped
+    ~DBuf() {
+        if (pool) pool->free.emplace(words, p);
+    }
+};
+struct DCt {
+    std::shared_ptr<DBuf> buf;
+    int level = 0;
+    double scale = 0;
+    u64* data() const { return buf->p; }
+};
+
+struct LtEval {
+    Context& c;
+    DevPool& pool;   // released device buffers (single in-order stream: reuse is ordered)
+    hipStream_t s;
+    int m;   // batch
+    const std::map<u64, const Key*>& glk;
+    long long N;
+    std::string who;              // prefix of error messages
+    bool giant_scatter = false;   // giant-step rotations through the accumulating scatter of the key MAC (ckks_rotate_ext)
+
+    LtEval(Context& c_, DevPool& p, hipStream_t s_, int m_, const std::map<u64, const Key*>& g, const char* who_)
+        : c(c_), pool(p), s(s_), m(m_), glk(g), N(c_.n), who(who_) {}
+    long long stride(int level) const { return 2LL * (level + 1) * N; }
+    DCt alloc(int level, double scale) {
+        DCt o = alloc_words((size_t)m * stride(level));
+        o.level = level;
+        o.scale = scale;
+        return o;
+    }
+    DCt alloc_words(size_t words);
+    DCt wrap(u64* p, int level, double scale) const {   // the caller's [m][2][level+1][N], not pooled
+        auto b = std::make_shared<DBuf>();
+        b->p = p;
+        return DCt{b, level, scale};
+    }
+    // extended ciphertext [2][level+1+k][N] over Q_level u P (ops.hip, ckks_rotate_many_ext); `level` and `scale` as for the
+    // ciphertext it will be divided down to
+    long long stride_ext(int level) const { return 2LL * (level + 1 + c.np) * N; }
+    DCt alloc_ext(int level, double scale) {
+        DCt o = alloc_words((size_t)m * stride_ext(level));
+        o.level = level;
+        o.scale = scale;
+        return o;
+    }
+    RowMap rm_ext(int level) const {   // both polynomials' rows of an extended ciphertext
+        RowMap rm;
+        rm.period = level + 1 + c.np;
+        for (int j = 0; j <= level; j++) rm.mod_of[j] = (unsigned char)j;
+        for (int i = 0; i < c.np; i++) rm.mod_of[level + 1 + i] = (unsigned char)c.p_mod(i);
+        return rm;
+    }
+    RowMap rm2(int level) const {   // both polynomials' limbs
+        RowMap rm;
+        rm.period = level + 1;
+        for (int j = 0; j <= level; j++) rm.mod_of[j] = (unsigned char)j;
+        return rm;
+    }
+    double q(int level) const { return (double)c.T.mod[level]; }
+
+    DCt addsub(const DCt& a, const DCt& b, EwOp op) {
+        LSA_REQUIRE(a.level == b.level && std::fabs(a.scale / b.scale - 1) < 1e-9, who + ": operands of add/sub differ in level or scale");
+        DCt o = alloc(a.level, a.scale);
+        launch_elementwise(c, op, a.data(), b.data(), o.data(), m, stride(a.level), stride(a.level), stride(a.level),
+                           2 * (a.level + 1), rm2(a.level), s);
+        return o;
+    }
+    DCt add(const DCt& a, const DCt& b) { return addsub(a, b, EW_ADD); }
+    DCt sub(const DCt& a, const DCt& b) { return addsub(a, b, EW_SUB); }
+    DCt rescale(const DCt& a) {
+        DCt o = alloc(a.level - 1, a.scale / q(a.level));
+        ckks_rescale(c, a.level, 2, a.data(), o.data(), m, stride(a.level), stride(a.level - 1), s);
+        return o;
+    }
+    const Key& gkey(u64 e) const {
+        auto it = glk.find(e);
+        LSA_REQUIRE(it != glk.end(), who + ": Galois key for element " + std::to_string(e) + " missing");
+        return *it->second;
+    }
+    u64 galois_of(int r) const {
+        u64 e = 1;
+        for (int i = 0; i < r; i++) e = e * 5 % (2ULL * c.n);
+        return e;
+    }
+    DCt rotate(const DCt& a, int r);
+    // rotations of one ciphertext by several steps with a single decomposition (hoisted); same residues as rotate()
+    std::map<int, DCt> rotate_many(const DCt& a, const std::vector<int>& steps);
+    // the same rotations WITHOUT their division by P: extended ciphertexts (step 0: the ciphertext times P)
+    std::map<int, DCt> rotate_many_ext(const DCt& a, const std::vector<int>& steps);
+    DCt moddown(const DCt& a);   // extended -> ciphertext; `a` is consumed
+    // out[g] = sum_b ct[b] * pt[g][b] for every giant step g, pt [ng][nb] (null: no such diagonal), rows = limbs per polynomial
+    void inner_sums(int nb, const u64* const* ct, long long sct, int ng, const u64* const* pt, u64* const* out, long long so,
+                    int limbs, const RowMap& rm);
+    DCt linear_transform_dh(const DCt& ct, const BtMatrix& mt, bool do_rescale);
+    DCt linear_transform(const DCt& ct, const BtMatrix& mt, bool do_rescale = true);
+};
+
+// ------------------------------------------------------------------------------------------------ public operator plan
+struct LinearTransform {
+    Context& c;
+    BtMatrix m;
+    bool double_hoist = true;
+    std::vector<u64> galois;   // elements of the non-zero rotations, ascending
+    std::vector<u64*> owned;
+    DevPool pool;
+    explicit LinearTransform(Context& ctx) : c(ctx) {}
+    ~LinearTransform();
+};
+LinearTransform* lt_create(Context& c, int level, int log_slots, int n_diag, const int* diag_index, const double* values,
+                           double pt_scale, double bsgs_ratio, bool double_hoist, hipStream_t s);
+void lt_run(LinearTransform& lt, const u64* in, long long sin, u64* out, long long sout, int batch, bool rescale,
+            const std::map<u64, const Key*>& glk, hipStream_t s);
+
+}  // namespace lsa

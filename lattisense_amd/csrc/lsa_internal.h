@@ -265,7 +265,8 @@ void launch_mac_plain(Context& c, int terms, const u64* const* ct, const long lo
                       const long long* spt, const u64* partial, long long spartial, u64* out, long long so, int batch,
                       int polys, int limbs, const RowMap& rm, hipStream_t s);
 void launch_mac_plain_multi(Context& c, int nb, const u64* const* ct, const long long* sct, int ng, const u64* const* pt,
-                            u64* const* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s);
+                            u64* const* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s,
+                            bool accumulate = false);   // out[g] += the sums (one block of a matrix wider than LSA_MACM_MAX)
 // out[p][j] = a[p][j] * pt[j] * 2^-64 mod q (+ acc[p][j]) over [batch][polys][limbs][N]: BFV ct x pt_mul in the NTT domain,
 // unfused form (k_mont_muladd); acc / a may be out
 void launch_mont_muladd(Context& c, const u64* a, long long sa, const u64* pt, long long spt, const u64* acc, long long sacc,
@@ -301,11 +302,12 @@ void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows
 // key-switch inner product: acc[h][tl] = sum_d ext(d,tl) * key[d][h][tl];  ext(d,tl) = cx[tl] when tl is in digit d
 // unfused_only: only the target limbs that do not take the fused kernel (ks_fused_limb; k_ntt_r16_ksmac did the others)
 // scatter (every target limb only): the result leaves as the ROTATED EXTENDED ciphertext acc[h][tl][scatter[x]] = sum(x) + (h == 0, tl < L:
-// P * base[tl][x]) -- gadget product, c0 * P and the automorphism of a baby-step rotation in one pass
+// P * base[tl][x]) -- gadget product, c0 * P and the automorphism of a baby-step rotation in one pass; accumulate: added to
+// what acc holds there (a giant-step rotation joining a running sum)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext,
                    const Key& key, u64* acc, long long sacc, int batch, hipStream_t s, bool unfused_only = false,
                    const u32* scatter = nullptr, const u64* base = nullptr, long long sbase = 0,
-                   const TensorFold* fold = nullptr);
+                   const TensorFold* fold = nullptr, bool accumulate = false);
 // out[h][i] = base[h][i] + (acc[h][i] - conv[h][i]) * Pinv_i       (base may be null)
 void launch_moddown_final(Context& c, int level, const u64* acc, long long sacc, int acc_rows_per_poly, const u64* conv,
                           long long sconv, const u64* base, long long sbase, int base_rows_per_poly, int base_polys,
@@ -409,7 +411,7 @@ void ckks_lift_ext(Context& c, int level, const u64* in, u64* out, int batch, lo
 void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
                           int batch, long long sin, long long sout, hipStream_t s);
 void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, bool accumulate, int batch,
-                     long long sin, long long sout, hipStream_t s);
+                     long long sin, long long sout, hipStream_t s, bool scatter_mac = false);
 void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
 void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                 hipStream_t s);

@@ -544,11 +544,26 @@ void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const
     });
 }
 
-// out (+)= automorphism_g( (P c0 + ks0, ks1) ): one rotation without its division by P, optionally added to `out`
+// out (+)= automorphism_g( (P c0 + ks0, ks1) ): one rotation without its division by P, optionally added to `out`.
+// scatter_mac (and LSA_ROT_SCATTER not 0): the key MAC writes / adds the rotated extended ciphertext itself
+// (out[perm[x]] (+)= mac(x) + P c0(x), as ckks_rotate_many_ext does for baby steps) -- no k_permute_ext pass over 2(L+k) limbs, but
+// the extension transform's second pass cannot be fused with that MAC.  Otherwise decompose + MAC (fused where the shape
+// allows) + k_permute_ext.  Same residues.
 void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, bool accumulate, int batch,
-                     long long sin, long long sout, hipStream_t s) {
+                     long long sin, long long sout, hipStream_t s, bool scatter_mac) {
     const long long N = c.n;
     const int L = level + 1;
+    if (scatter_mac && rotation_scatter_on()) {
+        const u32* scatter = inverse_perm(c, g);
+        for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+            const u64* ct = in + (size_t)b0 * sin;
+            KsTile t(c, level, nb, ws, st);
+            t.decompose(ct + (long long)L * N, sin);
+            launch_ks_mac(c, level, ct + (long long)L * N, sin, t.ext, t.s_ext, glk, out + (size_t)b0 * sout, sout, nb, st, false, scatter,
+                          ct, sin, nullptr, accumulate);
+        });
+        return;
+    }
     const u32* perm = c.ntt_perm(g);
     for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* ct = in + (size_t)b0 * sin;

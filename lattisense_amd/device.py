@@ -364,3 +364,82 @@ class BootstrapPlan:
             check(lib().lsa_bootstrap_matrix_info(self.h, i, ctypes.byref(lv), None, None, None, 0))
             out[k] = lv.value
         return out
+
+
+def plan_rotations(period, diag_index, ratio=0.0):
+    """(n1, rotations): the baby-step count (0: no split) and the non-zero rotations a diagonal index set gets -- host only"""
+    idx = (ctypes.c_int * len(diag_index))(*[int(k) for k in diag_index])
+    n1, cnt = ctypes.c_int(), ctypes.c_int()
+    check(lib().lsa_lt_plan_rotations(period, len(diag_index), idx, ratio, ctypes.byref(n1), None, 0, ctypes.byref(cnt)))
+    rot = (ctypes.c_int * max(cnt.value, 1))()
+    check(lib().lsa_lt_plan_rotations(period, len(diag_index), idx, ratio, ctypes.byref(n1), rot, cnt.value, ctypes.byref(cnt)))
+    return n1.value, [int(r) for r in rot[: cnt.value]]
+
+
+class LinearTransformPlan:
+    """A plaintext matrix in diagonal form, encoded for ciphertexts at `level` (include/lattisense_amd.h: lsa_lt_*).
+    diags: {k: complex array of length period}, d_k[t] multiplies x[(t + k) mod period], period = 2^log_slots (default: the
+    arrays' length)."""
+
+    def __init__(self, ctx, level, diags, log_slots=None, pt_scale=0, ratio=0, double_hoist=True):
+        self.ctx = ctx
+        self.h = None
+        ks = list(diags)
+        assert ks, "at least one diagonal"
+        period = len(diags[ks[0]]) if log_slots is None else 1 << log_slots
+        assert period & (period - 1) == 0 and all(len(diags[k]) == period for k in ks), "diagonals must have 2^log_slots entries"
+        vals = np.empty((len(ks), period, 2), dtype=np.float64)
+        for i, k in enumerate(ks):
+            d = np.asarray(diags[k], dtype=np.complex128)
+            vals[i, :, 0], vals[i, :, 1] = d.real, d.imag
+        idx = (ctypes.c_int * len(ks))(*[int(k) for k in ks])
+        h = ctypes.c_void_p()
+        check(lib().lsa_lt_create(ctx.h, level, period.bit_length() - 1, len(ks), idx,
+                                  vals.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(pt_scale), float(ratio),
+                                  int(bool(double_hoist)), ctx.stream, ctypes.byref(h)))
+        self.h = h
+        lv, pe, nd, n1, rows, ng, dh, sc = (ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(),
+                                            ctypes.c_int(), ctypes.c_int(), ctypes.c_double())
+        check(lib().lsa_lt_info(self.h, ctypes.byref(lv), ctypes.byref(pe), ctypes.byref(nd), ctypes.byref(n1), ctypes.byref(rows),
+                                ctypes.byref(ng), ctypes.byref(dh), ctypes.byref(sc)))
+        self.level, self.period, self.n1, self.rows = lv.value, pe.value, n1.value, rows.value
+        self.double_hoist, self.pt_scale = bool(dh.value), sc.value
+        kk = (ctypes.c_int * nd.value)()
+        check(lib().lsa_lt_diagonals(self.h, kk, nd.value))
+        self.diagonals = [int(k) for k in kk]
+        g = (ctypes.c_uint64 * max(ng.value, 1))()
+        check(lib().lsa_lt_galois_elements(self.h, g, ng.value))
+        self.galois_elements = [int(x) for x in g[: ng.value]]
+
+    def close(self):
+        if self.h:
+            lib().lsa_lt_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def oracle_plains(self):
+        """{k (reduced mod period): plaintext [rows][N]}: what oracle/ckks_bootstrap.py linear_transform takes as `plains`"""
+        out = {}
+        for i, k in enumerate(self.diagonals):
+            pt = np.empty((self.rows, self.ctx.n), dtype=np.uint64)
+            check(lib().lsa_lt_plaintext(self.h, i, pt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), pt.size))
+            out[k] = pt
+        return out
+
+    def run(self, in_buf, batch, glk, rescale=True, out=None):
+        """in_buf: device [batch][2][level+1][N]; glk: {galois element: key handle}; returns device
+        [batch][2][level (rescale) | level+1][N]"""
+        n = self.ctx.n
+        lo = self.level if rescale else self.level + 1
+        if out is None:
+            out = self.ctx.alloc(max(batch, 1) * 2 * lo * n)
+        elts = (ctypes.c_uint64 * max(len(glk), 1))(*glk.keys())
+        keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
+        check(lib().lsa_ckks_linear_transform(self.ctx.h, self.h, in_buf.ptr, out.ptr, batch, 2 * (self.level + 1) * n, 2 * lo * n,
+                                              int(bool(rescale)), len(glk), elts, keys, self.ctx.stream))
+        return out
