@@ -112,7 +112,7 @@ int lsa_bfv_rotate(lsa_context ctx, int level, const uint64_t* in, uint64_t galo
 /* BFV ciphertext x pt_mul plaintext.  A pt_mul plaintext ([level+1][N] words) is the message lifted to Q, in the NTT domain
  * and in Montgomery form (the frontend's BfvPlaintextMulNode).  Per poly and limb: out = INTT(NTT(ct) . pt . 2^-64 mod q),
  * Lattigo v4's mulPlaintextMul.  ct / out: [2][level+1][N] per batch item; out may be ct.  LSA_PTMUL_FUSED=0 selects the
- * unfused form (read per call). */
+ * unfused form (when it is read: INTEGRATION.md section 6). */
 int lsa_bfv_mult_plain_mul(lsa_context ctx, int level, const uint64_t* ct, const uint64_t* pt, uint64_t* out, int batch,
                            long long sct, long long spt, long long sout, void* stream);
 /* out = sum_{i<n} cts[i] x pts[i] (+ partial when not null), n >= 1, the same products as lsa_bfv_mult_plain_mul, summed in
@@ -126,7 +126,7 @@ int lsa_bfv_mac_plain_mul(lsa_context ctx, int level, int n, const uint64_t* con
  * element needs its Galois key; elements may repeat.  pts[i]: pt_mul plaintexts as for lsa_bfv_mult_plain_mul, batch stride
  * spts[i] (0: one plaintext for the whole batch).  Bit-identical to lsa_bfv_rotate_many followed by lsa_bfv_mac_plain_mul
  * on the same terms.  The input is transformed and decomposed once; the rotations stay in the NTT domain and the rotated
- * ciphertexts are never written.  out may overlap no input.  LSA_ROTMAC_FUSED=0 (read per call) selects the two-step form. */
+ * ciphertexts are never written.  out may overlap no input.  LSA_ROTMAC_FUSED=0 selects the two-step form (section 6). */
 int lsa_bfv_rotate_mac_plain_mul(lsa_context ctx, int level, const uint64_t* in, int n, const uint64_t* galois_elements,
                                  const lsa_key* glk, const uint64_t* const* pts, const long long* spts, const uint64_t* partial,
                                  long long spartial, uint64_t* out, int batch, long long sin, long long sout, void* stream);
@@ -235,8 +235,8 @@ int lsa_lt_plaintext(lsa_linear_transform lt, int diag_pos, uint64_t* host_out, 
 /* in [batch][2][level+1][N] (NTT domain) -> out [batch][2][level (rescale) | level+1 (no rescale)][N], batch strides sin / sout in
  * words; out may not overlap in (LSA_ERR_ARG); batch <= 0 is a no-op.  glk_elements / glk: n_glk Galois keys, in any order and
  * possibly more than needed; a missing one fails with LSA_ERR_ARG (the message names the element) before any work is queued.
- * Switches read per call: LSA_LT_BLOCKED_MAC=0 (matrices beyond 8 x 8 baby / giant steps: one multiply-accumulate launch per
- * giant step instead of 8 x 8 blocks), LSA_ROT_SCATTER=0 (rotations as MAC + permutation kernel), LSA_LT_GIANT_SCATTER=0 / 1
+ * Switches (when each is read: INTEGRATION.md section 6): LSA_LT_BLOCKED_MAC=0 (matrices beyond 8 x 8 baby / giant steps: one
+ * multiply-accumulate launch per giant step instead of 8 x 8 blocks), LSA_ROT_SCATTER=0 (rotations as MAC + permutation kernel), LSA_LT_GIANT_SCATTER=0 / 1
  * (giant-step rotations alone).  Every combination produces the same words. */
 int lsa_ckks_linear_transform(lsa_context ctx, lsa_linear_transform lt, const uint64_t* in, uint64_t* out, int batch,
                               long long sin, long long sout, int rescale, int n_glk, const uint64_t* glk_elements,

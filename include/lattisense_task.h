@@ -156,7 +156,7 @@ int lsa_task_last_run_direct(fhe_task_handle handle, int* loads, int* stores);
  * the converted device copy instead of staging, uploading and converting it again (the reference re-exports and re-uploads every
  * key on every run, cxx_sdk_v2/cxx_argument.h:178-260).  A regenerated key or another key object is detected and replaces the
  * copy; a caller that rewrites a key in place must call lsa_task_drop_keys (frees the device copies; the next run uploads).
- * LSA_NO_KEY_CACHE=1 in the environment restores upload-per-run. */
+ * LSA_NO_KEY_CACHE=1 in the environment restores upload-per-run (when it is read: INTEGRATION.md section 6). */
 int lsa_task_drop_keys(fhe_task_handle handle);
 int lsa_task_last_run_keys(fhe_task_handle handle, int* uploaded, int* reused);
 

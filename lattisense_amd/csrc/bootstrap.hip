@@ -188,7 +188,7 @@ struct Bootstrap {
     void build(hipStream_t s) {
         const int n = c.n / 2;
         top_level = c.nq - 1;
-        if (const char* e = std::getenv("LSA_BT_DOUBLE_HOIST")) double_hoist = e[0] != '0';
+        double_hoist = sw::bt_double_hoist(double_hoist);
         LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, "bootstrap: CKKS only");
         LSA_REQUIRE(sine_deg >= 1 && sine_deg <= 63, "bootstrap: sine degree outside 1..63");
         LSA_REQUIRE(arcsine_deg >= 0 && arcsine_deg <= 15 && (arcsine_deg == 0 || (arcsine_deg & 1)), "bootstrap: arcsine degree must be odd and at most 15");
@@ -555,8 +555,7 @@ void bootstrap_run(Bootstrap& bt, const u64* in, long long sin, u64* out, long l
     Eval ev(c, bt, s, batch, rlk, glk);
     const long long N = c.n;
     // diagnostic: LSA_BT_STOP=<step> returns the first out_level+1 limbs of that step's intermediate instead
-    const char* stop_env = getenv("LSA_BT_STOP");
-    const int stop = stop_env ? atoi(stop_env) : -1;
+    const int stop = sw::bt_stop();
     const int out_level = bootstrap_out_level(bt);
     int step = 0;
     auto emit = [&](const DCt& v) {

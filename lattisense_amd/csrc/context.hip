@@ -34,15 +34,13 @@ Context::Context(int algo_, int n_, const u64* q, int nq_, const u64* p, int np_
 #ifndef LSA_NTT_TAU
 #define LSA_NTT_TAU 12   // log2 of the LDS tile (points per workgroup pass)
 #endif
-    int mu_a = 0;
-    if (const char* e = std::getenv("LSA_NTT_MU_A")) mu_a = std::atoi(e);   // A/B: stages of the first pass
-    plan = make_ntt_plan(logn, LSA_NTT_TAU, mu_a);
+    plan = make_ntt_plan(logn, LSA_NTT_TAU, sw::ntt_mu_a());   // (A/B: stages of the first pass)
     // N = 2^13 / 2^14: the whole limb also fits one workgroup's LDS (69 / 136 KiB) and can be transformed in a single pass
     // of 512 / 1024 threads: half the HBM traffic, but one or two workgroups per CU and R limbs fill only R CUs --
     // launch_ntt picks per launch; LSA_NTT_WIDE=0 / 1 forces never / always.
     plan_wide = make_ntt_plan(logn, (logn == 13 || logn == 14) ? logn : LSA_NTT_TAU);
-    if (const char* e = std::getenv("LSA_NTT_FP_RAW")) fp_raw = e[0] != '0';
-    if (const char* wide = std::getenv("LSA_NTT_WIDE")) wide_mode = wide[0] == '0' ? 0 : wide[0] == '1' ? 1 : 2;
+    fp_raw = sw::ntt_fp_raw(fp_raw);
+    wide_mode = sw::ntt_wide(wide_mode);
     LSA_REQUIRE(plan.npass == 1 || plan.pass[1].mu <= plan.pass[1].tau, "ring degree too large for the NTT tile size");
 
     int ndev = 0;
@@ -217,7 +215,7 @@ const BaseConvPlan* Context::baseconv(const std::vector<int>& src, const std::ve
         K->half_dst[j] = mul_mod_host(mul_mod_host((all + pj - 1 % pj) % pj, (pj + 1) >> 1, pj), scale, pj);
     }
     // SPLIT is proved for k_baseconv's up to LSA_BC_NARROW_SRC terms; wider conversions take the 128-bit form
-    bool small = std::getenv("LSA_BC_NO_SPLIT") == nullptr && ns <= LSA_BC_NARROW_SRC;
+    bool small = !sw::bc_no_split() && ns <= LSA_BC_NARROW_SRC;
     for (int i = 0; i < ns; i++) small = small && (T.mod[src[i]] >> 58) == 0;
     for (int j = 0; j < nd; j++) small = small && (T.mod[dst[j]] >> 58) == 0;
     K->split29 = small ? 1 : 0;

@@ -168,91 +168,43 @@ __global__ __launch_bounds__(LSA_R16_THREADS, LSA_R16_WAVES) void k_ntt_r8x3(Ntt
     r16_sync<1>();
     r8x3_phase<FZ>(a, bc, tid, lds, 3, v);
 }
-static bool ntt_launch_r16(const NttPassArgs& a, int npass, bool fused, long long nblocks, hipStream_t s) {
-    static const bool enabled = [] {
-        const char* e = getenv("LSA_NTT_R16");
-        return !(e && e[0] == '0');
-    }();
-    if (!enabled || !ntt_r16_shape_ok(a, npass)) return false;
+// The FZ variant of a pass (k_ntt_pass): which fused tail it can execute.  The prologue lives in the pass that holds stage 0,
+// the epilogue in the pass that reduces and stores the final values; the product prologue and the pt_mul / rotate-and-MAC
+// epilogues come alone.
+static int ntt_pass_fz(const NttPassArgs& a, bool fused) {
     const bool pro = fused && a.fz_pro && a.fz_first, epi = fused && a.fz_epi && a.final_reduce;
-    const size_t lds_bytes = (size_t)LSA_R16_LDS_WORDS * sizeof(u64);
-    const dim3 grid((unsigned)nblocks), block(LSA_R16_THREADS);
-    if (pro && a.fz_pro == 3) {   // the product prologue (FZ bit 16): the first executed pass of an inverse transform = a second pass
-        if (a.lambda || !a.inverse) return false;
-        if (a.mu == 9) {
-            const char* e = getenv("LSA_NTT_R8X3");
-            if (e && e[0] == '0') return false;
-            hipLaunchKernelGGL((k_ntt_r8x3<16>), grid, block, lds_bytes, s, a);
-        } else if (a.mu == 8) {
-            hipLaunchKernelGGL((k_ntt_r16<1, 16, 8>), grid, block, lds_bytes, s, a);
-        } else {
-            hipLaunchKernelGGL((k_ntt_r16<1, 16, 7>), grid, block, lds_bytes, s, a);
-        }
-        LSA_HIP(hipGetLastError());
-        return true;
-    }
-    if (epi && a.fz_epi == 3) {   // the pt_mul epilogue (FZ bit 4): second passes only, it has no prologue
-        if (a.lambda) return false;
-        if (a.mu == 9) {
-            const char* e = getenv("LSA_NTT_R8X3");
-            if (e && e[0] == '0') return false;
-            hipLaunchKernelGGL((k_ntt_r8x3<4>), grid, block, lds_bytes, s, a);
-        } else if (a.mu == 8) {
-            hipLaunchKernelGGL((k_ntt_r16<1, 4, 8>), grid, block, lds_bytes, s, a);
-        } else {
-            hipLaunchKernelGGL((k_ntt_r16<1, 4, 7>), grid, block, lds_bytes, s, a);
-        }
-        LSA_HIP(hipGetLastError());
-        return true;
-    }
-    if (epi && a.fz_epi == 4) {   // the rotate-and-MAC epilogue (FZ bit 8): likewise second passes only
-        if (a.lambda) return false;
-        if (a.mu == 9) {
-            const char* e = getenv("LSA_NTT_R8X3");
-            if (e && e[0] == '0') return false;
-            hipLaunchKernelGGL((k_ntt_r8x3<8>), grid, block, lds_bytes, s, a);
-        } else if (a.mu == 8) {
-            hipLaunchKernelGGL((k_ntt_r16<1, 8, 8>), grid, block, lds_bytes, s, a);
-        } else {
-            hipLaunchKernelGGL((k_ntt_r16<1, 8, 7>), grid, block, lds_bytes, s, a);
-        }
-        LSA_HIP(hipGetLastError());
-        return true;
-    }
-    // the two-operand prologue: 394 us per headline launch here against 450 on the staged kernel once the lift's block-uniform
-    // cases became branches (628 before: both lifts were evaluated per element, profiles/r03/ab_r16_prologue_epilogue_branches.log);
-    // LSA_R16_PRO=0 keeps it on the staged kernel (A/B)
-    static const bool pro_enabled = [] {
-        const char* e = getenv("LSA_R16_PRO");
-        return !(e && e[0] == '0');
-    }();
-    if (a.lambda) {
-        if (epi || (pro && !pro_enabled)) return false;   // (a first pass is never the last one of a two-pass plan)
-        if (a.mu == 8) {
-            if (pro) hipLaunchKernelGGL((k_ntt_r16<0, 1, 8>), grid, block, lds_bytes, s, a);
-            else hipLaunchKernelGGL((k_ntt_r16<0, 0, 8>), grid, block, lds_bytes, s, a);
-        } else {
-            if (pro) return false;
-            hipLaunchKernelGGL((k_ntt_r16<0, 0, 7>), grid, block, lds_bytes, s, a);
-        }
-    } else {
-        if (pro) return false;
-        if (a.mu == 9) {
-            static const bool r8x3_enabled = [] {
-                const char* e = getenv("LSA_NTT_R8X3");   // =0: the nine-stage second pass on the staged kernel (A/B)
-                return !(e && e[0] == '0');
-            }();
-            if (!r8x3_enabled) return false;
-            if (epi) hipLaunchKernelGGL((k_ntt_r8x3<2>), grid, block, lds_bytes, s, a);
-            else hipLaunchKernelGGL((k_ntt_r8x3<0>), grid, block, lds_bytes, s, a);
-        } else if (a.mu == 8) {
-            if (epi) hipLaunchKernelGGL((k_ntt_r16<1, 2, 8>), grid, block, lds_bytes, s, a);
-            else hipLaunchKernelGGL((k_ntt_r16<1, 0, 8>), grid, block, lds_bytes, s, a);
-        } else {
-            if (epi) hipLaunchKernelGGL((k_ntt_r16<1, 2, 7>), grid, block, lds_bytes, s, a);
-            else hipLaunchKernelGGL((k_ntt_r16<1, 0, 7>), grid, block, lds_bytes, s, a);
+    if (pro && a.fz_pro == 3) return 16;
+    if (epi && a.fz_epi == 3) return 4;
+    if (epi && a.fz_epi == 4) return 8;
+    return (pro ? 1 : 0) | (epi ? 2 : 0);
+}
+template <int FZ>
+static auto ntt_r16_second_pass(int mu) {
+    return mu == 9 ? &k_ntt_r8x3<FZ> : mu == 8 ? &k_ntt_r16<1, FZ, 8> : &k_ntt_r16<1, FZ, 7>;
+}
+// false: this pass is not covered, the caller takes the staged kernel
+static bool ntt_launch_r16(const NttPassArgs& a, int npass, bool fused, long long nblocks, hipStream_t s) {
+    if (!sw::ntt_r16() || !ntt_r16_shape_ok(a, npass)) return false;
+    const int fz = ntt_pass_fz(a, fused);
+    void (*k)(NttPassArgs) = nullptr;
+    if (a.lambda) {   // a first pass (seven or eight stages): plain, or the two-operand prologue at eight stages; it is never the
+                      // last pass of a two-pass plan, and the product prologue's first executed pass is a second pass
+        // the two-operand prologue: 394 us per headline launch here against 450 on the staged kernel once the lift's block-uniform
+        // cases became branches (628 before: both lifts were evaluated per element, profiles/r03/ab_r16_prologue_epilogue_branches.log);
+        // LSA_R16_PRO=0 keeps it on the staged kernel (A/B)
+        if (fz == 1 && a.mu == 8 && sw::r16_pro()) k = &k_ntt_r16<0, 1, 8>;
+        else if (fz == 0) k = a.mu == 8 ? &k_ntt_r16<0, 0, 8> : &k_ntt_r16<0, 0, 7>;
+    } else if (a.mu != 9 || sw::ntt_r8x3()) {   // a second pass; LSA_NTT_R8X3=0: the nine-stage one on the staged kernel (A/B)
+        switch (fz) {   // it has no two-operand prologue (FZ 1, 3), and the product prologue belongs to inverse transforms
+            case 0: k = ntt_r16_second_pass<0>(a.mu); break;
+            case 2: k = ntt_r16_second_pass<2>(a.mu); break;
+            case 4: k = ntt_r16_second_pass<4>(a.mu); break;
+            case 8: k = ntt_r16_second_pass<8>(a.mu); break;
+            case 16: k = a.inverse ? ntt_r16_second_pass<16>(a.mu) : nullptr; break;
         }
     }
+    if (!k) return false;
+    hipLaunchKernelGGL(k, dim3((unsigned)nblocks), dim3(LSA_R16_THREADS), (size_t)LSA_R16_LDS_WORDS * sizeof(u64), s, a);
     LSA_HIP(hipGetLastError());
     return true;
 }
@@ -353,9 +305,8 @@ __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMA
 }
 
 bool ks_fused_enabled(const Context& c) {
-    const char* e = getenv("LSA_KS_FUSED");   // read per call: the parity tests flip it inside one process (a key uploaded either
-    const bool on = !(e && e[0] == '0');      // way works with either setting: the fused path needs key.fp and is skipped without it)
-    if (!on || c.plan.npass != 2 || !c.fp_raw) return false;
+    // (a key uploaded under either setting works with both: the fused path needs key.fp and is skipped without it)
+    if (!sw::ks_fused() || c.plan.npass != 2 || !c.fp_raw) return false;
     const NttPassShape& p = c.plan.pass[1];
     return p.tau == 12 && p.lambda == 0 && (p.mu == 7 || p.mu == 8 || p.mu == 9) && p.s_lo == c.logn - p.mu;
 }
@@ -364,11 +315,7 @@ int ks_fused_engines(const Context& c) {
     // integer-engine target limbs measured slower fused than apart (two lazy REDCs per product and digit, 256 VGPRs and still
     // spilling: 593 us against ~500 for pass + MAC on the headline's 5 integer limbs), FP64-engine limbs faster (643 us for 36
     // transforms + their MAC against ~1050): profiles/r03/ab_ks_fused_kernel_stats.log
-    static const int e = [] {
-        const char* v = getenv("LSA_KS_FUSED_ENGINES");
-        return v ? atoi(v) & 3 : 2;
-    }();
-    return c.fp64_ntt ? e : 0;
+    return c.fp64_ntt ? sw::ks_fused_engines() : 0;
 }
 
 bool ks_fused_limb(const Context& c, int L, int tl) { return (ks_fused_engines(c) >> (c.fp_engine(c.qp_mod(L, tl)) ? 1 : 0)) & 1; }
@@ -426,9 +373,8 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
         if (!g.n_tl) continue;
         const long long nblocks = (long long)batch * g.n_tl * (1 << (c.logn - 12));
         LSA_REQUIRE(nblocks < (1LL << 31), "ntt: grid too large");
-        const char* xcd_env = getenv("LSA_KSMAC_XCD");   // =0: plain batch-fastest order (A/B: +0.45 % headline with the deal, ab_ksmac_xcd_deal.log)
-        const bool xcd = !(xcd_env && xcd_env[0] == '0');
-        g.xcd_deal = xcd && ((g.n_tl << (c.logn - 12)) % 8 == 0) ? 1 : 0;
+        // LSA_KSMAC_XCD=0: plain batch-fastest order (A/B: +0.45 % headline with the deal, ab_ksmac_xcd_deal.log)
+        g.xcd_deal = sw::ksmac_xcd() && ((g.n_tl << (c.logn - 12)) % 8 == 0) ? 1 : 0;
         const double ntt_bytes = 16.0 * c.n * transforms * batch / 2;
         // (tensor fold: the own digit of a Q target reads a0, a1, b0, b1 instead of cx)
         const double fold_bytes = fold ? 3.0 * 8 * c.n * q_targets * batch : 0.0;
@@ -465,27 +411,16 @@ static void ntt_launch_variant(const NttPassArgs& a, long long nblocks, size_t l
 template <int NT>
 static void ntt_launch_pass(const NttPassArgs& a, bool fused, long long nblocks, size_t lds_bytes, hipStream_t s) {
     LSA_REQUIRE((1 << a.tau) <= 2 * LSA_NTT_STAGE_PAIRS * NT, "ntt: tile larger than the staging registers");
-    // which fused tail this pass can execute: the prologue lives in the pass that holds stage 0, the epilogue in the pass
-    // that reduces and stores the final values
-    const bool pro = fused && a.fz_pro && a.fz_first, epi = fused && a.fz_epi && a.final_reduce;
-    if (pro && a.fz_pro == 3) {   // the product prologue (FZ bit 16, no epilogue): only tiles of the two-pass shape take it
-        if constexpr (NT == LSA_NTT_THREADS) ntt_launch_variant<16, NT>(a, nblocks, lds_bytes, s);
-        else LSA_REQUIRE(false, "ntt: the product prologue needs a tile of at most 4096 points");
-        return;
-    }
-    if (epi && a.fz_epi == 3) {   // the pt_mul epilogue (FZ bit 4, no prologue)
-        ntt_launch_variant<4, NT>(a, nblocks, lds_bytes, s);
-        return;
-    }
-    if (epi && a.fz_epi == 4) {   // the rotate-and-MAC epilogue (FZ bit 8, no prologue)
-        ntt_launch_variant<8, NT>(a, nblocks, lds_bytes, s);
-        return;
-    }
-    switch ((pro ? 1 : 0) | (epi ? 2 : 0)) {
+    switch (ntt_pass_fz(a, fused)) {
         case 0: ntt_launch_variant<0, NT>(a, nblocks, lds_bytes, s); break;
         case 1: ntt_launch_variant<1, NT>(a, nblocks, lds_bytes, s); break;
         case 2: ntt_launch_variant<2, NT>(a, nblocks, lds_bytes, s); break;
-        default: ntt_launch_variant<3, NT>(a, nblocks, lds_bytes, s); break;
+        case 3: ntt_launch_variant<3, NT>(a, nblocks, lds_bytes, s); break;
+        case 4: ntt_launch_variant<4, NT>(a, nblocks, lds_bytes, s); break;
+        case 8: ntt_launch_variant<8, NT>(a, nblocks, lds_bytes, s); break;
+        default:   // 16, the product prologue: only tiles of the two-pass shape take it
+            if constexpr (NT == LSA_NTT_THREADS) ntt_launch_variant<16, NT>(a, nblocks, lds_bytes, s);
+            else LSA_REQUIRE(false, "ntt: the product prologue needs a tile of at most 4096 points");
     }
 }
 
@@ -1041,7 +976,7 @@ void launch_mac_plain_multi(Context& c, int nb, const u64* const* ct, const long
     LSA_REQUIRE(polys == 1 || polys == 2, "mac: one or two polynomials per ciphertext");
     const int pieces = limbs * (c.n / (2 * TPB));
     g.batch = batch;
-    g.xcd_map = (pieces % 8 == 0 && !std::getenv("LSA_MACM_NO_XCD")) ? 1 : 0;
+    g.xcd_map = (pieces % 8 == 0 && !sw::macm_no_xcd()) ? 1 : 0;
     LSA_REQUIRE(c.n >= 2 * TPB, "ring degree too small for the elementwise kernels (need N >= 512)");
     const dim3 grid((unsigned)(pieces * batch));
     if (polys == 2 && accumulate) hipLaunchKernelGGL((k_mac_plain_multi<2, true>), grid, dim3(TPB), 0, s, g);

@@ -41,12 +41,6 @@ std::vector<double> slots_to_coeffs(std::vector<cplx> v, const std::vector<int>&
     return out;
 }
 
-// LSA_LT_BLOCKED_MAC=0 (read per call): matrices beyond 8 x 8 baby / giant steps form their inner sums with one k_mac_plain
-// launch per giant step and 16 terms (the form before the blocked kernel; A/B and parity)
-bool blocked_mac_on() {
-    const char* e = std::getenv("LSA_LT_BLOCKED_MAC");
-    return !(e && e[0] == '0');
-}
 }  // namespace
 
 std::vector<int> rot_group(int n_slots) {
@@ -272,7 +266,7 @@ DCt LtEval::moddown(const DCt& a) {
 void LtEval::inner_sums(int nb, const u64* const* ct, long long sct, int ng, const u64* const* pt, u64* const* out, long long so,
                         int limbs, const RowMap& rm) {
     const bool one = nb <= LSA_MACM_MAX && ng <= LSA_MACM_MAX;
-    if (one || blocked_mac_on()) {
+    if (one || sw::lt_blocked_mac()) {
         for (int g0 = 0; g0 < ng; g0 += LSA_MACM_MAX) {
             const int gn = std::min(LSA_MACM_MAX, ng - g0);
             for (int b0 = 0; b0 < nb; b0 += LSA_MACM_MAX) {
@@ -417,7 +411,7 @@ DCt LtEval::linear_transform(const DCt& ct, const BtMatrix& mt, bool do_rescale)
         return do_rescale ? rescale(acc) : acc;
     }
     const bool fits = babies.size() <= LSA_MACM_MAX && by_giant.size() <= LSA_MACM_MAX;
-    if ((fits || blocked_mac_on()) && by_giant.size() > 1 && !std::getenv("LSA_BT_NO_MULTI_MAC")) {
+    if ((fits || sw::lt_blocked_mac()) && by_giant.size() > 1 && !sw::bt_no_multi_mac()) {
         // all inner sums together: every baby-step ciphertext is read once per block of giant steps, not once per giant step
         std::vector<int> bsteps;
         std::vector<const u64*> cp;
@@ -471,14 +465,9 @@ LinearTransform::~LinearTransform() {
 
 // Giant-step rotations of the public operator: the accumulating scatter of the key MAC (out[perm[x]] += mac(x) + P base(x))
 // or decompose + MAC (fused with the extension transform's second pass where the shape allows) + k_permute_ext.
-// LSA_ROT_SCATTER=0 selects the permutation form everywhere; LSA_LT_GIANT_SCATTER=0 / 1 (read per call) overrides the
-// default for the giant steps alone (A/B, parity).  Default: DESIGN.md 4.7.
-static bool lt_giant_scatter() {
-    if (const char* e = std::getenv("LSA_ROT_SCATTER"))
-        if (e[0] == '0') return false;
-    if (const char* e = std::getenv("LSA_LT_GIANT_SCATTER")) return e[0] != '0';
-    return false;
-}
+// LSA_ROT_SCATTER=0 selects the permutation form everywhere; LSA_LT_GIANT_SCATTER=0 / 1 overrides the default for the giant
+// steps alone (A/B, parity).  Default: DESIGN.md 4.7.
+static bool lt_giant_scatter() { return sw::rot_scatter() && sw::lt_giant_scatter(); }
 
 LinearTransform* lt_create(Context& c, int level, int log_slots, int n_diag, const int* diag_index, const double* values,
                            double pt_scale, double bsgs_ratio, bool double_hoist, hipStream_t s) {

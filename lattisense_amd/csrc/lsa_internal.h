@@ -11,6 +11,7 @@
 
 #include "../../include/lattisense_amd.h"
 #include "ntt_plan.h"
+#include "switches.h"
 #include "tables.h"
 
 namespace lsa {

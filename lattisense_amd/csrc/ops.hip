@@ -330,10 +330,6 @@ static void key_switch(Context& c, int level, const u64* cx, long long scx, cons
 // the automorphism X -> X^g of a rotation as the SCATTER map of the key switch's last store: out[i] = in[perm_g[i]] is
 // out[perm_{g^-1}[x]] = in[x] (the maps of g and g^-1 are inverse permutations).  Null when the store cannot take it
 // (unfused tails, LSA_ROT_SCATTER=0): the caller then permutes afterwards.
-static bool rotation_scatter_on() {   // read per call (not cached): the parity tests flip it inside one process
-    const char* e = std::getenv("LSA_ROT_SCATTER");
-    return !(e && e[0] == '0');
-}
 static const u32* inverse_perm(Context& c, u64 g) {
     const u64 mask = 2 * (u64)c.n - 1;
     u64 inv = g;   // Newton iteration for the inverse modulo a power of two: doubles the correct low bits each step
@@ -342,7 +338,7 @@ static const u32* inverse_perm(Context& c, u64 g) {
     return c.ntt_perm(inv);
 }
 static const u32* rotation_scatter(Context& c, u64 g) {
-    return rotation_scatter_on() && c.fuse_tails ? inverse_perm(c, g) : nullptr;
+    return sw::rot_scatter() && c.fuse_tails ? inverse_perm(c, g) : nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------ rescale
@@ -525,7 +521,7 @@ void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const
     if (n_rot <= 0) return;
     const long long N = c.n;
     const int L = level + 1;
-    const bool one_pass = rotation_scatter_on();   // the MAC writes the rotated extended ciphertext itself (LSA_ROT_SCATTER=0: MAC, then k_permute_ext)
+    const bool one_pass = sw::rot_scatter();   // the MAC writes the rotated extended ciphertext itself (LSA_ROT_SCATTER=0: MAC, then k_permute_ext)
     std::vector<const u32*> perms(n_rot);
     for (int i = 0; i < n_rot; i++) perms[i] = one_pass ? inverse_perm(c, g[i]) : c.ntt_perm(g[i]);
     for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
@@ -553,7 +549,7 @@ void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk
                      long long sin, long long sout, hipStream_t s, bool scatter_mac) {
     const long long N = c.n;
     const int L = level + 1;
-    if (scatter_mac && rotation_scatter_on()) {
+    if (scatter_mac && sw::rot_scatter()) {
         const u32* scatter = inverse_perm(c, g);
         for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
             const u64* ct = in + (size_t)b0 * sin;
@@ -599,17 +595,12 @@ void ckks_mult_relin_rescale(Context& c, int level, const u64* a, const u64* b, 
                              long long sa, long long sb, long long so, hipStream_t s) {
     ckks_mult_relin_rescale_rpp(c, level, a, b, rlk, out, batch, sa, sb, so, s, 0, 0);
 }
-// Tensor fold (fused tails; LSA_HMULT_FOLD=0 keeps the three steps apart, read per call: the parity tests flip it inside one
-// process).  d0, d1 and d2 = k_tensor's outputs are each read again by one consumer only, and each consumer can take them
+// Tensor fold (fused tails; LSA_HMULT_FOLD=0 keeps the three steps apart).  d0, d1 and d2 = k_tensor's outputs are each read again by one consumer only, and each consumer can take them
 // from a and b itself, residue for residue:
 //   ModUp input  d2 = a1 b1                   (formed by the load of the decomposition's inverse transform, never stored)
 //   MAC          own digit of Q target j: d2_j = a1_j b1_j, and acc'_j = acc_j + P * d_j  (d = (d0, d1), TensorFold)
 //   ModDown      (acc'_j * P^-1 - NTT(in)) * q_l^-1 = (acc_j * P^-1 - NTT(in) + d_j) * q_l^-1;
 //                INTT(acc'_l) * P^-1 = INTT(acc_l) * P^-1 + INTT(d_l)       (the merged tail with base_polys = 0)
-static bool hmult_fold_on() {
-    const char* e = std::getenv("LSA_HMULT_FOLD");
-    return !(e && e[0] == '0');
-}
 
 // a_rpp / b_rpp: rows per polynomial of a / b when an operand sits at a higher level than `level` (0: level + 1) -- its leading
 // rows ARE the operand at this level, so callers with operands at mixed levels (polynomial evaluation) need no copies
@@ -618,7 +609,7 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
     LSA_REQUIRE(level >= 1, "mult+relin+rescale needs level >= 1");
     const long long N = c.n;
     const int L = level + 1;
-    const bool fold = c.fuse_tails && hmult_fold_on();
+    const bool fold = c.fuse_tails && sw::hmult_fold();
     const size_t r_d3 = (fold ? 0 : 3) * (size_t)L, r_r2 = 2 * (size_t)L;
     const size_t r_shared = std::max(KsTile::rows(c, level), rescale_ws_rows(level, 2));
     const long long sd = (long long)r_d3 * N, sr = 2LL * L * N;
@@ -692,8 +683,7 @@ void bfv_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int ba
     // folded (default; LSA_BFV_FOLD=0: the separate element-wise steps): the Q limbs are transformed straight from the operands into
     // the extended buffer (no copy), and the two element-wise steps around the last conversion -- (aux - ext) * Q^-1 before it,
     // * t after it -- live in its source load and its constants (Context::BaseConvFold)
-    const char* fold_env = std::getenv("LSA_BFV_FOLD");   // read per call: the parity tests flip it inside one process
-    const bool fold_on = !(fold_env && fold_env[0] == '0');
+    const bool fold_on = sw::bfv_fold();
     const BaseConvPlan* kQA = c.baseconv(qmods, amods, true);
     const BaseConvPlan* kAQ = c.baseconv(amods, qmods, true);
     BaseConvRows rQA{}, rAQ{};
@@ -828,7 +818,7 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
     const long long sp = 2LL * L * N;
     // the one-pass tail stages a limb in LDS (N <= 2^14); larger rings keep the two steps, which measured faster than gathering
     // from global memory
-    const bool gather_on = rotation_scatter_on() && c.fuse_tails && c.logn <= LSA_PERM_LDS_MAX_LOGN;
+    const bool gather_on = sw::rot_scatter() && c.fuse_tails && c.logn <= LSA_PERM_LDS_MAX_LOGN;
     std::vector<const u32*> perms(n_rot);
     std::vector<bool> direct(n_rot);
     std::vector<int> order;   // an output that overlaps the input goes last: every other rotation still reads the intact c0
@@ -871,13 +861,9 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
 // ---- BFV ct x pt_mul.  A pt_mul plaintext is the message lifted to Q, in the NTT domain and in Montgomery form (the
 // reference frontend's BfvPlaintextMulNode); per poly and limb ct x pt = INTT(NTT(ct) . pt . 2^-64 mod q), Lattigo v4's
 // mulPlaintextMul.  The Montgomery product rides on the store of the forward transform's last pass (fz_epi = 3, FZ bit 4);
-// LSA_PTMUL_FUSED=0 (read per call) runs the forward transform, k_mont_muladd and the inverse transform instead.  A MAC sums
+// LSA_PTMUL_FUSED=0 runs the forward transform, k_mont_muladd and the inverse transform instead.  A MAC sums
 // its terms in the NTT domain (canonical residues: the same values as a per-term multiply and adds) and runs one inverse
 // transform per output; the partial sum is added after it, in the coefficient domain.
-static bool ptmul_fused_on() {
-    const char* e = std::getenv("LSA_PTMUL_FUSED");
-    return !(e && e[0] == '0');
-}
 static bool spans_apart(const u64* a, long long sa, size_t wa, const u64* b, long long sb, size_t wb, int batch) {
     const u64* ea = a + (size_t)(batch - 1) * sa + wa;
     const u64* eb = b + (size_t)(batch - 1) * sb + wb;
@@ -888,7 +874,7 @@ static bool spans_apart(const u64* a, long long sa, size_t wa, const u64* b, lon
 static void ptmul_term(Context& c, int L, const u64* ct, long long sct, const u64* pt, long long spt, bool acc, u64* out,
                        long long so, u64* tmp, long long stmp, int nb, hipStream_t s) {
     const RowMap rm = rm_seq(L);
-    if (ptmul_fused_on()) {
+    if (sw::ptmul_fused()) {
         NttFusion fz;
         fz.epi = 3;
         fz.limbs = L;
@@ -957,13 +943,8 @@ void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, cons
 // rotated ciphertext is never written.  Per tile: NTT(c0) and NTT(c1) once, one decomposition; identity terms (g = 1) are
 // a Montgomery product of NTT(ct); a rotation term is its key MAC and a ModDown whose last store applies the automorphism,
 // the pt_mul product and the running sum (fz_epi = 4).  One inverse transform per output, then the partial sum.
-// LSA_ROTMAC_FUSED=0 (read per call), unfused tails and LSA_ROT_SCATTER=0 run each rotation term in two steps instead:
+// LSA_ROTMAC_FUSED=0, unfused tails and LSA_ROT_SCATTER=0 run each rotation term in two steps instead:
 // the NTT-domain ModDown into the workspace (scattered, or k_permute after it), then k_mont_muladd.
-static bool rotmac_fused_on() {
-    const char* e = std::getenv("LSA_ROTMAC_FUSED");
-    return !(e && e[0] == '0');
-}
-
 void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const u64* g, const Key* const* glk,
                               const u64* const* pts, const long long* spts, const u64* partial, long long spartial, u64* out,
                               int batch, long long sin, long long sout, hipStream_t s) {
@@ -988,7 +969,7 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
         LSA_REQUIRE(spans_apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_rotate_mac_plain_mul: out overlaps a plaintext");
     LSA_REQUIRE(!partial || spans_apart(out, sout, wct, partial, spartial, wct, batch),
                 "bfv_rotate_mac_plain_mul: out overlaps the partial sum");
-    const bool fused = rotmac_fused_on() && c.fuse_tails && rotation_scatter_on();
+    const bool fused = sw::rotmac_fused() && c.fuse_tails && sw::rot_scatter();
     std::vector<const u32*> scatters(n, nullptr), perms(n, nullptr);
     for (int i = 0; i < n; i++) {
         if (g[i] == 1) continue;

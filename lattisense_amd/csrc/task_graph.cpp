@@ -2,6 +2,7 @@
 // Behaviour follows mega_ag_runners/mega_ag.cpp:125-657 (see task_graph.h); written for this runtime's level-batched
 // scheduler (top_level drives execution order, bottom_level is kept as the reference's priority).
 #include "task_graph.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -68,7 +69,7 @@ TaskGraph TaskGraph::load_for_gpu(const std::string& json_path) {
     TaskGraph g;
     g.parse(json_path);
     g.validate_structure();
-    if (!getenv("LSA_NO_GRAPH_FUSION")) {
+    if (!lsa::sw::no_graph_fusion()) {
         g.fuse_accumulations();
         g.fuse_mult_relin_rescale();
         g.fuse_rotate_mac();

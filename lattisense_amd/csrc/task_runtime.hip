@@ -109,10 +109,6 @@ void hip_buf_release(void* p, int device, bool pinned) {
     else (void)hipFree(p);
     if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
 }
-size_t pool_cap_bytes(const char* env, double default_gib) {
-    const char* v = getenv(env);
-    return (size_t)((v ? atof(v) : default_gib) * 1073741824.0);
-}
 
 struct Slab {
     u64* ptr = nullptr;
@@ -193,9 +189,7 @@ class StagePool {
   private:
     StagePool() {
         const int hw = (int)std::thread::hardware_concurrency();
-        int nthreads = std::max(1, std::min(16, hw > 0 ? hw : 1) - 2);
-        if (const char* e = std::getenv("LSA_STAGE_THREADS")) nthreads = std::max(1, std::atoi(e));
-        nthreads = std::min(nthreads, 32);
+        const int nthreads = std::min(sw::stage_threads(std::max(1, std::min(16, hw > 0 ? hw : 1) - 2)), 32);
         for (int t = 1; t < nthreads; t++) workers_.emplace_back([this] { loop(); });
     }
     void work(const std::function<void(size_t)>& f, size_t n) {
@@ -373,8 +367,8 @@ struct fhe_task_handle_st {
     // A released device buffer only returns to ITS lane's pool, so reuse stays ordered by that lane's in-order stream.
     // Pools are keyed by (device, lane): one task handle may be run on any device, one run() at a time (the reference's
     // multi-GPU mode, README.md:195-202 / gpu_wrapper.cu:148-149); run() calls on one handle are serialised by run_mu.
-    LanePools pools{BufAllocator{hip_buf_alloc, hip_buf_release}, pool_cap_bytes("LSA_POOL_MAX_DEV_GIB", 48.0),
-                    pool_cap_bytes("LSA_POOL_MAX_PIN_GIB", 16.0)};   // declared first: destroyed last
+    LanePools pools{BufAllocator{hip_buf_alloc, hip_buf_release}, (size_t)(sw::pool_max_dev_gib() * 1073741824.0),
+                    (size_t)(sw::pool_max_pin_gib() * 1073741824.0)};   // declared first: destroyed last
     std::mutex run_mu;
     std::shared_ptr<Slab> dslab(size_t words) { return std::make_shared<Slab>(pools.device_pool(tls_exec.device, tls_exec.lane), words); }
     std::shared_ptr<Slab> pslab(size_t words) { return std::make_shared<Slab>(pools.pinned_pool(tls_exec.device), words); }
@@ -391,7 +385,7 @@ struct fhe_task_handle_st {
         KeyP key;
     };
     std::map<std::pair<int, NodeIndex>, CachedKey> key_cache;   // touched by the thread that runs the shared levels / the fan-out only
-    bool keep_keys = getenv("LSA_NO_KEY_CACHE") == nullptr;
+    bool keep_keys = !sw::no_key_cache();
     int last_key_uploads = 0, last_key_hits = 0;
     static uint64_t ksk_fingerprint(const CKeySwitchKey* k, int n) {
         uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)k->n_public_key;
@@ -474,7 +468,7 @@ struct fhe_task_handle_st {
         for (auto& kv : g.computes) levels[kv.second.sched_meta.top_level].push_back(&kv.second);
         for (auto& lv : levels)
             std::sort(lv.begin(), lv.end(), [](const ComputeNode* a, const ComputeNode* b) { return a->index < b->index; });
-        if (!getenv("LSA_NO_PIPELINE")) plan_pipeline(1);
+        if (!sw::no_pipeline()) plan_pipeline(1);
     }
 
     // Independent subgraphs = connected components of the compute nodes over the non-key data (evaluation keys are shared
@@ -531,8 +525,7 @@ struct fhe_task_handle_st {
             const bool ringt = d.fhe_prop->p && d.fhe_prop->p->is_ringt;
             in_bytes += 8.0 * n_ring * (d.datum_type == TYPE_CIPHERTEXT ? d.fhe_prop->degree + 1 : 1) * (ringt ? 1 : d.fhe_prop->level + 1);
         }
-        const char* min_mib = getenv("LSA_PIPELINE_MIN_MIB");   // tests force the pipelined path on small graphs with 0
-        if (in_bytes < (min_mib ? atof(min_mib) : 256.0) * 1048576.0) return;
+        if (in_bytes < sw::pipeline_min_mib() * 1048576.0) return;   // (tests force the pipelined path on small graphs with 0)
         const int nchunks = plan_chunk_count(comps.size(), n_shards);
         std::unordered_map<const ComputeNode*, int> chunk_of;
         int ci = 0;
@@ -1411,7 +1404,7 @@ struct fhe_task_handle_st {
         std::lock_guard<std::mutex> run_lock(run_mu);   // one run at a time per handle (the graph state is shared)
         const auto t_start = std::chrono::steady_clock::now();
         const std::vector<int> devs = run_devices(device);
-        if (!getenv("LSA_NO_PIPELINE") && planned_shards_ != (int)devs.size()) plan_pipeline((int)devs.size());   // chunk count follows the shard count
+        if (!sw::no_pipeline() && planned_shards_ != (int)devs.size()) plan_pipeline((int)devs.size());   // chunk count follows the shard count
         // shards: one device + two lanes each; chunks of independent subgraphs are dealt out to them (shard_plan.h)
         const ShardPlan plan = plan_shards(chunk_levels.empty() ? std::vector<int>{devs[0]} : devs, (int)chunk_levels.size());
         const int up_dev = plan.upload_device();
@@ -1479,7 +1472,7 @@ struct fhe_task_handle_st {
         last_key_peer_copies = 0;
         last_key_uploads = last_key_hits = 0;
 
-        const bool trace = getenv("LSA_TASK_TRACE") != nullptr;
+        const bool trace = sw::task_trace();
         auto tick = [&]() { return std::chrono::steady_clock::now(); };
         auto ms_since = [&](std::chrono::steady_clock::time_point t0) {
             return std::chrono::duration<double, std::milli>(tick() - t0).count();

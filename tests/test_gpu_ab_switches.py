@@ -1,5 +1,7 @@
 """The run-time A/B switches that select an older form of an operator must not change a single
-residue: every form is compared with the CPU oracle on the same inputs, in one process (the switches are read per call)."""
+residue: every form is compared with the CPU oracle on the same inputs, in one process.  That works for the switches flipped
+here -- LSA_ROT_SCATTER, LSA_KSMAC_XCD, LSA_KS_FUSED and LSA_BFV_FOLD have the CALL lifetime (read at every operator call);
+a PROCESS switch (LSA_NTT_R16, LSA_KS_FUSED_ENGINES, ...) only changes in a fresh child process."""
 import numpy as np
 import pytest
 

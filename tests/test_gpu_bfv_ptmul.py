@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from lattisense_amd import params
-from tests.gpu_util import need_gpu, rand_ct
+from tests.gpu_util import env, need_gpu, rand_ct
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,21 +39,6 @@ def _want_mac(o, L, cts, pts, partial=None):
 
 def _rand_pt(rng, mods, n, batch):
     return rand_ct(rng, mods, 1, n, batch)[:, 0]
-
-
-class _Env:
-    def __init__(self, key, value):
-        self.key, self.value, self.old = key, value, None
-
-    def __enter__(self):
-        self.old = os.environ.get(self.key)
-        os.environ[self.key] = self.value
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop(self.key, None)
-        else:
-            os.environ[self.key] = self.old
 
 
 def _ctx(n, q, p, t):
@@ -98,7 +83,7 @@ def test_n4096_fp64_engine_terms_and_switches(fused):
     ctx, o = _ctx(4096, P["q"], P["p"], P["t"])
     rng = np.random.default_rng(4096 + int(fused))
     try:
-        with _Env("LSA_PTMUL_FUSED", fused):
+        with env(LSA_PTMUL_FUSED=fused):
             for fp64 in (1, 0):
                 ctx.set_fp64_ntt(fp64)
                 for tile in (0, 1):
@@ -117,7 +102,7 @@ def test_default_chains_every_level(n, fused):
     ctx, o = _ctx(n, P["q"], P["p"], P["t"])
     rng = np.random.default_rng(n + int(fused))
     try:
-        with _Env("LSA_PTMUL_FUSED", fused):
+        with env(LSA_PTMUL_FUSED=fused):
             for lvl in range(len(P["q"])):
                 _check_level(ctx, o, lvl, 2, rng, terms=(2,))
             top = len(P["q"]) - 1
@@ -136,7 +121,7 @@ def test_n16_chain_full_ring():
     rng = np.random.default_rng(65536)
     try:
         for fused in ("1", "0"):
-            with _Env("LSA_PTMUL_FUSED", fused):
+            with env(LSA_PTMUL_FUSED=fused):
                 _check_level(ctx, o, len(C["q"]) - 1, 1, rng, terms=(4,))
     finally:
         ctx.close()
@@ -157,7 +142,7 @@ def test_fused_equals_unfused_and_batch_position_independent():
         Pt = np.stack([pt] * batch)
         res = {}
         for fused in ("1", "0"):
-            with _Env("LSA_PTMUL_FUSED", fused):
+            with env(LSA_PTMUL_FUSED=fused):
                 res[fused] = ctx.download(ctx.bfv_mult_plain_mul(lvl, ctx.upload(A), ctx.upload(Pt), batch), (batch, 2, L, n))
                 mac = ctx.download(ctx.bfv_mac_plain_mul(lvl, [ctx.upload(A)] * 3, [ctx.upload(Pt)] * 3, batch), (batch, 2, L, n))
                 for b in range(batch):
@@ -193,7 +178,7 @@ def test_decrypts_to_product():
         cts = [c.bfv_encrypt(m, lvl) for m in m1]
         pts = [pt_mul(m) for m in m2]
         for fused in ("1", "0"):
-            with _Env("LSA_PTMUL_FUSED", fused):
+            with env(LSA_PTMUL_FUSED=fused):
                 got = ctx.download(ctx.bfv_mult_plain_mul(lvl, ctx.upload(cts[0][None]), ctx.upload(pts[0][None]), 1), (1, 2, L, n))[0]
                 assert np.array_equal(c.bfv_decrypt(got), m1[0] * m2[0] % tm), fused
                 part = c.bfv_encrypt(mp, lvl)
@@ -228,7 +213,7 @@ def test_task_fixtures(fused):
     bfv_n16384_cmpac_mul20 (20 terms: 16-term cmp_sum + 4-term cmpac_sum) through FheTaskGpu"""
     need_gpu()
     from lattisense_amd.task import Argument, Ciphertext, Plaintext
-    with _Env("LSA_PTMUL_FUSED", fused):
+    with env(LSA_PTMUL_FUSED=fused):
         g, P, o, c = _load("bfv_n4096_cmp_mul")
         n, lvl = P["n"], 2
         L = lvl + 1

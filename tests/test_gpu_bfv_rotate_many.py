@@ -4,14 +4,13 @@ CPU oracle, under every switch that changes the path (LSA_ROT_SCATTER, fused tai
 input; at the full N = 2^16 ring; at message level (decrypt == the rotated vector, unittests/test_gpu_bfv.cpp:493-528); and
 through the task runtime on the reference's BFV_4_advanced_rotate_col graphs, which now run as ONE hoisted batch."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 from lattisense_amd import params
 from tests import ref_suite as rs
-from tests.gpu_util import need_gpu, rand_ct
+from tests.gpu_util import env, need_gpu, rand_ct
 
 pytestmark = pytest.mark.gpu
 
@@ -64,30 +63,25 @@ def test_operator_parity_every_path(n14):
     for g in els:
         refs[g] = ctx.download(ctx.bfv_rotate(lvl, da, g, keys[g], batch), shape)
         assert np.array_equal(refs[g][1], o.bfv_rotate(lvl, A[1], g, raw[g], klvl)), g
-    old = os.environ.get("LSA_ROT_SCATTER")
     try:
         for scatter in ("1", "0"):
-            os.environ["LSA_ROT_SCATTER"] = scatter
-            for fuse in (1, 0):
-                check(lib().lsa_set_fuse_tails(ctx.h, fuse))
-                for tile in (0, 1, 3):
-                    ctx.set_tile_batch(tile)
-                    outs = ctx.bfv_rotate_many(lvl, da, keys, batch)
-                    for g in els:
-                        assert np.array_equal(ctx.download(outs[g], shape), refs[g]), (scatter, fuse, tile, g)
-                    # an output that IS the input (the first one: the others must still see the intact ciphertext)
-                    alias = ctx.upload(A)
-                    others = [ctx.alloc(batch * 2 * L * n) for _ in els[1:]]
-                    check(_rotate_many_raw(ctx, lvl, alias.ptr, els, [keys[g] for g in els], [alias.ptr] + [b.ptr for b in others],
-                                           batch))
-                    assert np.array_equal(ctx.download(alias, shape), refs[els[0]]), (scatter, fuse, tile)
-                    for g, b in zip(els[1:], others):
-                        assert np.array_equal(ctx.download(b, shape), refs[g]), (scatter, fuse, tile, g)
+            with env(LSA_ROT_SCATTER=scatter):
+                for fuse in (1, 0):
+                    check(lib().lsa_set_fuse_tails(ctx.h, fuse))
+                    for tile in (0, 1, 3):
+                        ctx.set_tile_batch(tile)
+                        outs = ctx.bfv_rotate_many(lvl, da, keys, batch)
+                        for g in els:
+                            assert np.array_equal(ctx.download(outs[g], shape), refs[g]), (scatter, fuse, tile, g)
+                        # an output that IS the input (the first one: the others must still see the intact ciphertext)
+                        alias = ctx.upload(A)
+                        others = [ctx.alloc(batch * 2 * L * n) for _ in els[1:]]
+                        check(_rotate_many_raw(ctx, lvl, alias.ptr, els, [keys[g] for g in els], [alias.ptr] + [b.ptr for b in others],
+                                               batch))
+                        assert np.array_equal(ctx.download(alias, shape), refs[els[0]]), (scatter, fuse, tile)
+                        for g, b in zip(els[1:], others):
+                            assert np.array_equal(ctx.download(b, shape), refs[g]), (scatter, fuse, tile, g)
     finally:
-        if old is None:
-            os.environ.pop("LSA_ROT_SCATTER", None)
-        else:
-            os.environ["LSA_ROT_SCATTER"] = old
         check(lib().lsa_set_fuse_tails(ctx.h, 1))
         ctx.set_tile_batch(0)
     # one element: the same as bfv_rotate

@@ -12,26 +12,9 @@ import numpy as np
 import pytest
 
 from lattisense_amd import params
-from tests.gpu_util import need_gpu, rand_ct
+from tests.gpu_util import env, need_gpu, rand_ct
 
 pytestmark = pytest.mark.gpu
-
-
-class _Env:
-    def __init__(self, **kv):
-        self.kv, self.old = kv, {}
-
-    def __enter__(self):
-        for k, v in self.kv.items():
-            self.old[k] = os.environ.get(k)
-            os.environ[k] = v
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _minv(q):
@@ -129,7 +112,7 @@ def test_n4096_fp64_engine(form):
     els = _els(4096, [1, 3, -7])
     r = _Ring(4096, P["q"], P["p"], P["t"], els, 4096 + int(form))
     try:
-        with _Env(LSA_ROTMAC_FUSED=form):
+        with env(LSA_ROTMAC_FUSED=form):
             for fp64 in (1, 0):
                 r.ctx.set_fp64_ntt(fp64)
                 for tile in (0, 1):
@@ -174,7 +157,7 @@ def test_n14_switches(n14):
     try:
         for form in ("1", "0"):
             for scatter in ("1", "0"):
-                with _Env(LSA_ROTMAC_FUSED=form, LSA_ROT_SCATTER=scatter):
+                with env(LSA_ROTMAC_FUSED=form, LSA_ROT_SCATTER=scatter):
                     for fuse in (1, 0):
                         check(lib().lsa_set_fuse_tails(r.ctx.h, fuse))
                         for tile in (0, 1):
@@ -211,7 +194,7 @@ def test_n14_batch_position_independent(n14):
     terms = [els[2], 1, els[4]]
     res = {}
     for form in ("1", "0"):
-        with _Env(LSA_ROTMAC_FUSED=form):
+        with env(LSA_ROTMAC_FUSED=form):
             res[form] = r.fused(lvl, da, terms, dps, batch, None)
             for b in range(batch):
                 assert np.array_equal(res[form][b], res[form][0]), (form, b)
@@ -267,7 +250,7 @@ def test_n15_full_ring():
     r = _Ring(32768, P["q"], P["p"], P["t"], els, 32768)
     try:
         for form in ("1", "0"):
-            with _Env(LSA_ROTMAC_FUSED=form):
+            with env(LSA_ROTMAC_FUSED=form):
                 r.rng = np.random.default_rng(15)
                 r.check(len(P["q"]) - 1, [1] + els, batch=1, tag=(form,))
     finally:
@@ -282,7 +265,7 @@ def test_n16_chain_full_ring():
     r = _Ring(C["n"], C["q"], C["p"], C["t"], els, 65536)
     try:
         for form in ("1", "0"):
-            with _Env(LSA_ROTMAC_FUSED=form):
+            with env(LSA_ROTMAC_FUSED=form):
                 r.check(len(C["q"]) - 1, els + [1], batch=1, tag=(form,))
     finally:
         r.close()
@@ -329,7 +312,7 @@ def test_decrypts_to_rotated_dot_product():
                 r = np.concatenate([np.roll(x[:h], -s), np.roll(x[h:], -s)])
             exp = (exp + r * m % tm) % tm
         for form in ("1", "0"):
-            with _Env(LSA_ROTMAC_FUSED=form):
+            with env(LSA_ROTMAC_FUSED=form):
                 terms = [(g, keys.get(g), ctx.upload(pt_mul(m)[None])) for g, m in zip(els, ms)]
                 out = ctx.bfv_rotate_mac_plain_mul(lvl, ctx.upload(A), terms, 1, partial=ctx.upload(part))
                 got = ctx.download(out, (1, 2, L, n))[0]
@@ -416,12 +399,12 @@ def test_runtime_fixtures(name):
     for k, (a, b) in enumerate(zip(got, want)):
         assert np.array_equal(a, b), (name, k)
     assert st["gpu_batches"] == fused, (name, st)
-    with _Env(LSA_NO_GRAPH_FUSION="1"):
+    with env(LSA_NO_GRAPH_FUSION="1"):
         got2, _, st2 = _run_fixture(name, 7)
     for a, b in zip(got, got2):
         assert np.array_equal(a, b), name
     assert st2["gpu_batches"] == plain, (name, st2)
-    with _Env(LSA_ROTMAC_FUSED="0"):
+    with env(LSA_ROTMAC_FUSED="0"):
         got3, _, _ = _run_fixture(name, 7)
     for a, b in zip(got, got3):
         assert np.array_equal(a, b), name
@@ -444,7 +427,7 @@ def test_n14_plaintext_stride_zero(n14):
     one = [ctx.upload(p) for p in pts]
     out = ctx.alloc(batch * s)
     for form in ("1", "0"):
-        with _Env(LSA_ROTMAC_FUSED=form):
+        with env(LSA_ROTMAC_FUSED=form):
             check(lib().lsa_bfv_rotate_mac_plain_mul(ctx.h, lvl, da.ptr, 2, (ctypes.c_uint64 * 2)(*terms),
                                                      (ctypes.c_void_p * 2)(None, r.keys[els[1]].value),
                                                      (ctypes.c_void_p * 2)(*[p.ptr for p in one]), (ctypes.c_longlong * 2)(0, 0),

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from lattisense_amd import params
-from tests.gpu_util import need_gpu, rand_ct
+from tests.gpu_util import env, need_gpu, rand_ct
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,24 +36,17 @@ def _boundary_run(q, p, t, levels, seed):
     klvl = len(q) - 1
     key = _rand_key(rng, q, p, klvl, n)
     k = ctx.upload_key(key, klvl)
-    old = os.environ.get("LSA_BFV_FOLD")
-    try:
-        for lvl in levels:
-            A, Bc = rand_ct(rng, q[: lvl + 1], 2, n, 2), rand_ct(rng, q[: lvl + 1], 2, n, 2)
-            want = np.stack([o.bfv_mult_relin(lvl, A[i], Bc[i], key, klvl) for i in range(2)])
-            da, db = ctx.upload(A), ctx.upload(Bc)
-            for fold in ("1", "0"):
-                os.environ["LSA_BFV_FOLD"] = fold
+    for lvl in levels:
+        A, Bc = rand_ct(rng, q[: lvl + 1], 2, n, 2), rand_ct(rng, q[: lvl + 1], 2, n, 2)
+        want = np.stack([o.bfv_mult_relin(lvl, A[i], Bc[i], key, klvl) for i in range(2)])
+        da, db = ctx.upload(A), ctx.upload(Bc)
+        for fold in ("1", "0"):
+            with env(LSA_BFV_FOLD=fold):
                 for tb in (0, 1):
                     ctx.set_tile_batch(tb)
                     out = ctx.bfv_mult_relin(lvl, da, db, k, 2)
                     assert np.array_equal(ctx.download(out, want.shape), want), (lvl, fold, tb)
-            ctx.set_tile_batch(0)
-    finally:
-        if old is None:
-            os.environ.pop("LSA_BFV_FOLD", None)
-        else:
-            os.environ["LSA_BFV_FOLD"] = old
+        ctx.set_tile_batch(0)
     ctx.destroy_key(k)
     ctx.close()
 

@@ -25,30 +25,12 @@ import pytest
 
 from lattisense_amd import params
 from tests.boundary import ORDERS, PATTERNS, fp_engine, head_flags, pattern_ct, pattern_key, primes_above, straddle_chain
-from tests.gpu_util import need_gpu
+from tests.gpu_util import env, need_gpu
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMBOS = [(p, dom) for dom in (0, 1) for p in PATTERNS]   # dom 1: the pattern is the coefficient-domain content
 KEY_PATTERN = {"ascending": "max", "descending": "top", "interleaved": "half"}
-
-
-class _Env:
-    def __init__(self, key, value):
-        self.key, self.value, self.old = key, value, None
-
-    def __enter__(self):
-        self.old = os.environ.get(self.key)
-        if self.value is None:
-            os.environ.pop(self.key, None)
-        else:
-            os.environ[self.key] = self.value
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop(self.key, None)
-        else:
-            os.environ[self.key] = self.old
 
 
 def _combo_ct(o, mods, n, rng, first, batch=3):
@@ -175,7 +157,7 @@ def _ckks_levels(n, order, levels, seed, np_=3, tiles=(1, 2)):
                     for fold in ("1", "0"):
                         for tile in (0,) + (tiles if tails else ()):
                             ctx.set_tile_batch(tile)
-                            with _Env("LSA_HMULT_FOLD", None if fold == "1" else "0"):
+                            with env(LSA_HMULT_FOLD=None if fold == "1" else "0"):
                                 got = ctx.download(ctx.ckks_mult_relin_rescale(lvl, da, db, k, 3), want.shape)
                             assert np.array_equal(got, want), tag + ("fold=" + fold, tile, np.argwhere((got != want).any(axis=-1))[:8])
                         ctx.set_tile_batch(0)
@@ -228,7 +210,7 @@ def test_ckks_rotate_rotate_many_conjugate(logn, order):
                 da = ctx.upload(A)
                 want = {g: np.stack([o.ckks_rotate(lvl, A[b], g, keys[g], klvl) for b in range(3)]) for g in gs}
                 for scatter in (None, "0"):
-                    with _Env("LSA_ROT_SCATTER", scatter):
+                    with env(LSA_ROT_SCATTER=scatter):
                         for g in gs:
                             got = ctx.download(ctx.ckks_rotate(lvl, da, g, hk[g], 3), want[g].shape)
                             assert np.array_equal(got, want[g]), (order, lvl, fp64, scatter, g)
@@ -269,7 +251,7 @@ def _digit_edges(n, cases, seed):
                 beta, T = (L + np_ - 1) // np_, L + np_
                 assert ctx.key_switch_fused(lvl, k) == (beta * T <= 192), (np_, L, "fused key MAC expected up to beta T = 192")
                 assert (np_, L) not in FUSED_EXPECTED or ctx.key_switch_fused(lvl, k) == FUSED_EXPECTED[(np_, L)], (np_, L)
-                with _Env("LSA_KS_FUSED", "0"):
+                with env(LSA_KS_FUSED="0"):
                     assert not ctx.key_switch_fused(lvl, k), (np_, L, "LSA_KS_FUSED=0 must take the unfused path")
                 A = _combo_ct(o, mods, n, rng, L)
                 B = _combo_ct(o, mods, n, rng, L + 9)
@@ -278,7 +260,7 @@ def _digit_edges(n, cases, seed):
                 g = int(pow(5, 77, 2 * n))
                 outs = {}
                 for fused in (None, "0"):
-                    with _Env("LSA_KS_FUSED", fused):
+                    with env(LSA_KS_FUSED=fused):
                         outs[fused] = (ctx.download(ctx.ckks_mult_relin_rescale(lvl, da, db, k, 3), (3, 2, lvl, n)),
                                        ctx.download(ctx.ckks_rotate(lvl, da, g, k, 3), (3, 2, L, n)))
                 assert np.array_equal(outs[None][0], outs["0"][0]), (np_, L, "hmult fused != unfused")
@@ -411,7 +393,7 @@ def test_bfv_operators(logn, chain, monkeypatch):
             dp = [ctx.upload(x) for x in pts]
             tag = (chain, logn, no_split)
             for fold in (None, "0"):
-                with _Env("LSA_BFV_FOLD", fold):
+                with env(LSA_BFV_FOLD=fold):
                     got = ctx.download(ctx.bfv_mult_relin(lvl, da, db, k, 3), want_mul.shape)
                 assert np.array_equal(got, want_mul), tag + ("mult_relin", fold)
             outs = ctx.bfv_rotate_many(lvl, da, hk, 3)
@@ -421,7 +403,7 @@ def test_bfv_operators(logn, chain, monkeypatch):
             got = ctx.download(ctx.bfv_mac_plain_mul(lvl, [da, db], dp, 3), want_mac.shape)
             assert np.array_equal(got, want_mac), tag + ("pt_mul MAC",)
             for fused in (None, "0"):
-                with _Env("LSA_ROTMAC_FUSED", fused):
+                with env(LSA_ROTMAC_FUSED=fused):
                     got = ctx.download(ctx.bfv_rotate_mac_plain_mul(lvl, da, [(g, hk[g], dp[i]) for i, g in enumerate(gs)], 3), want_rmac.shape)
                 assert np.array_equal(got, want_rmac), tag + ("rotate-and-MAC", fused)
             # which conversions ran split: ModUp digits and ModDown have at most np sources and stay inside Q u P; the
@@ -454,7 +436,7 @@ def test_bfv_conversion_with_16_and_17_sources_on_58_bit_primes(nq):
     B = pattern_ct(("max", "alt", "uniform"), q, 2, n, rng)
     want = np.stack([o.bfv_mult_relin(lvl, A[b], B[b], key, klvl) for b in range(3)])
     for no_split in (None, "1"):
-        with _Env("LSA_BC_NO_SPLIT", no_split):
+        with env(LSA_BC_NO_SPLIT=no_split):
             ctx = DeviceContext(ALGO_BFV, n, q, p, t)
             try:
                 k = ctx.upload_key(key, klvl)
@@ -493,7 +475,7 @@ def test_split_accumulate_with_8_and_16_terms(np_):
     want_rot = np.stack([oc.ckks_rotate(lvl, A[b], g, key, klvl) for b in range(3)])
     want_bfv = np.stack([ob.bfv_mult_relin(lvl, A[b], B[b], key, klvl) for b in range(3)])
     for no_split in (None, "1"):
-        with _Env("LSA_BC_NO_SPLIT", no_split):
+        with env(LSA_BC_NO_SPLIT=no_split):
             ctx = DeviceContext(ALGO_CKKS, n, q, p)
             try:
                 k = ctx.upload_key(key, klvl)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from lattisense_amd import params
-from tests.gpu_util import need_gpu
+from tests.gpu_util import env, need_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -25,24 +25,10 @@ def _rand(rng, mods, shape, n):
     return out
 
 
-def _set_fold(on):
-    if on:
-        os.environ.pop("LSA_HMULT_FOLD", None)
-    else:
-        os.environ["LSA_HMULT_FOLD"] = "0"
-
-
 def _hmult(ctx, lvl, da, db, k, batch, fold):
-    old = os.environ.get("LSA_HMULT_FOLD")
-    try:
-        _set_fold(fold)
+    with env(LSA_HMULT_FOLD=None if fold else "0"):
         out = ctx.ckks_mult_relin_rescale(lvl, da, db, k, batch)
         return ctx.download(out, (batch, 2, lvl, ctx.n))
-    finally:
-        if old is None:
-            os.environ.pop("LSA_HMULT_FOLD", None)
-        else:
-            os.environ["LSA_HMULT_FOLD"] = old
 
 
 def _fold_vs_old(n, q, p, levels, klvl, batch, seed, square=False, oracle_levels=(), fp64=True):
@@ -175,6 +161,5 @@ def test_fused_key_mac_on_both_engines_in_a_child():
     code = ("from lattisense_amd import params; from tests.test_gpu_hmult_fold import _fold_vs_old; "
             "P = params.CKKS_BOOTSTRAP_65536; _fold_vs_old(1 << 16, P['q'], P['p'], (24, 7), 24, 2, 33, oracle_levels=(7,)); "
             "C = params.CKKS_DEFAULT[65536]; _fold_vs_old(1 << 16, C['q'][:13], C['p'][:4], (12,), 12, 2, 34)")
-    env = dict(os.environ, LSA_KS_FUSED_ENGINES="3")
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, LSA_KS_FUSED_ENGINES="3"), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
