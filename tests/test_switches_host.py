@@ -135,3 +135,52 @@ def test_tests_and_tools_set_only_table_switches():
                 for name in re.findall(pat, text):
                     assert name not in PROCESS, "%s sets the per-process switch %s in process: it would test nothing" % (f, name)
     assert {"LSA_KS_FUSED", "LSA_KS_FUSED_ENGINES", "LSA_NTT_R16", "LSA_NO_GRAPH_FUSION"} <= seen   # the scan finds each form
+
+
+# switches the rule below asks a GPU parity test for, and that have none: each with its reason
+PARITY_EXEMPT = {
+    "LSA_STAGE_THREADS": "host threads that stage task inputs and outputs: no device code path depends on it; its parse is held above",
+}
+
+
+def test_every_path_selecting_switch_is_named_by_a_gpu_parity_test(table):
+    """A switch whose lifetime is PROCESS or CONTEXT, or whose text starts with "A/B", selects device code that the default never
+    runs: it is named in at least one tests/test_gpu_*.py (which hold every form to the oracle), or exempt above with a reason.
+    A new switch cannot arrive without one or the other.  (LSA_TASK_TRACE, the pool caps and LSA_PIPELINE_MIN_MIB fall outside
+    the rule: CALL / PLAN lifetime, not A/B -- they print, or bound what is kept, and select no kernel.)"""
+    text = {}
+    for line in table["markdown"].splitlines():
+        m = re.match(r"^\| `(LSA_[A-Z0-9_]+)` \| (\w+) \| (.*) \|$", line)
+        if m:
+            text[m.group(1)] = m.group(3)
+    assert set(text) == set(table["rows"])
+    gpu = {f: open(f).read() for f in glob.glob(os.path.join(ROOT, "tests", "test_gpu_*.py"))}
+    assert len(gpu) > 15
+    assert set(PARITY_EXEMPT) <= set(text) and all(len(r) > 10 for r in PARITY_EXEMPT.values())
+    required = [n for n, (_, life) in table["rows"].items() if life in ("PROCESS", "CONTEXT") or text[n].startswith("A/B")]
+    assert {"LSA_NTT_R16", "LSA_NTT_R8X3", "LSA_R16_PRO", "LSA_NTT_MU_A", "LSA_NTT_FP_RAW", "LSA_KS_FUSED", "LSA_MACM_NO_XCD"} <= set(required)
+    for name in required:
+        if name in PARITY_EXEMPT:
+            continue
+        users = [os.path.basename(f) for f, t in gpu.items() if re.search(r"\b%s\b" % name, t)]
+        assert users, "%s selects a device path and no tests/test_gpu_*.py names it" % name
+    assert set(PARITY_EXEMPT) <= set(required)          # no exemption for a switch the rule does not ask about
+
+
+def test_first_pass_override_rule_of_make_ntt_plan(tmp_path):
+    """the rule tests/test_gpu_ntt_switches.py::accepted_mu_a states, against ntt_plan.h itself: which LSA_NTT_MU_A values change
+    the plan at N = 2^13 .. 2^17, and what the default is"""
+    src = tmp_path / "plan.cpp"
+    src.write_text('#include <cstdio>\n#define LSA_EMULATE 1\n#include "ntt_plan.h"\nint main() { for (int n = 13; n <= 17; n++) for (int m = 0; m <= 16; m++) {'
+                   ' NttPlan p = make_ntt_plan(n, 12, m); std::printf("%d %d %d %d %d\\n", n, m, p.npass, p.pass[0].mu, p.pass[1].mu); } }\n')
+    exe = str(tmp_path / "plan")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", CSRC, str(src), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout
+    from tests.test_gpu_ntt_switches import TAU, accepted_mu_a
+    assert TAU == 12
+    rows = [tuple(int(x) for x in line.split()) for line in out.splitlines()]
+    assert len(rows) == 5 * 17
+    for n, m, npass, mu_a, mu_b in rows:
+        default = min(n // 2, TAU - 4)
+        assert npass == 2 and mu_a + mu_b == n
+        assert mu_a == (m if m in accepted_mu_a(n) else default), (n, m)
