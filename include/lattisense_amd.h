@@ -246,6 +246,34 @@ int lsa_ckks_linear_transform(lsa_context ctx, lsa_linear_transform lt, const ui
 int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double bsgs_ratio, int* n1, int* rotations,
                           int capacity, int* count);
 
+/* ---- CKKS polynomial evaluation: p(x) = sum_k coef[k] B_k(x) on a ciphertext, B_k the Chebyshev polynomial T_k (basis 0) or
+ * the monomial x^k (basis 1), by a baby-step / giant-step (Paterson-Stockmeyer) plan of depth k = ceil(log2(n_coef)), k >= 1:
+ * the powers P_j for j < 2^log_baby and P_(2^j) above them (P_j from P_ceil(j/2) and P_floor(j/2); only those that are used),
+ * binary splitting p = hi * P_half + lo with top-down target scales down to LEAVES of degree < 2^log_baby, each leaf one
+ * rescaled linear combination of the baby powers by integer constants.  All-zero halves cost nothing, a constant upper half
+ * costs no multiplication.  The recursion is written out in DESIGN.md 4.8 and restated in tests/poly_model.py; with
+ * log_baby = 1 it is oracle/ckks_bootstrap.py eval_chebyshev / eval_monomial word for word.
+ * n_coef: 1..256, any value (zero-padded to 2^k); a polynomial of degree 0 is refused.  log_baby: 0 = the value in 1..min(4, k)
+ * with the fewest ciphertext multiplications (ties: the smaller), else 1..4.  [a, b]: the interval of x; (-1, 1) = none,
+ * otherwise u = (2x - a - b) / (b - a) is formed first and costs one more level.  level_in - depth >= 0 is required.
+ * scale_out: 0 = q[level_out + 1] (the oracle's default).  Errors are LSA_ERR_ARG with a message that begins "poly". */
+typedef struct lsa_polynomial_st* lsa_polynomial;
+/* host only, needs no device and no context: the counts lsa_poly_create will arrive at (any output pointer may be null) */
+int lsa_poly_plan(int basis, int n_coef, const double* coef, int log_baby, int level_in, int with_interval, int* depth,
+                  int* log_baby_out, int* n_mult, int* n_leaves, int* n_leaf_launches);
+int lsa_poly_create(lsa_context ctx, int basis, int n_coef, const double* coef, double a, double b, int level_in, double scale_in,
+                    double scale_out, int log_baby, lsa_polynomial* out);
+void lsa_poly_destroy(lsa_polynomial p);
+int lsa_poly_info(lsa_polynomial p, int* level_in, int* level_out, double* scale_out, int* depth, int* log_baby, int* n_mult,
+                  int* n_leaves, int* n_leaf_launches, int* n_constants);
+/* every integer constant of the plan: the interval's two, one per Chebyshev power (ascending), per leaf its K_j (ascending j) and
+ * its constant term if non-zero (leaves in the recursion's order, upper half first), then the constant lower halves */
+int lsa_poly_constants(lsa_polynomial p, long long* out, int capacity);
+/* in [batch][2][level_in+1][N] (NTT domain, scale_in) -> out [batch][2][level_out+1][N] at scale_out; batch strides in words;
+ * out may not overlap in; batch <= 0 is a no-op.  The only key is the relinearisation key (at level_in or above). */
+int lsa_ckks_poly_eval(lsa_context ctx, lsa_polynomial p, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                       long long sout, lsa_key rlk, void* stream);
+
 /* diagnostic builds only (-DLSA_NTT_DIAG_STAMPS): device buffer of 8192*8 u64 receiving per-workgroup phase time stamps
  * of every following NTT launch; NULL turns it off.  Ignored by the normal build. */
 int lsa_debug_set_ntt_stamps(lsa_context ctx, void* device_buffer);

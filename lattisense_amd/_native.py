@@ -121,6 +121,16 @@ SIGNATURES = {
                                           c_vp]),
     "lsa_lt_plan_rotations": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.c_double, ctypes.POINTER(c_int),
                                       ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int)]),
+    "lsa_poly_plan": (c_int, [c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int, c_int, c_int, ctypes.POINTER(c_int),
+                              ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "lsa_poly_create": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, c_int,
+                                ctypes.c_double, ctypes.c_double, c_int, ctypes.POINTER(c_vp)]),
+    "lsa_poly_destroy": (None, [c_vp]),
+    "lsa_poly_info": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double),
+                              ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                              ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "lsa_poly_constants": (c_int, [c_vp, ctypes.POINTER(c_ll), c_int]),
+    "lsa_ckks_poly_eval": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_vp, c_vp]),
     "lsa_profile_begin": (c_int, [c_vp, c_int]),
     "lsa_profile_end": (c_int, [c_vp]),
     "lsa_profile_read": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),

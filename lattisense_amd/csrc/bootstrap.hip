@@ -19,7 +19,7 @@
 #include <map>
 #include <memory>
 
-#include "linear_transform.h"
+#include "poly_eval.h"
 
 namespace lsa {
 
@@ -342,88 +342,19 @@ struct Bootstrap {
 // ------------------------------------------------------------------------------------------------ device evaluator
 namespace {
 
-// the linear transforms and the ciphertext bookkeeping come from LtEval (linear_transform.h); what is added here is EvalMod
-struct Eval : LtEval {
+// the linear transforms and the ciphertext bookkeeping come from LtEval (linear_transform.h), the multiply and the constant
+// helpers from CtEval (poly_eval.h, shared with the polynomial operator); what is added here is EvalMod
+struct Eval : CtEval {
     Bootstrap& bt;
-    const Key& rlk;
 
     Eval(Context& c_, Bootstrap& b, hipStream_t s_, int m_, const Key& rlk_, const std::map<u64, const Key*>& g)
-        : LtEval(c_, b.pool, s_, m_, g, "bootstrap"), bt(b), rlk(rlk_) {}
-    DCt mul(const DCt& a0, const DCt& b0) {
-        // operands at different levels: the leading rows of each polynomial of the higher one ARE it at the lower level, the
-        // tensor kernel takes the rows per polynomial -- no copy (k_copy_rows was 2 % of a bootstrap)
-        const int lvl = std::min(a0.level, b0.level);
-        DCt o = alloc(lvl - 1, a0.scale * b0.scale / q(lvl));
-        ckks_mult_relin_rescale_rpp(c, lvl, a0.data(), b0.data(), rlk, o.data(), m, stride(a0.level), stride(b0.level), stride(lvl - 1), s,
-                                    a0.level + 1, b0.level + 1);
-        return o;
-    }
+        : CtEval(c_, b.pool, s_, m_, rlk_, g, "bootstrap"), bt(b) {}
     DCt conj(const DCt& a) {
         const u64 e = 2ULL * c.n - 1;
         DCt o = alloc(a.level, a.scale);
         ckks_rotate(c, a.level, a.data(), e, gkey(e), o.data(), m, stride(a.level), stride(a.level), s);
         return o;
     }
-    // per-limb constant vectors, cached on the context by value
-    const u64* kvec(long long k, int level, bool montgomery) {
-        std::vector<int> mods(level + 1);
-        std::vector<u64> vals(level + 1);
-        for (int j = 0; j <= level; j++) {
-            mods[j] = j;
-            const long long qq = (long long)c.T.mod[j];
-            long long r = k % qq;
-            if (r < 0) r += qq;
-            vals[j] = (u64)r;
-        }
-        const std::string name = std::string(montgomery ? "btm" : "btr") + std::to_string(level) + "_" + std::to_string(k);
-        return montgomery ? c.const_vec(name, mods, vals) : c.raw_vec(name, vals);
-    }
-    // level < a.level: the product at that lower level, read from a's leading rows (no copy to drop it first)
-    DCt mul_int_raw(const DCt& a, long long k, double new_scale, int level = -1) {
-        if (level < 0) level = a.level;
-        DCt o = alloc(level, new_scale);
-        unsigned char lm[LSA_MAX_PERIOD];
-        for (int j = 0; j <= level; j++) lm[j] = (unsigned char)j;
-        launch_sub_mul_general(c, 2, level + 1, lm, kvec(k, level, true), a.data(), stride(a.level), a.level + 1, nullptr, 0,
-                               0, nullptr, 0, 0, 0, o.data(), stride(level), level + 1, m, s);
-        return o;
-    }
-    DCt mul_int(const DCt& a, long long k) { return mul_int_raw(a, k, a.scale); }
-    DCt mul_const(const DCt& a, double cst, double const_scale, int level = -1) {
-        return mul_int_raw(a, round_even(cst * const_scale, "bootstrap"), a.scale * const_scale, level);
-    }
-    // per-row vectors over BOTH polynomials: [value for the L limbs of c0 | `second` for the L limbs of c1]
-    const u64* kvec2(long long k0, long long k1, int level, bool montgomery) {
-        const int L = level + 1;
-        std::vector<int> mods(2 * L);
-        std::vector<u64> vals(2 * L);
-        for (int p = 0; p < 2; p++)
-            for (int j = 0; j < L; j++) {
-                mods[p * L + j] = j;
-                const long long qq = (long long)c.T.mod[j];
-                long long r = (p == 0 ? k0 : k1) % qq;
-                if (r < 0) r += qq;
-                vals[p * L + j] = (u64)r;
-            }
-        const std::string name = std::string(montgomery ? "b2m" : "b2r") + std::to_string(level) + "_" + std::to_string(k0) + "_" + std::to_string(k1);
-        return montgomery ? c.const_vec(name, mods, vals) : c.raw_vec(name, vals);
-    }
-    RowMap rm_both(int level) const {
-        RowMap rm;
-        rm.period = 2 * (level + 1);
-        for (int p = 0; p < 2; p++)
-            for (int j = 0; j <= level; j++) rm.mod_of[p * (level + 1) + j] = (unsigned char)j;
-        return rm;
-    }
-    // a * factor + cst in every slot, one pass (factor 1: plain add_const)
-    DCt mul_int_add_const(const DCt& a, long long factor, double cst) {
-        const long long k = round_even(cst * a.scale, "bootstrap");
-        DCt o = alloc(a.level, a.scale);
-        launch_add_const(c, a.data(), stride(a.level), kvec2(k, 0, a.level, false), o.data(), stride(a.level), 2 * (a.level + 1),
-                         rm_both(a.level), m, s, factor == 1 ? nullptr : kvec2(factor, factor, a.level, true));
-        return o;
-    }
-    DCt add_const(const DCt& a, double cst) { return mul_int_add_const(a, 1, cst); }
     // every polynomial times a shared plaintext (stride 0 over the batch)
     DCt mul_plain(const DCt& a, const u64* pt, double pt_scale) {
         DCt o = alloc(a.level, a.scale * pt_scale);

@@ -2,6 +2,7 @@
 // error codes: nothing throws across the C boundary (the reference does, SURVEY §8b "Errors").
 #include "build_flags.h"
 #include "linear_transform.h"
+#include "poly_eval.h"
 #include "lsa_internal.h"
 
 namespace lsa {
@@ -651,6 +652,66 @@ int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double 
         if (count) *count = (int)rot.size();
         LSA_REQUIRE(rotations == nullptr || (int)rot.size() <= capacity, "buffer too small");
         if (rotations) std::copy(rot.begin(), rot.end(), rotations);
+    });
+}
+
+// ---- CKKS polynomial evaluation (poly_eval.hip)
+struct lsa_polynomial_st {
+    Polynomial* p;
+    Context* c;
+};
+int lsa_poly_plan(int basis, int n_coef, const double* coef, int log_baby, int level_in, int with_interval, int* depth,
+                  int* log_baby_out, int* n_mult, int* n_leaves, int* n_leaf_launches) {
+    return guard([&] { poly_plan(basis, n_coef, coef, log_baby, level_in, with_interval != 0, depth, log_baby_out, n_mult, n_leaves, n_leaf_launches); });
+}
+int lsa_poly_create(lsa_context ctx, int basis, int n_coef, const double* coef, double a, double b, int level_in, double scale_in,
+                    double scale_out, int log_baby, lsa_polynomial* out) {
+    return guard([&] {
+        LSA_REQUIRE(out != nullptr, "null argument");
+        auto h = std::make_unique<lsa_polynomial_st>();
+        h->c = &C(ctx);
+        h->p = poly_create(*h->c, basis, n_coef, coef, a, b, level_in, scale_in, scale_out, log_baby, nullptr);
+        *out = h.release();
+    });
+}
+void lsa_poly_destroy(lsa_polynomial p) {
+    if (!p) return;
+    delete p->p;
+    delete p;
+}
+int lsa_poly_info(lsa_polynomial p, int* level_in, int* level_out, double* scale_out, int* depth, int* log_baby, int* n_mult,
+                  int* n_leaves, int* n_leaf_launches, int* n_constants) {
+    return guard([&] {
+        LSA_REQUIRE(p != nullptr, "null polynomial handle");
+        const Polynomial& P = *p->p;
+        if (level_in) *level_in = P.level_in;
+        if (level_out) *level_out = P.level_out;
+        if (scale_out) *scale_out = P.scale_out;
+        if (depth) *depth = P.depth;
+        if (log_baby) *log_baby = P.st.log_baby;
+        if (n_mult) *n_mult = P.st.mults;
+        if (n_leaves) *n_leaves = (int)P.st.jobs.size();
+        if (n_leaf_launches) *n_leaf_launches = (int)P.st.groups.size();
+        if (n_constants) *n_constants = (int)P.constants.size();
+    });
+}
+int lsa_poly_constants(lsa_polynomial p, long long* out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(p != nullptr && out != nullptr, "null argument");
+        const auto& k = p->p->constants;
+        LSA_REQUIRE((int)k.size() <= capacity, "buffer too small");
+        std::copy(k.begin(), k.end(), out);
+    });
+}
+int lsa_ckks_poly_eval(lsa_context ctx, lsa_polynomial p, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                       long long sout, lsa_key rlk, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(p != nullptr, "null polynomial handle");
+        LSA_REQUIRE(p->c == &C(ctx), "poly: the plan belongs to another context");
+        if (batch <= 0) return;
+        LSA_REQUIRE(in != nullptr && out != nullptr, "null argument");
+        LSA_REQUIRE(rlk != nullptr && rlk->key.data != nullptr, "poly: the relinearisation key is missing");
+        poly_run(*p->p, in, sin, out, sout, batch, K(rlk), S(stream));
     });
 }
 

@@ -6,6 +6,7 @@
 #include "build_flags.h"
 #include "lsa_internal.h"
 #include "ntt_r16.h"
+#include "poly_lincomb.h"
 
 namespace lsa {
 
@@ -983,6 +984,100 @@ void launch_mac_plain_multi(Context& c, int nb, const u64* const* ct, const long
     else if (polys == 2) hipLaunchKernelGGL((k_mac_plain_multi<2, false>), grid, dim3(TPB), 0, s, g);
     else if (accumulate) hipLaunchKernelGGL((k_mac_plain_multi<1, true>), grid, dim3(TPB), 0, s, g);
     else hipLaunchKernelGGL((k_mac_plain_multi<1, false>), grid, dim3(TPB), 0, s, g);
+    LSA_HIP(hipGetLastError());
+}
+
+// Leaves of a polynomial evaluation (poly_eval.hip): n_out linear combinations of the same nsrc ciphertexts by per-limb integer
+// constants, out[g] = sum_i K[g][i] * src_i (+ A[g] on polynomial 0), one launch.  Every source element is read once for all
+// outputs; the sources sit at different levels and only their leading `rows` rows per polynomial are read (own batch stride and
+// rows per polynomial each, no copy to drop levels).  The constants are uniform per workgroup (one row): scalar loads.  The
+// products are summed in 128 bits and reduced once per output (poly_lincomb.h).
+struct PolyLincombArgs {
+    const u64* src[LSA_PLC_MAX_SRC];
+    long long ss[LSA_PLC_MAX_SRC];
+    int rpp[LSA_PLC_MAX_SRC];
+    u64* out;          // [n_out][batch][2][rows][N]
+    const u64* ktab;   // [n_out][nsrc][rows], Montgomery form
+    const u64* atab;   // [n_out][rows] plain residues added to polynomial 0, or null
+    const ModDev* mods;
+    int nsrc, n_out, rows, logn, batch;
+};
+
+// One workgroup = one 512-coefficient piece of one row of one polynomial of one batch item, batch index fastest (the batch
+// items of a piece share its constants); 16 B per lane.
+template <int GMAX>
+__global__ __launch_bounds__(TPB) void k_poly_lincomb(PolyLincombArgs g) {
+    const int chunks = (1 << g.logn) / (2 * TPB);
+    const int b = (int)blockIdx.x % g.batch, piece = (int)blockIdx.x / g.batch;
+    const int prow = piece / chunks;   // poly * rows + row
+    const int poly = prow / g.rows, row = prow % g.rows;
+    const int x = ((piece % chunks) * TPB + threadIdx.x) * 2;
+    const ModDev m = g.mods[row];
+    PlcAcc a0[GMAX], a1[GMAX];
+#pragma unroll
+    for (int gi = 0; gi < GMAX; gi++) {
+        plc_init(a0[gi]);
+        plc_init(a1[gi]);
+    }
+    for (int i = 0; i < g.nsrc; i++) {
+        const ulonglong2 v = ld2(g.src[i] + (long long)b * g.ss[i] + (((long long)poly * g.rpp[i] + row) << g.logn) + x);
+#pragma unroll
+        for (int gi = 0; gi < GMAX; gi++)
+            if (gi < g.n_out) {
+                const u64 k = g.ktab[((long long)gi * g.nsrc + i) * g.rows + row];
+                if (k) {   // uniform: a power this output does not use
+                    plc_term(a0[gi], i, v.x, k, m.q, m.qinv);
+                    plc_term(a1[gi], i, v.y, k, m.q, m.qinv);
+                } else if (i == 8) {
+                    plc_fold(a0[gi], m.q, m.qinv);
+                    plc_fold(a1[gi], m.q, m.qinv);
+                }
+            }
+    }
+#pragma unroll
+    for (int gi = 0; gi < GMAX; gi++)
+        if (gi < g.n_out) {
+            u64 r0 = plc_finish(a0[gi], m.q, m.qinv), r1 = plc_finish(a1[gi], m.q, m.qinv);
+            if (g.atab && poly == 0) {
+                const u64 add = g.atab[(long long)gi * g.rows + row];
+                r0 = add_mod(r0, add, m.q);
+                r1 = add_mod(r1, add, m.q);
+            }
+            st2(g.out + ((((long long)gi * g.batch + b) * 2 * g.rows + prow) << g.logn) + x, r0, r1);
+        }
+}
+
+void launch_poly_lincomb(Context& c, int nsrc, const u64* const* src, const long long* ss, const int* rpp, int n_out,
+                         const u64* d_k, const u64* d_a, u64* out, int rows, int batch, hipStream_t s) {
+    if (batch <= 0) return;
+    LSA_REQUIRE(nsrc >= 1 && nsrc <= LSA_PLC_MAX_SRC && n_out >= 1 && n_out <= LSA_PLC_MAX_OUT, "poly: too many sources or outputs for one launch");
+    LSA_REQUIRE(rows >= 1 && rows <= c.nq, "poly: rows beyond the modulus chain");
+    LSA_REQUIRE(c.n >= 2 * TPB, "ring degree too small for the elementwise kernels (need N >= 512)");
+    PolyLincombArgs g{};
+    for (int i = 0; i < nsrc; i++) {
+        LSA_REQUIRE(rpp[i] >= rows && ss[i] >= 2LL * rpp[i] * c.n, "poly: a source with fewer rows than the launch reads");
+        g.src[i] = src[i];
+        g.ss[i] = ss[i];
+        g.rpp[i] = rpp[i];
+    }
+    g.out = out;
+    g.ktab = d_k;
+    g.atab = d_a;
+    g.mods = c.d_mods;
+    g.nsrc = nsrc;
+    g.n_out = n_out;
+    g.rows = rows;
+    g.logn = c.logn;
+    g.batch = batch;
+    const long long blocks = 2LL * rows * (c.n / (2 * TPB)) * batch;
+    LSA_REQUIRE(blocks < (1LL << 31), "poly: grid too large");
+    // algorithmic bytes: every source row read once, every output row written once
+    ProfScope ps(c, PROF_ELEMWISE, 16.0 * c.n * rows * batch * (nsrc + n_out), s);
+    const dim3 grid((unsigned)blocks);
+    if (n_out == 1) hipLaunchKernelGGL((k_poly_lincomb<1>), grid, dim3(TPB), 0, s, g);
+    else if (n_out == 2) hipLaunchKernelGGL((k_poly_lincomb<2>), grid, dim3(TPB), 0, s, g);
+    else if (n_out <= 4) hipLaunchKernelGGL((k_poly_lincomb<4>), grid, dim3(TPB), 0, s, g);
+    else hipLaunchKernelGGL((k_poly_lincomb<8>), grid, dim3(TPB), 0, s, g);
     LSA_HIP(hipGetLastError());
 }
 

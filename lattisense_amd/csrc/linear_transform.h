@@ -65,7 +65,8 @@ struct DCt {
     std::shared_ptr<DBuf> buf;
     int level = 0;
     double scale = 0;
-    u64* data() const { return buf->p; }
+    size_t off = 0;   // words into the buffer: one ciphertext batch of several that share an allocation
+    u64* data() const { return buf->p + off; }
 };
 
 struct LtEval {

@@ -268,6 +268,10 @@ void launch_mac_plain(Context& c, int terms, const u64* const* ct, const long lo
 void launch_mac_plain_multi(Context& c, int nb, const u64* const* ct, const long long* sct, int ng, const u64* const* pt,
                             u64* const* out, long long so, int batch, int polys, int limbs, const RowMap& rm, hipStream_t s,
                             bool accumulate = false);   // out[g] += the sums (one block of a matrix wider than LSA_MACM_MAX)
+// out[g][b][poly][row] = sum_i K[g][i][row] * src_i[b][poly][row] (+ A[g][row] on polynomial 0) mod q_row, rows 0..rows-1 of
+// every polynomial; src_i has rpp[i] >= rows rows per polynomial and batch stride ss[i]; out is [G][batch][2][rows][N]
+void launch_poly_lincomb(Context& c, int nsrc, const u64* const* src, const long long* ss, const int* rpp, int n_out,
+                         const u64* d_k, const u64* d_a, u64* out, int rows, int batch, hipStream_t s);
 // out[p][j] = a[p][j] * pt[j] * 2^-64 mod q (+ acc[p][j]) over [batch][polys][limbs][N]: BFV ct x pt_mul in the NTT domain,
 // unfused form (k_mont_muladd); acc / a may be out
 void launch_mont_muladd(Context& c, const u64* a, long long sa, const u64* pt, long long spt, const u64* acc, long long sacc,

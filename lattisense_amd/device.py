@@ -443,3 +443,62 @@ class LinearTransformPlan:
         check(lib().lsa_ckks_linear_transform(self.ctx.h, self.h, in_buf.ptr, out.ptr, batch, 2 * (self.level + 1) * n, 2 * lo * n,
                                               int(bool(rescale)), len(glk), elts, keys, self.ctx.stream))
         return out
+
+
+BASES = {"chebyshev": 0, "monomial": 1}
+
+
+def plan_polynomial(coeffs, level, basis="chebyshev", log_baby=0, interval=False):
+    """{depth, log_baby, mults, leaves, leaf_launches} of the evaluation plan a coefficient list gets -- host only"""
+    cf = (ctypes.c_double * len(coeffs))(*[float(x) for x in coeffs])
+    d, b, mu, lv, la = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(lib().lsa_poly_plan(BASES[basis], len(coeffs), cf, int(log_baby), int(level), int(bool(interval)), ctypes.byref(d),
+                              ctypes.byref(b), ctypes.byref(mu), ctypes.byref(lv), ctypes.byref(la)))
+    return {"depth": d.value, "log_baby": b.value, "mults": mu.value, "leaves": lv.value, "leaf_launches": la.value}
+
+
+class PolynomialPlan:
+    """sum_k coeffs[k] T_k(u) (basis "chebyshev") or sum_k coeffs[k] u^k ("monomial") on ciphertexts at `level` and scale
+    `scale_in`, u = x mapped from `interval` to [-1, 1] (include/lattisense_amd.h: lsa_poly_*)."""
+
+    def __init__(self, ctx, coeffs, level, scale_in, basis="chebyshev", interval=(-1, 1), scale_out=None, log_baby=0):
+        self.ctx = ctx
+        self.h = None
+        cf = (ctypes.c_double * len(coeffs))(*[float(x) for x in coeffs])
+        h = ctypes.c_void_p()
+        check(lib().lsa_poly_create(ctx.h, BASES[basis], len(coeffs), cf, float(interval[0]), float(interval[1]), int(level),
+                                    float(scale_in), float(scale_out or 0.0), int(log_baby), ctypes.byref(h)))
+        self.h = h
+        li, lo, d, b, mu, lv, la, nc = (ctypes.c_int() for _ in range(8))
+        sc = ctypes.c_double()
+        check(lib().lsa_poly_info(self.h, ctypes.byref(li), ctypes.byref(lo), ctypes.byref(sc), ctypes.byref(d), ctypes.byref(b),
+                                  ctypes.byref(mu), ctypes.byref(lv), ctypes.byref(la), ctypes.byref(nc)))
+        self.level_in, self.level_out, self.scale_out, self.depth, self.log_baby = li.value, lo.value, sc.value, d.value, b.value
+        self.mults, self.leaves, self.leaf_launches, self.n_constants = mu.value, lv.value, la.value, nc.value
+        self.basis, self.scale_in = basis, float(scale_in)
+
+    def close(self):
+        if self.h:
+            lib().lsa_poly_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def constants(self):
+        """every integer constant of the plan, in the planner's order (what tests/poly_model.py consumes)"""
+        k = (ctypes.c_longlong * max(self.n_constants, 1))()
+        check(lib().lsa_poly_constants(self.h, k, self.n_constants))
+        return [int(x) for x in k[: self.n_constants]]
+
+    def run(self, in_buf, batch, rlk, out=None):
+        """in_buf: device [batch][2][level_in+1][N]; rlk: relinearisation key handle; returns device [batch][2][level_out+1][N]"""
+        n = self.ctx.n
+        if out is None:
+            out = self.ctx.alloc(max(batch, 1) * 2 * (self.level_out + 1) * n)
+        check(lib().lsa_ckks_poly_eval(self.ctx.h, self.h, in_buf.ptr, out.ptr, batch, 2 * (self.level_in + 1) * n,
+                                       2 * (self.level_out + 1) * n, rlk, self.ctx.stream))
+        return out
