@@ -101,6 +101,21 @@ int lsa_drop_level(lsa_context ctx, int level, int polys, const uint64_t* in, ui
 int lsa_ckks_mult_relin_rescale(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, lsa_key rlk,
                                 uint64_t* out, int batch, long long stride_a, long long stride_b,
                                 long long stride_out, void* stream);
+/* Encrypted inner product: sum_{i<n} a_i x b_i of n >= 1 pairs of ciphertexts with ONE relinearisation (the degree-2 tensors are
+ * summed, which is exact; one key switch and one rescale follow).  as[i], bs[i]: [2][rpp][N] per batch item, NTT domain; a_rpp[i],
+ * b_rpp[i] rows per polynomial (a null array or an entry of 0: level + 1; an operand kept at a higher level is read through its
+ * leading rows); sas[i], sbs[i] batch strides in words, 0 = one ciphertext shared by the whole batch; as[i] == bs[i] squares.
+ * addend (nullable): a ciphertext [2][level+1][N] at the product's scale added before the key switch.  The output overlaps no
+ * input.  Word for word the composition lsa_ckks_mult per pair, lsa_poly_addsub, lsa_ckks_relin (, lsa_ckks_rescale); with
+ * n == 1, no addend and rescale != 0 that is lsa_ckks_mult_relin_rescale.  batch <= 0 is a no-op. */
+/* d3 = sum_{i<n} a_i (x) b_i (+ (addend_0, addend_1, 0)):  [3][level+1][N], NTT domain */
+int lsa_ckks_mult_sum(lsa_context ctx, int level, int n, const uint64_t* const* as, const long long* sas, const int* a_rpp,
+                      const uint64_t* const* bs, const long long* sbs, const int* b_rpp, const uint64_t* addend,
+                      long long s_addend, uint64_t* d3, int batch, long long sd, void* stream);
+/* out = relin(d3 above), then rescaled when rescale != 0:  [2][level (rescale) | level+1][N] */
+int lsa_ckks_dot(lsa_context ctx, int level, int n, const uint64_t* const* as, const long long* sas, const int* a_rpp,
+                 const uint64_t* const* bs, const long long* sbs, const int* b_rpp, const uint64_t* addend,
+                 long long s_addend, lsa_key rlk, uint64_t* out, int batch, long long sout, int rescale, void* stream);
 
 /* ---- BFV (coefficient-domain ciphertexts) ---------------------------------------------------------------- */
 int lsa_bfv_mult(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, uint64_t* d3, int batch,

@@ -68,6 +68,11 @@ SIGNATURES = {
     "lsa_ckks_rotate": (c_int, [c_vp, c_int, c_vp, ctypes.c_uint64, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),
     "lsa_drop_level": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),
     "lsa_ckks_mult_relin_rescale": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_ll, c_vp]),
+    "lsa_ckks_mult_sum": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_int),
+                                  ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_int), c_vp, c_ll, c_vp, c_int, c_ll, c_vp]),
+    "lsa_ckks_dot": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_int),
+                             ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_int), c_vp, c_ll, c_vp, c_vp, c_int, c_ll, c_int,
+                             c_vp]),
     "lsa_bfv_mult": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_ll, c_vp]),
     "lsa_bfv_relin": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),
     "lsa_bfv_rotate": (c_int, [c_vp, c_int, c_vp, ctypes.c_uint64, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),

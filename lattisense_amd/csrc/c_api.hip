@@ -256,6 +256,26 @@ int lsa_ckks_mult_relin_rescale(lsa_context ctx, int level, const uint64_t* a, c
     return guard([&] { ckks_mult_relin_rescale(C(ctx), level, a, b, K(rlk), out, batch, sa, sb, so, S(stream)); });
 }
 
+// ---- CKKS encrypted inner product (ops.hip ckks_mult_sum / ckks_dot)
+int lsa_ckks_mult_sum(lsa_context ctx, int level, int n, const uint64_t* const* as, const long long* sas, const int* a_rpp,
+                      const uint64_t* const* bs, const long long* sbs, const int* b_rpp, const uint64_t* addend, long long s_addend,
+                      uint64_t* d3, int batch, long long sd, void* stream) {
+    return guard([&] {
+        const DotTerms t{n, as, sas, a_rpp, bs, sbs, b_rpp, addend, s_addend};
+        ckks_mult_sum(C(ctx), level, t, d3, batch, sd, S(stream));
+    });
+}
+int lsa_ckks_dot(lsa_context ctx, int level, int n, const uint64_t* const* as, const long long* sas, const int* a_rpp,
+                 const uint64_t* const* bs, const long long* sbs, const int* b_rpp, const uint64_t* addend, long long s_addend,
+                 lsa_key rlk, uint64_t* out, int batch, long long sout, int rescale, void* stream) {
+    return guard([&] {
+        Context& c = C(ctx);
+        LSA_REQUIRE(rlk != nullptr && rlk->key.data != nullptr, "dot: the relinearisation key is missing");
+        const DotTerms t{n, as, sas, a_rpp, bs, sbs, b_rpp, addend, s_addend};
+        ckks_dot(c, level, t, rlk->key, out, batch, sout, rescale != 0, S(stream));
+    });
+}
+
 // ---- BFV
 int lsa_bfv_mult(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, uint64_t* d3, int batch, long long sa,
                  long long sb, long long sd, void* stream) {

@@ -7,6 +7,7 @@
 #include "lsa_internal.h"
 #include "ntt_r16.h"
 #include "poly_lincomb.h"
+#include "tensor_sum.h"
 
 namespace lsa {
 
@@ -1141,6 +1142,106 @@ void launch_tensor(Context& c, const u64* a, const u64* b, u64* d, int batch, lo
     fill_rowmap(g.mod_of, period, rm, c.nmod);
     ProfScope ps(c, PROF_TENSOR, 7.0 * 8 * c.n * limbs * batch, s);
     hipLaunchKernelGGL(k_tensor, ew_grid(c, limbs, batch), dim3(TPB), 0, s, g);
+    LSA_HIP(hipGetLastError());
+}
+
+// Sum of tensor products (ckks_mult_sum / ckks_dot): d = sum_i a_i (x) b_i (+ (addend_0, addend_1, 0)) (+ d, ACC), up to
+// LSA_DOT_MAX_TERMS pairs per launch.  Every operand row is read once and the three output rows are written once per launch; the
+// products are summed in 128 bits per coefficient and reduced once per output (tensor_sum.h).  Each pair has its own batch stride
+// (0: one ciphertext for the whole batch) and rows per polynomial (an operand kept at a higher level is read through its leading
+// rows).  The term loop is uniform: pointers, strides and offsets are read from the argument struct by the scalar unit.
+struct TensorSumArgs {
+    const u64* a[LSA_DOT_MAX_TERMS];
+    const u64* b[LSA_DOT_MAX_TERMS];
+    long long sa[LSA_DOT_MAX_TERMS], sb[LSA_DOT_MAX_TERMS];   // batch strides
+    long long pa[LSA_DOT_MAX_TERMS], pb[LSA_DOT_MAX_TERMS];   // elements between the two polynomials
+    const u64* addend;   // [2][limbs][N] per batch item, or null
+    u64* d;              // [3][limbs][N] per batch item
+    long long s_addend, sd;
+    const ModDev* mods;
+    int terms, limbs, logn;
+    unsigned char mod_of[LSA_MAX_PERIOD];
+};
+
+// grid as k_tensor: x = limbs * (N/2/TPB), y = batch; 16 B per lane
+template <bool ACC>
+__global__ __launch_bounds__(TPB) void k_tensor_sum(TensorSumArgs g) {
+    const int chunks = (1 << g.logn) / (2 * TPB);
+    const int limb = blockIdx.x / chunks;
+    const int x = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
+    const ModDev m = g.mods[g.mod_of[limb]];
+    const long long b = blockIdx.y;
+    const long long poly = (long long)g.limbs << g.logn;
+    const long long off = ((long long)limb << g.logn) + x;
+    u64* pd = g.d + b * g.sd + off;
+    TsAcc t0, t1;   // the two coefficients of this lane
+    ts_init(t0);
+    ts_init(t1);
+    if (ACC) {
+        const ulonglong2 v0 = ld2(pd), v1 = ld2(pd + poly), v2 = ld2(pd + 2 * poly);
+        ts_seed(t0.l0, v0.x);
+        ts_seed(t1.l0, v0.y);
+        ts_seed(t0.l1, v1.x);
+        ts_seed(t1.l1, v1.y);
+        ts_seed(t0.l2, v2.x);
+        ts_seed(t1.l2, v2.y);
+    }
+    if (g.addend) {
+        const u64* pe = g.addend + b * g.s_addend + off;
+        const ulonglong2 v0 = ld2(pe), v1 = ld2(pe + poly);
+        ts_seed(t0.l0, v0.x);
+        ts_seed(t1.l0, v0.y);
+        ts_seed(t0.l1, v1.x);
+        ts_seed(t1.l1, v1.y);
+    }
+    for (int i = 0; i < g.terms; i++) {
+        const u64* pa = g.a[i] + b * g.sa[i] + off;
+        const u64* pb = g.b[i] + b * g.sb[i] + off;
+        const ulonglong2 a0 = ld2(pa), a1 = ld2(pa + g.pa[i]), b0 = ld2(pb), b1 = ld2(pb + g.pb[i]);
+        ts_term(t0, i, a0.x, a1.x, b0.x, b1.x, m);
+        ts_term(t1, i, a0.y, a1.y, b0.y, b1.y, m);
+    }
+    st2(pd, ts_finish(t0.h0, t0.l0, m), ts_finish(t1.h0, t1.l0, m));
+    st2(pd + poly, ts_finish(t0.h1, t0.l1, m), ts_finish(t1.h1, t1.l1, m));
+    st2(pd + 2 * poly, ts_finish(t0.h2, t0.l2, m), ts_finish(t1.h2, t1.l2, m));
+}
+
+void launch_tensor_sum(Context& c, int terms, const u64* const* a, const long long* sa, const int* a_rpp, const u64* const* b,
+                       const long long* sb, const int* b_rpp, const u64* addend, long long s_addend, bool accumulate, u64* d,
+                       long long sd, int batch, int limbs, const RowMap& rm, hipStream_t s) {
+    if (batch <= 0) return;
+    LSA_REQUIRE(terms >= 1 && terms <= LSA_DOT_MAX_TERMS, "dot: too many terms for one launch");
+    LSA_REQUIRE(rm.period == limbs && limbs <= LSA_MAX_PERIOD, "dot: row map must cover the limbs");
+    LSA_REQUIRE(sd >= 3LL * limbs * c.n, "dot: output stride below three polynomials");
+    TensorSumArgs g{};
+    for (int i = 0; i < terms; i++) {
+        const int ra = a_rpp && a_rpp[i] ? a_rpp[i] : limbs, rb = b_rpp && b_rpp[i] ? b_rpp[i] : limbs;
+        LSA_REQUIRE(a[i] && b[i], "dot: null operand");
+        LSA_REQUIRE(ra >= limbs && rb >= limbs, "dot: rows per polynomial below the limb count");
+        LSA_REQUIRE((sa[i] == 0 || sa[i] >= 2LL * ra * c.n) && (sb[i] == 0 || sb[i] >= 2LL * rb * c.n), "dot: batch stride below one ciphertext");
+        g.a[i] = a[i];
+        g.b[i] = b[i];
+        g.sa[i] = sa[i];
+        g.sb[i] = sb[i];
+        g.pa[i] = (long long)ra << c.logn;
+        g.pb[i] = (long long)rb << c.logn;
+    }
+    LSA_REQUIRE(!addend || s_addend == 0 || s_addend >= 2LL * limbs * c.n, "dot: addend stride below one ciphertext");
+    g.addend = addend;
+    g.s_addend = s_addend;
+    g.d = d;
+    g.sd = sd;
+    g.mods = c.d_mods;
+    g.terms = terms;
+    g.limbs = limbs;
+    g.logn = c.logn;
+    int period;
+    fill_rowmap(g.mod_of, period, rm, c.nmod);
+    for (int i = 0; i < limbs; i++) LSA_REQUIRE(g.mod_of[i] != LSA_ROW_SKIP, "dot: every limb needs a modulus");
+    // algorithmic bytes: four operand rows per term, three output rows (+ two addend rows) (+ the three rows read back)
+    ProfScope ps(c, PROF_TENSOR, 8.0 * c.n * limbs * batch * (4 * terms + 3 + (addend ? 2 : 0) + (accumulate ? 3 : 0)), s);
+    if (accumulate) hipLaunchKernelGGL((k_tensor_sum<true>), ew_grid(c, limbs, batch), dim3(TPB), 0, s, g);
+    else hipLaunchKernelGGL((k_tensor_sum<false>), ew_grid(c, limbs, batch), dim3(TPB), 0, s, g);
     LSA_HIP(hipGetLastError());
 }
 

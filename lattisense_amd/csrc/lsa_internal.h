@@ -285,6 +285,12 @@ void launch_lift_ringt(Context& c, int mode, int level, const u64* pt, long long
 // `limbs` rows of each polynomial are the operand at this level -- no copy needed to "drop" it)
 void launch_tensor(Context& c, const u64* a, const u64* b, u64* d, int batch, long long sa, long long sb, long long sd,
                    int limbs, const RowMap& rm, hipStream_t s, int a_rpp = 0, int b_rpp = 0);
+// d = sum_{i<terms} a_i (x) b_i (+ (addend_0, addend_1, 0)) (+ d when accumulate), terms <= LSA_DOT_MAX_TERMS (tensor_sum.h), one
+// launch of k_tensor_sum; sa[i] / sb[i] batch strides (0: one ciphertext for the whole batch), a_rpp / b_rpp rows per polynomial
+// (null or 0: limbs)
+void launch_tensor_sum(Context& c, int terms, const u64* const* a, const long long* sa, const int* a_rpp, const u64* const* b,
+                       const long long* sb, const int* b_rpp, const u64* addend, long long s_addend, bool accumulate, u64* d,
+                       long long sd, int batch, int limbs, const RowMap& rm, hipStream_t s);
 // the tensor product folded into the relinearisation's key MAC (CKKS HMult+relin+rescale): for a Q target limb j the MAC
 // takes its own digit as d2_j = a1_j * b1_j and adds P * d0_j to the first and P * d1_j to the second running sum
 // (d0 = a0 b0, d1 = a0 b1 + a1 b0): acc'_j = acc_j + P * d_j.  a / b point at the tile's first item, [2][rpp][N] each.
@@ -412,6 +418,27 @@ void ckks_mult_relin_rescale(Context& c, int level, const u64* a, const u64* b, 
                              long long sa, long long sb, long long so, hipStream_t s);
 void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch,
                                  long long sa, long long sb, long long so, hipStream_t s, int a_rpp, int b_rpp);
+// Encrypted inner product.  The operands of sum_{i<n} a_i (x) b_i: NTT-domain ciphertexts [2][rpp][N], a batch stride each
+// (0: one ciphertext shared by the batch) and rows per polynomial each (null array or 0: level + 1); addend (nullable): a
+// ciphertext [2][level+1][N] at the product's scale
+struct DotTerms {
+    int n;
+    const u64* const* as;
+    const long long* sas;
+    const int* a_rpp;
+    const u64* const* bs;
+    const long long* sbs;
+    const int* b_rpp;
+    const u64* addend;
+    long long s_addend;
+};
+// d3 = the summed degree-2 tensor (+ addend on polynomials 0 and 1), [3][level+1][N]: the words of ckks_mult per pair and
+// poly_addsub; d3 overlaps no input
+void ckks_mult_sum(Context& c, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s);
+// out = relin(d3 above), rescaled when `rescale`: ONE key switch for the whole sum; the words of ckks_relin (and ckks_rescale) on
+// ckks_mult_sum's d3; out overlaps no input
+void ckks_dot(Context& c, int level, const DotTerms& t, const Key& rlk, u64* out, int batch, long long so, bool rescale,
+              hipStream_t s);
 void ckks_lift_ext(Context& c, int level, const u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
 void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
                           int batch, long long sin, long long sout, hipStream_t s);

@@ -7,6 +7,7 @@
 //   rotate      = key-switch c1, add c0, then apply the automorphism (Evaluator.Automorphism)
 //   BFV mult    = centred extension Q->QMul, tensor in Q u QMul, round(./Q), centred return to Q, times t
 #include "lsa_internal.h"
+#include "tensor_sum.h"
 
 namespace lsa {
 
@@ -631,6 +632,89 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
         launch_tensor(c, a + (size_t)b0 * sa, b + (size_t)b0 * sb, d3, nb, sa, sb, sd, L, rm_seq(L), st, a_rpp, b_rpp);
         KsOut o{.p = r2, .sp = sr, .base = d3, .sbase = sd, .base_rpp = L, .base_polys = 2};
         if (c.fuse_tails) {
+            o.form = KsOut::RESCALE;
+            o.rs = {out + (size_t)b0 * so, so};
+            key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
+            return;
+        }
+        key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
+        rescale(c, level, 2, r2, sr, out + (size_t)b0 * so, so, nb, true, sub, st);
+    });
+}
+
+// ---- encrypted inner product: sum_i a_i (x) b_i with ONE relinearisation.  The degree-2 tensors are summed exactly (k_tensor_sum:
+// every operand row read once, d3 written once), then the sum takes the key switch and the rescale of a single HMult.
+static const u64* span_end(const u64* p, long long stride, size_t words, int batch) { return p + (size_t)(batch - 1) * stride + words; }
+
+// every argument error of the two entry points, before any work is queued; false: nothing to do (batch <= 0)
+static bool dot_check(const Context& c, int level, const DotTerms& t, bool rescale, const u64* out, long long so, size_t wout, int batch) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, "dot: context is not CKKS");
+    LSA_REQUIRE(t.n >= 1, "dot: needs at least one term");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "dot: level out of range");
+    LSA_REQUIRE(!rescale || level >= 1, "dot: rescale needs level >= 1");
+    if (batch <= 0) return false;
+    const int L = level + 1;
+    const size_t N = (size_t)c.n;
+    LSA_REQUIRE(t.as && t.sas && t.bs && t.sbs && out, "dot: null argument");
+    LSA_REQUIRE(so >= (long long)wout, "dot: output stride below one result");
+    const u64* out_end = span_end(out, so, wout, batch);
+    auto operand = [&](const u64* p, long long stride, int rpp, const char* what) {
+        LSA_REQUIRE(p != nullptr, std::string("dot: ") + what + " is null");
+        LSA_REQUIRE(rpp >= L, std::string("dot: rows per polynomial of ") + what + " below level + 1");
+        const size_t words = 2 * (size_t)rpp * N;
+        LSA_REQUIRE(stride == 0 || stride >= (long long)words, std::string("dot: batch stride of ") + what + " below one ciphertext");
+        LSA_REQUIRE(out_end <= p || span_end(p, stride, words, batch) <= out, std::string("dot: the output overlaps ") + what);
+    };
+    for (int i = 0; i < t.n; i++) {
+        operand(t.as[i], t.sas[i], t.a_rpp && t.a_rpp[i] ? t.a_rpp[i] : L, "an operand");
+        operand(t.bs[i], t.sbs[i], t.b_rpp && t.b_rpp[i] ? t.b_rpp[i] : L, "an operand");
+    }
+    if (t.addend) operand(t.addend, t.s_addend, L, "the addend");
+    return true;
+}
+
+// the tile's summed tensor: launches of up to LSA_DOT_MAX_TERMS pairs, the later ones adding to d3; the addend rides in the first
+static void dot_tensor(Context& c, int level, const DotTerms& t, int b0, u64* d3, long long sd, int nb, hipStream_t s) {
+    const int L = level + 1;
+    for (int i0 = 0; i0 < t.n; i0 += LSA_DOT_MAX_TERMS) {
+        const int m = std::min(LSA_DOT_MAX_TERMS, t.n - i0);
+        const u64 *a[LSA_DOT_MAX_TERMS], *b[LSA_DOT_MAX_TERMS];
+        for (int i = 0; i < m; i++) {
+            a[i] = t.as[i0 + i] + (size_t)b0 * t.sas[i0 + i];
+            b[i] = t.bs[i0 + i] + (size_t)b0 * t.sbs[i0 + i];
+        }
+        const bool first = i0 == 0;
+        launch_tensor_sum(c, m, a, t.sas + i0, t.a_rpp ? t.a_rpp + i0 : nullptr, b, t.sbs + i0, t.b_rpp ? t.b_rpp + i0 : nullptr,
+                          first && t.addend ? t.addend + (size_t)b0 * t.s_addend : nullptr, t.s_addend, !first, d3, sd, nb, L, rm_seq(L), s);
+    }
+}
+
+void ckks_mult_sum(Context& c, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s) {
+    if (!dot_check(c, level, t, false, d3, sd, 3 * (size_t)(level + 1) * c.n, batch)) return;
+    dot_tensor(c, level, t, 0, d3, sd, batch, s);
+}
+
+void ckks_dot(Context& c, int level, const DotTerms& t, const Key& rlk, u64* out, int batch, long long so, bool with_rescale,
+              hipStream_t s) {
+    if (!dot_check(c, level, t, with_rescale, out, so, 2 * (size_t)(with_rescale ? level : level + 1) * c.n, batch)) return;
+    const long long N = c.n;
+    const int L = level + 1;
+    const size_t r_d3 = 3 * (size_t)L, r_r2 = 2 * (size_t)L;
+    const size_t r_shared = std::max(KsTile::rows(c, level), rescale_ws_rows(level, 2));
+    const long long sd = (long long)r_d3 * N, sr = 2LL * L * N;
+    for_tiles(c, r_d3 + r_r2 + r_shared, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
+        u64* d3 = ws;
+        u64* r2 = d3 + r_d3 * N * tb;
+        u64* sub = r2 + r_r2 * N * tb;
+        dot_tensor(c, level, t, b0, d3, sd, nb, st);
+        KsOut o{.p = r2, .sp = sr, .base = d3, .sbase = sd, .base_rpp = L, .base_polys = 2};
+        if (!with_rescale) {
+            o.p = out + (size_t)b0 * so;
+            o.sp = so;
+            key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
+            return;
+        }
+        if (c.fuse_tails) {   // the merged ModDown + rescale tail
             o.form = KsOut::RESCALE;
             o.rs = {out + (size_t)b0 * so, so};
             key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);

@@ -189,6 +189,32 @@ class DeviceContext:
                                                 2 * L * self.n, 2 * level * self.n, self.stream))
         return out
 
+    def _dot_terms(self, level, a_list, b_list, addend):
+        n, w = len(a_list), 2 * (level + 1) * self.n
+        assert n == len(b_list), "as many b operands as a operands"
+        pa = (ctypes.c_void_p * max(n, 1))(*[a.ptr for a in a_list])
+        pb = (ctypes.c_void_p * max(n, 1))(*[b.ptr for b in b_list])
+        st = (ctypes.c_longlong * max(n, 1))(*([w] * n))
+        return n, pa, st, None, pb, st, None, addend.ptr if addend is not None else None, w
+
+    def ckks_mult_sum(self, level, a_list, b_list, batch, addend=None, out=None):
+        """d3 = sum_i a_list[i] (x) b_list[i] (+ addend on polynomials 0 and 1): [batch][3][level+1][N]"""
+        L = level + 1
+        if out is None:
+            out = self.alloc(batch * 3 * L * self.n)
+        check(lib().lsa_ckks_mult_sum(self.h, level, *self._dot_terms(level, a_list, b_list, addend), out.ptr, batch,
+                                      3 * L * self.n, self.stream))
+        return out
+
+    def ckks_dot(self, level, a_list, b_list, rlk, batch, rescale=True, addend=None, out=None):
+        """sum_i a_list[i] x b_list[i] (+ addend) with one relinearisation (and one rescale): [batch][2][level | level+1][N]"""
+        rows = level if rescale else level + 1
+        if out is None:
+            out = self.alloc(batch * 2 * rows * self.n)
+        check(lib().lsa_ckks_dot(self.h, level, *self._dot_terms(level, a_list, b_list, addend), rlk, out.ptr, batch,
+                                 2 * rows * self.n, int(bool(rescale)), self.stream))
+        return out
+
     def bfv_mult(self, level, a, b, batch):
         L = level + 1
         out = self.alloc(batch * 3 * L * self.n)
