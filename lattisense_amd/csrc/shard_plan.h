@@ -4,7 +4,7 @@
 //
 // The reference's only multi-device mode is one run() per device on sub-batches (README.md:195-202,
 // mega_ag_runners/gpu/gpu_wrapper.cu:148-149), which exports and uploads every evaluation key once per device and run.  Here
-// the independent subgraphs the runtime already finds (task_runtime.hip, plan_pipeline: connected components over the
+// the independent subgraphs the runtime already finds (task_pipeline.h, plan_pipeline: connected components over the
 // non-key data, grouped into chunks) are dealt out to SHARDS, a shard being one device plus its own pair of execution lanes;
 // every key is exported and uploaded ONCE, on the first device of the list, converted there, and copied device-to-device
 // to each other distinct device.  A device may appear more than once in the list (two logical shards on one device: the CPU

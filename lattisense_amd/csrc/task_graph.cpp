@@ -219,7 +219,7 @@ void TaskGraph::validate_structure() const {
             if (k != TYPE_RELIN_KEY && k != TYPE_GALOIS_KEY && k != TYPE_SWITCH_KEY) bad(c, "second operand " + c.input_nodes[1]->id + " is not a key");
         }
         // Relations between an operator's operands and its result.  The runtime sizes the result slab from the result's
-        // declared level / degree and launches over the first operand's rows (task_runtime.hip, run_gpu_bucket): a file
+        // declared level / degree and launches over the first operand's rows (task_dispatch.hip, run_gpu_bucket): a file
         // that declares, say, an `add` whose result is lower than its operands, or a second operand of lower level or
         // degree, would make a kernel write or read past a slab.  What the frontend emits always satisfies these
         // (frontend/custom_task.py:971-1371: results are created from the operands' level and degree).
