@@ -117,6 +117,52 @@ int lsa_ckks_dot(lsa_context ctx, int level, int n, const uint64_t* const* as, c
                  const uint64_t* const* bs, const long long* sbs, const int* b_rpp, const uint64_t* addend,
                  long long s_addend, lsa_key rlk, uint64_t* out, int batch, long long sout, int rescale, void* stream);
 
+/* ---- CKKS plaintext and constant operands: a ciphertext combined with something that is not encrypted.  Ciphertexts ct / out are
+ * [2][level+1][N] per batch item, plaintexts pt [level+1][N], all NTT domain; batch strides (s*) in words; batch <= 0 is a no-op; a
+ * BFV context is LSA_ERR_ARG; error messages begin with the entry point's name.  The words are those of oracle/ckks_bootstrap.py
+ * Evaluator.mul_plain / add / sub / mul_const / add_const / mul_by_i on the same operands.  rescale != 0 (level >= 1) runs
+ * lsa_ckks_rescale on the result: out is then [2][level][N] and may overlap no input.  Without a rescale the element-wise forms
+ * (mult_plain, addsub_plain, mult_const, add_const, affine_const) accept out == ct with sout == sct, and otherwise no overlap.
+ * The kernels move 16 bytes per lane: every device pointer must be 16-byte aligned and every batch stride even (LSA_ERR_ARG).
+ *
+ * lsa_ckks_encode: host complex vectors -> device plaintexts at `scale`.  values: [batch][2^log_slots][2] doubles (re, im),
+ * log_slots in 0..log2(N)-1, a shorter vector is tiled over the N/2 slots; out_dev: [batch][level+1][N].  Word for word
+ * lsa_lt_plaintext of an lsa_lt_create plan with n_diag = 1, index 0, the same values, pt_scale = scale, double_hoist = 0.
+ * LSA_ERR_ARG: scale <= 0, level or log_slots out of range, a value that is not finite or encodes beyond 2^62 (then nothing is
+ * written).  Returns after the plaintexts are complete on `stream`. */
+int lsa_ckks_encode(lsa_context ctx, int level, int log_slots, const double* values, double scale, uint64_t* out_dev, long long sout,
+                    int batch, void* stream);
+/* out = ct x pt on both polynomials; spt == 0: one plaintext shared by the whole batch */
+int lsa_ckks_mult_plain(lsa_context ctx, int level, const uint64_t* ct, long long sct, const uint64_t* pt, long long spt, uint64_t* out,
+                        long long sout, int batch, int rescale, void* stream);
+/* op 0: c0 + pt, 1: c0 - pt; c1 is copied when out != ct */
+int lsa_ckks_addsub_plain(lsa_context ctx, int op, int level, const uint64_t* ct, long long sct, const uint64_t* pt, long long spt,
+                          uint64_t* out, long long sout, int batch, void* stream);
+/* out = sum_{i<n} cts[i] x pts[i] (+ addend, a ciphertext at the products' scale; nullable), n >= 1; spts[i] == 0: shared plaintext.
+ * 16 terms per launch, later launches add to out; out overlaps no input */
+int lsa_ckks_mac_plain(lsa_context ctx, int level, int n, const uint64_t* const* cts, const long long* scts, const uint64_t* const* pts,
+                       const long long* spts, const uint64_t* addend, long long s_addend, uint64_t* out, long long sout, int batch,
+                       int rescale, void* stream);
+/* out = ct x (kre + kim X^(N/2)), kre = round(re * const_scale), kim = round(im * const_scale) (ties to even; beyond 2^62:
+ * LSA_ERR_ARG): the slot-wise product with the complex constant re + i im, at scale ct_scale * const_scale.  No plaintext is read
+ * (k_cconst).  const_scale = 1, re = 0, im = +-1 is the exact multiplication by +-i. */
+int lsa_ckks_mult_const(lsa_context ctx, int level, const uint64_t* ct, long long sct, double re, double im, double const_scale,
+                        uint64_t* out, long long sout, int batch, int rescale, void* stream);
+/* c0 += round(re * ct_scale) + round(im * ct_scale) X^(N/2): re + i im added to every slot of a ciphertext at scale ct_scale.
+ * The rounded integers are 64-bit like every other encoded constant: |re|, |im| times ct_scale must stay below 4.6e18 (about
+ * 2^62), else LSA_ERR_ARG -- at ct_scale = 2^60 a constant up to 4 in magnitude, at 2^80 none worth adding.  (The oracle's
+ * add_const works on Python integers and has no such cap.) */
+int lsa_ckks_add_const(lsa_context ctx, int level, const uint64_t* ct, long long sct, double re, double im, double ct_scale,
+                       uint64_t* out, long long sout, int batch, void* stream);
+/* out = ct x (re + i im) + (add_re + i add_im) in one pass: the words of lsa_ckks_mult_const(re, im, const_scale) followed by
+ * lsa_ckks_add_const(add_re, add_im, ct_scale * const_scale), ct_scale the scale of ct (, then the rescale).  The addend is
+ * encoded at the PRODUCT of the two scales, so add_const's cap reads |add_re|, |add_im| < 2^62 / (ct_scale * const_scale): with
+ * both scales at 2^40 (2^80) the fused form refuses any addend that does not round to zero.  Keep the product below 2^62 / |beta|
+ * (2^30 x 2^30, 2^40 x 2^20), or multiply, rescale and add the constant at the rescaled scale with lsa_ckks_add_const. */
+int lsa_ckks_affine_const(lsa_context ctx, int level, const uint64_t* ct, long long sct, double re, double im, double const_scale,
+                          double add_re, double add_im, double ct_scale, uint64_t* out, long long sout, int batch, int rescale,
+                          void* stream);
+
 /* ---- BFV (coefficient-domain ciphertexts) ---------------------------------------------------------------- */
 int lsa_bfv_mult(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, uint64_t* d3, int batch,
                  long long stride_a, long long stride_b, long long stride_d, void* stream);

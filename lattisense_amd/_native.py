@@ -73,6 +73,17 @@ SIGNATURES = {
     "lsa_ckks_dot": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_int),
                              ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_int), c_vp, c_ll, c_vp, c_vp, c_int, c_ll, c_int,
                              c_vp]),
+    "lsa_ckks_encode": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_vp, c_ll, c_int, c_vp]),
+    "lsa_ckks_mult_plain": (c_int, [c_vp, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_vp]),
+    "lsa_ckks_addsub_plain": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
+    "lsa_ckks_mac_plain": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_vp),
+                                   ctypes.POINTER(c_ll), c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_vp]),
+    "lsa_ckks_mult_const": (c_int, [c_vp, c_int, c_vp, c_ll, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_ll, c_int,
+                                    c_int, c_vp]),
+    "lsa_ckks_add_const": (c_int, [c_vp, c_int, c_vp, c_ll, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_ll, c_int,
+                                   c_vp]),
+    "lsa_ckks_affine_const": (c_int, [c_vp, c_int, c_vp, c_ll, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, c_vp, c_ll, c_int, c_int, c_vp]),
     "lsa_bfv_mult": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_ll, c_vp]),
     "lsa_bfv_relin": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),
     "lsa_bfv_rotate": (c_int, [c_vp, c_int, c_vp, ctypes.c_uint64, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),

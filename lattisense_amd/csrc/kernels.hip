@@ -6,6 +6,7 @@
 #include "build_flags.h"
 #include "lsa_internal.h"
 #include "ntt_r16.h"
+#include "plain_ops.h"
 #include "poly_lincomb.h"
 #include "tensor_sum.h"
 
@@ -2446,6 +2447,105 @@ void launch_lift_ringt(Context& c, int mode, int level, const u64* pt, long long
     }
     ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * (1 + L) * batch, s);
     hipLaunchKernelGGL(k_lift_ringt, ew_grid(c, L, batch), dim3(TPB), 0, s, g);
+    LSA_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------ CKKS plaintext / constant operands
+// The encoder's device half: v [batch][N] rounded coefficients (signed 64-bit) -> out [batch][limbs][N], row j = v mod q_j in
+// [0, q_j) (plain_ops.h lift_i64).  The host uploads 8N bytes per plaintext instead of 8 (level + 1) N; launch_ntt then
+// transforms the rows in place.  grid: x = limbs * (N/2/TPB), y = batch
+struct LiftI64Args {
+    const long long* v;
+    u64* out;
+    long long sv, so;
+    const ModDev* mods;
+    int logn;
+};
+__global__ __launch_bounds__(TPB) void k_lift_i64(LiftI64Args g) {
+    const int chunks = (1 << g.logn) / (2 * TPB);
+    const int limb = blockIdx.x / chunks;
+    const int x = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
+    const long long b = blockIdx.y;
+    const ModDev m = g.mods[limb];
+    const longlong2 v = *reinterpret_cast<const longlong2*>(g.v + b * g.sv + x);
+    st2(g.out + b * g.so + ((long long)limb << g.logn) + x, lift_i64(v.x, m), lift_i64(v.y, m));
+}
+void launch_lift_i64(Context& c, const long long* v, long long sv, u64* out, long long so, int limbs, int batch, hipStream_t s) {
+    if (batch <= 0 || limbs <= 0) return;
+    LSA_REQUIRE(limbs <= c.nq, "lift_i64: more rows than the Q chain has primes");
+    LiftI64Args g{};
+    g.v = v;
+    g.out = out;
+    g.sv = sv;
+    g.so = so;
+    g.mods = c.d_mods;
+    g.logn = c.logn;
+    ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * (1 + limbs) * batch, s);
+    hipLaunchKernelGGL(k_lift_i64, ew_grid(c, limbs, batch), dim3(TPB), 0, s, g);
+    LSA_HIP(hipGetLastError());
+}
+
+// Ciphertext times / plus a complex constant (plain_ops.h): out[p][j][x] = a[p][j][x] * k(j, x) (MUL) + beta(j, x) (ADD, on
+// polynomial 0 only), k and beta one of two per-limb constants picked by bit `sel_bit` of the point's index (the sign of
+// X^(N/2) there).  No plaintext is read: one read and one write per row.  An addition alone copies polynomial 1.
+// grid: x = rows * (N/2/TPB), y = batch; rows = 2 * limbs, or limbs for an addition in place
+struct CconstArgs {
+    const u64* a;
+    u64* out;
+    long long sa, so;
+    const ModDev* mods;
+    int limbs, logn, sel_bit, sel_pol;   // point x takes the "minus" constants when ((x >> sel_bit) & 1) != sel_pol
+    CconstLimb k[LSA_CCONST_MAX_LIMBS];
+};
+template <bool MUL, bool ADD>
+__global__ __launch_bounds__(TPB) void k_cconst(CconstArgs g) {
+    const int chunks = (1 << g.logn) / (2 * TPB);
+    const int row = blockIdx.x / chunks;             // poly * limbs + limb
+    const int limb = row % g.limbs;
+    const int x = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
+    const long long b = blockIdx.y, off = ((long long)row << g.logn) + x;
+    const ulonglong2 v = ld2(g.a + b * g.sa + off);
+    const bool add = ADD && row < g.limbs;
+    if (!MUL && !add) {
+        st2(g.out + b * g.so + off, v.x, v.y);
+        return;
+    }
+    const ModDev m = g.mods[limb];
+    const CconstLimb k = g.k[limb];
+    const bool m0 = ((x >> g.sel_bit) & 1) != g.sel_pol, m1 = (((x + 1) >> g.sel_bit) & 1) != g.sel_pol;
+    u64 r0, r1;
+    if (add) {
+        r0 = cconst_word<MUL, true>(v.x, m0 ? k.k_minus : k.k_plus, m0 ? k.b_minus : k.b_plus, m);
+        r1 = cconst_word<MUL, true>(v.y, m1 ? k.k_minus : k.k_plus, m1 ? k.b_minus : k.b_plus, m);
+    } else {
+        r0 = cconst_word<MUL, false>(v.x, m0 ? k.k_minus : k.k_plus, 0, m);
+        r1 = cconst_word<MUL, false>(v.y, m1 ? k.k_minus : k.k_plus, 0, m);
+    }
+    st2(g.out + b * g.so + off, r0, r1);
+}
+void launch_cconst(Context& c, bool mul, bool add, const u64* a, long long sa, const CconstLimb* k, int sel_bit, int sel_pol,
+                   u64* out, long long so, int limbs, int batch, hipStream_t s) {
+    if (batch <= 0 || limbs <= 0) return;
+    LSA_REQUIRE(mul || add, "cconst: nothing to do");
+    LSA_REQUIRE(limbs <= c.nq && limbs <= LSA_CCONST_MAX_LIMBS, "cconst: too many limbs for one launch");
+    LSA_REQUIRE(sel_bit >= 0 && sel_bit < c.logn && (sel_pol == 0 || sel_pol == 1), "cconst: bad selector");
+    CconstArgs g{};
+    g.a = a;
+    g.out = out;
+    g.sa = sa;
+    g.so = so;
+    g.mods = c.d_mods;
+    g.limbs = limbs;
+    g.logn = c.logn;
+    g.sel_bit = sel_bit;
+    g.sel_pol = sel_pol;
+    for (int j = 0; j < limbs; j++) g.k[j] = k[j];
+    const int rows = !mul && out == a && so == sa ? limbs : 2 * limbs;   // an addition in place leaves polynomial 1 alone
+    ProfScope ps(c, PROF_ELEMWISE, 16.0 * c.n * rows * batch, s);
+    const dim3 grid = ew_grid(c, rows, batch);
+    if (mul && add) hipLaunchKernelGGL((k_cconst<true, true>), grid, dim3(TPB), 0, s, g);
+    else if (mul) hipLaunchKernelGGL((k_cconst<true, false>), grid, dim3(TPB), 0, s, g);
+    else hipLaunchKernelGGL((k_cconst<false, true>), grid, dim3(TPB), 0, s, g);
     LSA_HIP(hipGetLastError());
 }
 

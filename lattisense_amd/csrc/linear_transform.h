@@ -40,6 +40,12 @@ struct BtMatrix {
 // ext: the same integer polynomial at the special primes too, rows level+1 .. level+k (operand of extended ciphertexts)
 u64* lt_upload_plain(Context& c, const std::vector<double>& coef, double scale, int level, hipStream_t s, bool ext,
                      std::vector<u64*>& owned, const char* who);
+// The public encoder (lsa_ckks_encode): `batch` complex vectors of 2^log_slots values, tiled over the N/2 slots, -> NTT-domain
+// plaintexts [level+1][N] at `scale`, the words lt_upload_plain gives for the same values.  The floating-point work (slots to
+// coefficients, rounding, the 2^62 refusal) is the host's and finishes before anything is queued; the device gets the N rounded
+// coefficients of each plaintext and forms the residue rows itself (k_lift_i64).
+void ckks_encode(Context& c, int level, int log_slots, const double* values, double scale, u64* out, long long sout, int batch,
+                 hipStream_t s);
 // one matrix -> plaintexts (diagonals of period `period`, tiled over the N/2 slots) + the Galois elements of its rotations
 // (added to `gal`).  Keys of `mat` are reduced mod period.
 BtMatrix lt_make_matrix(Context& c, const Diags& mat, int level, int period, double pt_scale, double ratio, bool double_hoist,

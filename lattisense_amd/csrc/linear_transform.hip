@@ -132,6 +132,43 @@ u64* lt_upload_plain(Context& c, const std::vector<double>& coef, double scale, 
     return d;
 }
 
+void ckks_encode(Context& c, int level, int log_slots, const double* values, double scale, u64* out, long long sout, int batch,
+                 hipStream_t s) {
+    const char* who = "lsa_ckks_encode";
+    LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, std::string(who) + ": context is not CKKS");
+    LSA_REQUIRE(level >= 0 && level < c.nq, std::string(who) + ": level out of range");
+    LSA_REQUIRE(log_slots >= 0 && (2 << log_slots) <= c.n, std::string(who) + ": log_slots beyond log2(N) - 1");
+    LSA_REQUIRE(std::isfinite(scale) && scale > 0, std::string(who) + ": scale must be positive");
+    if (batch <= 0) return;
+    const int L = level + 1, n = c.n / 2, period = 1 << log_slots;
+    const size_t N = (size_t)c.n;
+    LSA_REQUIRE(values && out, std::string(who) + ": null argument");
+    LSA_REQUIRE(sout >= (long long)(L * N), std::string(who) + ": output stride below one plaintext");
+    // k_lift_i64 stores 16 bytes per lane at out + item * sout
+    LSA_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && (sout & 1) == 0,
+                std::string(who) + ": out must be 16-byte aligned with an even batch stride");
+    const std::vector<int> rg = rot_group(n);
+    std::vector<long long> coef((size_t)batch * N);
+    std::vector<cplx> z(n);
+    for (int b = 0; b < batch; b++) {
+        const double* v = values + (size_t)b * period * 2;
+        for (int t = 0; t < period; t++)
+            LSA_REQUIRE(std::isfinite(v[2 * t]) && std::isfinite(v[2 * t + 1]), std::string(who) + ": value not finite");
+        for (int t = 0; t < n; t++) z[t] = cplx(v[2 * (t % period)], v[2 * (t % period) + 1]);
+        const std::vector<double> m = slots_to_coeffs(z, rg);
+        for (size_t x = 0; x < N; x++) coef[(size_t)b * N + x] = round_even(m[x] * scale, who);
+    }
+    // nothing has been queued so far: a refused value leaves the output untouched
+    long long* d = reinterpret_cast<long long*>(c.workspace(coef.size(), s));
+    LSA_HIP(hipMemcpyAsync(d, coef.data(), coef.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    launch_lift_i64(c, d, (long long)N, out, sout, L, batch, s);
+    RowMap rm;
+    rm.period = L;
+    for (int j = 0; j < L; j++) rm.mod_of[j] = (unsigned char)j;
+    launch_ntt(c, out, out, batch, sout, L, rm, false, s);
+    LSA_HIP(hipStreamSynchronize(s));   // `coef` goes out of scope
+}
+
 BtMatrix lt_make_matrix(Context& c, const Diags& mat, int level, int period, double pt_scale, double ratio, bool double_hoist,
                         hipStream_t s, std::vector<u64*>& owned, std::map<u64, bool>& gal, const char* who) {
     const int n = c.n / 2;

@@ -11,6 +11,7 @@
 
 #include "../../include/lattisense_amd.h"
 #include "ntt_plan.h"
+#include "plain_ops.h"
 #include "switches.h"
 #include "tables.h"
 
@@ -134,6 +135,12 @@ struct Context {
     std::map<u64, u32*> perm_ntt;                   // galois element -> device gather table (NTT domain)
     std::map<u64, u32*> perm_coeff;                 // galois element -> device scatter table with sign bit
     std::map<std::string, u64*> consts;             // misc per-level device constant vectors
+    // where NTT(X^(N/2)) is +I_j and where -I_j (ops.hip cconst_selector: measured once per context with launch_ntt, checked
+    // on the host): the word at point x of limb j is I[j] when bit `bit` of x equals `pol`, q_j - I[j] otherwise
+    struct CconstSelector {
+        int bit = -1, pol = 0;
+        std::vector<u64> I;   // [nq] psi_j^(N/2)
+    } cconst;
 
     // workspace arena: grows on demand, reused across calls (single in-flight operator per context)
     u64* ws = nullptr;
@@ -379,6 +386,13 @@ void launch_mul_const(Context& c, const u64* a, long long sa, const u64* kvec, u
 // out[row] = a[row] * mvec[row] + kvec[row] (kvec: plain residues, mvec: Montgomery-form factors or null)
 void launch_add_const(Context& c, const u64* a, long long sa, const u64* kvec, u64* out, long long so, int rows,
                       const RowMap& rm, int batch, hipStream_t s, const u64* mvec = nullptr);
+// CKKS plaintext / constant operands (plain_ops.h).  out[b][j] = v[b] mod q_j, j < limbs: the rounded coefficients of `batch`
+// plaintexts [N] (signed, |v| < 2^63) -> canonical residue rows [limbs][N], coefficient domain
+void launch_lift_i64(Context& c, const long long* v, long long sv, u64* out, long long so, int limbs, int batch, hipStream_t s);
+// out = a * k (mul) + beta (add; polynomial 0 only) over [batch][2][limbs][N], k / beta the "plus" or "minus" constant of limb j
+// at point x by bit sel_bit of x (minus when the bit differs from sel_pol); an addition alone copies polynomial 1 (out != a)
+void launch_cconst(Context& c, bool mul, bool add, const u64* a, long long sa, const CconstLimb* k, int sel_bit, int sel_pol,
+                   u64* out, long long so, int limbs, int batch, hipStream_t s);
 void launch_probe_copy(u64* dst, const u64* src, size_t n, hipStream_t s);
 void launch_probe_mulhi(u64* buf, size_t n, int iters, hipStream_t s);
 
@@ -439,6 +453,22 @@ void ckks_mult_sum(Context& c, int level, const DotTerms& t, u64* d3, int batch,
 // ckks_mult_sum's d3; out overlaps no input
 void ckks_dot(Context& c, int level, const DotTerms& t, const Key& rlk, u64* out, int batch, long long so, bool rescale,
               hipStream_t s);
+// CKKS plaintext and constant operands (the lsa_ckks_*_plain / *_const entry points; semantics in include/lattisense_amd.h).
+// ct / out [2][level+1][N], pt [level+1][N] (batch stride 0: one plaintext for the whole batch), NTT domain; `rescale` runs
+// ckks_rescale on the result, out then [2][level][N] and apart from every input
+void ckks_mult_plain(Context& c, int level, const u64* ct, long long sct, const u64* pt, long long spt, u64* out, long long so,
+                     int batch, bool rescale, hipStream_t s);
+void ckks_addsub_plain(Context& c, int op, int level, const u64* ct, long long sct, const u64* pt, long long spt, u64* out,
+                       long long so, int batch, hipStream_t s);
+void ckks_mac_plain(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
+                    const long long* spts, const u64* addend, long long s_addend, u64* out, long long so, int batch, bool rescale,
+                    hipStream_t s);
+void ckks_mult_const(Context& c, int level, const u64* ct, long long sct, double re, double im, double const_scale, u64* out,
+                     long long so, int batch, bool rescale, hipStream_t s);
+void ckks_add_const(Context& c, int level, const u64* ct, long long sct, double re, double im, double ct_scale, u64* out,
+                    long long so, int batch, hipStream_t s);
+void ckks_affine_const(Context& c, int level, const u64* ct, long long sct, double re, double im, double const_scale, double add_re,
+                       double add_im, double ct_scale, u64* out, long long so, int batch, bool rescale, hipStream_t s);
 void ckks_lift_ext(Context& c, int level, const u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
 void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
                           int batch, long long sin, long long sout, hipStream_t s);

@@ -6,7 +6,9 @@
 //   CKKS rescale = divide-and-round by the last prime (DivRoundByLastModulusNTT)
 //   rotate      = key-switch c1, add c0, then apply the automorphism (Evaluator.Automorphism)
 //   BFV mult    = centred extension Q->QMul, tensor in Q u QMul, round(./Q), centred return to Q, times t
+#include "linear_transform.h"
 #include "lsa_internal.h"
+#include "plain_ops.h"
 #include "tensor_sum.h"
 
 namespace lsa {
@@ -1109,6 +1111,241 @@ void bfv_rescale(Context& c, int level, int polys, const u64* in, u64* out, int 
     for_tiles(c, rescale_ws_rows(level, polys), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         rescale(c, level, polys, in + (size_t)b0 * sin, sin, out + (size_t)b0 * sout, sout, nb, false, ws, st);
     });
+}
+
+// ================================================================================================ CKKS plaintext / constant operands
+// Ciphertext (NTT domain, [2][level+1][N]) combined with something that is not encrypted: an encoded plaintext [level+1][N]
+// (lsa_ckks_encode, linear_transform.hip) or a complex constant.  Every word is the oracle's (oracle/ckks_bootstrap.py
+// Evaluator.mul_plain / add / mul_const / add_const / mul_by_i): canonical residues of exact modular products and sums, so the
+// kernel that forms them is free -- plaintext products run on k_mac_plain, sums on k_elementwise, constants on k_cconst, which
+// reads no plaintext at all (plain_ops.h).  A rescale is the existing ckks_rescale on the product, kept in the second arena.
+namespace {
+
+struct PlainCall {   // the checks every entry point shares; messages begin with the entry point's name
+    const Context& c;
+    std::string who;
+    int level, batch, L;
+    size_t wct, wpt;
+    PlainCall(const Context& c_, const char* who_, int level_, int batch_, bool rescale) : c(c_), who(who_), level(level_), batch(batch_) {
+        LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, who + ": context is not CKKS");
+        LSA_REQUIRE(level >= 0 && level < c.nq, who + ": level out of range");
+        LSA_REQUIRE(!rescale || level >= 1, who + ": rescale needs level >= 1");
+        L = level + 1;
+        wct = 2 * (size_t)L * c.n;
+        wpt = (size_t)L * c.n;
+    }
+    // the element-wise kernels move 16 bytes per lane at base + item * stride: every item has to start on a 16-byte boundary
+    void aligned(const u64* p, long long stride, const char* what) const {
+        LSA_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15) == 0 && (stride & 1) == 0,
+                    who + ": " + what + " must be 16-byte aligned with an even batch stride");
+    }
+    void ciphertext(const u64* p, long long stride, const char* what) const {
+        LSA_REQUIRE(p != nullptr, who + ": " + what + " is null");
+        LSA_REQUIRE(stride >= (long long)wct, who + ": batch stride of " + what + " below one ciphertext");
+        aligned(p, stride, what);
+    }
+    void plaintext(const u64* p, long long stride, const char* what) const {
+        LSA_REQUIRE(p != nullptr, who + ": " + what + " is null");
+        LSA_REQUIRE(stride == 0 || stride >= (long long)wpt, who + ": batch stride of " + what + " below one plaintext (0: shared by the batch)");
+        aligned(p, stride, what);
+    }
+    // the output [2][level + 1 | level][N]: `same` (nullable) is the input it may coincide with when nothing is rescaled
+    void output(const u64* out, long long so, bool rescale, const u64* same, long long s_same) const {
+        LSA_REQUIRE(out != nullptr, who + ": out is null");
+        const size_t wout = rescale ? 2 * (size_t)level * c.n : wct;
+        LSA_REQUIRE(so >= (long long)wout, who + ": output stride below one result");
+        aligned(out, so, "out");
+        if (!same) return;
+        if (rescale) LSA_REQUIRE(spans_apart(out, so, wout, same, s_same, wct, batch), who + ": out overlaps the ciphertexts (a rescaled result may not)");
+        else LSA_REQUIRE((out == same && so == s_same) || spans_apart(out, so, wct, same, s_same, wct, batch), who + ": out must be ct or not overlap it");
+    }
+    void apart(const u64* out, long long so, bool rescale, const u64* p, long long sp, size_t words, const char* what) const {
+        const size_t wout = rescale ? 2 * (size_t)level * c.n : wct;
+        LSA_REQUIRE(spans_apart(out, so, wout, p, sp, words, batch), who + ": out overlaps " + what);
+    }
+};
+
+// fn(dst, stride) writes the unrescaled result: into out, or into the second arena with ckks_rescale behind it
+template <typename F>
+void plain_finish(Context& c, int level, bool rescale, u64* out, long long so, int batch, hipStream_t s, F&& fn) {
+    if (!rescale) {
+        fn(out, so);
+        return;
+    }
+    const long long st = 2LL * (level + 1) * c.n;
+    u64* tmp = c.workspace2((size_t)st * batch, s);
+    fn(tmp, st);
+    ckks_rescale(c, level, 2, tmp, out, batch, st, so, s);
+}
+
+// The sign pattern of NTT(X^(N/2)), measured rather than assumed: the monomial goes through launch_ntt once per context, at every
+// prime of the chain, and the host checks that each word is I_j = psi_j^(N/2) or q_j - I_j and that one bit of the index decides
+// which -- the same bit, the same way round, at every limb.
+const Context::CconstSelector& cconst_selector(Context& c, hipStream_t s) {
+    if (c.cconst.bit >= 0) return c.cconst;
+    const int nq = c.nq;
+    const size_t N = (size_t)c.n;
+    std::vector<u64> w((size_t)nq * N, 0);
+    for (int j = 0; j < nq; j++) w[(size_t)j * N + N / 2] = 1;
+    u64* d = c.workspace(w.size(), s);
+    LSA_HIP(hipMemcpyAsync(d, w.data(), w.size() * sizeof(u64), hipMemcpyHostToDevice, s));
+    launch_ntt(c, d, d, 1, (long long)w.size(), nq, rm_seq(nq), false, s);
+    LSA_HIP(hipMemcpyAsync(w.data(), d, w.size() * sizeof(u64), hipMemcpyDeviceToHost, s));
+    LSA_HIP(hipStreamSynchronize(s));
+    auto internal = [](const std::string& m) { throw Error(LSA_ERR_INTERNAL, "complex constant: " + m); };
+    std::vector<u64> I(nq);
+    for (int j = 0; j < nq; j++) {
+        I[j] = c.T.psi[((size_t)j * N + 1) * 2];   // psi^brv(1) = psi^(N/2)
+        if (mul_mod_host(I[j], I[j], c.T.mod[j]) != c.T.mod[j] - 1) internal("psi^(N/2) is no square root of -1");
+    }
+    int pol = -1;
+    if (w[0] == I[0]) pol = 0;
+    else if (w[0] == c.T.mod[0] - I[0]) pol = 1;
+    else internal("the transformed monomial holds a word that is not +-psi^(N/2)");
+    for (int bit = 0; bit < c.logn; bit++) {
+        bool ok = true;
+        for (int j = 0; j < nq && ok; j++) {
+            const u64 q = c.T.mod[j], plus = I[j], minus = q - I[j];
+            const u64* row = w.data() + (size_t)j * N;
+            for (size_t x = 0; x < N && ok; x++) ok = row[x] == ((int)((x >> bit) & 1) == pol ? plus : minus);
+        }
+        if (ok) {
+            c.cconst.pol = pol;
+            c.cconst.I = I;
+            c.cconst.bit = bit;
+            return c.cconst;
+        }
+    }
+    internal("the sign of the transformed monomial is not a function of one index bit");
+    return c.cconst;
+}
+
+struct Cplx64 {   // a complex constant as two rounded integers
+    long long re = 0, im = 0;
+};
+Cplx64 cconst_round(double re, double im, double scale, const std::string& who) {
+    LSA_REQUIRE(std::isfinite(re) && std::isfinite(im), who + ": constant not finite");
+    LSA_REQUIRE(std::isfinite(scale) && scale > 0, who + ": scale must be positive");
+    Cplx64 k;
+    k.re = round_even(re * scale, who.c_str());
+    k.im = round_even(im * scale, who.c_str());
+    return k;
+}
+
+void cconst_run(Context& c, const PlainCall& pc, const Cplx64* alpha, const Cplx64* beta, const u64* ct, long long sct, u64* out,
+                long long so, bool rescale, hipStream_t s) {
+    LSA_REQUIRE(pc.L <= LSA_CCONST_MAX_LIMBS, pc.who + ": more than " + std::to_string(LSA_CCONST_MAX_LIMBS) + " limbs");
+    const Context::CconstSelector& sel = cconst_selector(c, s);
+    CconstLimb k[LSA_CCONST_MAX_LIMBS] = {};
+    for (int j = 0; j < pc.L; j++) {
+        const ModDev& m = c.T.mods[j];
+        if (alpha) {
+            const CconstPair p = cconst_pair(alpha->re, alpha->im, sel.I[j], m);
+            k[j].k_plus = cconst_to_mont(p.plus, m);
+            k[j].k_minus = cconst_to_mont(p.minus, m);
+        }
+        if (beta) {
+            const CconstPair p = cconst_pair(beta->re, beta->im, sel.I[j], m);
+            k[j].b_plus = p.plus;
+            k[j].b_minus = p.minus;
+        }
+    }
+    plain_finish(c, pc.level, rescale, out, so, pc.batch, s, [&](u64* dst, long long sd) {
+        launch_cconst(c, alpha != nullptr, beta != nullptr, ct, sct, k, sel.bit, sel.pol, dst, sd, pc.L, pc.batch, s);
+    });
+}
+
+}  // namespace
+
+void ckks_mult_plain(Context& c, int level, const u64* ct, long long sct, const u64* pt, long long spt, u64* out, long long so,
+                     int batch, bool rescale, hipStream_t s) {
+    const PlainCall pc(c, "lsa_ckks_mult_plain", level, batch, rescale);
+    if (batch <= 0) return;
+    pc.ciphertext(ct, sct, "ct");
+    pc.plaintext(pt, spt, "pt");
+    pc.output(out, so, rescale, ct, sct);
+    pc.apart(out, so, rescale, pt, spt, pc.wpt, "the plaintexts");
+    plain_finish(c, level, rescale, out, so, batch, s, [&](u64* dst, long long sd) {
+        launch_mac_plain(c, 1, &ct, &sct, &pt, &spt, nullptr, 0, dst, sd, batch, 2, pc.L, rm_seq(pc.L), s);
+    });
+}
+
+void ckks_addsub_plain(Context& c, int op, int level, const u64* ct, long long sct, const u64* pt, long long spt, u64* out,
+                       long long so, int batch, hipStream_t s) {
+    const PlainCall pc(c, "lsa_ckks_addsub_plain", level, batch, false);
+    LSA_REQUIRE(op == 0 || op == 1, pc.who + ": op must be 0 (add) or 1 (sub)");
+    if (batch <= 0) return;
+    pc.ciphertext(ct, sct, "ct");
+    pc.plaintext(pt, spt, "pt");
+    pc.output(out, so, false, ct, sct);
+    pc.apart(out, so, false, pt, spt, pc.wpt, "the plaintexts");
+    const int L = pc.L;
+    launch_elementwise(c, op == 0 ? EW_ADD : EW_SUB, ct, pt, out, batch, sct, spt, so, L, rm_seq(L), s);
+    if (out != ct) {   // c1 rides along
+        std::vector<int> rows(L);
+        for (int j = 0; j < L; j++) rows[j] = j;
+        launch_copy_rows(c, ct + (size_t)L * c.n, sct, out + (size_t)L * c.n, so, L, rows.data(), batch, s);
+    }
+}
+
+void ckks_mac_plain(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
+                    const long long* spts, const u64* addend, long long s_addend, u64* out, long long so, int batch, bool rescale,
+                    hipStream_t s) {
+    const PlainCall pc(c, "lsa_ckks_mac_plain", level, batch, rescale);
+    LSA_REQUIRE(n >= 1, pc.who + ": needs at least one term");
+    if (batch <= 0) return;
+    LSA_REQUIRE(cts && scts && pts && spts, pc.who + ": null argument");
+    pc.output(out, so, rescale, nullptr, 0);
+    // out holds the running sum while later terms are read: it may alias none of them
+    for (int i = 0; i < n; i++) {
+        pc.ciphertext(cts[i], scts[i], "a ciphertext");
+        pc.plaintext(pts[i], spts[i], "a plaintext");
+        pc.apart(out, so, rescale, cts[i], scts[i], pc.wct, "a ciphertext");
+        pc.apart(out, so, rescale, pts[i], spts[i], pc.wpt, "a plaintext");
+    }
+    if (addend) {
+        pc.ciphertext(addend, s_addend, "the addend");
+        pc.apart(out, so, rescale, addend, s_addend, pc.wct, "the addend");
+    }
+    plain_finish(c, level, rescale, out, so, batch, s, [&](u64* dst, long long sd) {
+        for (int i0 = 0; i0 < n; i0 += LSA_MAC_MAX_TERMS) {   // later launches add to the sum so far
+            const int m = std::min(LSA_MAC_MAX_TERMS, n - i0);
+            launch_mac_plain(c, m, cts + i0, scts + i0, pts + i0, spts + i0, i0 ? dst : addend, i0 ? sd : s_addend, dst, sd, batch, 2,
+                             pc.L, rm_seq(pc.L), s);
+        }
+    });
+}
+
+void ckks_mult_const(Context& c, int level, const u64* ct, long long sct, double re, double im, double const_scale, u64* out,
+                     long long so, int batch, bool rescale, hipStream_t s) {
+    const PlainCall pc(c, "lsa_ckks_mult_const", level, batch, rescale);
+    const Cplx64 alpha = cconst_round(re, im, const_scale, pc.who);
+    if (batch <= 0) return;
+    pc.ciphertext(ct, sct, "ct");
+    pc.output(out, so, rescale, ct, sct);
+    cconst_run(c, pc, &alpha, nullptr, ct, sct, out, so, rescale, s);
+}
+
+void ckks_add_const(Context& c, int level, const u64* ct, long long sct, double re, double im, double ct_scale, u64* out,
+                    long long so, int batch, hipStream_t s) {
+    const PlainCall pc(c, "lsa_ckks_add_const", level, batch, false);
+    const Cplx64 beta = cconst_round(re, im, ct_scale, pc.who);
+    if (batch <= 0) return;
+    pc.ciphertext(ct, sct, "ct");
+    pc.output(out, so, false, ct, sct);
+    cconst_run(c, pc, nullptr, &beta, ct, sct, out, so, false, s);
+}
+
+void ckks_affine_const(Context& c, int level, const u64* ct, long long sct, double re, double im, double const_scale, double add_re,
+                       double add_im, double ct_scale, u64* out, long long so, int batch, bool rescale, hipStream_t s) {
+    const PlainCall pc(c, "lsa_ckks_affine_const", level, batch, rescale);
+    const Cplx64 alpha = cconst_round(re, im, const_scale, pc.who);
+    LSA_REQUIRE(std::isfinite(ct_scale) && ct_scale > 0, pc.who + ": scale must be positive");
+    const Cplx64 beta = cconst_round(add_re, add_im, ct_scale * const_scale, pc.who);   // the product's scale
+    if (batch <= 0) return;
+    pc.ciphertext(ct, sct, "ct");
+    pc.output(out, so, rescale, ct, sct);
+    cconst_run(c, pc, &alpha, &beta, ct, sct, out, so, rescale, s);
 }
 
 }  // namespace lsa

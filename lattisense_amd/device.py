@@ -215,6 +215,78 @@ class DeviceContext:
                                  2 * rows * self.n, int(bool(rescale)), self.stream))
         return out
 
+    # ---- CKKS plaintext and constant operands (ct / out: [batch][2][level+1][N], pt: [batch][level+1][N], compact strides)
+    def _plain_out(self, level, batch, rescale, out):
+        rows = level if rescale else level + 1
+        if out is None:
+            out = self.alloc(max(batch, 1) * 2 * rows * self.n)
+        return out, 2 * rows * self.n
+
+    def ckks_encode(self, level, values, scale, batch=1, out=None):
+        """values: [batch][2^log_slots] complex (tiled over the N/2 slots) -> device plaintexts [batch][level+1][N] at `scale`"""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.complex128).reshape(max(batch, 1), -1))
+        period = v.shape[1]
+        assert period >= 1 and period & (period - 1) == 0, "2^log_slots values per plaintext"
+        w = (level + 1) * self.n
+        if out is None:
+            out = self.alloc(max(batch, 1) * w)
+        check(lib().lsa_ckks_encode(self.h, level, period.bit_length() - 1, v.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                    float(scale), out.ptr, w, batch, self.stream))
+        return out
+
+    def ckks_mult_plain(self, level, ct, pt, batch, rescale=False, out=None, spt=None):
+        """ct x pt on both polynomials (then rescaled); spt: the plaintexts' batch stride in words (0: one for the whole batch)"""
+        out, so = self._plain_out(level, batch, rescale, out)
+        L = level + 1
+        check(lib().lsa_ckks_mult_plain(self.h, level, ct.ptr, 2 * L * self.n, pt.ptr, L * self.n if spt is None else spt, out.ptr, so,
+                                        batch, int(bool(rescale)), self.stream))
+        return out
+
+    def ckks_addsub_plain(self, op, level, ct, pt, batch, out=None, spt=None):
+        """op 0: c0 + pt, 1: c0 - pt; c1 unchanged"""
+        out, so = self._plain_out(level, batch, False, out)
+        L = level + 1
+        check(lib().lsa_ckks_addsub_plain(self.h, op, level, ct.ptr, 2 * L * self.n, pt.ptr, L * self.n if spt is None else spt, out.ptr,
+                                          so, batch, self.stream))
+        return out
+
+    def ckks_mac_plain(self, level, cts, pts, batch, rescale=False, addend=None, out=None, spts=None):
+        """sum_i cts[i] x pts[i] (+ addend); spts: per-term plaintext strides (0: shared by the batch), default compact"""
+        out, so = self._plain_out(level, batch, rescale, out)
+        L, n = level + 1, len(cts)
+        assert n == len(pts), "as many plaintexts as ciphertexts"
+        pc = (ctypes.c_void_p * max(n, 1))(*[c.ptr for c in cts])
+        sc = (ctypes.c_longlong * max(n, 1))(*([2 * L * self.n] * n))
+        pp = (ctypes.c_void_p * max(n, 1))(*[p.ptr for p in pts])
+        sp = (ctypes.c_longlong * max(n, 1))(*([L * self.n] * n if spts is None else spts))
+        check(lib().lsa_ckks_mac_plain(self.h, level, n, pc, sc, pp, sp, addend.ptr if addend is not None else None, 2 * L * self.n,
+                                       out.ptr, so, batch, int(bool(rescale)), self.stream))
+        return out
+
+    def ckks_mult_const(self, level, ct, value, const_scale, batch, rescale=False, out=None):
+        """ct x round(value * const_scale), value complex: slot-wise; const_scale = 1 and value = +-1j multiplies by +-i exactly"""
+        out, so = self._plain_out(level, batch, rescale, out)
+        v = complex(value)
+        check(lib().lsa_ckks_mult_const(self.h, level, ct.ptr, 2 * (level + 1) * self.n, v.real, v.imag, float(const_scale), out.ptr, so,
+                                        batch, int(bool(rescale)), self.stream))
+        return out
+
+    def ckks_add_const(self, level, ct, value, ct_scale, batch, out=None):
+        """ct + value in every slot, value complex, ct at scale ct_scale"""
+        out, so = self._plain_out(level, batch, False, out)
+        v = complex(value)
+        check(lib().lsa_ckks_add_const(self.h, level, ct.ptr, 2 * (level + 1) * self.n, v.real, v.imag, float(ct_scale), out.ptr, so,
+                                       batch, self.stream))
+        return out
+
+    def ckks_affine_const(self, level, ct, alpha, const_scale, beta, ct_scale, batch, rescale=False, out=None):
+        """ct x alpha + beta in one pass (alpha at const_scale, beta at ct_scale * const_scale; then rescaled)"""
+        out, so = self._plain_out(level, batch, rescale, out)
+        a, b = complex(alpha), complex(beta)
+        check(lib().lsa_ckks_affine_const(self.h, level, ct.ptr, 2 * (level + 1) * self.n, a.real, a.imag, float(const_scale), b.real,
+                                          b.imag, float(ct_scale), out.ptr, so, batch, int(bool(rescale)), self.stream))
+        return out
+
     def bfv_mult(self, level, a, b, batch):
         L = level + 1
         out = self.alloc(batch * 3 * L * self.n)
