@@ -69,6 +69,40 @@ def straddle_chain(n, np_, order="ascending"):
     return {"n": n, "q": q, "p": p}
 
 
+def is_ceiling(m):
+    """eight products of residues fit under the lazy REDC's bound m 2^64, nine of the largest do not"""
+    return 8 * (m - 1) ** 2 < (m << 64) < 9 * (m - 1) ** 2
+
+
+def ceiling_chain(n, nq, np_):
+    """P: the np_ largest NTT primes below 2^61, Q: the next nq largest.  Every prime is at the ceiling of the
+    multiply-accumulate kernels: 8 (q - 1)^2 < q 2^64 < 9 (q - 1)^2, so a sum of nine products of the largest residues has
+    left the range the lazy REDC is written for, and a fold that comes one term late shows."""
+    pr = params.ntt_primes_below(61, n, nq + np_)
+    p, q = pr[:np_], pr[np_:]
+    assert len(set(pr)) == nq + np_ and all(params._is_prime(m) and (m - 1) % (2 * n) == 0 and m >> 61 == 0 for m in pr)
+    assert all(is_ceiling(m) for m in pr), [m for m in pr if not is_ceiling(m)]
+    return {"n": n, "q": q, "p": p}
+
+
+def ceiling_mixed_chain(n, np_):
+    """Q alternates ceiling primes with the 30-, 40-, 47- and 48-bit classes of straddle_chain (9 primes, a ceiling prime at
+    every even position, the largest small primes first); P: the np_ largest primes below 2^61.  Over the levels a 61-bit limb
+    is dropped onto 61-bit targets (near) and onto small ones (not near), and a small limb onto 61-bit targets."""
+    pr = params.ntt_primes_below(61, n, np_ + 5)
+    p, big = pr[:np_], pr[np_:]
+    small = [params.ntt_primes_below(b, n, 1)[0] for b in (48, 47, 40, 30)]
+    q = [x for pair in zip(big, small + [None]) for x in pair if x is not None]
+    assert len(set(q + p)) == 9 + np_ and all(params._is_prime(m) and (m - 1) % (2 * n) == 0 for m in q + p)
+    assert all(is_ceiling(m) for m in big + p) and [m.bit_length() for m in small] == [48, 47, 40, 30]
+    drops = {(is_ceiling(q[l]), is_ceiling(q[i])) + head_flags(q[l], q[i]) for l in range(1, len(q)) for i in range(l)}
+    assert (True, True, True, False) in drops, "a 61-bit limb dropped onto a 61-bit target: near"
+    assert any(d[:3] == (True, False, False) for d in drops), "a 61-bit limb dropped onto a small target: not near"
+    assert any(d[:2] == (False, True) and d[2] for d in drops), "a small limb dropped onto a 61-bit target"
+    assert {d[3] for d in drops} == {True, False}, "fp_lift"
+    return {"n": n, "q": q, "p": p}
+
+
 def pattern(name, q, n, rng):
     """one limb-polynomial of n residues modulo q"""
     q = int(q)
@@ -113,3 +147,44 @@ def pattern_ct(names, mods, polys, n, rng, oracle=None):
 def pattern_key(name, mods, beta, n, rng):
     """a switching key [beta][2][len(mods)][n] whose every limb carries the pattern"""
     return pattern_ct([name] * beta, mods, 2, n, rng)
+
+
+# ---------------------------------------------------------------- the long sums at the ceiling (tests/test_gpu_ceiling.py, cases A and B)
+
+CEILING_SLOTS = ("top", "uniform", "top")     # the batch: two worst-case slots around a uniform control
+MAC_TERMS = (8, 9, 16, 17, 33)                # on both sides of the fold at 8, of the launch bound 16, and two launches + 1
+DOT_TERMS = (4, 5, 8, 9, 16, 17, 33)          # ... and of d1's fold at 4
+CEILING_LOGN = {8: 12, 9: 13, 16: 12, 17: 13, 33: 12, 4: 12, 5: 13}   # the ring each term count runs at
+
+
+def ceiling_mac_operands(logn):
+    """case A: ceiling_chain with 4 Q limbs; three ciphertext batches [3][2][4][N] and four plaintext batches [3][4][N] in the
+    CEILING_SLOTS patterns, the addend all q - 1.  Term i of a sum multiplies ciphertext i % 3 by plaintext i % 4; every third
+    plaintext (i % 3 == 2) is batch item 0 for the whole batch."""
+    n = 1 << logn
+    C = ceiling_chain(n, 4, 1)
+    rng = np.random.default_rng(6100 + logn)
+    cts = [pattern_ct(CEILING_SLOTS, C["q"], 2, n, rng) for _ in range(3)]
+    pts = [pattern_ct(CEILING_SLOTS, C["q"], 1, n, rng)[:, 0] for _ in range(4)]
+    addend = pattern_ct(("max",) * len(CEILING_SLOTS), C["q"], 2, n, rng)
+    return C, cts, pts, addend
+
+
+def mac_term(i):
+    """(ciphertext, plaintext, shared) of term i"""
+    return i % 3, i % 4, i % 3 == 2
+
+
+def ceiling_dot_operands(logn):
+    """case B: the same chain; three a and three b ciphertext batches; term i is a[i % 3] (x) b[(2 i + 1) % 3] (nine pairs)"""
+    n = 1 << logn
+    C = ceiling_chain(n, 4, 1)
+    rng = np.random.default_rng(6200 + logn)
+    As = [pattern_ct(CEILING_SLOTS, C["q"], 2, n, rng) for _ in range(3)]
+    Bs = [pattern_ct(CEILING_SLOTS, C["q"], 2, n, rng) for _ in range(3)]
+    addend = pattern_ct(("max",) * len(CEILING_SLOTS), C["q"], 2, n, rng)
+    return C, As, Bs, addend
+
+
+def dot_term(i):
+    return i % 3, (2 * i + 1) % 3

@@ -116,11 +116,12 @@ def test_plain_transform_skip_rows(logn):
 
 # ---------------------------------------------------------------- CKKS rescale, three steps, fused operator
 
-def _ckks_levels(n, order, levels, seed, np_=3, tiles=(1, 2)):
+def _ckks_levels(n, order, levels, seed, np_=3, tiles=(1, 2), chain=None):
+    """chain: another {"q", "p"} than straddle_chain(n, np_, order); `order` then only picks the key pattern and the combos"""
     from lattisense_amd._native import check, lib
     from lattisense_amd.device import ALGO_CKKS, DeviceContext
     from oracle.pyoracle import Oracle
-    C = straddle_chain(n, np_, order)
+    C = chain if chain is not None else straddle_chain(n, np_, order)
     q, p = C["q"], C["p"]
     o = Oracle(n, q, p, 0)
     rng = np.random.default_rng(seed)

@@ -21,6 +21,10 @@ def _chain(name):
     if name == "headline":                    # 13 Q limbs of the FP64 engine (q < 2^47 but q_0) + 4 P
         P = params.CKKS_DEFAULT[65536]
         return P["q"][:13], P["p"]
+    if name == "ceiling":                     # N = 2^13: every Q and P prime within 2^23 of 2^61 (tests/boundary.py)
+        from tests.boundary import ceiling_chain
+        C = ceiling_chain(1 << 13, 4, 2)
+        return C["q"], C["p"]
     B = params.CKKS_BOOTSTRAP_65536           # 60- and 61-bit primes next to 40-bit ones: integer engine, unfused key MAC
     return B["q"][:8], B["p"]
 
@@ -165,6 +169,18 @@ def test_whole_limb_rings(log_n, monkeypatch):
         _check(rig, 5, _diags(rng, range(200), P), P, n1=16, env_variants=SWITCHES[2:3], monkeypatch=monkeypatch, seed=2)
     else:
         _check(rig, 12, _diags(rng, range(64), P), P, n1=8, env_variants=SWITCHES[1:2], monkeypatch=monkeypatch, seed=2)
+
+
+def test_ceiling_chain(monkeypatch):
+    """N = 2^13, four Q limbs and two special primes at the 61-bit ceiling, plaintexts at the scale q_3: the moduli of
+    k_mac_plain_multi, the scattering key MAC and the extended ModDown at the ceiling (the plaintext words are encoder outputs,
+    not worst-case residues)"""
+    need_gpu()
+    rig = Rig(13, "ceiling", 61)
+    rng = np.random.default_rng(61)
+    P = rig.N // 2
+    _check(rig, 3, _diags(rng, range(-3, 4), P), P, env_variants=SWITCHES, monkeypatch=monkeypatch, seed=61)
+    _check(rig, 3, _diags(rng, range(64), P), P, n1=8, double_hoist=False, seed=62)
 
 
 @pytest.mark.parametrize("chain,level,index", [("headline", 12, list(range(64))), ("headline", 12, list(range(200))),

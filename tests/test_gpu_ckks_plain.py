@@ -4,8 +4,9 @@ mul_const / add_const / mul_by_i) and, for the encoder, against lsa_lt_plaintext
 arithmetic on the same operands, so every comparison is word for word: no tolerance anywhere.
 
 Rings: N = 2^12 (one-pass transform) on the smallest chain of params.py (CKKS_DEFAULT[4096]: 37- and 32-bit primes, FP64 engine),
-and N = 2^13 (two-pass transform, so the lifted rows and the selector monomial go through it) on a 60-bit prime followed by three
-40-bit primes of the bootstrap chain (integer and FP64 engines side by side).  Batch 3, output strides larger than the compact
+N = 2^13 (two-pass transform, so the lifted rows and the selector monomial go through it) on a 60-bit prime followed by three
+40-bit primes of the bootstrap chain (integer and FP64 engines side by side), and N = 2^13 on four primes at the 61-bit ceiling
+(tests/boundary.py ceiling_chain; the end-to-end scales are chosen for that modulus).  Batch 3, output strides larger than the compact
 size (the padding must stay untouched), plaintexts shared by the batch (stride 0) and per item, levels top and 1.
 Ciphertext and plaintext words are uniform residues: the operators are exact modular arithmetic on whatever words they get."""
 import ctypes
@@ -30,6 +31,10 @@ def _chain(name):
     if name == "n12":
         P = params.CKKS_DEFAULT[4096]
         return 12, P["q"], P["p"]
+    if name == "n13c":
+        from tests.boundary import ceiling_chain
+        C = ceiling_chain(1 << 13, 4, 1)
+        return 13, C["q"], C["p"]
     B = params.CKKS_BOOTSTRAP_65536
     return 13, B["q"][:4], B["p"][:1]
 
@@ -41,6 +46,7 @@ class Rig:
         from oracle.client import Client
         from oracle.pyoracle import Oracle
         log_n, self.q, self.p = _chain(name)
+        self.name = name
         self.N = 1 << log_n
         self.top = len(self.q) - 1
         self.levels = sorted({self.top, 1})
@@ -78,7 +84,7 @@ class Rig:
 _RIGS = {}
 
 
-@pytest.fixture(params=["n12", "n13"])
+@pytest.fixture(params=["n12", "n13", "n13c"])
 def rig(request):
     need_gpu()
     if request.param not in _RIGS:
@@ -403,7 +409,7 @@ def test_overlap_and_argument_refusals(rig):
         ctx.ckks_add_const(lvl, ct, 2.0, D40, b, out=sent)
         ctx.ckks_affine_const(lvl, ct, 2.0, D20, 1.0, D20, b, out=sent)
     assert np.all(ctx.download(sent, (BATCH * so,)) == SENT)
-    if rig.N == 1 << 13:                                              # a BFV context: once is enough
+    if rig.name == "n13":                                             # a BFV context: once is enough
         B = params.BFV_DEFAULT[8192]
         bfv = DeviceContext(ALGO_BFV, 8192, B["q"], B["p"], B["t"])
         x, y = bfv.alloc(2 * 3 * 8192), bfv.alloc(2 * 3 * 8192)
@@ -424,7 +430,8 @@ def test_encrypt_affine_mult_plain_rescale_decrypt(rig):
     ctx, N, ev, c = rig.ctx, rig.N, rig.ev, rig.c
     lvl = rig.top
     L = lvl + 1
-    s_ct, s_k, s_pt = (float(2 ** 20), float(2 ** 10), float(2 ** 20)) if N == 1 << 12 else (float(2 ** 30), float(2 ** 20), float(2 ** 30))
+    s_ct, s_k, s_pt = {"n12": (float(2 ** 20), float(2 ** 10), float(2 ** 20)), "n13": (float(2 ** 30), float(2 ** 20), float(2 ** 30)),
+                       "n13c": (float(2 ** 40), float(2 ** 21), float(2 ** 40))}[rig.name]   # n13c: 2^101 / q_3 leaves 2^40
     rng = np.random.default_rng(N)
     z = rng.uniform(-1, 1, N // 2) + 1j * rng.uniform(-1, 1, N // 2)
     wts = rng.uniform(-1, 1, N // 2) + 1j * rng.uniform(-1, 1, N // 2)

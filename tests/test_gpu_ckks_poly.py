@@ -25,6 +25,10 @@ def _chain(name):
     if name == "headline":                    # 13 Q limbs of the FP64 engine (q ~ 2^45 but q_0) + 4 P
         P = params.CKKS_DEFAULT[65536]
         return P["q"][:13], P["p"], float(2 ** 45)
+    if name == "ceiling":                     # N = 2^13: every Q and P prime within 2^23 of 2^61 (tests/boundary.py)
+        from tests.boundary import ceiling_chain
+        C = ceiling_chain(1 << 13, 6, 2)
+        return C["q"], C["p"], float(2 ** 61)
     B = params.CKKS_BOOTSTRAP_65536           # a 60-bit prime and 40-bit ones with 60/61-bit special primes: integer engine
     return B["q"][:8], B["p"], float(2 ** 40)
 
@@ -194,6 +198,16 @@ def test_bootstrap_chain_primes(monkeypatch):
     _check(rig, _dense(rng, 8), "chebyshev", 0, env_variants=SWITCHES, fp64_variants=(1, 0), monkeypatch=monkeypatch, seed=4)
     _check(rig, _dense(rng, 8), "monomial", 3, seed=5)
     _check(rig, _dense(rng, 8), "chebyshev", 1, pin=True, seed=6)
+
+
+def test_ceiling_chain(monkeypatch):
+    """N = 2^13, six Q limbs and two special primes at the 61-bit ceiling, scale 2^61: the moduli of k_poly_lincomb, of the
+    tensor and of the key switch at the ceiling (the constants are the plan's, not worst-case residues)"""
+    need_gpu()
+    rig = Rig(13, "ceiling", 83)
+    rng = np.random.default_rng(18)
+    _check(rig, _dense(rng, 8), "chebyshev", 0, env_variants=SWITCHES, fp64_variants=(1, 0), monkeypatch=monkeypatch, seed=7)
+    _check(rig, _dense(rng, 8), "monomial", 1, pin=True, seed=8)
 
 
 def test_batch_positions_and_strides():
