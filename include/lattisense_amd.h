@@ -75,29 +75,58 @@ size_t lsa_key_bytes(lsa_context ctx, int key_level);
 int lsa_ntt(lsa_context ctx, uint64_t* data, int batch, long long batch_stride, int rows, const int* mod_of,
             int period, int inverse, void* stream);
 
-/* ---- K3: limb-wise add / sub / negate over `polys` polynomials of level+1 limbs (ct+ct, ct-ct, -ct).
- * op: 0 add, 1 sub, 2 neg (b ignored).  Replaces HEArithmeticOperator::add/sub/negate (executors_gpu.cu:79-173). */
+/* ---- Layout and aliasing: the contract of the first-generation operators -- lsa_poly_addsub, lsa_ckks_mult / _relin / _rescale /
+ * _rotate / _rotate_many / _mult_relin_rescale, lsa_drop_level, lsa_bfv_mult / _relin / _rotate / _rescale / _mult_relin.  The library's
+ * own callers of these operators (task runtime, bootstrapping, linear transform, polynomial evaluation) go through the same checks;
+ * the task runtime's add / sub / negate, CKKS ct x ct tensor and multi-level drop launch their kernels directly, on slabs of its own.
+ *   Operands.  Item b of an operand is the `words` words at base + b * stride (stride in words): any base inside an allocation, any
+ *     stride >= one item, padding is never read or written.  The kernels move 16 bytes per lane, so every base is 16-byte aligned
+ *     and every stride even.
+ *   Shared operands.  A stride of 0 on an INPUT means one operand for the whole batch.  Accepted on a and b of lsa_poly_addsub,
+ *     lsa_ckks_mult, lsa_ckks_mult_relin_rescale (folded and unfolded paths), lsa_bfv_mult and lsa_bfv_mult_relin, whose kernels index
+ *     base + b * stride and nothing else; a == b (squaring, doubling) is allowed with any strides.  The one-input operators (relin,
+ *     rescale, rotate, rotate_many, drop_level) refuse it: batch copies of one result are no use, and "the output is the input"
+ *     would stop meaning one thing.  An output stride of 0 is always refused.
+ *   Overlap is exact: two operands overlap when an item of one shares a word with an item of the other.  Padding belongs to
+ *     nobody, so operands may interleave (an output slab between two far-apart inputs is fine).
+ *       lsa_poly_addsub: out may BE a and / or b (same pointer, same stride; element-wise), otherwise it overlaps neither.
+ *       lsa_ckks_rotate, lsa_bfv_rotate: out may BE in (same pointer, same stride; the rotation then runs in two steps through the
+ *         workspace), otherwise no overlap.
+ *       lsa_ckks_rotate_many: outputs overlap each other nowhere; each is apart from the input or IS the input -- so at most one is, and
+ *         that rotation is computed last, from the intact input, in two steps.  (lsa_bfv_rotate_many: the same rule.)
+ *       every other one: the output overlaps no input.  In particular rescale and drop_level store rows at other offsets than they
+ *         load them, so an in-place call would corrupt rows still to be read.
+ *   Refused with LSA_ERR_ARG before any kernel or copy is queued, the message beginning with the entry point's name: a null pointer
+ *     (except b with op neg) or key; a stride that is non-zero and below one item, negative, odd, or 0 where not accepted; a pointer
+ *     off the 16-byte grid; a level out of range (0..max, from 1 for rescale, drop_level, mult_relin_rescale); a key exported below
+ *     `level`; polys outside 1..3; a context of the other scheme (lsa_poly_addsub and lsa_drop_level serve both); a forbidden
+ *     overlap.  A refused call leaves every buffer untouched and the context usable.
+ *   batch <= 0 returns LSA_OK and touches nothing (scheme, level, polys and op are still checked). */
+/* ---- K3: limb-wise add / sub / negate over `polys` (1..3) polynomials of level+1 limbs (ct+ct, ct-ct, -ct).
+ * op: 0 add, 1 sub, 2 neg (b ignored, may be null).  out may be a and / or b.  Either scheme.
+ * Replaces HEArithmeticOperator::add/sub/negate (executors_gpu.cu:79-173). */
 int lsa_poly_addsub(lsa_context ctx, int op, int level, int polys, const uint64_t* a, const uint64_t* b,
                     uint64_t* out, int batch, long long stride_a, long long stride_b, long long stride_out,
                     void* stream);
 
 /* ---- CKKS (NTT-domain ciphertexts) ---------------------------------------------------------------------- */
-/* multiply (executors_gpu.cu:185,223): a,b = [2][L][N] -> d3 = [3][L][N] */
+/* multiply (executors_gpu.cu:185,223): a,b = [2][L][N] -> d3 = [3][L][N]; stride_a / stride_b 0: shared; d3 overlaps no input */
 int lsa_ckks_mult(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, uint64_t* d3, int batch,
                   long long stride_a, long long stride_b, long long stride_d, void* stream);
-/* relinearize (executors_gpu.cu:236): d3 -> out [2][L][N] */
+/* relinearize (executors_gpu.cu:236): d3 -> out [2][L][N]; out overlaps no input */
 int lsa_ckks_relin(lsa_context ctx, int level, const uint64_t* d3, lsa_key rlk, uint64_t* out, int batch,
                    long long stride_d, long long stride_out, void* stream);
-/* rescale (executors_gpu.cu:246): in [polys][L][N] -> out [polys][L-1][N] */
+/* rescale (executors_gpu.cu:246): in [polys][L][N] -> out [polys][L-1][N], level >= 1, polys 1..3; never in place */
 int lsa_ckks_rescale(lsa_context ctx, int level, int polys, const uint64_t* in, uint64_t* out, int batch,
                      long long stride_in, long long stride_out, void* stream);
-/* rotate_rows / conjugate (executors_gpu.cu:275,289): Galois element g, key of that element */
+/* rotate_rows / conjugate (executors_gpu.cu:275,289): Galois element g, key of that element; out may be in (same stride) */
 int lsa_ckks_rotate(lsa_context ctx, int level, const uint64_t* in, uint64_t galois_element, lsa_key glk,
                     uint64_t* out, int batch, long long stride_in, long long stride_out, void* stream);
-/* mod_drop (executors_gpu.cu:257): keep the first L-1 limbs of each polynomial */
+/* mod_drop (executors_gpu.cu:257): keep the first L-1 limbs of each polynomial, level >= 1, polys 1..3; either scheme; never in place */
 int lsa_drop_level(lsa_context ctx, int level, int polys, const uint64_t* in, uint64_t* out, int batch,
                    long long stride_in, long long stride_out, void* stream);
-/* fused HMult + relinearize + rescale: the BASELINE.json headline operator. out = [2][L-1][N] */
+/* fused HMult + relinearize + rescale: the BASELINE.json headline operator. out = [2][L-1][N], level >= 1; stride_a / stride_b 0:
+ * shared; out overlaps no input */
 int lsa_ckks_mult_relin_rescale(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, lsa_key rlk,
                                 uint64_t* out, int batch, long long stride_a, long long stride_b,
                                 long long stride_out, void* stream);
@@ -164,6 +193,8 @@ int lsa_ckks_affine_const(lsa_context ctx, int level, const uint64_t* ct, long l
                           void* stream);
 
 /* ---- BFV (coefficient-domain ciphertexts) ---------------------------------------------------------------- */
+/* Shapes as for their CKKS namesakes, layout and aliasing as stated above: mult and mult_relin take shared operands (stride 0) and
+ * overlap no input, relin and rescale overlap no input, rotate's out may be in (same stride). */
 int lsa_bfv_mult(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, uint64_t* d3, int batch,
                  long long stride_a, long long stride_b, long long stride_d, void* stream);
 int lsa_bfv_relin(lsa_context ctx, int level, const uint64_t* d3, lsa_key rlk, uint64_t* out, int batch,
@@ -214,7 +245,8 @@ int lsa_set_fuse_tails(lsa_context ctx, int enable);
  * second pass is served by the 256 MiB Infinity Cache (0 = one launch per pass over the whole batch). */
 int lsa_set_ntt_chunk_mib(lsa_context ctx, int mib);
 /* Rotations of the same ciphertexts by several Galois elements with ONE decomposition of the input ("hoisting"):
- * outs[i] = rotate(in, galois_elements[i]), each bit-identical to lsa_ckks_rotate's result. */
+ * outs[i] = rotate(in, galois_elements[i]), each bit-identical to lsa_ckks_rotate's result.  The outputs (all with stride sout)
+ * overlap each other nowhere; at most one may BE the input (same pointer, sout == sin), every other one is apart from it. */
 int lsa_ckks_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_rot, const uint64_t* galois_elements,
                          const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream);
 /* The same for BFV (coefficient-domain ciphertexts): outs[i] = rotate(in, galois_elements[i]), each bit-identical to

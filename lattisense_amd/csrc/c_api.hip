@@ -44,8 +44,8 @@ static Context& C(lsa_context h) {
     h->ctx.use_device();
     return h->ctx;
 }
-static const Key& K(lsa_key k) {
-    LSA_REQUIRE(k != nullptr && k->key.data != nullptr, "null key");
+static const Key& K(lsa_key k, const char* who = nullptr) {
+    LSA_REQUIRE(k != nullptr && k->key.data != nullptr, who ? std::string(who) + ": null key" : std::string("null key"));
     return k->key;
 }
 static hipStream_t S(void* s) { return (hipStream_t)s; }
@@ -237,7 +237,7 @@ int lsa_ckks_mult(lsa_context ctx, int level, const uint64_t* a, const uint64_t*
 }
 int lsa_ckks_relin(lsa_context ctx, int level, const uint64_t* d3, lsa_key rlk, uint64_t* out, int batch, long long sd,
                    long long so, void* stream) {
-    return guard([&] { ckks_relin(C(ctx), level, d3, K(rlk), out, batch, sd, so, S(stream)); });
+    return guard([&] { ckks_relin(C(ctx), level, d3, K(rlk, "lsa_ckks_relin"), out, batch, sd, so, S(stream)); });
 }
 int lsa_ckks_rescale(lsa_context ctx, int level, int polys, const uint64_t* in, uint64_t* out, int batch, long long si,
                      long long so, void* stream) {
@@ -245,7 +245,7 @@ int lsa_ckks_rescale(lsa_context ctx, int level, int polys, const uint64_t* in, 
 }
 int lsa_ckks_rotate(lsa_context ctx, int level, const uint64_t* in, uint64_t g, lsa_key glk, uint64_t* out, int batch,
                     long long si, long long so, void* stream) {
-    return guard([&] { ckks_rotate(C(ctx), level, in, g, K(glk), out, batch, si, so, S(stream)); });
+    return guard([&] { ckks_rotate(C(ctx), level, in, g, K(glk, "lsa_ckks_rotate"), out, batch, si, so, S(stream)); });
 }
 int lsa_drop_level(lsa_context ctx, int level, int polys, const uint64_t* in, uint64_t* out, int batch, long long si,
                    long long so, void* stream) {
@@ -253,7 +253,7 @@ int lsa_drop_level(lsa_context ctx, int level, int polys, const uint64_t* in, ui
 }
 int lsa_ckks_mult_relin_rescale(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, lsa_key rlk,
                                 uint64_t* out, int batch, long long sa, long long sb, long long so, void* stream) {
-    return guard([&] { ckks_mult_relin_rescale(C(ctx), level, a, b, K(rlk), out, batch, sa, sb, so, S(stream)); });
+    return guard([&] { ckks_mult_relin_rescale(C(ctx), level, a, b, K(rlk, "lsa_ckks_mult_relin_rescale"), out, batch, sa, sb, so, S(stream)); });
 }
 
 // ---- CKKS encrypted inner product (ops.hip ckks_mult_sum / ckks_dot)
@@ -336,11 +336,11 @@ int lsa_bfv_mult(lsa_context ctx, int level, const uint64_t* a, const uint64_t* 
 }
 int lsa_bfv_relin(lsa_context ctx, int level, const uint64_t* d3, lsa_key rlk, uint64_t* out, int batch, long long sd,
                   long long so, void* stream) {
-    return guard([&] { bfv_relin(C(ctx), level, d3, K(rlk), out, batch, sd, so, S(stream)); });
+    return guard([&] { bfv_relin(C(ctx), level, d3, K(rlk, "lsa_bfv_relin"), out, batch, sd, so, S(stream)); });
 }
 int lsa_bfv_rotate(lsa_context ctx, int level, const uint64_t* in, uint64_t g, lsa_key glk, uint64_t* out, int batch,
                    long long si, long long so, void* stream) {
-    return guard([&] { bfv_rotate(C(ctx), level, in, g, K(glk), out, batch, si, so, S(stream)); });
+    return guard([&] { bfv_rotate(C(ctx), level, in, g, K(glk, "lsa_bfv_rotate"), out, batch, si, so, S(stream)); });
 }
 int lsa_bfv_rescale(lsa_context ctx, int level, int polys, const uint64_t* in, uint64_t* out, int batch, long long si,
                     long long so, void* stream) {
@@ -348,14 +348,7 @@ int lsa_bfv_rescale(lsa_context ctx, int level, int polys, const uint64_t* in, u
 }
 int lsa_bfv_mult_relin(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, lsa_key rlk, uint64_t* out,
                        int batch, long long sa, long long sb, long long so, void* stream) {
-    return guard([&] {
-        Context& c = C(ctx);
-        const long long sd = 3LL * (level + 1) * c.n;
-        // d3 lives in the second arena so that the two pipelines' own arena use cannot overlap it
-        u64* d3 = c.workspace2((size_t)sd * batch, S(stream));
-        bfv_mult(c, level, a, b, d3, batch, sa, sb, sd, S(stream));
-        bfv_relin(c, level, d3, K(rlk), out, batch, sd, so, S(stream));
-    });
+    return guard([&] { bfv_mult_relin(C(ctx), level, a, b, K(rlk, "lsa_bfv_mult_relin"), out, batch, sa, sb, so, S(stream)); });
 }
 
 int lsa_profile_begin(lsa_context ctx, int stride) {
@@ -447,11 +440,11 @@ int lsa_debug_key_switch_fused(lsa_context ctx, int level, lsa_key key, int* fus
 int lsa_ckks_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_rot, const uint64_t* galois_elements,
                          const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(in != nullptr && n_rot >= 0 && (n_rot == 0 || (galois_elements && glk && outs)), "null argument");
+        LSA_REQUIRE(in != nullptr && n_rot >= 0 && (n_rot == 0 || (galois_elements && glk && outs)), "lsa_ckks_rotate_many: null argument");
         std::vector<const Key*> keys(n_rot);
         for (int i = 0; i < n_rot; i++) {
-            LSA_REQUIRE(glk[i] != nullptr && outs[i] != nullptr, "null key or output");
-            keys[i] = &K(glk[i]);
+            LSA_REQUIRE(glk[i] != nullptr && outs[i] != nullptr, "lsa_ckks_rotate_many: null key or output");
+            keys[i] = &K(glk[i], "lsa_ckks_rotate_many");
         }
         ckks_rotate_many(C(ctx), level, in, n_rot, galois_elements, keys.data(), outs, batch, sin, sout, S(stream));
     });

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "layout_check.h"
 #include "linear_transform.h"
 
 namespace lsa {
@@ -544,9 +545,8 @@ void lt_run(LinearTransform& lt, const u64* in, long long sin, u64* out, long lo
     const int level = lt.m.level, out_level = rescale ? level - 1 : level;
     LSA_REQUIRE(!rescale || level >= 1, "linear transform: a rescale needs level >= 1");
     LSA_REQUIRE(sin >= 2LL * (level + 1) * N && sout >= 2LL * (out_level + 1) * N, "linear transform: batch stride shorter than a ciphertext");
-    const u64* in_end = in + (size_t)(batch - 1) * sin + 2LL * (level + 1) * N;
-    const u64* out_end = out + (size_t)(batch - 1) * sout + 2LL * (out_level + 1) * N;
-    LSA_REQUIRE(out_end <= in || in_end <= out, "linear transform: out overlaps in");
+    LSA_REQUIRE(layout::apart(out, sout, 2 * (size_t)(out_level + 1) * N, in, sin, 2 * (size_t)(level + 1) * N, batch),
+                "linear transform: out overlaps in");
     LtEval ev(c, lt.pool, s, batch, glk, "linear transform");
     ev.giant_scatter = lt_giant_scatter();
     DCt x;

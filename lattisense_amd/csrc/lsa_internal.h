@@ -416,6 +416,11 @@ void bootstrap_run(Bootstrap& bt, const u64* in, long long sin, u64* out, long l
 
 // ---------------------------------------------------------------- operator pipelines (ops.hip)
 const std::string& last_error();
+// The first-generation operators below (mult, relin, rescale, rotate(_many), drop_level, addsub, mult_relin(_rescale), both
+// schemes) check their own arguments -- scheme, level, polys, null / short / odd / misaligned operands, overlap -- before anything
+// is queued, and return at once for batch <= 0: the contract of include/lattisense_amd.h, "Layout and aliasing".  Internal
+// callers of these functions get the same refusals as the C entry points.  (task_dispatch.hip launches k_elementwise, k_tensor and
+// k_copy_rows itself for add / sub / negate, the CKKS tensor and a drop of several levels: those paths do not come through here.)
 void ckks_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int batch, long long sa, long long sb, long long sd,
                hipStream_t s);
 void ckks_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, int batch, long long sd, long long so,
@@ -483,6 +488,8 @@ void bfv_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int ba
               hipStream_t s);
 void bfv_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, int batch, long long sd, long long so,
                hipStream_t s);
+void bfv_mult_relin(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch, long long sa,
+                    long long sb, long long so, hipStream_t s);
 void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, int batch, long long sin,
                 long long sout, hipStream_t s);
 void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,

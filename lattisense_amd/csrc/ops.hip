@@ -6,6 +6,7 @@
 //   CKKS rescale = divide-and-round by the last prime (DivRoundByLastModulusNTT)
 //   rotate      = key-switch c1, add c0, then apply the automorphism (Evaluator.Automorphism)
 //   BFV mult    = centred extension Q->QMul, tensor in Q u QMul, round(./Q), centred return to Q, times t
+#include "layout_check.h"
 #include "linear_transform.h"
 #include "lsa_internal.h"
 #include "plain_ops.h"
@@ -424,17 +425,74 @@ static void for_tiles(Context& c, size_t rows_per_ct, int batch, hipStream_t s, 
     if (dual) c.join_aux(s);
 }
 
+// ------------------------------------------------------------------------------------------------ argument checks
+// The layout, overlap and argument contract of the first-generation entry points (include/lattisense_amd.h, "Layout and
+// aliasing"), checked in the operators themselves so that the task dispatcher and the plan runners get it too.  Everything is
+// decided on the host before a kernel or a copy is queued; every refusal is LSA_ERR_ARG with a message that begins with the entry
+// point's name.  The span arithmetic is layout_check.h's.
+namespace {
+using layout::Span;
+
+struct EntryCheck {
+    const Context& c;
+    std::string who;
+    int level, batch;
+    size_t N;
+    // algo: LSA_ALGO_BFV / LSA_ALGO_CKKS, or -1 for an operator both schemes use; min_level: 1 for the operators that drop a limb
+    EntryCheck(const Context& c_, const char* who_, int algo, int level_, int min_level, int batch_)
+        : c(c_), who(who_), level(level_), batch(batch_), N((size_t)c_.n) {
+        LSA_REQUIRE(algo < 0 || c.algo == algo, who + (algo == LSA_ALGO_BFV ? ": context is not BFV" : ": context is not CKKS"));
+        LSA_REQUIRE(level >= min_level && level < c.nq,
+                    who + ": level out of range (" + std::to_string(min_level) + ".." + std::to_string(c.nq - 1) + ")");
+    }
+    void polys(int polys) const {   // a plaintext or one polynomial, a ciphertext, a degree-2 ciphertext
+        LSA_REQUIRE(polys >= 1 && polys <= 3, who + ": polys must be 1, 2 or 3");
+    }
+    void key(const Key& k, const char* what) const {
+        LSA_REQUIRE(k.data != nullptr, who + ": " + what + " is null");
+        LSA_REQUIRE(k.level >= level, who + ": " + what + " was exported at a lower level than the ciphertext");
+    }
+    // an operand of `words` words per batch item; shared_ok: a batch stride of 0 (one operand for the whole batch) is accepted
+    Span operand(const u64* p, long long stride, size_t words, const char* what, bool shared_ok) const {
+        LSA_REQUIRE(p != nullptr, who + ": " + what + " is null");
+        const Span sp = layout::span_of(p, stride, words);
+        LSA_REQUIRE(layout::stride_ok(sp, shared_ok), who + ": batch stride of " + what +
+                                                          (shared_ok ? " below one operand (0: shared by the batch)" : " below one operand"));
+        // the element-wise kernels move 16 bytes per lane at base + item * stride
+        LSA_REQUIRE(layout::aligned16(sp), who + ": " + what + " must be 16-byte aligned with an even batch stride");
+        return sp;
+    }
+    Span output(const u64* p, long long stride, size_t words, const char* what = "out") const { return operand(p, stride, words, what, false); }
+    void apart(const Span& out, const Span& in, const char* what) const {
+        LSA_REQUIRE(layout::apart(out, in, batch), who + ": the output overlaps " + what);
+    }
+    void same_or_apart(const Span& out, const Span& in, const char* what) const {
+        LSA_REQUIRE(layout::same_or_apart(out, in, batch),
+                    who + ": the output must be " + what + " itself (same pointer, same stride) or not overlap it");
+    }
+};
+}  // namespace
+
 // ================================================================================================ CKKS
 void ckks_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int batch, long long sa, long long sb,
                long long sd, hipStream_t s) {
-    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    const EntryCheck ck(c, "lsa_ckks_mult", LSA_ALGO_CKKS, level, 0, batch);
+    if (batch <= 0) return;
+    const size_t w = 2 * (size_t)(level + 1) * ck.N;
+    const Span out = ck.output(d3, sd, w / 2 * 3, "d3");
+    ck.apart(out, ck.operand(a, sa, w, "a", true), "a");
+    ck.apart(out, ck.operand(b, sb, w, "b", true), "b");
     launch_tensor(c, a, b, d3, batch, sa, sb, sd, level + 1, rm_seq(level + 1), s);
 }
 
 void ckks_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, int batch, long long sd, long long so,
                 hipStream_t s) {
+    const EntryCheck ck(c, "lsa_ckks_relin", LSA_ALGO_CKKS, level, 0, batch);
+    ck.key(rlk, "the relinearisation key");
+    if (batch <= 0) return;
     const long long N = c.n;
     const int L = level + 1;
+    ck.apart(ck.output(out, so, 2 * (size_t)L * N), ck.operand(d3, sd, 3 * (size_t)L * N, "d3", false), "d3");
     for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* d = d3 + (size_t)b0 * sd;
         key_switch(c, level, d + 2LL * L * N, sd, rlk, {.p = out + (size_t)b0 * so, .sp = so, .base = d, .sbase = sd, .base_rpp = L, .base_polys = 2},
@@ -444,6 +502,11 @@ void ckks_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, 
 
 void ckks_rescale(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                   hipStream_t s) {
+    // (the output's rows sit at other offsets than the input's: an in-place call would store over rows still to be read)
+    const EntryCheck ck(c, "lsa_ckks_rescale", LSA_ALGO_CKKS, level, 1, batch);
+    ck.polys(polys);
+    if (batch <= 0) return;
+    ck.apart(ck.output(out, sout, (size_t)polys * level * ck.N), ck.operand(in, sin, (size_t)polys * (level + 1) * ck.N, "in", false), "in");
     for_tiles(c, rescale_ws_rows(level, polys), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         rescale(c, level, polys, in + (size_t)b0 * sin, sin, out + (size_t)b0 * sout, sout, nb, true, ws, st);
     });
@@ -451,12 +514,18 @@ void ckks_rescale(Context& c, int level, int polys, const u64* in, u64* out, int
 
 void ckks_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, int batch, long long sin,
                  long long sout, hipStream_t s) {
+    const EntryCheck ck(c, "lsa_ckks_rotate", LSA_ALGO_CKKS, level, 0, batch);
+    ck.key(glk, "the Galois key");
+    if (batch <= 0) return;
     const long long N = c.n;
     const int L = level + 1;
     const size_t ks_rows = KsTile::rows(c, level);
     const long long sp = 2LL * L * N;
+    const Span sp_in = ck.operand(in, sin, 2 * (size_t)L * N, "in", false), sp_out = ck.output(out, sout, 2 * (size_t)L * N);
+    // out == in item for item, or no common word: a partial overlap would let one tile store over what another still reads
+    ck.same_or_apart(sp_out, sp_in, "in");
     // (an in-place rotation keeps the two-step form: the tail reads c0 from `in` while other workgroups already store)
-    const bool apart = out + (size_t)batch * sout <= in || in + (size_t)batch * sin <= out;
+    const bool apart = !layout::same(sp_out, sp_in);
     if (const u32* scatter = apart ? rotation_scatter(c, g) : nullptr) {
         // the permutation rides on the ModDown tail's store: no intermediate, no permutation kernel (2L reads + 2L writes less)
         for_tiles(c, ks_rows, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
@@ -481,15 +550,31 @@ void ckks_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u6
 // each identical to ckks_rotate's result
 void ckks_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
                       int batch, long long sin, long long sout, hipStream_t s) {
-    if (n_rot <= 0) return;
+    const EntryCheck ck(c, "lsa_ckks_rotate_many", LSA_ALGO_CKKS, level, 0, batch);
+    if (n_rot <= 0 || batch <= 0) return;
+    LSA_REQUIRE(g && glk && outs, ck.who + ": null argument");
     const long long N = c.n;
     const int L = level + 1;
     const size_t ks_rows = KsTile::rows(c, level);
     const long long sp = 2LL * L * N;
+    const Span sp_in = ck.operand(in, sin, 2 * (size_t)L * N, "in", false);
+    std::vector<Span> sp_out(n_rot);
     std::vector<const u32*> perms(n_rot), scatters(n_rot);
+    std::vector<int> order;   // the output that IS the input goes last: every other rotation still reads the intact ciphertext
+    int in_place = -1;
     for (int i = 0; i < n_rot; i++) {
-        const bool apart = outs[i] + (size_t)batch * sout <= in || in + (size_t)batch * sin <= outs[i];
-        scatters[i] = apart ? rotation_scatter(c, g[i]) : nullptr;
+        LSA_REQUIRE(glk[i] != nullptr, ck.who + ": a Galois key is null");
+        ck.key(*glk[i], "a Galois key");
+        sp_out[i] = ck.output(outs[i], sout, 2 * (size_t)L * N, "an output");
+        ck.same_or_apart(sp_out[i], sp_in, "in");
+        for (int j = 0; j < i; j++) LSA_REQUIRE(layout::apart(sp_out[i], sp_out[j], batch), ck.who + ": two outputs overlap");
+        const bool apart = !layout::same(sp_out[i], sp_in);
+        if (apart) order.push_back(i);
+        else in_place = i;   // (at most one: two of them would overlap each other)
+    }
+    if (in_place >= 0) order.push_back(in_place);
+    for (int i = 0; i < n_rot; i++) {   // (table look-ups upload on first use: only after every argument is accepted)
+        scatters[i] = i != in_place ? rotation_scatter(c, g[i]) : nullptr;
         perms[i] = scatters[i] ? nullptr : c.ntt_perm(g[i]);
     }
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
@@ -497,7 +582,7 @@ void ckks_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64
         const u64* ct = in + (size_t)b0 * sin;
         KsTile t(c, level, nb, ws, st);
         t.decompose(ct + (long long)L * N, sin);
-        for (int i = 0; i < n_rot; i++) {
+        for (int i : order) {
             t.mac(ct + (long long)L * N, sin, *glk[i]);
             if (scatters[i]) {   // the permutation rides on the ModDown tail's store
                 t.moddown({.p = outs[i] + (size_t)b0 * sout, .sp = sout, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1,
@@ -609,9 +694,17 @@ void ckks_mult_relin_rescale(Context& c, int level, const u64* a, const u64* b, 
 // rows ARE the operand at this level, so callers with operands at mixed levels (polynomial evaluation) need no copies
 void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch,
                                  long long sa, long long sb, long long so, hipStream_t s, int a_rpp, int b_rpp) {
-    LSA_REQUIRE(level >= 1, "mult+relin+rescale needs level >= 1");
+    const EntryCheck ck(c, "lsa_ckks_mult_relin_rescale", LSA_ALGO_CKKS, level, 1, batch);
+    ck.key(rlk, "the relinearisation key");
     const long long N = c.n;
     const int L = level + 1;
+    LSA_REQUIRE((a_rpp == 0 || a_rpp >= L) && (b_rpp == 0 || b_rpp >= L), ck.who + ": rows per polynomial below the limb count");
+    if (batch <= 0) return;
+    {   // an operand kept at a higher level spans its own rows per polynomial; a stride of 0 shares it with the whole batch
+        const Span sp_out = ck.output(out, so, 2 * (size_t)level * N);
+        ck.apart(sp_out, ck.operand(a, sa, 2 * (size_t)(a_rpp ? a_rpp : L) * N, "a", true), "a");
+        ck.apart(sp_out, ck.operand(b, sb, 2 * (size_t)(b_rpp ? b_rpp : L) * N, "b", true), "b");
+    }
     const bool fold = c.fuse_tails && sw::hmult_fold();
     const size_t r_d3 = (fold ? 0 : 3) * (size_t)L, r_r2 = 2 * (size_t)L;
     const size_t r_shared = std::max(KsTile::rows(c, level), rescale_ws_rows(level, 2));
@@ -623,7 +716,6 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
         if (fold) {
             const u64* ta = a + (size_t)b0 * sa;
             const u64* bt = b + (size_t)b0 * sb;
-            LSA_REQUIRE((a_rpp == 0 || a_rpp >= L) && (b_rpp == 0 || b_rpp >= L), "tensor: rows per polynomial below the limb count");
             const TensorFold tf{ta, bt, sa, sb, (long long)(a_rpp ? a_rpp : L) * N, (long long)(b_rpp ? b_rpp : L) * N};
             KsTile t(c, level, nb, sub, st, &rlk);
             t.decompose(nullptr, 0, nullptr, 0, &tf);
@@ -646,8 +738,6 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
 
 // ---- encrypted inner product: sum_i a_i (x) b_i with ONE relinearisation.  The degree-2 tensors are summed exactly (k_tensor_sum:
 // every operand row read once, d3 written once), then the sum takes the key switch and the rescale of a single HMult.
-static const u64* span_end(const u64* p, long long stride, size_t words, int batch) { return p + (size_t)(batch - 1) * stride + words; }
-
 // every argument error of the two entry points, before any work is queued; false: nothing to do (batch <= 0)
 static bool dot_check(const Context& c, int level, const DotTerms& t, bool rescale, const u64* out, long long so, size_t wout, int batch) {
     LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, "dot: context is not CKKS");
@@ -659,13 +749,12 @@ static bool dot_check(const Context& c, int level, const DotTerms& t, bool resca
     const size_t N = (size_t)c.n;
     LSA_REQUIRE(t.as && t.sas && t.bs && t.sbs && out, "dot: null argument");
     LSA_REQUIRE(so >= (long long)wout, "dot: output stride below one result");
-    const u64* out_end = span_end(out, so, wout, batch);
     auto operand = [&](const u64* p, long long stride, int rpp, const char* what) {
         LSA_REQUIRE(p != nullptr, std::string("dot: ") + what + " is null");
         LSA_REQUIRE(rpp >= L, std::string("dot: rows per polynomial of ") + what + " below level + 1");
         const size_t words = 2 * (size_t)rpp * N;
         LSA_REQUIRE(stride == 0 || stride >= (long long)words, std::string("dot: batch stride of ") + what + " below one ciphertext");
-        LSA_REQUIRE(out_end <= p || span_end(p, stride, words, batch) <= out, std::string("dot: the output overlaps ") + what);
+        LSA_REQUIRE(layout::apart(out, so, wout, p, stride, words, batch), std::string("dot: the output overlaps ") + what);
     };
     for (int i = 0; i < t.n; i++) {
         operand(t.as[i], t.sas[i], t.a_rpp && t.a_rpp[i] ? t.a_rpp[i] : L, "an operand");
@@ -729,7 +818,12 @@ void ckks_dot(Context& c, int level, const DotTerms& t, const Key& rlk, u64* out
 
 void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                 hipStream_t s) {
-    LSA_REQUIRE(level >= 1, "drop_level needs level >= 1");
+    // scheme-agnostic (a row copy).  The second polynomial's rows move towards lower addresses while other workgroups still
+    // read: in place is refused like any other overlap
+    const EntryCheck ck(c, "lsa_drop_level", -1, level, 1, batch);
+    ck.polys(polys);
+    if (batch <= 0) return;
+    ck.apart(ck.output(out, sout, (size_t)polys * level * ck.N), ck.operand(in, sin, (size_t)polys * (level + 1) * ck.N, "in", false), "in");
     std::vector<int> rows;
     for (int p = 0; p < polys; p++)
         for (int i = 0; i < level; i++) rows.push_back(p * (level + 1) + i);
@@ -738,8 +832,16 @@ void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int b
 
 void poly_addsub(Context& c, int op, int level, int polys, const u64* a, const u64* b, u64* out, int batch, long long sa,
                  long long sb, long long so, hipStream_t s) {
-    LSA_REQUIRE(op >= 0 && op <= 2, "op must be 0 add, 1 sub, 2 neg");
-    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    const EntryCheck ck(c, "lsa_poly_addsub", -1, level, 0, batch);
+    LSA_REQUIRE(op >= 0 && op <= 2, ck.who + ": op must be 0 add, 1 sub, 2 neg");
+    ck.polys(polys);
+    if (batch <= 0) return;
+    {   // element-wise: every lane reads its words before it stores them, so out may BE a or b (same pointer, same stride)
+        const size_t w = (size_t)polys * (level + 1) * ck.N;
+        const Span sp_out = ck.output(out, so, w);
+        ck.same_or_apart(sp_out, ck.operand(a, sa, w, "a", true), "a");
+        if (op != EW_NEG) ck.same_or_apart(sp_out, ck.operand(b, sb, w, "b", true), "b");   // (neg: b is ignored, null allowed)
+    }
     launch_elementwise(c, (EwOp)op, a, b, out, batch, sa, sb, so, polys * (level + 1), rm_seq(level + 1), s);
 }
 
@@ -748,11 +850,16 @@ static int bfv_aux_limbs(const Context& c, int level) { return bfv_aux_count(c.T
 
 void bfv_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int batch, long long sa, long long sb,
               long long sd, hipStream_t s0) {
-    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
-    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    const EntryCheck ck(c, "lsa_bfv_mult", LSA_ALGO_BFV, level, 0, batch);
     const long long N = c.n;
     const int L = level + 1, M = bfv_aux_limbs(c, level), T2 = L + M;
-    LSA_REQUIRE(M <= c.nmul, "auxiliary basis too small");
+    LSA_REQUIRE(M <= c.nmul, ck.who + ": auxiliary basis too small");
+    if (batch <= 0) return;
+    {   // a stride of 0 shares an operand with the whole batch: the transforms and conversions index base + item * stride
+        const Span out = ck.output(d3, sd, 3 * (size_t)L * N, "d3");
+        ck.apart(out, ck.operand(a, sa, 2 * (size_t)L * N, "a", true), "a");
+        ck.apart(out, ck.operand(b, sb, 2 * (size_t)L * N, "b", true), "b");
+    }
     const size_t rows = 2 * 2 * (size_t)T2 + 3 * (size_t)T2 + 3 * (size_t)M;
     const long long s_e = 2LL * T2 * N, s_d = 3LL * T2 * N, s_x = 3LL * M * N;
     std::vector<int> qmods, amods;
@@ -857,8 +964,12 @@ static void bfv_key_switch(Context& c, int level, const u64* cx, long long scx, 
 
 void bfv_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, int batch, long long sd, long long so,
                hipStream_t s) {
+    const EntryCheck ck(c, "lsa_bfv_relin", LSA_ALGO_BFV, level, 0, batch);
+    ck.key(rlk, "the relinearisation key");
+    if (batch <= 0) return;
     const long long N = c.n;
     const int L = level + 1;
+    ck.apart(ck.output(out, so, 2 * (size_t)L * N), ck.operand(d3, sd, 3 * (size_t)L * N, "d3", false), "d3");
     for_tiles(c, KsTile::rows(c, level) + L, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* d = d3 + (size_t)b0 * sd;
         bfv_key_switch(c, level, d + 2LL * L * N, sd, rlk,
@@ -867,10 +978,32 @@ void bfv_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, i
     });
 }
 
+// multiply + relinearise; the degree-2 tensor lives in the second arena so that the two pipelines' own arena use cannot overlap it
+void bfv_mult_relin(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch, long long sa,
+                    long long sb, long long so, hipStream_t s) {
+    const EntryCheck ck(c, "lsa_bfv_mult_relin", LSA_ALGO_BFV, level, 0, batch);
+    ck.key(rlk, "the relinearisation key");
+    if (batch <= 0) return;
+    const size_t w = 2 * (size_t)(level + 1) * ck.N;
+    const Span sp_out = ck.output(out, so, w);
+    ck.apart(sp_out, ck.operand(a, sa, w, "a", true), "a");
+    ck.apart(sp_out, ck.operand(b, sb, w, "b", true), "b");
+    const long long sd = 3LL * (level + 1) * c.n;
+    u64* d3 = c.workspace2((size_t)sd * batch, s);
+    bfv_mult(c, level, a, b, d3, batch, sa, sb, sd, s);
+    bfv_relin(c, level, d3, rlk, out, batch, sd, so, s);
+}
+
 void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, int batch, long long sin,
                 long long sout, hipStream_t s) {
+    const EntryCheck ck(c, "lsa_bfv_rotate", LSA_ALGO_BFV, level, 0, batch);
+    ck.key(glk, "the Galois key");
+    if (batch <= 0) return;
     const long long N = c.n;
     const int L = level + 1;
+    // always the two-step form (tail into the workspace, then the permutation): out == in item for item is safe, any other overlap
+    // would let one tile store over what another still reads
+    ck.same_or_apart(ck.output(out, sout, 2 * (size_t)L * N), ck.operand(in, sin, 2 * (size_t)L * N, "in", false), "in");
     const u32* perm = c.coeff_perm(g);
     const size_t ks_rows = KsTile::rows(c, level) + L;
     const long long sp = 2LL * L * N;
@@ -910,7 +1043,7 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
     std::vector<int> order;   // an output that overlaps the input goes last: every other rotation still reads the intact c0
     int overlapping = -1;
     for (int i = 0; i < n_rot; i++) {
-        const bool apart = outs[i] + (size_t)batch * sout <= in || in + (size_t)batch * sin <= outs[i];
+        const bool apart = layout::apart(outs[i], sout, 2 * (size_t)L * N, in, sin, 2 * (size_t)L * N, batch);
         perms[i] = c.coeff_perm(g[i]);
         direct[i] = apart && gather_on;
         if (apart) {
@@ -950,11 +1083,6 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
 // LSA_PTMUL_FUSED=0 runs the forward transform, k_mont_muladd and the inverse transform instead.  A MAC sums
 // its terms in the NTT domain (canonical residues: the same values as a per-term multiply and adds) and runs one inverse
 // transform per output; the partial sum is added after it, in the coefficient domain.
-static bool spans_apart(const u64* a, long long sa, size_t wa, const u64* b, long long sb, size_t wb, int batch) {
-    const u64* ea = a + (size_t)(batch - 1) * sa + wa;
-    const u64* eb = b + (size_t)(batch - 1) * sb + wb;
-    return ea <= b || eb <= a;
-}
 // out = NTT(ct) . pt . 2^-64 (+ out if acc) for nb ciphertexts; tmp receives the first pass of a two-pass transform (may be
 // out, or ct, when acc is false)
 static void ptmul_term(Context& c, int L, const u64* ct, long long sct, const u64* pt, long long spt, bool acc, u64* out,
@@ -986,9 +1114,9 @@ void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64
     if (batch <= 0) return;
     const int L = level + 1;
     const size_t wct = 2 * (size_t)L * c.n, wpt = (size_t)L * c.n;
-    LSA_REQUIRE((out == ct && sout == sct) || spans_apart(out, sout, wct, ct, sct, wct, batch),
+    LSA_REQUIRE((out == ct && sout == sct) || layout::apart(out, sout, wct, ct, sct, wct, batch),
                 "bfv_mult_plain_mul: out must be ct or not overlap it");
-    LSA_REQUIRE(spans_apart(out, sout, wct, pt, spt, wpt, batch), "bfv_mult_plain_mul: out overlaps the plaintexts");
+    LSA_REQUIRE(layout::apart(out, sout, wct, pt, spt, wpt, batch), "bfv_mult_plain_mul: out overlaps the plaintexts");
     ptmul_term(c, L, ct, sct, pt, spt, false, out, sout, out, sout, batch, s);
     launch_ntt(c, out, out, batch, sout, 2 * L, rm_seq(L), true, s);
 }
@@ -1005,10 +1133,10 @@ void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, cons
     const size_t wct = 2 * (size_t)L * N, wpt = (size_t)L * N;
     // out holds the running sum while the terms are read: it may alias none of them
     for (int i = 0; i < n; i++) {
-        LSA_REQUIRE(spans_apart(out, sout, wct, cts[i], scts[i], wct, batch), "bfv_mac_plain_mul: out overlaps a ciphertext");
-        LSA_REQUIRE(spans_apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_mac_plain_mul: out overlaps a plaintext");
+        LSA_REQUIRE(layout::apart(out, sout, wct, cts[i], scts[i], wct, batch), "bfv_mac_plain_mul: out overlaps a ciphertext");
+        LSA_REQUIRE(layout::apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_mac_plain_mul: out overlaps a plaintext");
     }
-    LSA_REQUIRE(!partial || spans_apart(out, sout, wct, partial, spartial, wct, batch), "bfv_mac_plain_mul: out overlaps the partial sum");
+    LSA_REQUIRE(!partial || layout::apart(out, sout, wct, partial, spartial, wct, batch), "bfv_mac_plain_mul: out overlaps the partial sum");
     // workspace: the first pass of terms 1.. (term 0 runs it in out)
     for_tiles(c, n > 1 ? 2 * (size_t)L : 0, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         u64* o = out + (size_t)b0 * sout;
@@ -1050,10 +1178,10 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
     const int L = level + 1;
     const size_t wct = 2 * (size_t)L * N, wpt = (size_t)L * N;
     // out holds the running sum while the input, the plaintexts and the partial sum are still read: it may alias none of them
-    LSA_REQUIRE(spans_apart(out, sout, wct, in, sin, wct, batch), "bfv_rotate_mac_plain_mul: out overlaps the input");
+    LSA_REQUIRE(layout::apart(out, sout, wct, in, sin, wct, batch), "bfv_rotate_mac_plain_mul: out overlaps the input");
     for (int i = 0; i < n; i++)
-        LSA_REQUIRE(spans_apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_rotate_mac_plain_mul: out overlaps a plaintext");
-    LSA_REQUIRE(!partial || spans_apart(out, sout, wct, partial, spartial, wct, batch),
+        LSA_REQUIRE(layout::apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_rotate_mac_plain_mul: out overlaps a plaintext");
+    LSA_REQUIRE(!partial || layout::apart(out, sout, wct, partial, spartial, wct, batch),
                 "bfv_rotate_mac_plain_mul: out overlaps the partial sum");
     const bool fused = sw::rotmac_fused() && c.fuse_tails && sw::rot_scatter();
     std::vector<const u32*> scatters(n, nullptr), perms(n, nullptr);
@@ -1108,6 +1236,10 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
 
 void bfv_rescale(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                  hipStream_t s) {
+    const EntryCheck ck(c, "lsa_bfv_rescale", LSA_ALGO_BFV, level, 1, batch);
+    ck.polys(polys);
+    if (batch <= 0) return;
+    ck.apart(ck.output(out, sout, (size_t)polys * level * ck.N), ck.operand(in, sin, (size_t)polys * (level + 1) * ck.N, "in", false), "in");
     for_tiles(c, rescale_ws_rows(level, polys), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         rescale(c, level, polys, in + (size_t)b0 * sin, sin, out + (size_t)b0 * sout, sout, nb, false, ws, st);
     });
@@ -1136,7 +1268,7 @@ struct PlainCall {   // the checks every entry point shares; messages begin with
     }
     // the element-wise kernels move 16 bytes per lane at base + item * stride: every item has to start on a 16-byte boundary
     void aligned(const u64* p, long long stride, const char* what) const {
-        LSA_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15) == 0 && (stride & 1) == 0,
+        LSA_REQUIRE(layout::aligned16(layout::span_of(p, stride, 0)),
                     who + ": " + what + " must be 16-byte aligned with an even batch stride");
     }
     void ciphertext(const u64* p, long long stride, const char* what) const {
@@ -1156,12 +1288,12 @@ struct PlainCall {   // the checks every entry point shares; messages begin with
         LSA_REQUIRE(so >= (long long)wout, who + ": output stride below one result");
         aligned(out, so, "out");
         if (!same) return;
-        if (rescale) LSA_REQUIRE(spans_apart(out, so, wout, same, s_same, wct, batch), who + ": out overlaps the ciphertexts (a rescaled result may not)");
-        else LSA_REQUIRE((out == same && so == s_same) || spans_apart(out, so, wct, same, s_same, wct, batch), who + ": out must be ct or not overlap it");
+        if (rescale) LSA_REQUIRE(layout::apart(out, so, wout, same, s_same, wct, batch), who + ": out overlaps the ciphertexts (a rescaled result may not)");
+        else LSA_REQUIRE((out == same && so == s_same) || layout::apart(out, so, wct, same, s_same, wct, batch), who + ": out must be ct or not overlap it");
     }
     void apart(const u64* out, long long so, bool rescale, const u64* p, long long sp, size_t words, const char* what) const {
         const size_t wout = rescale ? 2 * (size_t)level * c.n : wct;
-        LSA_REQUIRE(spans_apart(out, so, wout, p, sp, words, batch), who + ": out overlaps " + what);
+        LSA_REQUIRE(layout::apart(out, so, wout, p, sp, words, batch), who + ": out overlaps " + what);
     }
 };
 

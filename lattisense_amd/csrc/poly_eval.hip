@@ -15,6 +15,7 @@
 #include <cmath>
 #include <functional>
 
+#include "layout_check.h"
 #include "poly_eval.h"
 
 namespace lsa {
@@ -342,9 +343,8 @@ void poly_run(Polynomial& p, const u64* in, long long sin, u64* out, long long s
     const PolyStructure& st = p.st;
     LSA_REQUIRE(rlk.level >= p.level_in, "poly: the relinearisation key is below the input level");
     LSA_REQUIRE(sin >= 2LL * (p.level_in + 1) * N && sout >= 2LL * (p.level_out + 1) * N, "poly: batch stride shorter than a ciphertext");
-    const u64* in_end = in + (size_t)(batch - 1) * sin + 2LL * (p.level_in + 1) * N;
-    const u64* out_end = out + (size_t)(batch - 1) * sout + 2LL * (p.level_out + 1) * N;
-    LSA_REQUIRE(out_end <= in || in_end <= out, "poly: out overlaps in");
+    LSA_REQUIRE(layout::apart(out, sout, 2 * (size_t)(p.level_out + 1) * N, in, sin, 2 * (size_t)(p.level_in + 1) * N, batch),
+                "poly: out overlaps in");
     static const std::map<u64, const Key*> no_glk;
     CtEval ev(c, p.pool, s, batch, rlk, no_glk, "poly");
     const int m = batch;

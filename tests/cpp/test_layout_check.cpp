@@ -1,0 +1,26 @@
+// Host-side check of the span arithmetic behind every operator's argument checks (lattisense_amd/csrc/layout_check.h).
+// Lines on stdin, one answer line each on stdout:
+//   "base_a stride_a words_a base_b stride_b words_b batch"   (bases in BYTES, strides and sizes in words)
+//     -> "apart same same_or_apart ok_a ok_shared_a aligned_a end_hi end_lo"
+//        ok_a / ok_shared_a: stride_ok(a) without / with shared operands accepted; end: span_end(a) as two 64-bit halves
+// Driven by tests/test_layout_check_host.py, which marks every word of both operands in an array and compares.
+#include <cstdio>
+#include "../../lattisense_amd/csrc/layout_check.h"
+
+using namespace lsa::layout;
+
+int main() {
+    unsigned long long ba, wa, bb, wb;
+    long long sa, sb;
+    int batch;
+    while (std::scanf("%llu %lld %llu %llu %lld %llu %d", &ba, &sa, &wa, &bb, &sb, &wb, &batch) == 7) {
+        const Span a{(uintptr_t)ba, sa, (size_t)wa}, b{(uintptr_t)bb, sb, (size_t)wb};
+        const u128 end = span_end(a, batch);
+        // the pointer overload must agree with the span one
+        if (apart(reinterpret_cast<const void*>(a.base), sa, wa, reinterpret_cast<const void*>(b.base), sb, wb, batch) != apart(a, b, batch)) return 3;
+        std::printf("%d %d %d %d %d %d %llu %llu\n", apart(a, b, batch) ? 1 : 0, same(a, b) ? 1 : 0, same_or_apart(a, b, batch) ? 1 : 0,
+                    stride_ok(a, false) ? 1 : 0, stride_ok(a, true) ? 1 : 0, aligned16(a) ? 1 : 0, (unsigned long long)(end >> 64),
+                    (unsigned long long)end);
+    }
+    return 0;
+}

@@ -1,0 +1,121 @@
+"""CPU-only: the span arithmetic behind every operator's argument checks (lattisense_amd/csrc/layout_check.h, compiled for the
+host by tests/cpp/test_layout_check.cpp with g++ -fsanitize=undefined) against a word-by-word model.
+
+An operand is `batch` items of `words` words, item b at base + b * stride; stride 0 is one item shared by the batch.  Overlap is
+exact: padding belongs to nobody, operands may interleave.  The model marks, in a small array, every word the items of each
+operand really occupy (and every word of each hull, to see that interleaved cases are reached), and requires
+  apart  <=>  the items share no word            (layouts whose own items overlap: the hulls decide)
+over every combination of base offset, stride (0, dense, padded, padded odd) and batch 1..4 of two operands of equal and of
+different item sizes.  Two hand-made cases put strides near 2^40 words, where a 32-bit or a 64-bit intermediate would wrap."""
+import itertools
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SPACE = 112       # words of the model's address space
+ORIGIN = 1 << 20  # byte address of word 0 (16-byte aligned)
+
+
+def _exe(tmp_path):
+    exe = str(tmp_path / "test_layout_check")
+    subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-fsanitize=undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "cpp", "test_layout_check.cpp"), "-o", exe])
+    return exe
+
+
+def _run(exe, cases):
+    lines = ["%d %d %d %d %d %d %d\n" % c for c in cases]
+    out = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr
+    got = [tuple(int(x) for x in line.split()) for line in out.stdout.splitlines()]
+    assert len(got) == len(cases)
+    return got
+
+
+def _hull(base_w, stride, words, batch):
+    return set(range(base_w, base_w + (batch - 1) * stride + words))
+
+
+def _items(base_w, stride, words, batch):
+    s = set()
+    for b in range(batch):
+        s.update(range(base_w + b * stride, base_w + b * stride + words))
+    return s
+
+
+def test_spans_against_marked_words(tmp_path):
+    exe = _exe(tmp_path)
+    WA = 4
+    cases, model = [], []
+    for wb in (4, 2):
+        for sa, sb in itertools.product((0, WA, WA + 2, WA + 3, WA + 8), (0, wb, wb + 2, wb + 5, wb + 9)):
+            for batch in (1, 2, 3, 4):
+                base_a = 24
+                for base_b in range(0, 64):
+                    cases.append((ORIGIN + 8 * base_a, sa, WA, ORIGIN + 8 * base_b, sb, wb, batch))
+                    model.append((base_a, sa, WA, base_b, sb, wb, batch))
+    got = _run(exe, cases)
+    seen = {"apart": 0, "hull_only": 0, "real": 0, "same": 0, "interleaved": 0}
+    for (ba, sa, wa, bb, sb, wb, batch), g in zip(model, got):
+        apart, same, same_or_apart, ok, ok_shared, aligned, end_hi, end_lo = g
+        ha, hb = _hull(ba, sa, wa, batch), _hull(bb, sb, wb, batch)
+        assert max(ha) < SPACE and max(hb) < SPACE
+        ia, ib = _items(ba, sa, wa, batch), _items(bb, sb, wb, batch)
+        assert ia <= ha and ib <= hb
+        key = (ba, sa, wa, bb, sb, wb, batch)
+        valid = (sa == 0 or sa >= wa) and (sb == 0 or sb >= wb)
+        want_apart = not (ia & ib) if valid else not (ha & hb)
+        assert bool(apart) == want_apart, key
+        want_same = ba == bb and sa == sb and wa == wb
+        assert bool(same) == want_same, key
+        assert bool(same_or_apart) == (want_same or want_apart), key
+        assert bool(ok) == (sa >= wa), key
+        assert bool(ok_shared) == (sa >= wa or sa == 0), key
+        assert bool(aligned) == (ba % 2 == 0 and sa % 2 == 0), key
+        assert (end_hi << 64) + end_lo == ORIGIN + 8 * (max(ha) + 1), key
+        seen["apart"] += bool(apart)
+        seen["hull_only"] += bool((ha & hb) and not (ia & ib))
+        seen["interleaved"] += bool(apart and (ha & hb))
+        seen["real"] += bool(ia & ib)
+        seen["same"] += want_same
+    assert all(seen.values()), seen     # the sweep reached every kind of case
+
+
+def test_misaligned_base_and_negative_stride(tmp_path):
+    exe = _exe(tmp_path)
+    got = _run(exe, [(ORIGIN + 8, 8, 4, ORIGIN + 512, 8, 4, 2),       # base on an 8-byte, not a 16-byte boundary
+                     (ORIGIN + 4, 8, 4, ORIGIN + 512, 8, 4, 2),       # not even word aligned
+                     (ORIGIN, -8, 4, ORIGIN + 512, 8, 4, 2),          # a negative stride is no layout
+                     (ORIGIN, 3, 4, ORIGIN + 512, 8, 4, 2)])          # items overlap each other
+    assert [g[5] for g in got] == [0, 0, 1, 0]
+    assert [g[3] for g in got] == [1, 1, 0, 0]
+    assert [g[4] for g in got] == [1, 1, 0, 0]
+
+
+def test_strides_near_2_to_40_words(tmp_path):
+    exe = _exe(tmp_path)
+    S, W = (1 << 40) + 6, 1 << 12
+    base_a = 1 << 30
+    # batch 3: the hull is 2 S + W words.  (2 S * 8 = 2^44 + 96 bytes: a 32-bit product keeps only the 96.)
+    end3 = base_a + 8 * (2 * S + W)
+    # batch 2^31 - 1: the hull passes 2^64 bytes.  With 64-bit arithmetic the end wraps to a small address and everything
+    # above `a` would look apart.
+    big = (1 << 31) - 1
+    end_big = base_a + 8 * ((big - 1) * S + W)
+    assert end_big >= 1 << 64
+    k = 1 << 20                                            # item k of a starts past 2^63 bytes
+    item_k = base_a + 8 * k * S
+    assert (1 << 63) < item_k < (1 << 64)
+    cases = [(base_a, S, W, end3, S, W, 3),                 # b starts exactly where a's hull ends
+             (base_a, S, W, end3 - 8, S, W, 3),             # one word earlier: b's item 0 shares a's last word
+             (base_a, S, W, base_a + 8 * W, 0, W, 3),       # b shared, in a's first padding: interleaved, no common word
+             (base_a, S, W, base_a + 8 * (W - 1), 0, W, 3), # ... one word earlier
+             (base_a, S, W, base_a + 8 * W, S, W, 3),       # b's items all in a's paddings
+             (end3, 0, W, base_a, S, W, 3),                 # a shared and behind b's hull
+             (base_a, S, W, item_k + 8 * (W - 1), 0, W, big),   # a's hull passes 2^64; b shared, on the last word of item k
+             (base_a, S, W, item_k + 8 * W, 0, W, big),     # ... just behind item k
+             (base_a, S, W, base_a - 8 * W, 0, W, big)]     # ... and before a altogether
+    got = _run(exe, cases)
+    assert [g[0] for g in got] == [1, 0, 1, 0, 1, 1, 0, 1, 1]
+    assert (got[0][6] << 64) + got[0][7] == end3
+    assert (got[6][6] << 64) + got[6][7] == end_big
