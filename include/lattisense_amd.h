@@ -241,6 +241,10 @@ int lsa_set_dual_stream(lsa_context ctx, int enable);
 /* 1 (default): the ModDown and rescale element-wise tails run inside the NTT kernel's load/store phases; 0: separate
  * kernels (A/B measurement; identical results). */
 int lsa_set_fuse_tails(lsa_context ctx, int enable);
+/* 1 (default): a key-switch digit with one source limb below 2^53 gets no base-conversion launch, the load of its extension
+ * transform lifts it (x mod p_t); 0: the conversion kernel for those digits too (A/B measurement and parity; identical
+ * results).  Read by every operator call. */
+int lsa_set_modup_lift(lsa_context ctx, int enable);
 /* Two-pass NTTs (N > 2^12) run both passes over a chunk of at most `mib` MiB of limbs before moving on, so that the
  * second pass is served by the 256 MiB Infinity Cache (0 = one launch per pass over the whole batch). */
 int lsa_set_ntt_chunk_mib(lsa_context ctx, int mib);

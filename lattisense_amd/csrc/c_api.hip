@@ -407,6 +407,9 @@ int lsa_profile_read_primary(lsa_context ctx, int kind, double* total_bytes_prim
 int lsa_set_fuse_tails(lsa_context ctx, int enable) {
     return guard([&] { C(ctx).fuse_tails = enable ? 1 : 0; });
 }
+int lsa_set_modup_lift(lsa_context ctx, int enable) {
+    return guard([&] { C(ctx).modup_lift = enable ? 1 : 0; });
+}
 int lsa_set_dual_stream(lsa_context ctx, int enable) {
     return guard([&] { C(ctx).dual_stream = enable ? 1 : 0; });
 }

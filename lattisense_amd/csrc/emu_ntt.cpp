@@ -30,13 +30,13 @@ static void emu_block(const NttPassArgs& a, const NttBlockCtx& bc, u64* lds) {
 }
 
 // the radix-16-squared pass (ntt_r16.h): each phase for every thread in turn, a thread's registers kept between its phases
-template <int PASS, int MU>
+template <int PASS, int MU, int FZ = 3 | 16>
 static void emu_block_r16(const NttPassArgs& a, const NttBlockCtx& bc, u64* lds) {
     std::vector<std::array<u64, 16>> regs(LSA_R16_THREADS);
     for (int phase = 0; phase < 3; phase++)
         for (int t = 0; t < LSA_R16_THREADS; t++) {
             u64(&v)[16] = *reinterpret_cast<u64(*)[16]>(regs[t].data());
-            r16_phase<PASS, 3 | 16, MU>(a, bc, t, lds, phase, v);
+            r16_phase<PASS, FZ, MU>(a, bc, t, lds, phase, v);
         }
 }
 
@@ -52,8 +52,11 @@ static void emu_block_r8x3(const NttPassArgs& a, const NttBlockCtx& bc, u64* lds
 
 // pa / pb (inverse only): the product prologue, the transform's input is pa * pb (both [batch][rows][N], batch stride
 // batch_stride, as launch_ntt runs it for the tensor-fold key switch); data is then output only
+// lift (forward only): the single-source ModUp lift (fz_pro == 4), rows are [poly][lift_limbs]; polynomial p is lifted from row p of
+// lift ([batch][polys][N]), whose modulus is lift_mod + p; data is output only
 static int emu_ntt(int n, const u64* moduli, int nmod, u64* data, int batch, long long batch_stride, int rows,
-                   const unsigned char* mod_of, int period, int inverse, int tau_max, int allow_fp64, const u64* pa, const u64* pb) {
+                   const unsigned char* mod_of, int period, int inverse, int tau_max, int allow_fp64, const u64* pa, const u64* pb,
+                   const u64* lift = nullptr, int lift_mod = 0, int lift_limbs = 1) {
     const int row_inner = (allow_fp64 >> 1) & 1;   // bit 1: the (tile, row, batch) workgroup order
     const bool r16 = (allow_fp64 >> 2) & 1;        // bit 2: 8-stage passes through the radix-16-squared kernel
     allow_fp64 &= 1;
@@ -94,6 +97,14 @@ static int emu_ntt(int n, const u64* moduli, int nmod, u64* data, int batch, lon
         a.fz_a_stride = a.fz_b_stride = batch_stride;
         a.fz_a_rpp = a.fz_b_rpp = rows;
     }
+    if (lift) {
+        a.fz_pro = 4;
+        a.fz_limbs = lift_limbs;
+        a.fz_last = lift;
+        a.fz_last_stride = (long long)(rows / lift_limbs) * n;
+        a.fz_last_rpp = 1;
+        a.fz_ql_mod = lift_mod;
+    }
     // as launch_ntt: the grid covers the active rows only
     int launch_rows = 0;
     for (int r = 0; r < rows; r++)
@@ -113,6 +124,7 @@ static int emu_ntt(int n, const u64* moduli, int nmod, u64* data, int batch, lon
             if (bc.mod == LSA_ROW_SKIP) continue;
             if (r16 && ntt_r16_shape_ok(a, plan.npass)) {
                 if (a.mu == 9) emu_block_r8x3(a, bc, lds.data());
+                else if (a.lambda && lift) (a.mu == 8 ? emu_block_r16<0, 8, 32> : emu_block_r16<0, 7, 32>)(a, bc, lds.data());   // as ntt_launch_r16
                 else if (a.lambda && a.mu == 8) emu_block_r16<0, 8>(a, bc, lds.data());
                 else if (a.lambda) emu_block_r16<0, 7>(a, bc, lds.data());
                 else if (a.mu == 8) emu_block_r16<1, 8>(a, bc, lds.data());
@@ -135,4 +147,12 @@ extern "C" int lsa_emu_intt_prod(int n, const u64* moduli, int nmod, const u64* 
                                  int allow_fp64) {
     if (!pa || !pb) return -1;
     return emu_ntt(n, moduli, nmod, out, batch, batch_stride, rows, mod_of, period, 1, tau_max, allow_fp64, pa, pb);
+}
+
+extern "C" int lsa_emu_ntt_lift(int n, const u64* moduli, int nmod, const u64* src, int src_mod, int limbs, u64* out, int batch,
+                                long long batch_stride, int rows, const unsigned char* mod_of, int period, int tau_max,
+                                int allow_fp64) {
+    if (!src || limbs < 1 || rows % limbs || src_mod < 0 || src_mod + rows / limbs > nmod) return -1;
+    return emu_ntt(n, moduli, nmod, out, batch, batch_stride, rows, mod_of, period, 0, tau_max, allow_fp64, nullptr, nullptr, src,
+                   src_mod, limbs);
 }

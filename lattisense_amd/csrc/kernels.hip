@@ -65,8 +65,9 @@ __device__ __forceinline__ void ntt_butterfly_phases(const NttPassArgs& a, const
 // of the limb and go through LDS -- one fetch per workgroup, issued with the tile loads, instead of one per sub-pass.
 // FZ: 0 plain, 1 fused prologue only (first pass of a two-pass fused transform), 2 fused epilogue only (its last pass), 3 both
 // (single-pass transforms), 4 the pt_mul epilogue (fz_epi == 3) only, 8 the rotate-and-MAC epilogue (fz_epi == 4) only, 16 the
-// product prologue (fz_pro == 3, the first executed pass of an inverse transform) only.  Split so that a pass carries only the
-// tail code and registers it can execute.
+// product prologue (fz_pro == 3, the first executed pass of an inverse transform) only, 32 (k_ntt_r16 first passes) the single-source
+// lift prologue (fz_pro == 4) only; on k_ntt_pass the lift rides on FZ bit 1.  Split so that a pass carries only the tail code and
+// registers it can execute.
 template <int FZ, int NT, bool TWL = false>
 __global__ __launch_bounds__(NT, NT > 512 ? 1 : NT > 256 ? 2 : (FZ & 1) ? LSA_NTT_WAVES_FUSED : LSA_NTT_WAVES) void k_ntt_pass(NttPassArgs a) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
@@ -195,7 +196,9 @@ static bool ntt_launch_r16(const NttPassArgs& a, int npass, bool fused, long lon
         // the two-operand prologue: 394 us per headline launch here against 450 on the staged kernel once the lift's block-uniform
         // cases became branches (628 before: both lifts were evaluated per element, profiles/r03/ab_r16_prologue_epilogue_branches.log);
         // LSA_R16_PRO=0 keeps it on the staged kernel (A/B)
-        if (fz == 1 && a.mu == 8 && sw::r16_pro()) k = &k_ntt_r16<0, 1, 8>;
+        // the single-source lift (fz_pro == 4) has a variant of its own, FZ bit 32: one operand, the plain kernel's occupancy
+        if (fz == 1 && a.fz_pro == 4 && sw::r16_pro()) k = a.mu == 8 ? &k_ntt_r16<0, 32, 8> : &k_ntt_r16<0, 32, 7>;
+        else if (fz == 1 && a.fz_pro != 4 && a.mu == 8 && sw::r16_pro()) k = &k_ntt_r16<0, 1, 8>;
         else if (fz == 0) k = a.mu == 8 ? &k_ntt_r16<0, 0, 8> : &k_ntt_r16<0, 0, 7>;
     } else if (a.mu != 9 || sw::ntt_r8x3()) {   // a second pass; LSA_NTT_R8X3=0: the nine-stage one on the staged kernel (A/B)
         switch (fz) {   // it has no two-operand prologue (FZ 1, 3), and the product prologue belongs to inverse transforms
@@ -449,6 +452,8 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
         LSA_REQUIRE(!inverse || (fz->pro == 3 && !fz->epi), "inverse transforms take the product prologue only");
         LSA_REQUIRE(fz->pro != 3 || (inverse && !fz->epi && fz->a && fz->b && fz->limbs >= 1 && (passes & 1)),
                     "product prologue: an inverse transform from its first pass, two operands, no epilogue");
+        LSA_REQUIRE(fz->pro != 4 || (!inverse && !fz->epi && fz->last && fz->limbs >= 1 && (passes & 1)),
+                    "lift prologue: a forward transform from its first pass, one source row per polynomial, no epilogue");
         a.fz_epi = fz->epi;
         a.fz_pro = fz->pro;
         a.fz_limbs = fz->limbs;
@@ -535,6 +540,13 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
             any_int |= !fp;
         }
         a.row_inner = any_fp && any_int;
+        // the lift prologue: every row of a (polynomial, tile) reads the same source tile -- they run next to each other
+        // (-DLSA_LIFT_ROW_OUTER: the (row, tile, batch) order for A/B, profiles/r09/ab_lift_row_order.log)
+#if defined(LSA_LIFT_ROW_OUTER)
+        if (fz && fz->pro == 4) a.row_inner = 0;
+#else
+        if (fz && fz->pro == 4) a.row_inner = 1;
+#endif
     }
     int chunk = batch;
     if (plan.npass > 1 && c.ntt_chunk_mib > 0) {
@@ -555,6 +567,7 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
             a.fz_pt = fz->pt + (long long)b0 * fz->pt_stride;
             a.fz_out = fz->out + (long long)b0 * fz->out_stride;
         }
+        if (fz && fz->pro == 4) a.fz_last = fz->last + (long long)b0 * fz->last_stride;   // the lift prologue's source
         if (fz && fz->pro == 3) {   // and the product prologue's
             a.fz_a = fz->a + (long long)b0 * fz->a_stride;
             a.fz_b = fz->b + (long long)b0 * fz->b_stride;

@@ -95,6 +95,10 @@ struct NttPassArgs {
     //   fz_pro = 3:  in = fz_a[poly][limb] * fz_b[poly][limb] mod q   (NTT-domain canonical operands, rows per polynomial
     //                fz_a_rpp / fz_b_rpp; FZ bit 16, ntt_make_prod_fix): the tensor-fold HMult's ModUp input d2 = a1 b1, formed
     //                by the load of its inverse transform instead of being stored and read back
+    //   fz_pro = 4:  in = fz_last[poly] mod q_limb, unsigned (the ModUp of a digit with ONE source limb: the exact base
+    //                conversion is the identity, so the digit's extension rows are lifted by the load of their forward
+    //                transform).  poly = row / fz_limbs is the digit; its source row is row poly * fz_last_rpp of fz_last and
+    //                that row's modulus is fz_ql_mod + poly * fz_last_rpp (consecutive limbs of one polynomial)
     //   fz_epi = 2:  out = (fz_a * fz_k - v + fz_base) * fz_k2   (its tail: (acc*P^-1 - NTT(in) + base) * q_l^-1)
     //   fz_epi = 3:  out[poly][limb] = v * fz_a[limb] * 2^-64 (+ fz_base[poly][limb] if fz_base)   (BFV ct x pt_mul: the
     //                Montgomery-form plaintext, shared by both polys; kernels compiled with FZ bit 4, ntt_phase_store_ptm)
@@ -348,13 +352,45 @@ LSA_HD double fp_reduce(double x, double q, double qinv) { return __builtin_fma(
 #define LSA_NTT_HEAD_ROUNDS 2   // two-operand prologue: load rounds per tile (1 = all 16 operand pairs in flight at once)
 #endif
 struct NttLoadFix {   // per-block constants of the load-side conversions
-    bool head, add, fp, near, raw, fp_lift;
+    bool head, add, fp, near, raw, fp_lift, lift;
     u64 ql, h, hq;
-    double hd, qld;
+    double hd, qld;   // head: h and q_l as doubles; lift: 1 / q and q of this limb
     ModDev mi;
 };
+// the single-source lift (fz_pro == 4) of NE elements, x in [0, q_s) -> the form this limb's butterflies take.  Every case is
+// block-uniform: a branch around each loop, not selects inside one.
+//   FP64-engine limb, q_s < 2^52: the double of x, minus q once where q_s <= 2q (canonical), else one fp_reduce
+//     (|.| <= q/2 + 1, the raw hand-off range every pass takes); both exact
+//   otherwise the integer reduction (one conditional subtraction where q_s <= 2q), converted for an FP64-engine limb
+template <int NE>
+LSA_HD void ntt_lift_block(const NttLoadFix& f, u64* v) {
+    if (f.fp_lift && f.near) {
+#pragma unroll
+        for (int e = 0; e < NE; e++) {
+            const double x = u52_to_double(v[e]);
+            v[e] = d_to_bits(x >= f.qld ? x - f.qld : x);
+        }
+    } else if (f.fp_lift) {
+#pragma unroll
+        for (int e = 0; e < NE; e++) v[e] = d_to_bits(fp_reduce(u52_to_double(v[e]), f.qld, f.hd));
+    } else if (f.near) {
+#pragma unroll
+        for (int e = 0; e < NE; e++) v[e] = csub(v[e], f.mi.q);
+    } else {
+#pragma unroll
+        for (int e = 0; e < NE; e++) v[e] = reduce_u64(v[e], f.mi);
+    }
+    if (f.fp && !f.fp_lift) {
+#pragma unroll
+        for (int e = 0; e < NE; e++) v[e] = d_to_bits(u52_to_double(v[e]));
+    }
+}
 // v: the tile's own element; t: the last limb's element at the same position (head modes only)
 LSA_HD u64 ntt_load_fix(const NttLoadFix& f, u64 v, u64 t) {
+    if (f.lift) {   // (partial tiles; full tiles go through ntt_lift_block)
+        ntt_lift_block<1>(f, &v);
+        return v;
+    }
     if (f.fp_lift) {
         // FP64-engine limb, q_l below 2^48: the engine takes any integer-valued double of small magnitude that is congruent
         // to the input, so the centred remainder of the last limb (t if t <= h, else t - q_l) is used as it is -- no
@@ -375,14 +411,16 @@ LSA_HD u64 ntt_load_fix(const NttLoadFix& f, u64 v, u64 t) {
     return v;
 }
 // FZ = false compiles the fused prologue out (plain launches: fewer live constants, smaller code)
+// LIFT: 1 the single-source lift next to the head modes, 0 head modes only, 2 the lift only (the register-image first passes keep
+// one kernel per kind: the lift has one operand and runs at the plain kernel's occupancy)
 // the load-side constants of a block; g / gl: where the tile's own elements and the last limb's elements are read from
-template <bool FZ>
+template <bool FZ, int LIFT = 1>
 LSA_HD NttLoadFix ntt_make_load_fix(const NttPassArgs& a, const NttBlockCtx& bc, const u64*& g, const u64*& gl) {
     g = a.src + bc.base_src;
     gl = g;   // last-limb source of the head modes
     NttLoadFix f;
     // fused rescale head: the tile is derived from the (coefficient-domain) last limb
-    f.head = FZ && (a.fz_pro == 1 || a.fz_pro == 2) && a.fz_first;
+    f.head = FZ && LIFT != 2 && (a.fz_pro == 1 || a.fz_pro == 2) && a.fz_first;
     f.add = f.head && a.fz_pro == 2;
     f.fp = bc.fp != 0;
     f.raw = f.fp && a.fp_raw_in;   // (never together with a fused prologue: that belongs to the first pass)
@@ -391,6 +429,16 @@ LSA_HD NttLoadFix ntt_make_load_fix(const NttPassArgs& a, const NttBlockCtx& bc,
     f.ql = f.h = f.hq = 0;
     f.hd = f.qld = 0.0;
     f.near = f.fp_lift = false;
+    f.lift = FZ && LIFT != 0 && a.fz_pro == 4 && a.fz_first;
+    if (f.lift) {
+        const int poly = bc.row / a.fz_limbs;
+        g = gl = a.fz_last + (long long)bc.b * a.fz_last_stride + ((long long)poly * a.fz_last_rpp << a.logn);
+        f.ql = a.mods[a.fz_ql_mod + poly * a.fz_last_rpp].q;   // the source limb's modulus q_s
+        f.near = f.ql <= 2 * f.mi.q;
+        f.fp_lift = f.fp && (f.ql >> 52) == 0;
+        f.qld = (double)f.mi.q;
+        f.hd = 1.0 / f.qld;
+    }
     if (f.head) {
         gl = a.fz_last + (long long)bc.b * a.fz_last_stride + ((long long)(bc.row / a.fz_limbs) * a.fz_last_rpp << a.logn);
         if (!f.add) g = gl;
@@ -478,6 +526,16 @@ LSA_HD void ntt_phase_load(const NttPassArgs& a, const NttBlockCtx& bc, int tid,
         for (int p = 0; p < LSA_NTT_STAGE_PAIRS; p++) {
             const int x = ntt_tile_index(tm, 2 * (tid + p * NT));
             ntt_load_data_pair(g + x, st[2 * p], st[2 * p + 1]);
+        }
+        if (FZ && f.lift) {
+            ntt_lift_block<2 * LSA_NTT_STAGE_PAIRS>(f, st);
+#pragma unroll
+            for (int p = 0; p < LSA_NTT_STAGE_PAIRS; p++) {
+                const int l = 2 * (tid + p * NT);
+                lds[lds_addr(l)] = st[2 * p];
+                lds[lds_addr(l + 1)] = st[2 * p + 1];
+            }
+            return;
         }
 #pragma unroll
         for (int p = 0; p < LSA_NTT_STAGE_PAIRS; p++) {

@@ -146,15 +146,16 @@ LSA_HD unsigned r16_G1(const NttBlockCtx& bc, int k) {
 
 // global -> registers (stride-16 or contiguous-by-rows image; 8 bytes per lane, 16 lanes = one 128-byte line) with the
 // load-side conversions, IMAGE = 0 stride16, 1 contig (contig only ever direct in the first pass)
-template <int PASS, bool FZ, int IMAGE, int MU>
+// LIFT (with FZ): 0 the two-operand / rescale-head prologues, 2 the single-source lift only (ntt_core.h ntt_make_load_fix)
+template <int PASS, bool FZ, int IMAGE, int MU, int LIFT = 0>
 LSA_HD void r16_load_direct(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64 (&v)[16]) {
     const u64* g;
     const u64* gl;
-    const NttLoadFix f = ntt_make_load_fix<FZ>(a, bc, g, gl);
+    const NttLoadFix f = ntt_make_load_fix<FZ, LIFT>(a, bc, g, gl);
     int k, i;
     r16_lane<PASS, MU>(tid, k, i);
     u64 t[16];
-    if (FZ && f.add) {
+    if (FZ && LIFT != 2 && f.add) {
         // two operands per point (merged ModDown + rescale prologue): two rounds of eight so that 16, not 32, loads are in flight
 #pragma unroll
         for (int h = 0; h < 2; h++) {
@@ -182,7 +183,11 @@ LSA_HD void r16_load_direct(const NttPassArgs& a, const NttBlockCtx& bc, int tid
     }
 #pragma unroll
     for (int e = 0; e < 16; e++) v[e] = r16_load1(g + r16_x<PASS, MU>(a, bc.tile, k, r16_pt<MU, IMAGE>(i, e)));
-    if (!(FZ && f.head)) {   // plain load: the only conversion is u64 -> double on FP64-engine limbs that are not handed over raw
+    if (FZ && LIFT != 0 && f.lift) {   // the single-source ModUp lift (fz_pro == 4): one operand, block-uniform cases
+        ntt_lift_block<16>(f, v);
+        return;
+    }
+    if (!(FZ && LIFT != 2 && f.head)) {   // plain load: the only conversion is u64 -> double on FP64-engine limbs that are not handed over raw
         if (f.fp && !f.raw) {
 #pragma unroll
             for (int e = 0; e < 16; e++) v[e] = d_to_bits(u52_to_double(v[e]));
@@ -512,7 +517,7 @@ LSA_HD void r16_phase(const NttPassArgs& a, const NttBlockCtx& bc, int tid, u64*
 #endif
     if (!a.inverse) {
         if (phase == 0) {
-            r16_load_direct<PASS, (FZ & 1) != 0, 0, MU>(a, bc, tid, v);
+            r16_load_direct<PASS, (FZ & (1 | 32)) != 0, 0, MU, (FZ & 32) ? 2 : 0>(a, bc, tid, v);
             r16_group<PASS, 0, MU>(v, a, bc, L, G1);
             r16_lds_put<PASS, 0, MU>(tid, lds, v);
         } else if (phase == 1) {

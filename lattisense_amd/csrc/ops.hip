@@ -263,8 +263,21 @@ struct KsTile {
         }
         const u64* conv_src = cx_coef ? cx_coef : cxi;
         const long long s_src = cx_coef ? s_coef : s_cxi;
-        // 2. per digit: exact conversion of the digit's limbs to every other limb of Q u P
+        // 2. per digit: exact conversion of the digit's limbs to every other limb of Q u P.  A digit with ONE source limb q_s
+        //    needs none: (Q_d/q_s)^-1 = 1, y = x, v = 0, every target row is x mod p_t -- the load of its extension transform
+        //    lifts it (fz_pro = 4) and the rows are never stored in the coefficient domain (lsa_set_modup_lift(ctx, 0): converted as the others).
+        //    v = 0 holds for the conversion as it is computed -- v = (int)RN(double(y) / double(q_s)) -- while q_s < 2^53: y and q_s
+        //    are exact doubles and y / q_s <= 1 - 1/q_s < 1 - 2^-53 rounds below 1.  A larger q_s has residues next to q_s whose
+        //    quotient rounds to 1.0 (the conversion then yields y - q_s): such a digit keeps the conversion kernel, residue for residue.
+        const bool lift_on = c.modup_lift != 0;
+        auto lifted = [&](int d) { return lift_on && std::min(d * np + np, L) - d * np == 1 && (c.T.mods[d * np].q >> 53) == 0; };
+        bool any_lift = false, any_conv = false;
         for (int d = 0; d < beta; d++) {
+            if (lifted(d)) {
+                any_lift = true;
+                continue;
+            }
+            any_conv = true;
             const int d0 = d * np, d1 = std::min(d0 + np, L);
             std::vector<int> src, dst;
             BaseConvRows rows{};
@@ -281,19 +294,30 @@ struct KsTile {
         }
         // 3. extended limbs into the NTT domain (the digit's own limbs are taken from cx directly by the MAC)
         auto own = [&](int d, int tl) { return tl >= d * np && tl < std::min((d + 1) * np, L); };
+        NttFusion lf;   // the lifted digits: digit d reads row d * np of conv_src (only read), modulus index d * np
+        lf.pro = 4;
+        lf.limbs = T;
+        lf.last = conv_src;
+        lf.last_stride = s_src;
+        lf.last_rpp = np;
+        lf.ql_mod = 0;
         if (beta * T <= LSA_MAX_PERIOD) {
-            RowMap rm;
-            rm.period = beta * T;
+            RowMap rm, rl;
+            rm.period = rl.period = beta * T;
             for (int d = 0; d < beta; d++)
-                for (int tl = 0; tl < T; tl++) rm.mod_of[d * T + tl] = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
-            launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, fused ? 1 : 3);
+                for (int tl = 0; tl < T; tl++) {
+                    const unsigned char m = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
+                    rm.mod_of[d * T + tl] = lifted(d) ? LSA_ROW_SKIP : m;
+                    rl.mod_of[d * T + tl] = lifted(d) ? m : LSA_ROW_SKIP;
+                }
+            if (any_conv) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, fused ? 1 : 3);
+            if (any_lift) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rl, false, s, &lf, fused ? 1 : 3);
             if (!fused) return;
             // the target limbs that do not take the fused kernel get their second pass here (stand-alone MAC later)
             bool any = false;
             for (int i = 0; i < beta * T; i++) {
-                if (rm.mod_of[i] == LSA_ROW_SKIP) continue;
-                if (ks_fused_limb(c, L, i % T)) rm.mod_of[i] = LSA_ROW_SKIP;
-                else any = true;
+                rm.mod_of[i] = own(i / T, i % T) || ks_fused_limb(c, L, i % T) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, i % T);
+                any |= rm.mod_of[i] != LSA_ROW_SKIP;
             }
             if (any) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, 2);
             return;
@@ -302,7 +326,9 @@ struct KsTile {
             RowMap rm;
             rm.period = T;
             for (int tl = 0; tl < T; tl++) rm.mod_of[tl] = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
-            launch_ntt(c, ext + (size_t)d * T * N, ext + (size_t)d * T * N, nb, s_ext, s_ext, T, rm, false, s);
+            lf.last = conv_src + (size_t)d * np * N;   // (one digit per launch: polynomial 0 of the launch is digit d)
+            lf.ql_mod = d * np;
+            launch_ntt(c, ext + (size_t)d * T * N, ext + (size_t)d * T * N, nb, s_ext, s_ext, T, rm, false, s, lifted(d) ? &lf : nullptr);
         }
     }
 

@@ -99,6 +99,10 @@ class DeviceContext:
         check(lib().lsa_debug_key_switch_fused(self.h, level, key, ctypes.byref(out)))
         return bool(out.value)
 
+    def set_modup_lift(self, enable):
+        """0: single-limb key-switch digits go through the base-conversion kernel like the others (A/B, identical results)"""
+        check(lib().lsa_set_modup_lift(self.h, int(enable)))
+
     def set_fp64_ntt(self, enable):
         check(lib().lsa_set_fp64_ntt(self.h, int(enable)))
 
