@@ -246,7 +246,10 @@ int lsa_set_fuse_tails(lsa_context ctx, int enable);
  * results).  Read by every operator call. */
 int lsa_set_modup_lift(lsa_context ctx, int enable);
 /* Two-pass NTTs (N > 2^12) run both passes over a chunk of at most `mib` MiB of limbs before moving on, so that the
- * second pass is served by the 256 MiB Infinity Cache (0 = one launch per pass over the whole batch). */
+ * second pass is served by the 256 MiB Infinity Cache (0, the default = one launch per pass over the whole batch).  Results are
+ * identical for every value: the setting only changes how many batch items one launch covers, and the operands of the fused
+ * load / store steps follow their chunk.  Single-pass rings (N <= 2^12) ignore it; a negative value is refused (LSA_ERR_ARG)
+ * and leaves the setting as it was. */
 int lsa_set_ntt_chunk_mib(lsa_context ctx, int mib);
 /* Rotations of the same ciphertexts by several Galois elements with ONE decomposition of the input ("hoisting"):
  * outs[i] = rotate(in, galois_elements[i]), each bit-identical to lsa_ckks_rotate's result.  The outputs (all with stride sout)

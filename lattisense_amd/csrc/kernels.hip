@@ -548,30 +548,13 @@ void launch_ntt(Context& c, const u64* src, u64* dst, int batch, long long src_s
         if (fz && fz->pro == 4) a.row_inner = 1;
 #endif
     }
-    int chunk = batch;
-    if (plan.npass > 1 && c.ntt_chunk_mib > 0) {
-        const double per_item = 8.0 * c.n * std::max(active_rows, 1);
-        chunk = (int)std::max(1.0, std::min((double)batch, c.ntt_chunk_mib * 1048576.0 / per_item));
-    }
+    // (every fused operand follows its chunk -- block batch indices restart at 0 -- through the one function of ntt_chunk.h)
+    const int chunk = plan.npass > 1 ? ntt_chunk_items(c.n, active_rows, batch, c.ntt_chunk_mib) : batch;
+    const NttPassArgs whole = a;
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
+        a = ntt_chunk_rebase(whole, b0);
         a.batch = nb;
-        if (fz && fz->epi == 3) {   // the pt_mul epilogue's operands follow the chunk (block batch indices restart at 0)
-            a.fz_a = fz->a + (long long)b0 * fz->a_stride;
-            a.fz_base = fz->base ? fz->base + (long long)b0 * fz->base_stride : nullptr;
-            a.fz_out = fz->out + (long long)b0 * fz->out_stride;
-        }
-        if (fz && fz->epi == 4) {   // so do the rotate-and-MAC epilogue's
-            a.fz_a = fz->a + (long long)b0 * fz->a_stride;
-            a.fz_base = fz->base ? fz->base + (long long)b0 * fz->base_stride : nullptr;
-            a.fz_pt = fz->pt + (long long)b0 * fz->pt_stride;
-            a.fz_out = fz->out + (long long)b0 * fz->out_stride;
-        }
-        if (fz && fz->pro == 4) a.fz_last = fz->last + (long long)b0 * fz->last_stride;   // the lift prologue's source
-        if (fz && fz->pro == 3) {   // and the product prologue's
-            a.fz_a = fz->a + (long long)b0 * fz->a_stride;
-            a.fz_b = fz->b + (long long)b0 * fz->b_stride;
-        }
         bool first = true;
         for (int step = 0; step < plan.npass; step++) {
             if (plan.npass == 2 && !((passes >> step) & 1)) continue;

@@ -11,6 +11,7 @@
 
 #include "../../include/lattisense_amd.h"
 #include "ntt_plan.h"
+#include "ntt_chunk.h"
 #include "plain_ops.h"
 #include "switches.h"
 #include "tables.h"

@@ -84,6 +84,10 @@ class DeviceContext:
     def set_tile_batch(self, tb):
         check(lib().lsa_set_tile_batch(self.h, tb))
 
+    def set_ntt_chunk_mib(self, mib):
+        """> 0: two-pass transforms run both passes over chunks of at most `mib` MiB of the batch (identical results); 0: off"""
+        check(lib().lsa_set_ntt_chunk_mib(self.h, int(mib)))
+
     def baseconv_plans(self):
         """the base-conversion plans built so far: a list of (source limbs, destination limbs, runs the 29-bit split)"""
         cnt = ctypes.c_int()

@@ -20,7 +20,7 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 def emu():
     so = os.path.join(CSRC, "libls_emu.so")
     srcs = [os.path.join(CSRC, f) for f in ("emu_ntt.cpp", "tables.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("ntt_core.h", "ntt_r16.h", "ntt_plan.h", "modarith.h", "tables.h")]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("ntt_core.h", "ntt_r16.h", "ntt_plan.h", "ntt_chunk.h", "modarith.h", "tables.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-DLSA_EMULATE"] + os.environ.get("LSA_EXTRA_FLAGS", "").split() + ["-o", so] + srcs)
     L = ctypes.CDLL(so)

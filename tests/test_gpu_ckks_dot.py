@@ -171,7 +171,7 @@ def test_headline_shape_tiles_streams_and_batch_positions():
 
 
 def test_every_level_small_ring():
-    """N = 2^13: levels 1..12 at n = 3; the oracle at levels 1, 4 and 12"""
+    """N = 2^13: levels 1..12 at n = 3; the oracle at levels 1, 4 and 12, there also under lsa_set_ntt_chunk_mib(1)"""
     need_gpu()
     C = params.CKKS_DEFAULT[65536]
     rig = Rig(1 << 13, C["q"][:13], C["p"][:4], 12, 1301)
@@ -188,6 +188,12 @@ def test_every_level_small_ring():
                     want = oracle_dot(rig.o, lvl, [x[1] for x in hA], [x[1] for x in hB], rig.key, rig.klvl, True,
                                       hE[1] if addend is not None else None)
                     assert np.array_equal(got[1], want), ("oracle", lvl)
+                    rig.ctx.set_ntt_chunk_mib(1)          # the two-pass transforms in 1 MiB chunks: item 1 is in a later one
+                    try:
+                        cut = dot(rig, lvl, dA, dB, batch, rescale, addend)
+                    finally:
+                        rig.ctx.set_ntt_chunk_mib(0)
+                    assert np.array_equal(cut[1], want) and np.array_equal(cut, got), ("ntt chunk", lvl)
     finally:
         rig.close()
 

@@ -65,8 +65,9 @@ def _reduced(diags, period):
 
 
 def _check(rig, level, diags, period, ratio=2.0, double_hoist=True, rescale=True, batch=1, n1=None, env_variants=(),
-           monkeypatch=None, fp64_variants=(1,), seed=0):
-    """device == oracle word for word; the switch variants == the default run; message precision; returns the plan's info"""
+           monkeypatch=None, fp64_variants=(1,), seed=0, chunk_mib=0):
+    """device == oracle word for word; the switch variants == the default run; message precision; returns the plan's info.
+    chunk_mib: one more run under lsa_set_ntt_chunk_mib, the same words (every batch item of `got` was held to the oracle)"""
     from lattisense_amd.device import LinearTransformPlan
     from oracle.ckks_bootstrap import Ct, apply_plain, linear_transform, rotations_of
     from oracle.client import galois_element_for_col_rotation, mean_precision_bits
@@ -108,6 +109,13 @@ def _check(rig, level, diags, period, ratio=2.0, double_hoist=True, rescale=True
             for k in env:
                 monkeypatch.delenv(k)
             assert np.array_equal(alt, got), (env, fp)
+    if chunk_mib:
+        ctx.set_ntt_chunk_mib(chunk_mib)
+        try:
+            alt = ctx.download(plan.run(xin, batch, glk, rescale=rescale), (batch, 2, lo, N))
+        finally:
+            ctx.set_ntt_chunk_mib(0)
+        assert np.array_equal(alt, got), ("ntt chunk", chunk_mib)
     info = (plan.n1, plan.rows)
     plan.close()
     return info
@@ -157,13 +165,15 @@ def test_sparse_packing(monkeypatch):
 
 @pytest.mark.parametrize("log_n", [13, 14])
 def test_whole_limb_rings(log_n, monkeypatch):
-    """N = 2^13 / 2^14: whole-limb and seven-stage transform plans; batch 3 in tiles of 2 (uneven last tile)"""
+    """N = 2^13 / 2^14: whole-limb and seven-stage transform plans; batch 3 in tiles of 2 (uneven last tile), once more with the
+    two-pass transforms cut into 1 MiB chunks (at 13 + 4 limbs: every item a chunk)"""
     need_gpu()
     rig = Rig(log_n, "headline", 30 + log_n)
     rng = np.random.default_rng(log_n)
     P = rig.N // 2
     rig.ctx.set_tile_batch(2)
-    _check(rig, 12, _diags(rng, range(-3, 4), P), P, batch=3, env_variants=SWITCHES, monkeypatch=monkeypatch, fp64_variants=(1, 0), seed=1)
+    _check(rig, 12, _diags(rng, range(-3, 4), P), P, batch=3, env_variants=SWITCHES, monkeypatch=monkeypatch, fp64_variants=(1, 0), seed=1,
+           chunk_mib=1)
     rig.ctx.set_tile_batch(0)
     if log_n == 14:
         _check(rig, 5, _diags(rng, range(200), P), P, n1=16, env_variants=SWITCHES[2:3], monkeypatch=monkeypatch, seed=2)

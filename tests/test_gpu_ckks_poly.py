@@ -58,8 +58,9 @@ def _reference(basis, coeffs, x, interval):
 
 
 def _check(rig, coeffs, basis, log_baby, level=None, interval=(-1, 1), scale_out=None, batch=1, pin=False, env_variants=(),
-           fp64_variants=(1,), monkeypatch=None, seed=0):
-    """device == restatement (== frozen oracle when `pin`) word for word; counts, constants, message; switch variants"""
+           fp64_variants=(1,), monkeypatch=None, seed=0, chunk_mib=0):
+    """device == restatement (== frozen oracle when `pin`) word for word; counts, constants, message; switch variants.
+    chunk_mib: one more run under lsa_set_ntt_chunk_mib, the same words (every batch item of `got` was held to the restatement)"""
     from lattisense_amd.device import PolynomialPlan
     from oracle.ckks_bootstrap import Ct, eval_chebyshev, eval_monomial
     from oracle.client import mean_precision_bits
@@ -113,6 +114,13 @@ def _check(rig, coeffs, basis, log_baby, level=None, interval=(-1, 1), scale_out
             for k in env:
                 monkeypatch.delenv(k)
             assert np.array_equal(alt, got), (env, fp)
+    if chunk_mib:
+        ctx.set_ntt_chunk_mib(chunk_mib)
+        try:
+            alt = ctx.download(plan.run(xin, batch, rig.rlk), shape)
+        finally:
+            ctx.set_ntt_chunk_mib(0)
+        assert np.array_equal(alt, got), ("ntt chunk", chunk_mib)
     info = got_plan
     plan.close()
     return info
@@ -172,12 +180,14 @@ def test_planner_choice_beats_binary_splitting_on_the_device():
 
 @pytest.mark.parametrize("log_n", [13, 14])
 def test_whole_limb_rings(log_n, monkeypatch):
-    """N = 2^13 / 2^14: whole-limb transform plans; batch 3 in tiles of 2 (uneven last tile)"""
+    """N = 2^13 / 2^14: whole-limb transform plans; batch 3 in tiles of 2 (uneven last tile), once more with the two-pass
+    transforms cut into 1 MiB chunks"""
     need_gpu()
     rig = Rig(log_n, "headline", 60 + log_n)
     rng = np.random.default_rng(log_n)
     rig.ctx.set_tile_batch(2)
-    _check(rig, _dense(rng, 32), "chebyshev", 3, batch=3, env_variants=SWITCHES, fp64_variants=(1, 0), monkeypatch=monkeypatch, seed=1)
+    _check(rig, _dense(rng, 32), "chebyshev", 3, batch=3, env_variants=SWITCHES, fp64_variants=(1, 0), monkeypatch=monkeypatch, seed=1,
+           chunk_mib=1)
     rig.ctx.set_tile_batch(0)
     _check(rig, _dense(rng, 32), "monomial", 0, env_variants=SWITCHES[:1], monkeypatch=monkeypatch, seed=2)
 

@@ -157,7 +157,12 @@ def _ok(rc):
 
 
 def _padded(r, case):
-    arrays, extra, wout, fn = _cases(r)[case]
+    _padded_call(r, case, *_cases(r)[case])
+
+
+def _padded_call(r, case, arrays, extra, wout, fn):
+    """one case of the shape _cases() returns, under the tag `case` (entry point, ':', variant); shared with
+    tests/test_gpu_ntt_chunk.py"""
     name = case.split(":")[0]
     want = r.want(case, lambda i: fn(*[np.ascontiguousarray(a[i]) for a in arrays]))
     ins = padded_inputs(r.ctx, arrays, r.batch)
