@@ -346,6 +346,47 @@ int lsa_ckks_linear_transform(lsa_context ctx, lsa_linear_transform lt, const ui
 int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double bsgs_ratio, int* n1, int* rotations,
                           int capacity, int* count);
 
+/* ---- CKKS slot sum: out = sum_{i<count} rot(ct, i*step), the sum over slots that follows a packed product (Lattigo InnerSum);
+ * Replicate is the same operation with a negative step (step = -batch_size).  The plan is a state (x, s, n, tail) starting at
+ * (ct, step, count, none) with the invariant  result = sum_{i<n} rot(x, i*s) + tail.  While n > 1 one STEP runs, one decomposition of
+ * x's c1 with up to four Galois keys:
+ *   1. n odd: the rotation (n-1)*s joins the step with destination TAIL, n -= 1;
+ *   2. radix 4 and n % 4 == 0: the rotations s, 2s, 3s with destination NEXT, s *= 4, n /= 4;
+ *      otherwise: the rotation s with destination NEXT, s *= 2, n /= 2;
+ *   3. x <- x + ModDown(sum of the NEXT rotations), the sum formed over Q_level u P and divided by P once; the TAIL rotation is
+ *      added to an extended accumulator that is not divided.
+ * At n == 1: out = x + ModDown(tail) if a tail exists, else x.  Rotations are reduced mod N/2.  Every extended rotation is
+ * automorphism_g(P c0 + ks0, ks1) with ks the gadget product of c1 with the key of g = 5^rotation mod 2N; the CPU restatement is
+ * tests/slot_sum_model.py on oracle/ckks_bootstrap.py (rotate_ext, add_ext, moddown, add), whose words the device gives exactly.
+ * radix: 2 (the key set of Lattigo's InnerSumLog: 2^i * step for i < floor(log2 count), plus one offset per set bit of count
+ * below the highest), 4 (one decomposition and one division less per two bits of count, one more key MAC and Galois key), or
+ * 0 = the default, 4: faster than 2 on the MI355X at every measured shape.  count == 1 is a copy and needs no key.
+ * Errors (LSA_ERR_ARG, the message names the argument): count < 1, count > N/2, radix not 0 / 2 / 4, a step that makes a planned
+ * rotation a multiple of N/2; for a plan also a BFV context and a level out of range. */
+typedef struct lsa_slot_sum_st* lsa_slot_sum;
+/* host only, needs no device and no context: the counts of the plan (steps = decompositions, key MACs, divisions by P) and its
+ * rotations (ascending, distinct, reduced mod N/2).  Any output pointer may be null; n_rot receives the number of rotations;
+ * LSA_ERR_ARG if `rotations` is given and capacity is less. */
+int lsa_slot_sum_plan(int n_ring, long long step, int count, int radix, int* n_steps, int* n_keyswitch, int* n_moddown,
+                      int* rotations, int capacity, int* n_rot);
+int lsa_slot_sum_create(lsa_context ctx, int level, long long step, int count, int radix, lsa_slot_sum* out);
+void lsa_slot_sum_destroy(lsa_slot_sum plan);
+/* radix: the one in force (never 0); any output pointer may be null */
+int lsa_slot_sum_info(lsa_slot_sum plan, int* level, int* count, int* radix, int* n_steps, int* n_keyswitch, int* n_moddown,
+                      int* n_galois);
+/* Galois elements of the rotations a run needs a key for (ascending) */
+int lsa_slot_sum_galois_elements(lsa_slot_sum plan, uint64_t* out, int capacity);
+/* A/B and parity: 1 makes the steps with several keys run ONE multi-key MAC launch (k_ks_mac_multi: every digit value read once
+ * for all keys, each key's product in its own buffer, k_ext_sum joining them) instead of one single-key MAC launch per key, each
+ * adding to its destination (default 0: the multi-key launch measured 6-10 % slower).  The same words either way. */
+int lsa_slot_sum_set_multi_mac(lsa_slot_sum plan, int enable);
+/* in [batch][2][level+1][N] (NTT domain) -> out, the same shape; batch strides sin / sout in words.  out may be in itself (same
+ * pointer, same stride) and otherwise may not overlap it (LSA_ERR_ARG); batch <= 0 is a no-op.  galois_elements / keys: n_keys
+ * Galois keys at the plan's level or above, in any order and possibly more than needed; a missing one fails with LSA_ERR_ARG (the
+ * message names the element) before any work is queued.  The plan belongs to its context. */
+int lsa_ckks_slot_sum(lsa_context ctx, lsa_slot_sum plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                      long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
+
 /* ---- CKKS polynomial evaluation: p(x) = sum_k coef[k] B_k(x) on a ciphertext, B_k the Chebyshev polynomial T_k (basis 0) or
  * the monomial x^k (basis 1), by a baby-step / giant-step (Paterson-Stockmeyer) plan of depth k = ceil(log2(n_coef)), k >= 1:
  * the powers P_j for j < 2^log_baby and P_(2^j) above them (P_j from P_ceil(j/2) and P_floor(j/2); only those that are used),

@@ -724,6 +724,77 @@ int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double 
     });
 }
 
+// ---- CKKS slot sum (slot_sum.h, ops.hip slot_sum_run)
+struct lsa_slot_sum_st {
+    SlotSum* p;
+    Context* c;
+};
+int lsa_slot_sum_plan(int n_ring, long long step, int count, int radix, int* n_steps, int* n_keyswitch, int* n_moddown,
+                      int* rotations, int capacity, int* n_rot) {
+    return guard([&] {
+        const SlotSumPlanHost p = slot_sum_plan_checked(n_ring, step, count, radix);
+        if (n_steps) *n_steps = (int)p.steps.size();
+        if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
+        if (n_moddown) *n_moddown = p.n_moddown;
+        if (n_rot) *n_rot = (int)p.rotations.size();
+        LSA_REQUIRE(rotations == nullptr || (int)p.rotations.size() <= capacity, "slot sum: buffer too small for the rotations");
+        if (rotations) std::copy(p.rotations.begin(), p.rotations.end(), rotations);
+    });
+}
+int lsa_slot_sum_create(lsa_context ctx, int level, long long step, int count, int radix, lsa_slot_sum* out) {
+    return guard([&] {
+        LSA_REQUIRE(out != nullptr, "null argument");
+        auto h = std::make_unique<lsa_slot_sum_st>();
+        h->c = &C(ctx);
+        h->p = slot_sum_create(*h->c, level, step, count, radix);
+        *out = h.release();
+    });
+}
+void lsa_slot_sum_destroy(lsa_slot_sum plan) {
+    if (!plan) return;
+    delete plan->p;
+    delete plan;
+}
+int lsa_slot_sum_info(lsa_slot_sum plan, int* level, int* count, int* radix, int* n_steps, int* n_keyswitch, int* n_moddown,
+                      int* n_galois) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr, "null slot-sum handle");
+        const SlotSumPlanHost& p = plan->p->plan;
+        if (level) *level = plan->p->level;
+        if (count) *count = p.count;
+        if (radix) *radix = p.radix;
+        if (n_steps) *n_steps = (int)p.steps.size();
+        if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
+        if (n_moddown) *n_moddown = p.n_moddown;
+        if (n_galois) *n_galois = (int)plan->p->galois.size();
+    });
+}
+int lsa_slot_sum_galois_elements(lsa_slot_sum plan, uint64_t* out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr && out != nullptr, "null argument");
+        const auto& g = plan->p->galois;
+        LSA_REQUIRE((int)g.size() <= capacity, "buffer too small");
+        std::copy(g.begin(), g.end(), out);
+    });
+}
+int lsa_slot_sum_set_multi_mac(lsa_slot_sum plan, int enable) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr, "null slot-sum handle");
+        plan->p->multi_mac = enable != 0;
+    });
+}
+int lsa_ckks_slot_sum(lsa_context ctx, lsa_slot_sum plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                      long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr, "null slot-sum handle");
+        LSA_REQUIRE(plan->c == &C(ctx), "slot sum: the plan belongs to another context");
+        LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "slot sum: null argument");
+        std::map<u64, const Key*> g;
+        for (int i = 0; i < n_keys; i++) g[galois_elements[i]] = &K(keys[i], "lsa_ckks_slot_sum");
+        slot_sum_run(*plan->p, in, sin, out, sout, batch, g, S(stream));
+    });
+}
+
 // ---- CKKS polynomial evaluation (poly_eval.hip)
 struct lsa_polynomial_st {
     Polynomial* p;

@@ -13,6 +13,7 @@
 #include "ntt_plan.h"
 #include "ntt_chunk.h"
 #include "plain_ops.h"
+#include "slot_sum.h"
 #include "switches.h"
 #include "tables.h"
 
@@ -354,6 +355,20 @@ void launch_permute_ntt(Context& c, const u32* perm, const u64* in, long long si
                         int batch, hipStream_t s);
 void launch_permute_coeff(Context& c, const u32* perm, const u64* in, long long sin, u64* out, long long sout, int rows,
                           const RowMap& rm, int batch, hipStream_t s);
+// one decomposition, n_keys = 2..4 keys in ONE launch (slot_sum.hip k_ks_mac_multi; arithmetic: ks_mac_multi.h): key k's product
+// leaves as launch_ks_mac's scattered extended form, outs[k][h][tl][scatter_k[x]] = sum_k(x) + (h == 0, tl < L: P * base[tl][x]), in key
+// k's own buffer [batch][2][L+k][N] (batch stride sout); every digit value is read once for all keys.  The same words as n_keys
+// launch_ks_mac calls with `scatter` and `base`.
+struct KsMacMultiKey {
+    const Key* key;
+    const u32* scatter;
+    u64* out;
+};
+void launch_ks_mac_multi(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, int n_keys,
+                         const KsMacMultiKey* keys, long long sout, const u64* base, long long sbase, int batch, hipStream_t s);
+// out (+)= sum_{k<n_in} in[k] over the 2(L+k) rows of extended ciphertexts, n_in = 1..3 (k_ext_sum); no addend is `out`
+void launch_ext_sum(Context& c, int level, int n_in, const u64* const* in, long long sin, u64* out, long long sout, bool accumulate,
+                    int batch, hipStream_t s);
 // extended (Q_level u P) ciphertext: out (+)= perm(acc + P * base) -- a rotation without its division by P (k_permute_ext)
 void launch_permute_ext(Context& c, int level, const u32* perm, const u64* acc, long long sacc, const u64* base, long long sbase,
                         int base_polys, u64* out, long long sout, bool accumulate, int batch, hipStream_t s);
@@ -482,6 +497,24 @@ void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const
 void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, bool accumulate, int batch,
                      long long sin, long long sout, hipStream_t s, bool scatter_mac = false);
 void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
+// CKKS slot sum  out = sum_{i<count} rot(in, i*step)  (lsa_slot_sum_* / lsa_ckks_slot_sum; plan rule: slot_sum.h).  Every step is one
+// decomposition whose 1..4 rotations stay over Q_level u P (the words of ckks_rotate_ext); the NEXT group is divided by P once with
+// x riding on the ModDown tail's base, the TAIL rotations gather in an extended accumulator divided once at the end.
+struct SlotSum {
+    Context& c;
+    int level;
+    SlotSumPlanHost plan;
+    std::vector<u64> galois;    // elements of plan.rotations, ascending
+    // steps with 2..4 keys: true = one k_ks_mac_multi launch + k_ext_sum; false = one launch_ks_mac per key, each adding to its
+    // destination.  The same words; the default is the faster form on the MI355X (the multi-key launch lost 6-10 %)
+    bool multi_mac = false;
+    SlotSum(Context& ctx, int level_) : c(ctx), level(level_) {}
+};
+#define LSA_SLOTSUM_DEFAULT_RADIX 4   // what radix 0 stands for: measured, DESIGN 4.11
+SlotSumPlanHost slot_sum_plan_checked(int n_ring, long long step, int count, int radix);   // slot_sum_plan, refusals as LSA_ERR_ARG
+SlotSum* slot_sum_create(Context& c, int level, long long step, int count, int radix);
+void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
+                  const std::map<u64, const Key*>& glk, hipStream_t s);
 void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                 hipStream_t s);
 void poly_addsub(Context& c, int op, int level, int polys, const u64* a, const u64* b, u64* out, int batch, long long sa,

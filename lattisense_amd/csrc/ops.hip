@@ -1506,4 +1506,135 @@ void ckks_affine_const(Context& c, int level, const u64* ct, long long sct, doub
     cconst_run(c, pc, &alpha, &beta, ct, sct, out, so, rescale, s);
 }
 
+// ------------------------------------------------------------------------------------------------ CKKS slot sum
+// out = sum_{i<count} rot(in, i*step) by the plan of slot_sum.h.  Per tile the steps run back to back: one decomposition of x's c1,
+// the gadget products of the step's 1..4 keys written as rotated extended ciphertexts (launch_ks_mac with `scatter`: the words of
+// ckks_rotate_ext) -- several keys in ONE k_ks_mac_multi launch, each into its own buffer, k_ext_sum joining them -- then
+// x <- x + ModDown(NEXT sum) with x riding on the ModDown tail's base (base_polys = 2).  That store is index for index, so from
+// the second step on x lives in `out` and is updated in place, and out == in is allowed.  The TAIL rotations gather in an extended
+// accumulator that is divided once, after the last step.  All temporaries are the tile's workspace: the KsTile rows, up to three more
+// extended ciphertexts for the keys of a multi-key launch beyond the first, and one for the tail.
+SlotSumPlanHost slot_sum_plan_checked(int n_ring, long long step, int count, int radix) {
+    try {
+        return slot_sum_plan(n_ring, step, count, radix, LSA_SLOTSUM_DEFAULT_RADIX);
+    } catch (const std::invalid_argument& e) {
+        throw Error(LSA_ERR_ARG, e.what());
+    }
+}
+
+static u64 galois_of_rotation(int r, int n_ring) {   // 5^r mod 2N
+    const u64 mask = 2 * (u64)n_ring - 1;
+    u64 e = 1, b = 5;
+    for (; r; r >>= 1, b = b * b & mask)
+        if (r & 1) e = e * b & mask;
+    return e;
+}
+
+SlotSum* slot_sum_create(Context& c, int level, long long step, int count, int radix) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, "slot sum: context is not CKKS");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "slot sum: level out of range");
+    auto p = std::make_unique<SlotSum>(c, level);
+    p->plan = slot_sum_plan_checked(c.n, step, count, radix);
+    LSA_REQUIRE(p->plan.steps.empty() || c.np >= 1, "slot sum: key switching needs at least one special prime");
+    for (int r : p->plan.rotations) p->galois.push_back(galois_of_rotation(r, c.n));
+    std::sort(p->galois.begin(), p->galois.end());
+    return p.release();
+}
+
+void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
+                  const std::map<u64, const Key*>& glk, hipStream_t s) {
+    Context& c = p.c;
+    const int level = p.level;
+    const EntryCheck ck(c, "lsa_ckks_slot_sum", LSA_ALGO_CKKS, level, 0, batch);
+    std::map<int, const Key*> key_of;   // every key is looked up before anything is queued
+    for (int r : p.plan.rotations) {
+        const u64 e = galois_of_rotation(r, c.n);
+        auto it = glk.find(e);
+        LSA_REQUIRE(it != glk.end() && it->second, ck.who + ": Galois key for element " + std::to_string(e) + " missing");
+        ck.key(*it->second, "a Galois key");
+        key_of[r] = it->second;
+    }
+    if (batch <= 0) return;
+    const long long N = c.n;
+    const int L = level + 1, T = L + c.np;
+    const size_t w = 2 * (size_t)L * N;
+    const Span sp_in = ck.operand(in, sin, w, "in", false), sp_out = ck.output(out, sout, w);
+    ck.same_or_apart(sp_out, sp_in, "in");
+    if (p.plan.steps.empty()) {   // count == 1: a copy
+        if (layout::same(sp_out, sp_in)) return;
+        std::vector<int> rows(2 * L);
+        for (int i = 0; i < 2 * L; i++) rows[i] = i;
+        launch_copy_rows(c, in, sin, out, sout, 2 * L, rows.data(), batch, s);
+        return;
+    }
+    std::map<int, const u32*> scatter_of;   // (table look-ups upload on first use: only after every argument is accepted)
+    for (int r : p.plan.rotations) scatter_of[r] = inverse_perm(c, galois_of_rotation(r, c.n));
+    const size_t ks_rows = KsTile::rows(c, level);
+    const bool multi = p.multi_mac;
+    // extended buffers beyond KsTile's acc: one per key of a multi-key launch that is neither the first NEXT key nor the first
+    // TAIL key of the plan (the most any step needs), and the tail accumulator
+    int n_more = 0;
+    {
+        bool live = false;
+        for (const SlotSumStep& step : p.plan.steps) {
+            int more = 0, next = 0;
+            for (const SlotSumKey& k : step.keys) more += k.tail ? (live ? 1 : 0) : (next++ ? 1 : 0);
+            for (const SlotSumKey& k : step.keys) live = live || k.tail;
+            if (multi && step.keys.size() >= 2) n_more = std::max(n_more, more);
+        }
+    }
+    const int n_extra = n_more + (p.plan.has_tail ? 1 : 0);
+    for_tiles(c, ks_rows + (size_t)n_extra * 2 * T, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
+        KsTile t(c, level, nb, ws, st);
+        const long long s_ext2 = t.s_acc;   // [2][T][N] per batch item, like t.acc
+        u64* extra[LSA_SLOTSUM_MAX_KEYS];
+        for (int i = 0; i < n_extra; i++) extra[i] = ws + (ks_rows * tb + (size_t)i * 2 * T * tb) * N;
+        u64* tail = p.plan.has_tail ? extra[n_more] : nullptr;
+        const u64* x = in + (size_t)b0 * sin;
+        long long sx = sin;
+        u64* o = out + (size_t)b0 * sout;
+        bool tail_live = false;
+        for (const SlotSumStep& step : p.plan.steps) {
+            const u64* cx = x + (long long)L * N;
+            t.decompose(cx, sx);
+            const int nk = (int)step.keys.size();
+            const bool one_launch = multi && nk >= 2;
+            KsMacMultiKey mk[LSA_SLOTSUM_MAX_KEYS];
+            bool add_to[LSA_SLOTSUM_MAX_KEYS];   // sequential form: the key's product is added to its destination
+            const u64* next_more[LSA_SLOTSUM_MAX_KEYS];
+            const u64* tail_more = nullptr;
+            int n_next = 0, n_sum = 0, used = 0;
+            for (int i = 0; i < nk; i++) {
+                const SlotSumKey& k = step.keys[i];
+                u64* dst;
+                if (k.tail) {
+                    add_to[i] = tail_live;
+                    dst = !tail_live || !one_launch ? tail : extra[used++];
+                    if (dst != tail) tail_more = dst;
+                } else {
+                    add_to[i] = n_next > 0;
+                    dst = n_next == 0 || !one_launch ? t.acc : extra[used++];
+                    if (dst != t.acc) next_more[n_sum++] = dst;
+                    n_next++;
+                }
+                mk[i] = {key_of.at(k.rot), scatter_of.at(k.rot), dst};
+            }
+            if (one_launch) {
+                launch_ks_mac_multi(c, level, cx, sx, t.ext, t.s_ext, nk, mk, s_ext2, x, sx, nb, st);
+                if (n_sum) launch_ext_sum(c, level, n_sum, next_more, s_ext2, t.acc, s_ext2, true, nb, st);
+                if (tail_more) launch_ext_sum(c, level, 1, &tail_more, s_ext2, tail, s_ext2, true, nb, st);
+            } else {
+                for (int i = 0; i < nk; i++)
+                    launch_ks_mac(c, level, cx, sx, t.ext, t.s_ext, *mk[i].key, mk[i].out, s_ext2, nb, st, false, mk[i].scatter, x, sx, nullptr,
+                                  add_to[i]);
+            }
+            for (int i = 0; i < nk; i++) tail_live = tail_live || step.keys[i].tail;
+            t.moddown({.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2});
+            x = o;
+            sx = sout;
+        }
+        if (tail_live) ks_moddown(c, level, tail, s_ext2, t.conv, {.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2}, nb, st);
+    });
+}
+
 }  // namespace lsa

@@ -551,6 +551,71 @@ class LinearTransformPlan:
         return out
 
 
+def plan_slot_sum(n, step, count, radix=0):
+    """{steps, keyswitches, moddowns, rotations} of the slot sum sum_{i<count} rot(ct, i*step) at ring degree n -- host only
+    (include/lattisense_amd.h: lsa_slot_sum_plan).  radix: 2, 4 or 0 = the default; rotations ascending, reduced mod n/2."""
+    ns, nk, nm, cnt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    args = (int(n), int(step), int(count), int(radix), ctypes.byref(ns), ctypes.byref(nk), ctypes.byref(nm))
+    check(lib().lsa_slot_sum_plan(*args, None, 0, ctypes.byref(cnt)))
+    rot = (ctypes.c_int * max(cnt.value, 1))()
+    check(lib().lsa_slot_sum_plan(*args, rot, cnt.value, ctypes.byref(cnt)))
+    return {"steps": ns.value, "keyswitches": nk.value, "moddowns": nm.value, "rotations": [int(r) for r in rot[: cnt.value]]}
+
+
+class SlotSumPlan:
+    """out = sum_{i<count} rot(ct, i*step) on ciphertexts at `level` (include/lattisense_amd.h: lsa_slot_sum_*); Replicate is
+    step = -batch_size.  Planning needs no GPU (`.rotations`, `.galois_elements`, the counts); the device plan is made by the
+    first run."""
+
+    def __init__(self, ctx, level, step, count, radix=0):
+        self.ctx, self.level, self.step, self.count = ctx, int(level), int(step), int(count)
+        self.h = None
+        self.multi_mac = False   # True: steps with several keys in one k_ks_mac_multi launch (A/B; the same words)
+        n = ctx.n
+        info = plan_slot_sum(n, step, count, radix)
+        self.steps, self.keyswitches, self.moddowns, self.rotations = info["steps"], info["keyswitches"], info["moddowns"], info["rotations"]
+        self.radix = int(radix)
+        self.galois_elements = sorted(pow(5, r, 2 * n) for r in self.rotations)
+
+    def _handle(self):
+        if self.h is None:
+            h = ctypes.c_void_p()   # (a context without a device has no handle: the library refuses, there is no CPU path)
+            check(lib().lsa_slot_sum_create(self.ctx.h, self.level, self.step, self.count, self.radix, ctypes.byref(h)))
+            self.h = h
+            rx, ng = ctypes.c_int(), ctypes.c_int()
+            check(lib().lsa_slot_sum_info(self.h, None, None, ctypes.byref(rx), None, None, None, ctypes.byref(ng)))
+            g = (ctypes.c_uint64 * max(ng.value, 1))()
+            check(lib().lsa_slot_sum_galois_elements(self.h, g, ng.value))
+            assert [int(x) for x in g[: ng.value]] == self.galois_elements
+            self.radix = rx.value
+        return self.h
+
+    def close(self):
+        if self.h:
+            lib().lsa_slot_sum_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, in_buf, batch, glk, out=None):
+        """in_buf: device [batch][2][level+1][N]; glk: {galois element: key handle}; returns device [batch][2][level+1][N]
+        (out may be in_buf)"""
+        h = self._handle()
+        n = self.ctx.n
+        words = 2 * (self.level + 1) * n
+        if out is None:
+            out = self.ctx.alloc(max(batch, 1) * words)
+        check(lib().lsa_slot_sum_set_multi_mac(h, int(bool(self.multi_mac))))
+        elts = (ctypes.c_uint64 * max(len(glk), 1))(*glk.keys())
+        keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
+        check(lib().lsa_ckks_slot_sum(self.ctx.h, h, in_buf.ptr, out.ptr, batch, words, words, len(glk), elts, keys, self.ctx.stream))
+        return out
+
+
 BASES = {"chebyshev": 0, "monomial": 1}
 
 
