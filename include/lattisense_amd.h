@@ -227,8 +227,47 @@ int lsa_bfv_rescale(lsa_context ctx, int level, int polys, const uint64_t* in, u
 int lsa_bfv_mult_relin(lsa_context ctx, int level, const uint64_t* a, const uint64_t* b, lsa_key rlk,
                        uint64_t* out, int batch, long long stride_a, long long stride_b, long long stride_out,
                        void* stream);
+/* Encrypted inner product: sum_{i<n} a_i x b_i of n >= 1 pairs of BFV ciphertexts with ONE scale-down by Q and ONE relinearisation.
+ * Only the extension of the operands to Q u QMul and the tensor depend on the pair; the tensors are summed over Q u QMul, where the
+ * sum is exact while the auxiliary basis holds it, and the inverse transform, the six base conversions of the division by Q and the
+ * key switch run once per output.  The result carries one rounding and one key-switch error instead of n of each, so its words
+ * differ from the eager sum of lsa_bfv_mult_relin.
+ *   Operands.  as[i], bs[i]: [2][level+1][N] per batch item, coefficient domain, all at `level` (a BFV level change is no row
+ *     prefix); sas[i], sbs[i] batch strides in words, 0 = one ciphertext shared by the whole batch (extended once); as[i] == bs[i]
+ *     with equal strides is a square and is extended once.  addend (nullable): a ciphertext [2][level+1][N] added to polynomials 0
+ *     and 1 AFTER the division, with the words of lsa_poly_addsub.  The output overlaps no input.  Layout as for the first-generation
+ *     operators: 16-byte aligned pointers, even strides.
+ *   Headroom rule.  The auxiliary basis is sized for ONE product: nmul = ceil((bitlen(Q_full) + log N) / 61) primes of 61 bits
+ *     (a coefficient of one tensor is below N (Q/2)^2 * 2, and Q * QMul / 2 has to exceed it).  A sum of m products is at most m
+ *     times as large: ceil(log2 m) bits more.  At `level` the context's nmul primes leave
+ *         G = min(30, 61 nmul - bitlen(Q_level) - log N) >= 0 bits,   max_terms = 2^G.
+ *     The n terms are cut into consecutive groups of max_terms (the last may be shorter).  A group of m terms runs over Q_level and
+ *     the FIRST M(m) = (bitlen(Q_level) + log N + ceil(log2 m) + 60) / 61 auxiliary primes -- M(1) is lsa_bfv_mult's count and
+ *     M(max_terms) <= nmul -- and is divided by Q on its own; the group results are added in Q (the words of lsa_poly_addsub), and
+ *     ONE relinearisation follows.  At the shipped sets the split is rare (G = 24 at N = 2^14 with 6 Q primes, 17 at N = 2^15,
+ *     7 at N = 2^13, 30 at every lower level): it is the fallback that keeps every n legal.  lsa_bfv_dot_plan states what a call will do.
+ *   With n == 1 and no addend the words are exactly lsa_bfv_mult / lsa_bfv_mult_relin; lsa_bfv_dot equals lsa_bfv_relin of
+ *     lsa_bfv_mult_sum word for word.  LSA_BFV_FOLD=0 selects the unfolded extension and tail as it does for lsa_bfv_mult.
+ *   LSA_ERR_ARG before anything is queued, the message beginning "bfv_dot": a CKKS context, n < 1, level out of range, a null
+ *     pointer, a short, negative or odd stride, a pointer off the 16-byte grid, a missing key or one exported below `level`, an
+ *     overlap of the output with an input.  batch <= 0 is a no-op. */
+/* d3 = t * round( sum_i a_i (x) b_i / Q ) (+ (addend_0, addend_1, 0)):  [3][level+1][N], coefficient domain */
+int lsa_bfv_mult_sum(lsa_context ctx, int level, int n, const uint64_t* const* as, const long long* sas, const uint64_t* const* bs,
+                     const long long* sbs, const uint64_t* addend, long long s_addend, uint64_t* d3, int batch, long long sd,
+                     void* stream);
+/* out = relin(d3 above):  [2][level+1][N] */
+int lsa_bfv_dot(lsa_context ctx, int level, int n, const uint64_t* const* as, const long long* sas, const uint64_t* const* bs,
+                const long long* sbs, const uint64_t* addend, long long s_addend, lsa_key rlk, uint64_t* out, int batch,
+                long long sout, void* stream);
+/* host only, no context and no device: what the two entry points above will do with `terms` pairs at `level` of the chain q[nq] at
+ * ring degree n_ring -- max_terms = 2^G, the number of groups, and the auxiliary limbs M(min(terms, max_terms)) of the first group
+ * (a full one when there are several).  Every output pointer is nullable. */
+int lsa_bfv_dot_plan(int n_ring, const uint64_t* q, int nq, int level, int terms, int* max_terms, int* n_groups, int* aux_limbs);
 
 /* ---- tuning / introspection */
+/* pairs that lsa_bfv_mult_sum / lsa_bfv_dot extend per tensor launch (0 = the measured default; at most 16, and never so many that
+ * the batch tile falls below lsa_bfv_mult's).  The words are the same for every value; workspace grows by 4 (L + M) rows per pair. */
+int lsa_set_bfv_dot_chunk(lsa_context ctx, int pairs);
 /* ciphertexts processed per kernel wave inside the fused operators (0 = automatic) */
 int lsa_set_tile_batch(lsa_context ctx, int tile_batch);
 /* NTT butterfly engine for limbs with q < 2^47: 1 (default) = exact FP64-FMA butterflies, 0 = integer Montgomery for

@@ -89,6 +89,13 @@ SIGNATURES = {
     "lsa_bfv_rotate": (c_int, [c_vp, c_int, c_vp, ctypes.c_uint64, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),
     "lsa_bfv_rescale": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),
     "lsa_bfv_mult_relin": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_ll, c_vp]),
+    "lsa_bfv_mult_sum": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_vp),
+                                 ctypes.POINTER(c_ll), c_vp, c_ll, c_vp, c_int, c_ll, c_vp]),
+    "lsa_bfv_dot": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_ll), ctypes.POINTER(c_vp), ctypes.POINTER(c_ll),
+                            c_vp, c_ll, c_vp, c_vp, c_int, c_ll, c_vp]),
+    "lsa_bfv_dot_plan": (c_int, [c_int, c_u64p, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                 ctypes.POINTER(c_int)]),
+    "lsa_set_bfv_dot_chunk": (c_int, [c_vp, c_int]),
     "lsa_set_tile_batch": (c_int, [c_vp, c_int]),
     "lsa_set_fp64_ntt": (c_int, [c_vp, c_int]),
     "lsa_set_dual_stream": (c_int, [c_vp, c_int]),

@@ -351,6 +351,39 @@ int lsa_bfv_mult_relin(lsa_context ctx, int level, const uint64_t* a, const uint
     return guard([&] { bfv_mult_relin(C(ctx), level, a, b, K(rlk, "lsa_bfv_mult_relin"), out, batch, sa, sb, so, S(stream)); });
 }
 
+// ---- BFV encrypted inner product (ops.hip bfv_mult_sum / bfv_dot; the plan is tables.cpp's and needs no device)
+int lsa_bfv_mult_sum(lsa_context ctx, int level, int n, const uint64_t* const* as, const long long* sas, const uint64_t* const* bs,
+                     const long long* sbs, const uint64_t* addend, long long s_addend, uint64_t* d3, int batch, long long sd,
+                     void* stream) {
+    return guard([&] {
+        const DotTerms t{n, as, sas, nullptr, bs, sbs, nullptr, addend, s_addend};
+        bfv_mult_sum(C(ctx), level, t, d3, batch, sd, S(stream));
+    });
+}
+int lsa_bfv_dot(lsa_context ctx, int level, int n, const uint64_t* const* as, const long long* sas, const uint64_t* const* bs,
+                const long long* sbs, const uint64_t* addend, long long s_addend, lsa_key rlk, uint64_t* out, int batch, long long sout,
+                void* stream) {
+    return guard([&] {
+        const DotTerms t{n, as, sas, nullptr, bs, sbs, nullptr, addend, s_addend};
+        bfv_dot(C(ctx), level, t, rlk ? &rlk->key : nullptr, out, batch, sout, S(stream));
+    });
+}
+int lsa_bfv_dot_plan(int n_ring, const uint64_t* q, int nq, int level, int terms, int* max_terms, int* n_groups, int* aux_limbs) {
+    return guard([&] {
+        LSA_REQUIRE(n_ring >= 2 && n_ring <= (1 << 20) && (n_ring & (n_ring - 1)) == 0, "bfv_dot: the ring degree must be a power of two");
+        LSA_REQUIRE(q != nullptr && nq >= 1, "bfv_dot: null argument");
+        LSA_REQUIRE(level >= 0 && level < nq, "bfv_dot: level out of range");
+        LSA_REQUIRE(terms >= 1, "bfv_dot: needs at least one term");
+        for (int i = 0; i < nq; i++) LSA_REQUIRE(q[i] >= 2 && (q[i] >> 61) == 0, "bfv_dot: a modulus is out of range");
+        int logn = 0;
+        while ((1 << logn) < n_ring) logn++;
+        const BfvDotPlan p = bfv_dot_plan(q, nq, level, logn, terms);
+        if (max_terms) *max_terms = p.max_terms;
+        if (n_groups) *n_groups = p.n_groups;
+        if (aux_limbs) *aux_limbs = p.aux_limbs;
+    });
+}
+
 int lsa_profile_begin(lsa_context ctx, int stride) {
     return guard([&] {
         Context& c = C(ctx);
@@ -859,6 +892,12 @@ int lsa_set_ntt_chunk_mib(lsa_context ctx, int mib) {
     return guard([&] {
         LSA_REQUIRE(mib >= 0, "chunk size must be >= 0");
         C(ctx).ntt_chunk_mib = mib;
+    });
+}
+int lsa_set_bfv_dot_chunk(lsa_context ctx, int pairs) {
+    return guard([&] {
+        LSA_REQUIRE(pairs >= 0, "chunk size must be >= 0");
+        C(ctx).bfv_dot_chunk = pairs;
     });
 }
 int lsa_set_fp64_ntt(lsa_context ctx, int enable) {

@@ -119,6 +119,7 @@ struct Context {
     void join_aux(hipStream_t s);   // s waits for everything enqueued on the aux stream
     unsigned long long* ntt_diag = nullptr;   // device buffer for LSA_NTT_DIAG_STAMPS builds (8 stamps per workgroup)
     int ntt_chunk_mib = 0;          // >0: two-pass NTTs run pass A+B per chunk of this many MiB (Infinity-Cache reuse)
+    int bfv_dot_chunk = 0;          // >0: pairs extended per k_tensor_sum launch of bfv_mult_sum / bfv_dot (0: LSA_BFV_DOT_CHUNK)
 
     // sampled HIP-event timing of kernel launches (bench.py roofline leg); off unless lsa_profile_begin was called
     struct ProfSample {
@@ -525,6 +526,12 @@ void bfv_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, i
                hipStream_t s);
 void bfv_mult_relin(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch, long long sa,
                     long long sb, long long so, hipStream_t s);
+// BFV encrypted inner product (semantics and the headroom rule: include/lattisense_amd.h, tables.h bfv_dot_plan).  The operands of
+// DotTerms are coefficient-domain ciphertexts [2][level+1][N]; a_rpp / b_rpp are not used.  d3 = t * round(sum_i a_i (x) b_i / Q)
+// (+ addend on polynomials 0 and 1), [3][level+1][N]: with n == 1 and no addend the words of bfv_mult
+void bfv_mult_sum(Context& c, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s);
+// out = bfv_relin(d3 above): ONE scale-down per group of terms and ONE key switch for the whole sum
+void bfv_dot(Context& c, int level, const DotTerms& t, const Key* rlk, u64* out, int batch, long long so, hipStream_t s);
 void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, int batch, long long sin,
                 long long sout, hipStream_t s);
 void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,

@@ -1020,6 +1020,209 @@ void bfv_mult_relin(Context& c, int level, const u64* a, const u64* b, const Key
     bfv_relin(c, level, d3, rlk, out, batch, sd, so, s);
 }
 
+// ---- BFV encrypted inner product: t * round(sum_i a_i (x) b_i / Q) with ONE scale-down and ONE relinearisation.  Only the
+// extension of the operands and the tensor depend on the pair; the tensors are summed in Q u QMul (k_tensor_sum), where the sum is
+// exact while the auxiliary basis holds it (tables.h bfv_dot_plan: groups of at most max_terms pairs, a group of m over the first
+// M(m) auxiliary primes), and the inverse transform, the six conversions of the division by Q and the key switch run once.
+// The extension and the tail below restate bfv_mult's launches for a basis of M auxiliary primes; bfv_mult itself is untouched.
+#define LSA_BFV_DOT_CHUNK 4   // pairs extended per k_tensor_sum launch (measured, and why not more)
+
+namespace {
+struct BfvDotBasis {   // Q_level u the first M auxiliary primes: row maps, conversion plans and folded constants
+    int L = 0, M = 0, T2 = 0;
+    RowMap rmT, rmAux;
+    const BaseConvPlan *kQA = nullptr, *kAQ = nullptr, *kAQf = nullptr;
+    BaseConvRows rQA{}, rAQ{};
+    const u64 *kQinv = nullptr, *kT = nullptr;
+    unsigned char lmA[LSA_MAX_PERIOD], lmQ[LSA_MAX_PERIOD];
+    std::vector<int> sub_rows;
+};
+
+BfvDotBasis bfv_dot_basis(Context& c, int level, int M, bool fold_on) {
+    BfvDotBasis B;
+    const int L = level + 1, T2 = L + M;
+    LSA_REQUIRE(M >= 1 && M <= c.nmul && T2 <= LSA_MAX_PERIOD, "bfv_dot: auxiliary basis too small");
+    B.L = L, B.M = M, B.T2 = T2;
+    std::vector<int> qmods, amods;
+    B.rmT.period = T2;
+    for (int i = 0; i < L; i++) {
+        qmods.push_back(i);
+        B.rmT.mod_of[i] = (unsigned char)i;
+        B.rQA.src_row[i] = i, B.rAQ.dst_row[i] = i;
+        B.lmQ[i] = (unsigned char)i;
+    }
+    for (int i = 0; i < M; i++) {
+        amods.push_back(c.aux_mod(i));
+        B.rmT.mod_of[L + i] = (unsigned char)c.aux_mod(i);
+        B.rQA.dst_row[i] = i, B.rAQ.src_row[i] = i;
+        B.lmA[i] = (unsigned char)c.aux_mod(i);
+    }
+    B.rmAux = B.rmT;   // the auxiliary rows only
+    for (int i = 0; i < L; i++) B.rmAux.mod_of[i] = LSA_ROW_SKIP;
+    std::vector<u64> qinv(M), tq(L);   // Q^-1 mod aux_i and t mod q_i
+    for (int i = 0; i < M; i++) {
+        const u64 p = c.T.mod[c.aux_mod(i)];
+        u64 pr = 1;
+        for (int l = 0; l < L; l++) pr = mul_mod_host(pr, c.T.mod[l] % p, p);
+        qinv[i] = inv_mod(pr, p);
+    }
+    for (int i = 0; i < L; i++) tq[i] = c.t % c.T.mod[i];
+    const std::string tag = std::to_string(L) + "m" + std::to_string(M);
+    B.kQA = c.baseconv(qmods, amods, true);
+    if (fold_on) {
+        Context::BaseConvFold fold{"bfv_dot" + tag, qinv, tq};
+        B.kAQf = c.baseconv(amods, qmods, true, false, &fold);
+    } else {
+        B.kAQ = c.baseconv(amods, qmods, true);
+        B.kQinv = c.const_vec("bfv_dot_qinv" + tag, amods, qinv);
+        B.kT = c.const_vec("bfv_dot_t" + tag, qmods, tq);
+    }
+    B.sub_rows.resize(M);
+    for (int i = 0; i < M; i++) B.sub_rows[i] = i;
+    return B;
+}
+
+// one operand into [2][T2][N] per item: the Q limbs transformed (folded: from where they are), the auxiliary limbs by the centred
+// exact extension, then transformed -- bfv_mult's extension
+void bfv_dot_extend(Context& c, const BfvDotBasis& B, bool fold_on, const u64* src, long long ss, u64* e, int nb, hipStream_t s) {
+    const long long N = c.n;
+    const int L = B.L, T2 = B.T2;
+    const long long s_e = 2LL * T2 * N;
+    for (int p = 0; p < 2; p++) {
+        std::vector<int> rr(L);
+        for (int i = 0; i < L; i++) rr[i] = p * L + i;
+        if (fold_on) launch_ntt(c, src + (size_t)p * L * N, e + (size_t)p * T2 * N, nb, ss, s_e, L, rm_seq(L), false, s);
+        else launch_copy_rows(c, src, ss, e + (size_t)p * T2 * N, s_e, L, rr.data(), nb, s);
+        launch_baseconv(c, B.kQA, B.rQA, src + (size_t)p * L * N, e + ((size_t)p * T2 + L) * N, nb, ss, s_e, s);
+    }
+    launch_ntt(c, e, e, nb, s_e, 2 * T2, fold_on ? B.rmAux : B.rmT, false, s);
+}
+
+// d [3][T2][N] (NTT domain) -> o3 = t * round(d / Q) [3][L][N]: bfv_mult's tail
+void bfv_dot_tail(Context& c, const BfvDotBasis& B, bool fold_on, u64* d, u64* ext, u64* o3, long long so, int nb, hipStream_t s) {
+    const long long N = c.n;
+    const int L = B.L, M = B.M, T2 = B.T2;
+    const long long s_d = 3LL * T2 * N, s_x = 3LL * M * N;
+    launch_ntt(c, d, d, nb, s_d, 3 * T2, B.rmT, true, s);
+    for (int k = 0; k < 3; k++) launch_baseconv(c, B.kQA, B.rQA, d + (size_t)k * T2 * N, ext + (size_t)k * M * N, nb, s_d, s_x, s);
+    if (fold_on) {
+        for (int k = 0; k < 3; k++)
+            launch_baseconv(c, B.kAQf, B.rAQ, d + ((size_t)k * T2 + L) * N, o3 + (size_t)k * L * N, nb, s_d, so, s, ext + (size_t)k * M * N,
+                            s_x, B.sub_rows.data());
+        return;
+    }
+    launch_sub_mul_general(c, 3, M, B.lmA, B.kQinv, d + (size_t)L * N, s_d, T2, ext, s_x, M, nullptr, 0, 0, 0, d + (size_t)L * N, s_d,
+                           T2, nb, s);
+    for (int k = 0; k < 3; k++) launch_baseconv(c, B.kAQ, B.rAQ, d + ((size_t)k * T2 + L) * N, o3 + (size_t)k * L * N, nb, s_d, so, s);
+    launch_sub_mul_general(c, 3, L, B.lmQ, B.kT, o3, so, L, nullptr, 0, 0, nullptr, 0, 0, 0, o3, so, L, nb, s);
+}
+
+// every argument error of the two entry points, before anything is queued; false: nothing to do (batch <= 0)
+bool bfv_dot_check(const Context& c, int level, const DotTerms& t, const Key* rlk, bool with_relin, const u64* out, long long so,
+                   int out_polys, int batch) {
+    const EntryCheck ck(c, "bfv_dot", LSA_ALGO_BFV, level, 0, batch);
+    LSA_REQUIRE(t.n >= 1, ck.who + ": needs at least one term");
+    if (with_relin) {
+        LSA_REQUIRE(rlk != nullptr, ck.who + ": the relinearisation key is null");
+        ck.key(*rlk, "the relinearisation key");
+    }
+    if (batch <= 0) return false;
+    LSA_REQUIRE(t.as && t.sas && t.bs && t.sbs, ck.who + ": null argument");
+    const size_t w = 2 * (size_t)(level + 1) * ck.N;
+    const Span sp_out = ck.output(out, so, w / 2 * out_polys, "the output");
+    for (int i = 0; i < t.n; i++) {
+        ck.apart(sp_out, ck.operand(t.as[i], t.sas[i], w, "an operand", true), "an operand");
+        ck.apart(sp_out, ck.operand(t.bs[i], t.sbs[i], w, "an operand", true), "an operand");
+    }
+    if (t.addend) ck.apart(sp_out, ck.operand(t.addend, t.s_addend, w, "the addend", true), "the addend");
+    return true;
+}
+
+void bfv_mult_sum_run(Context& c, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s0) {
+    const long long N = c.n;
+    const int L = level + 1;
+    const BfvDotPlan plan = bfv_dot_plan(c.T.mod.data(), c.nq, level, c.logn, t.n);
+    const bool fold_on = sw::bfv_fold();
+    // the groups' bases: a full group's and, where it differs, the shorter last group's
+    std::vector<BfvDotBasis> bases;
+    auto basis_of = [&](int m) -> const BfvDotBasis& {
+        const int M = bfv_dot_aux_count(c.T.mod.data(), L, c.logn, m);
+        for (const auto& B : bases)
+            if (B.M == M) return B;
+        bases.push_back(bfv_dot_basis(c, level, M, fold_on));
+        return bases.back();
+    };
+    bases.reserve(2);
+    const int Mx = basis_of(std::min(t.n, plan.max_terms)).M, Tx = L + Mx;
+    if (plan.n_groups > 1 && t.n % plan.max_terms) basis_of(t.n % plan.max_terms);
+    // pairs per launch: the setting, at most one launch's and one group's terms, and no more than leaves the tile bfv_mult gets
+    auto rows_of = [&](int g) { return 4 * (size_t)g * Tx + 3 * (size_t)Tx + 3 * (size_t)Mx; };
+    int g = std::min({c.bfv_dot_chunk > 0 ? c.bfv_dot_chunk : LSA_BFV_DOT_CHUNK, LSA_DOT_MAX_TERMS, t.n, plan.max_terms});
+    {
+        const int M1 = bfv_aux_limbs(c, level);
+        const int tile1 = pick_tile(c, 7 * (size_t)(L + M1) + 3 * (size_t)M1, batch);
+        while (g > 1 && pick_tile(c, rows_of(g), batch) < tile1) g--;
+    }
+    for_tiles(c, rows_of(g), batch, s0, [&](int nb, int b0, u64* ws, int tb, hipStream_t s) {
+        u64* o3 = d3 + (size_t)b0 * sd;
+        for (int gi = 0, i0 = 0; gi < plan.n_groups; gi++) {
+            const int m = std::min(plan.max_terms, t.n - i0);
+            const BfvDotBasis& B = basis_of(m);
+            const int T2 = B.T2;
+            const long long s_e = 2LL * T2 * N, s_d = 3LL * T2 * N;
+            const size_t slot = (size_t)tb * s_e;
+            u64* e = ws;
+            u64* d = e + 2 * (size_t)g * slot;
+            u64* ext = d + (size_t)tb * s_d;
+            for (int j0 = 0; j0 < m; j0 += g) {
+                const int mm = std::min(g, m - j0);
+                const u64 *pa[LSA_DOT_MAX_TERMS], *pb[LSA_DOT_MAX_TERMS];
+                long long sa[LSA_DOT_MAX_TERMS], sb[LSA_DOT_MAX_TERMS];
+                for (int j = 0; j < mm; j++) {
+                    const int i = i0 + j0 + j;
+                    // an operand shared by the batch (stride 0) is extended once and read by every item of the tensor
+                    u64* ea = e + (size_t)(2 * j) * slot;
+                    bfv_dot_extend(c, B, fold_on, t.as[i] + (size_t)b0 * t.sas[i], t.sas[i], ea, t.sas[i] ? nb : 1, s);
+                    pa[j] = ea, sa[j] = t.sas[i] ? s_e : 0;
+                    if (t.as[i] == t.bs[i] && t.sas[i] == t.sbs[i]) {   // a square
+                        pb[j] = pa[j], sb[j] = sa[j];
+                        continue;
+                    }
+                    u64* eb = e + (size_t)(2 * j + 1) * slot;
+                    bfv_dot_extend(c, B, fold_on, t.bs[i] + (size_t)b0 * t.sbs[i], t.sbs[i], eb, t.sbs[i] ? nb : 1, s);
+                    pb[j] = eb, sb[j] = t.sbs[i] ? s_e : 0;
+                }
+                launch_tensor_sum(c, mm, pa, sa, nullptr, pb, sb, nullptr, nullptr, 0, j0 > 0, d, s_d, nb, T2, B.rmT, s);
+            }
+            if (gi == 0) {
+                bfv_dot_tail(c, B, fold_on, d, ext, o3, sd, nb, s);
+            } else {   // a later group: scaled down on its own into the (now free) extension slots, then added in Q
+                const long long st = 3LL * L * N;
+                bfv_dot_tail(c, B, fold_on, d, ext, e, st, nb, s);
+                launch_elementwise(c, EW_ADD, o3, e, o3, nb, sd, st, sd, 3 * L, rm_seq(L), s);
+            }
+            i0 += m;
+        }
+        if (t.addend)
+            launch_elementwise(c, EW_ADD, o3, t.addend + (size_t)b0 * t.s_addend, o3, nb, sd, t.s_addend, sd, 2 * L, rm_seq(L), s);
+    });
+}
+}  // namespace
+
+void bfv_mult_sum(Context& c, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s) {
+    if (!bfv_dot_check(c, level, t, nullptr, false, d3, sd, 3, batch)) return;
+    bfv_mult_sum_run(c, level, t, d3, batch, sd, s);
+}
+
+// the summed, scaled-down tensor lives in the second arena, as in bfv_mult_relin
+void bfv_dot(Context& c, int level, const DotTerms& t, const Key* rlk, u64* out, int batch, long long so, hipStream_t s) {
+    if (!bfv_dot_check(c, level, t, rlk, true, out, so, 2, batch)) return;
+    const long long sd = 3LL * (level + 1) * c.n;
+    u64* d3 = c.workspace2((size_t)sd * batch, s);
+    bfv_mult_sum_run(c, level, t, d3, batch, sd, s);
+    bfv_relin(c, level, d3, *rlk, out, batch, sd, so, s);
+}
+
 void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, int batch, long long sin,
                 long long sout, hipStream_t s) {
     const EntryCheck ck(c, "lsa_bfv_rotate", LSA_ALGO_BFV, level, 0, batch);

@@ -1,5 +1,6 @@
 // tables.cpp — number theory + per-modulus table generation (host only).
 #include "tables.h"
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 
@@ -120,6 +121,24 @@ int product_bitlen(const u64* q, int k) {
 }
 
 int bfv_aux_count(const u64* q, int k, int logn) { return (product_bitlen(q, k) + logn + 60) / 61; }
+
+int bfv_ceil_log2(int m) {
+    int b = 0;
+    while (b < 31 && (1LL << b) < (long long)m) b++;
+    return b;
+}
+
+int bfv_dot_aux_count(const u64* q, int k, int logn, int m) { return (product_bitlen(q, k) + logn + bfv_ceil_log2(m) + 60) / 61; }
+
+BfvDotPlan bfv_dot_plan(const u64* q, int nq, int level, int logn, int terms) {
+    const int nmul = bfv_aux_count(q, nq, logn);
+    BfvDotPlan p;
+    p.headroom_bits = std::min(30, 61 * nmul - product_bitlen(q, level + 1) - logn);   // >= 0: Q_level divides the full chain
+    p.max_terms = 1 << p.headroom_bits;
+    p.n_groups = (int)(((long long)terms + p.max_terms - 1) / p.max_terms);
+    p.aux_limbs = bfv_dot_aux_count(q, level + 1, logn, std::min(terms, p.max_terms));
+    return p;
+}
 
 std::vector<u64> gen_aux_primes(int n, int count, const std::vector<u64>& avoid) {
     std::vector<u64> out;

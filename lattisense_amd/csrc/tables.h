@@ -15,6 +15,19 @@ u64 smallest_primitive_root(u64 q);
 int product_bitlen(const u64* q, int k);
 // BFV auxiliary basis: count = ceil((bitlen(prod q) + logn)/61); primes = 61-bit, == 1 mod 2n, descending from 2^61
 int bfv_aux_count(const u64* q, int k, int logn);
+// BFV encrypted inner product (ops.hip bfv_mult_sum / bfv_dot): how a sum of `terms` tensors is laid over the auxiliary basis.
+// bfv_aux_count sizes QMul for ONE product, 61 M >= bitlen(Q_level) + logn; a sum of m products is at most m times as large,
+// ceil(log2 m) bits more.  The context holds nmul = bfv_aux_count(full chain) auxiliary primes, so at `level`
+//   G = min(30, 61 nmul - bitlen(Q_level) - logn) >= 0 spare bits,   max_terms = 2^G products per group,
+// the terms are cut into consecutive groups of max_terms (the last may be shorter), and a group of m terms runs over Q_level and
+// the FIRST M(m) = (bitlen(Q_level) + logn + ceil(log2 m) + 60) / 61 auxiliary primes: M(1) = bfv_aux_count, M(max_terms) <= nmul.
+int bfv_ceil_log2(int m);                                          // m >= 1
+int bfv_dot_aux_count(const u64* q, int k, int logn, int m);   // M(m) over the first k limbs of q
+struct BfvDotPlan {
+    int headroom_bits, max_terms, n_groups;
+    int aux_limbs;   // M(min(terms, max_terms)): of the first group, a full one when there are several
+};
+BfvDotPlan bfv_dot_plan(const u64* q, int nq, int level, int logn, int terms);   // 0 <= level < nq, terms >= 1
 std::vector<u64> gen_aux_primes(int n, int count, const std::vector<u64>& avoid);
 
 struct HostTables {

@@ -107,6 +107,10 @@ class DeviceContext:
         """0: single-limb key-switch digits go through the base-conversion kernel like the others (A/B, identical results)"""
         check(lib().lsa_set_modup_lift(self.h, int(enable)))
 
+    def set_bfv_dot_chunk(self, pairs):
+        """pairs that bfv_mult_sum / bfv_dot extend per tensor launch (0: the default); the same words for every value"""
+        check(lib().lsa_set_bfv_dot_chunk(self.h, int(pairs)))
+
     def set_fp64_ntt(self, enable):
         check(lib().lsa_set_fp64_ntt(self.h, int(enable)))
 
@@ -383,6 +387,43 @@ class DeviceContext:
         check(lib().lsa_bfv_mult_relin(self.h, level, a.ptr, b.ptr, rlk, out.ptr, batch, 2 * L * self.n,
                                        2 * L * self.n, 2 * L * self.n, self.stream))
         return out
+
+    def _bfv_dot_terms(self, level, a_list, b_list, addend, sas=None, sbs=None):
+        n, w = len(a_list), 2 * (level + 1) * self.n
+        assert n == len(b_list), "as many b operands as a operands"
+        pa = (ctypes.c_void_p * max(n, 1))(*[a.ptr for a in a_list])
+        pb = (ctypes.c_void_p * max(n, 1))(*[b.ptr for b in b_list])
+        sa = (ctypes.c_longlong * max(n, 1))(*([w] * n if sas is None else sas))
+        sb = (ctypes.c_longlong * max(n, 1))(*([w] * n if sbs is None else sbs))
+        return n, pa, sa, pb, sb, addend.ptr if addend is not None else None, w
+
+    def bfv_mult_sum(self, level, a_list, b_list, batch, addend=None, out=None, sas=None, sbs=None):
+        """d3 = t * round(sum_i a_list[i] (x) b_list[i] / Q) (+ addend on polynomials 0 and 1): [batch][3][level+1][N]; sas / sbs:
+        per-term batch strides in words (0: one ciphertext shared by the batch), default compact"""
+        L = level + 1
+        if out is None:
+            out = self.alloc(max(batch, 1) * 3 * L * self.n)
+        check(lib().lsa_bfv_mult_sum(self.h, level, *self._bfv_dot_terms(level, a_list, b_list, addend, sas, sbs), out.ptr, batch,
+                                     3 * L * self.n, self.stream))
+        return out
+
+    def bfv_dot(self, level, a_list, b_list, rlk, batch, addend=None, out=None, sas=None, sbs=None):
+        """sum_i a_list[i] x b_list[i] (+ addend) with one scale-down and one relinearisation: [batch][2][level+1][N]"""
+        L = level + 1
+        if out is None:
+            out = self.alloc(max(batch, 1) * 2 * L * self.n)
+        check(lib().lsa_bfv_dot(self.h, level, *self._bfv_dot_terms(level, a_list, b_list, addend, sas, sbs), rlk, out.ptr, batch,
+                                2 * L * self.n, self.stream))
+        return out
+
+
+def bfv_dot_plan(n, q, level, terms):
+    """{max_terms, groups, aux_limbs} of the BFV inner product of `terms` pairs at `level` of the chain q at ring degree n -- host
+    only (include/lattisense_amd.h: lsa_bfv_dot_plan, with the headroom rule)"""
+    qa = (ctypes.c_uint64 * max(len(q), 1))(*[int(x) for x in q])
+    mt, ng, al = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(lib().lsa_bfv_dot_plan(int(n), qa, len(q), int(level), int(terms), ctypes.byref(mt), ctypes.byref(ng), ctypes.byref(al)))
+    return {"max_terms": mt.value, "groups": ng.value, "aux_limbs": al.value}
 
 
 class BootstrapPlan:
