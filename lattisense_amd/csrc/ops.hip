@@ -705,6 +705,27 @@ void ckks_switch_key(Context& c, int level, const u64* in, const Key& swk, u64* 
     });
 }
 
+// The relinearisation tail of a tile's degree-2 tensor d3 [3][L][N] (batch stride sd): out = (d0, d1) + KeySwitch(d2), rescaled when
+// `with_rescale`.  r2: [2][L][N] per item, the unrescaled result (or the merged tail's scratch); sub: the key switch's and the
+// rescale's rows
+static void ckks_relin_tail(Context& c, int level, const u64* d3, long long sd, const Key& rlk, u64* out, long long so,
+                            bool with_rescale, u64* r2, u64* sub, int nb, hipStream_t s) {
+    const int L = level + 1;
+    const long long sr = 2LL * L * c.n;
+    const u64* d2 = d3 + 2LL * L * c.n;
+    KsOut o{.p = r2, .sp = sr, .base = d3, .sbase = sd, .base_rpp = L, .base_polys = 2};
+    const bool merged = with_rescale && c.fuse_tails;   // the merged ModDown + rescale tail
+    if (!with_rescale) {
+        o.p = out;
+        o.sp = so;
+    } else if (merged) {
+        o.form = KsOut::RESCALE;
+        o.rs = {out, so};
+    }
+    key_switch(c, level, d2, sd, rlk, o, nb, sub, s);
+    if (with_rescale && !merged) rescale(c, level, 2, r2, sr, out, so, nb, true, sub, s);
+}
+
 void ckks_mult_relin_rescale(Context& c, int level, const u64* a, const u64* b, const Key& rlk, u64* out, int batch,
                              long long sa, long long sb, long long so, hipStream_t s) {
     ckks_mult_relin_rescale_rpp(c, level, a, b, rlk, out, batch, sa, sb, so, s, 0, 0);
@@ -750,15 +771,7 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
             return;
         }
         launch_tensor(c, a + (size_t)b0 * sa, b + (size_t)b0 * sb, d3, nb, sa, sb, sd, L, rm_seq(L), st, a_rpp, b_rpp);
-        KsOut o{.p = r2, .sp = sr, .base = d3, .sbase = sd, .base_rpp = L, .base_polys = 2};
-        if (c.fuse_tails) {
-            o.form = KsOut::RESCALE;
-            o.rs = {out + (size_t)b0 * so, so};
-            key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
-            return;
-        }
-        key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
-        rescale(c, level, 2, r2, sr, out + (size_t)b0 * so, so, nb, true, sub, st);
+        ckks_relin_tail(c, level, d3, sd, rlk, out + (size_t)b0 * so, so, true, r2, sub, nb, st);
     });
 }
 
@@ -818,27 +831,13 @@ void ckks_dot(Context& c, int level, const DotTerms& t, const Key& rlk, u64* out
     const int L = level + 1;
     const size_t r_d3 = 3 * (size_t)L, r_r2 = 2 * (size_t)L;
     const size_t r_shared = std::max(KsTile::rows(c, level), rescale_ws_rows(level, 2));
-    const long long sd = (long long)r_d3 * N, sr = 2LL * L * N;
+    const long long sd = (long long)r_d3 * N;
     for_tiles(c, r_d3 + r_r2 + r_shared, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* d3 = ws;
         u64* r2 = d3 + r_d3 * N * tb;
         u64* sub = r2 + r_r2 * N * tb;
         dot_tensor(c, level, t, b0, d3, sd, nb, st);
-        KsOut o{.p = r2, .sp = sr, .base = d3, .sbase = sd, .base_rpp = L, .base_polys = 2};
-        if (!with_rescale) {
-            o.p = out + (size_t)b0 * so;
-            o.sp = so;
-            key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
-            return;
-        }
-        if (c.fuse_tails) {   // the merged ModDown + rescale tail
-            o.form = KsOut::RESCALE;
-            o.rs = {out + (size_t)b0 * so, so};
-            key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
-            return;
-        }
-        key_switch(c, level, d3 + 2LL * L * N, sd, rlk, o, nb, sub, st);
-        rescale(c, level, 2, r2, sr, out + (size_t)b0 * so, so, nb, true, sub, st);
+        ckks_relin_tail(c, level, d3, sd, rlk, out + (size_t)b0 * so, so, with_rescale, r2, sub, nb, st);
     });
 }
 
@@ -874,104 +873,198 @@ void poly_addsub(Context& c, int op, int level, int polys, const u64* a, const u
 // ================================================================================================ BFV
 static int bfv_aux_limbs(const Context& c, int level) { return bfv_aux_count(c.T.mod.data(), level + 1, c.logn); }
 
-void bfv_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int batch, long long sa, long long sb,
-              long long sd, hipStream_t s0) {
-    const EntryCheck ck(c, "lsa_bfv_mult", LSA_ALGO_BFV, level, 0, batch);
-    const long long N = c.n;
-    const int L = level + 1, M = bfv_aux_limbs(c, level), T2 = L + M;
-    LSA_REQUIRE(M <= c.nmul, ck.who + ": auxiliary basis too small");
-    if (batch <= 0) return;
-    {   // a stride of 0 shares an operand with the whole batch: the transforms and conversions index base + item * stride
-        const Span out = ck.output(d3, sd, 3 * (size_t)L * N, "d3");
-        ck.apart(out, ck.operand(a, sa, 2 * (size_t)L * N, "a", true), "a");
-        ck.apart(out, ck.operand(b, sb, 2 * (size_t)L * N, "b", true), "b");
-    }
-    const size_t rows = 2 * 2 * (size_t)T2 + 3 * (size_t)T2 + 3 * (size_t)M;
-    const long long s_e = 2LL * T2 * N, s_d = 3LL * T2 * N, s_x = 3LL * M * N;
+// ---- BFV multiply: d3 = t * round(sum_i a_i (x) b_i / Q).  The operands are extended from Q_level to Q_level u the first M auxiliary
+// primes, multiplied there (exact while the auxiliary basis holds the sum: tables.h), and the division by Q is one inverse transform
+// and six exact base conversions.  bfv_mult is the one-term case; bfv_mult_sum / bfv_dot (below bfv_mult_relin) share every step.
+// Folded (default; LSA_BFV_FOLD=0: the separate element-wise steps): the Q limbs are transformed straight from the operands into
+// the extended buffer (no copy), and the two element-wise steps around the last conversion -- (aux - ext) * Q^-1 before it,
+// * t after it -- live in its source load and its constants (Context::BaseConvFold)
+
+namespace {
+// workspace rows per ciphertext of a tile: g pairs of extended operands [2][L+M] each, the tensor [3][L+M], the converted rows [3][M]
+size_t bfv_mult_rows(int L, int M, int g) { return (4 * (size_t)g + 3) * (size_t)(L + M) + 3 * (size_t)M; }
+
+struct BfvBasis {   // Q_level u the first M auxiliary primes: row maps, conversion plans and constants, folded or not
+    int L = 0, M = 0, T2 = 0;
+    bool fold = false;
+    RowMap rmT, rmAux;
+    const BaseConvPlan *kQA = nullptr, *kAQ = nullptr, *kAQf = nullptr;
+    BaseConvRows rQA{}, rAQ{};
+    const u64 *kQinv = nullptr, *kT = nullptr;
+    unsigned char lmA[LSA_MAX_PERIOD], lmQ[LSA_MAX_PERIOD];
+    std::vector<int> sub_rows;
+};
+
+// the only place that builds them.  The cached constants are keyed by L and M: one context runs a level with M(1) for a single
+// product and with M(m) > M(1) for a sum
+BfvBasis bfv_basis(Context& c, const char* who, int level, int M, bool fold_on) {
+    BfvBasis B;
+    const int L = level + 1, T2 = L + M;
+    LSA_REQUIRE(M >= 1 && M <= c.nmul && T2 <= LSA_MAX_PERIOD, std::string(who) + ": auxiliary basis too small");
+    B.L = L, B.M = M, B.T2 = T2, B.fold = fold_on;
     std::vector<int> qmods, amods;
-    RowMap rmT;
-    rmT.period = T2;
+    B.rmT.period = T2;
     for (int i = 0; i < L; i++) {
         qmods.push_back(i);
-        rmT.mod_of[i] = (unsigned char)i;
+        B.rmT.mod_of[i] = (unsigned char)i;
+        B.rQA.src_row[i] = i, B.rAQ.dst_row[i] = i;
+        B.lmQ[i] = (unsigned char)i;
     }
     for (int i = 0; i < M; i++) {
         amods.push_back(c.aux_mod(i));
-        rmT.mod_of[L + i] = (unsigned char)c.aux_mod(i);
+        B.rmT.mod_of[L + i] = (unsigned char)c.aux_mod(i);
+        B.rQA.dst_row[i] = i, B.rAQ.src_row[i] = i;
+        B.lmA[i] = (unsigned char)c.aux_mod(i);
     }
-    // folded (default; LSA_BFV_FOLD=0: the separate element-wise steps): the Q limbs are transformed straight from the operands into
-    // the extended buffer (no copy), and the two element-wise steps around the last conversion -- (aux - ext) * Q^-1 before it,
-    // * t after it -- live in its source load and its constants (Context::BaseConvFold)
-    const bool fold_on = sw::bfv_fold();
-    const BaseConvPlan* kQA = c.baseconv(qmods, amods, true);
-    const BaseConvPlan* kAQ = c.baseconv(amods, qmods, true);
-    BaseConvRows rQA{}, rAQ{};
-    for (int i = 0; i < L; i++) rQA.src_row[i] = i, rAQ.dst_row[i] = i;
-    for (int i = 0; i < M; i++) rQA.dst_row[i] = i, rAQ.src_row[i] = i;
-    std::vector<int> cp(2 * L);
-    // Q^-1 mod aux_i and t mod q_i
-    std::vector<u64> qinv(M), tq(L);
-    unsigned char lmA[LSA_MAX_PERIOD], lmQ[LSA_MAX_PERIOD];
+    B.rmAux = B.rmT;   // the auxiliary rows only
+    for (int i = 0; i < L; i++) B.rmAux.mod_of[i] = LSA_ROW_SKIP;
+    std::vector<u64> qinv(M), tq(L);   // Q^-1 mod aux_i and t mod q_i
     for (int i = 0; i < M; i++) {
         const u64 p = c.T.mod[c.aux_mod(i)];
         u64 pr = 1;
         for (int l = 0; l < L; l++) pr = mul_mod_host(pr, c.T.mod[l] % p, p);
         qinv[i] = inv_mod(pr, p);
-        lmA[i] = (unsigned char)c.aux_mod(i);
     }
-    for (int i = 0; i < L; i++) {
-        tq[i] = c.t % c.T.mod[i];
-        lmQ[i] = (unsigned char)i;
+    for (int i = 0; i < L; i++) tq[i] = c.t % c.T.mod[i];
+    const std::string tag = std::to_string(L) + "m" + std::to_string(M);
+    B.kQA = c.baseconv(qmods, amods, true);
+    if (fold_on) {
+        Context::BaseConvFold fold{"bfv_mul" + tag, qinv, tq};
+        B.kAQf = c.baseconv(amods, qmods, true, false, &fold);
+    } else {
+        B.kAQ = c.baseconv(amods, qmods, true);
+        B.kQinv = c.const_vec("bfv_qinv" + tag, amods, qinv);
+        B.kT = c.const_vec("bfv_t" + tag, qmods, tq);
     }
-    const u64* kQinv = c.const_vec("bfv_qinv" + std::to_string(L), amods, qinv);
-    const u64* kT = c.const_vec("bfv_t" + std::to_string(L), qmods, tq);
-    Context::BaseConvFold fold{"bfv_mul" + std::to_string(L), qinv, tq};
-    const BaseConvPlan* kAQf = fold_on ? c.baseconv(amods, qmods, true, false, &fold) : nullptr;
-    std::vector<int> sub_rows(M);
-    for (int i = 0; i < M; i++) sub_rows[i] = i;
-    RowMap rmAux = rmT;   // the auxiliary rows only
-    for (int i = 0; i < L; i++) rmAux.mod_of[i] = LSA_ROW_SKIP;
+    B.sub_rows.resize(M);
+    for (int i = 0; i < M; i++) B.sub_rows[i] = i;
+    return B;
+}
 
-    for_tiles(c, rows, batch, s0, [&](int nb, int b0, u64* ws, int tb, hipStream_t s) {
-        u64* ea = ws;
-        u64* eb = ea + (size_t)tb * 2 * T2 * N;
-        u64* d = eb + (size_t)tb * 2 * T2 * N;
-        u64* ext = d + (size_t)tb * 3 * T2 * N;
-        const u64* srcs[2] = {a + (size_t)b0 * sa, b + (size_t)b0 * sb};
-        const long long ss[2] = {sa, sb};
-        u64* es[2] = {ea, eb};
-        const int nops = (a == b && sa == sb) ? 1 : 2;
-        for (int o = 0; o < nops; o++) {
-            for (int p = 0; p < 2; p++) {
-                // Q limbs copied (folded: transformed from where they are), aux limbs by centred exact extension
-                std::vector<int> rr(L);
-                for (int i = 0; i < L; i++) rr[i] = p * L + i;
-                if (fold_on) launch_ntt(c, srcs[o] + (size_t)p * L * N, es[o] + (size_t)p * T2 * N, nb, ss[o], s_e, L, rm_seq(L), false, s);
-                else launch_copy_rows(c, srcs[o], ss[o], es[o] + (size_t)p * T2 * N, s_e, L, rr.data(), nb, s);
-                launch_baseconv(c, kQA, rQA, srcs[o] + (size_t)p * L * N, es[o] + ((size_t)p * T2 + L) * N, nb, ss[o],
-                                s_e, s);
-            }
-            launch_ntt(c, es[o], es[o], nb, s_e, 2 * T2, fold_on ? rmAux : rmT, false, s);
-        }
-        launch_tensor(c, ea, nops == 1 ? ea : eb, d, nb, s_e, s_e, s_d, T2, rmT, s);
-        launch_ntt(c, d, d, nb, s_d, 3 * T2, rmT, true, s);
+// one operand into [2][T2][N] per item: the Q limbs transformed (folded: from where they are; else copied first), the auxiliary
+// limbs by the centred exact extension, then transformed
+void bfv_extend(Context& c, const BfvBasis& B, const u64* src, long long ss, u64* e, int nb, hipStream_t s) {
+    const long long N = c.n;
+    const int L = B.L, T2 = B.T2;
+    const long long s_e = 2LL * T2 * N;
+    for (int p = 0; p < 2; p++) {
+        std::vector<int> rr(L);
+        for (int i = 0; i < L; i++) rr[i] = p * L + i;
+        if (B.fold) launch_ntt(c, src + (size_t)p * L * N, e + (size_t)p * T2 * N, nb, ss, s_e, L, rm_seq(L), false, s);
+        else launch_copy_rows(c, src, ss, e + (size_t)p * T2 * N, s_e, L, rr.data(), nb, s);
+        launch_baseconv(c, B.kQA, B.rQA, src + (size_t)p * L * N, e + ((size_t)p * T2 + L) * N, nb, ss, s_e, s);
+    }
+    launch_ntt(c, e, e, nb, s_e, 2 * T2, B.fold ? B.rmAux : B.rmT, false, s);
+}
+
+// d [3][T2][N] (NTT domain) -> o3 = t * round(d / Q) [3][L][N]; ext: [3][M][N] per item
+void bfv_scale_down(Context& c, const BfvBasis& B, u64* d, u64* ext, u64* o3, long long so, int nb, hipStream_t s) {
+    const long long N = c.n;
+    const int L = B.L, M = B.M, T2 = B.T2;
+    const long long s_d = 3LL * T2 * N, s_x = 3LL * M * N;
+    launch_ntt(c, d, d, nb, s_d, 3 * T2, B.rmT, true, s);
+    for (int k = 0; k < 3; k++) launch_baseconv(c, B.kQA, B.rQA, d + (size_t)k * T2 * N, ext + (size_t)k * M * N, nb, s_d, s_x, s);
+    if (B.fold) {
+        // out = t * conv_{A->Q}((aux - ext) * Q^-1): the subtraction on the conversion's source load, both factors in its constants
         for (int k = 0; k < 3; k++)
-            launch_baseconv(c, kQA, rQA, d + (size_t)k * T2 * N, ext + (size_t)k * M * N, nb, s_d, s_x, s);
+            launch_baseconv(c, B.kAQf, B.rAQ, d + ((size_t)k * T2 + L) * N, o3 + (size_t)k * L * N, nb, s_d, so, s, ext + (size_t)k * M * N,
+                            s_x, B.sub_rows.data());
+        return;
+    }
+    // aux part <- (aux - ext) * Q^-1     (= round(d/Q) in basis QMul), converted to Q, then * t
+    launch_sub_mul_general(c, 3, M, B.lmA, B.kQinv, d + (size_t)L * N, s_d, T2, ext, s_x, M, nullptr, 0, 0, 0, d + (size_t)L * N, s_d,
+                           T2, nb, s);
+    for (int k = 0; k < 3; k++) launch_baseconv(c, B.kAQ, B.rAQ, d + ((size_t)k * T2 + L) * N, o3 + (size_t)k * L * N, nb, s_d, so, s);
+    launch_sub_mul_general(c, 3, L, B.lmQ, B.kT, o3, so, L, nullptr, 0, 0, nullptr, 0, 0, 0, o3, so, L, nb, s);
+}
+
+#define LSA_BFV_DOT_CHUNK 4   // pairs extended per k_tensor_sum launch (DESIGN.md 4.12: measured, and why not more)
+
+// the summed product of checked arguments, tile by tile: per group of the plan, chunks of g pairs extended and summed into the tensor
+// (an operand shared by the batch once, a square once), one scale-down per group
+void bfv_mult_sum_run(Context& c, const char* who, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s0) {
+    const long long N = c.n;
+    const int L = level + 1;
+    const BfvDotPlan plan = bfv_dot_plan(c.T.mod.data(), c.nq, level, c.logn, t.n);
+    const bool fold_on = sw::bfv_fold();
+    // the groups' bases: a full group's and, where it differs, the shorter last group's
+    std::vector<BfvBasis> bases;
+    auto basis_of = [&](int m) -> const BfvBasis& {
+        const int M = bfv_dot_aux_count(c.T.mod.data(), L, c.logn, m);
+        for (const auto& B : bases)
+            if (B.M == M) return B;
+        bases.push_back(bfv_basis(c, who, level, M, fold_on));
+        return bases.back();
+    };
+    bases.reserve(2);
+    const int Mx = basis_of(std::min(t.n, plan.max_terms)).M;
+    if (plan.n_groups > 1 && t.n % plan.max_terms) basis_of(t.n % plan.max_terms);
+    // pairs per launch: the setting, at most one launch's and one group's terms, and no more than leaves the tile one product gets
+    auto rows_of = [&](int g) { return bfv_mult_rows(L, Mx, g); };
+    int g = std::min({c.bfv_dot_chunk > 0 ? c.bfv_dot_chunk : LSA_BFV_DOT_CHUNK, LSA_DOT_MAX_TERMS, t.n, plan.max_terms});
+    const int tile1 = pick_tile(c, bfv_mult_rows(L, bfv_aux_limbs(c, level), 1), batch);
+    while (g > 1 && pick_tile(c, rows_of(g), batch) < tile1) g--;
+    for_tiles(c, rows_of(g), batch, s0, [&](int nb, int b0, u64* ws, int tb, hipStream_t s) {
         u64* o3 = d3 + (size_t)b0 * sd;
-        if (fold_on) {
-            // out = t * conv_{A->Q}((aux - ext) * Q^-1): the subtraction on the conversion's source load, both factors in its constants
-            for (int k = 0; k < 3; k++)
-                launch_baseconv(c, kAQf, rAQ, d + ((size_t)k * T2 + L) * N, o3 + (size_t)k * L * N, nb, s_d, sd, s, ext + (size_t)k * M * N,
-                                s_x, sub_rows.data());
-            return;
+        for (int gi = 0, i0 = 0; gi < plan.n_groups; gi++) {
+            const int m = std::min(plan.max_terms, t.n - i0);
+            const BfvBasis& B = basis_of(m);
+            const int T2 = B.T2;
+            const long long s_e = 2LL * T2 * N, s_d = 3LL * T2 * N;
+            const size_t slot = (size_t)tb * s_e;
+            u64* e = ws;
+            u64* d = e + 2 * (size_t)g * slot;
+            u64* ext = d + (size_t)tb * s_d;
+            for (int j0 = 0; j0 < m; j0 += g) {
+                const int mm = std::min(g, m - j0);
+                const u64 *pa[LSA_DOT_MAX_TERMS], *pb[LSA_DOT_MAX_TERMS];
+                long long sa[LSA_DOT_MAX_TERMS], sb[LSA_DOT_MAX_TERMS];
+                for (int j = 0; j < mm; j++) {
+                    const int i = i0 + j0 + j;
+                    // an operand shared by the batch (stride 0) is extended once and read by every item of the tensor
+                    u64* ea = e + (size_t)(2 * j) * slot;
+                    bfv_extend(c, B, t.as[i] + (size_t)b0 * t.sas[i], t.sas[i], ea, t.sas[i] ? nb : 1, s);
+                    pa[j] = ea, sa[j] = t.sas[i] ? s_e : 0;
+                    if (t.as[i] == t.bs[i] && t.sas[i] == t.sbs[i]) {   // a square
+                        pb[j] = pa[j], sb[j] = sa[j];
+                        continue;
+                    }
+                    u64* eb = e + (size_t)(2 * j + 1) * slot;
+                    bfv_extend(c, B, t.bs[i] + (size_t)b0 * t.sbs[i], t.sbs[i], eb, t.sbs[i] ? nb : 1, s);
+                    pb[j] = eb, sb[j] = t.sbs[i] ? s_e : 0;
+                }
+                // a group of one pair is a plain product (k_tensor); both kernels write canonical residues of the same values
+                if (m == 1) launch_tensor(c, pa[0], pb[0], d, nb, sa[0], sb[0], s_d, T2, B.rmT, s);
+                else launch_tensor_sum(c, mm, pa, sa, nullptr, pb, sb, nullptr, nullptr, 0, j0 > 0, d, s_d, nb, T2, B.rmT, s);
+            }
+            if (gi == 0) {
+                bfv_scale_down(c, B, d, ext, o3, sd, nb, s);
+            } else {   // a later group: scaled down on its own into the (now free) extension slots, then added in Q
+                const long long st = 3LL * L * N;
+                bfv_scale_down(c, B, d, ext, e, st, nb, s);
+                launch_elementwise(c, EW_ADD, o3, e, o3, nb, sd, st, sd, 3 * L, rm_seq(L), s);
+            }
+            i0 += m;
         }
-        // aux part <- (aux - ext) * Q^-1     (= round(d/Q) in basis QMul)
-        launch_sub_mul_general(c, 3, M, lmA, kQinv, d + (size_t)L * N, s_d, T2, ext, s_x, M, nullptr, 0, 0, 0,
-                               d + (size_t)L * N, s_d, T2, nb, s);
-        for (int k = 0; k < 3; k++)
-            launch_baseconv(c, kAQ, rAQ, d + ((size_t)k * T2 + L) * N, o3 + (size_t)k * L * N, nb, s_d, sd, s);
-        launch_sub_mul_general(c, 3, L, lmQ, kT, o3, sd, L, nullptr, 0, 0, nullptr, 0, 0, 0, o3, sd, L, nb, s);
+        if (t.addend)
+            launch_elementwise(c, EW_ADD, o3, t.addend + (size_t)b0 * t.s_addend, o3, nb, sd, t.s_addend, sd, 2 * L, rm_seq(L), s);
     });
+}
+}  // namespace
+
+void bfv_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int batch, long long sa, long long sb,
+              long long sd, hipStream_t s) {
+    const EntryCheck ck(c, "lsa_bfv_mult", LSA_ALGO_BFV, level, 0, batch);
+    LSA_REQUIRE(bfv_aux_limbs(c, level) <= c.nmul, ck.who + ": auxiliary basis too small");
+    if (batch <= 0) return;
+    {   // a stride of 0 shares an operand with the whole batch
+        const size_t w = 2 * (size_t)(level + 1) * ck.N;
+        const Span out = ck.output(d3, sd, w / 2 * 3, "d3");
+        ck.apart(out, ck.operand(a, sa, w, "a", true), "a");
+        ck.apart(out, ck.operand(b, sb, w, "b", true), "b");
+    }
+    const DotTerms one{1, &a, &sa, nullptr, &b, &sb, nullptr, nullptr, 0};   // the one-term sum: M(1) auxiliary primes, k_tensor
+    bfv_mult_sum_run(c, "lsa_bfv_mult", level, one, d3, batch, sd, s);
 }
 
 // key switch of a coefficient-domain polynomial: NTT in, INTT out
@@ -1024,99 +1117,8 @@ void bfv_mult_relin(Context& c, int level, const u64* a, const u64* b, const Key
 // extension of the operands and the tensor depend on the pair; the tensors are summed in Q u QMul (k_tensor_sum), where the sum is
 // exact while the auxiliary basis holds it (tables.h bfv_dot_plan: groups of at most max_terms pairs, a group of m over the first
 // M(m) auxiliary primes), and the inverse transform, the six conversions of the division by Q and the key switch run once.
-// The extension and the tail below restate bfv_mult's launches for a basis of M auxiliary primes; bfv_mult itself is untouched.
-#define LSA_BFV_DOT_CHUNK 4   // pairs extended per k_tensor_sum launch (DESIGN.md 4.12: measured, and why not more)
-
+// The extension, the tensor and the scale-down are shared with bfv_mult (bfv_mult_sum_run above it).
 namespace {
-struct BfvDotBasis {   // Q_level u the first M auxiliary primes: row maps, conversion plans and folded constants
-    int L = 0, M = 0, T2 = 0;
-    RowMap rmT, rmAux;
-    const BaseConvPlan *kQA = nullptr, *kAQ = nullptr, *kAQf = nullptr;
-    BaseConvRows rQA{}, rAQ{};
-    const u64 *kQinv = nullptr, *kT = nullptr;
-    unsigned char lmA[LSA_MAX_PERIOD], lmQ[LSA_MAX_PERIOD];
-    std::vector<int> sub_rows;
-};
-
-BfvDotBasis bfv_dot_basis(Context& c, int level, int M, bool fold_on) {
-    BfvDotBasis B;
-    const int L = level + 1, T2 = L + M;
-    LSA_REQUIRE(M >= 1 && M <= c.nmul && T2 <= LSA_MAX_PERIOD, "bfv_dot: auxiliary basis too small");
-    B.L = L, B.M = M, B.T2 = T2;
-    std::vector<int> qmods, amods;
-    B.rmT.period = T2;
-    for (int i = 0; i < L; i++) {
-        qmods.push_back(i);
-        B.rmT.mod_of[i] = (unsigned char)i;
-        B.rQA.src_row[i] = i, B.rAQ.dst_row[i] = i;
-        B.lmQ[i] = (unsigned char)i;
-    }
-    for (int i = 0; i < M; i++) {
-        amods.push_back(c.aux_mod(i));
-        B.rmT.mod_of[L + i] = (unsigned char)c.aux_mod(i);
-        B.rQA.dst_row[i] = i, B.rAQ.src_row[i] = i;
-        B.lmA[i] = (unsigned char)c.aux_mod(i);
-    }
-    B.rmAux = B.rmT;   // the auxiliary rows only
-    for (int i = 0; i < L; i++) B.rmAux.mod_of[i] = LSA_ROW_SKIP;
-    std::vector<u64> qinv(M), tq(L);   // Q^-1 mod aux_i and t mod q_i
-    for (int i = 0; i < M; i++) {
-        const u64 p = c.T.mod[c.aux_mod(i)];
-        u64 pr = 1;
-        for (int l = 0; l < L; l++) pr = mul_mod_host(pr, c.T.mod[l] % p, p);
-        qinv[i] = inv_mod(pr, p);
-    }
-    for (int i = 0; i < L; i++) tq[i] = c.t % c.T.mod[i];
-    const std::string tag = std::to_string(L) + "m" + std::to_string(M);
-    B.kQA = c.baseconv(qmods, amods, true);
-    if (fold_on) {
-        Context::BaseConvFold fold{"bfv_dot" + tag, qinv, tq};
-        B.kAQf = c.baseconv(amods, qmods, true, false, &fold);
-    } else {
-        B.kAQ = c.baseconv(amods, qmods, true);
-        B.kQinv = c.const_vec("bfv_dot_qinv" + tag, amods, qinv);
-        B.kT = c.const_vec("bfv_dot_t" + tag, qmods, tq);
-    }
-    B.sub_rows.resize(M);
-    for (int i = 0; i < M; i++) B.sub_rows[i] = i;
-    return B;
-}
-
-// one operand into [2][T2][N] per item: the Q limbs transformed (folded: from where they are), the auxiliary limbs by the centred
-// exact extension, then transformed -- bfv_mult's extension
-void bfv_dot_extend(Context& c, const BfvDotBasis& B, bool fold_on, const u64* src, long long ss, u64* e, int nb, hipStream_t s) {
-    const long long N = c.n;
-    const int L = B.L, T2 = B.T2;
-    const long long s_e = 2LL * T2 * N;
-    for (int p = 0; p < 2; p++) {
-        std::vector<int> rr(L);
-        for (int i = 0; i < L; i++) rr[i] = p * L + i;
-        if (fold_on) launch_ntt(c, src + (size_t)p * L * N, e + (size_t)p * T2 * N, nb, ss, s_e, L, rm_seq(L), false, s);
-        else launch_copy_rows(c, src, ss, e + (size_t)p * T2 * N, s_e, L, rr.data(), nb, s);
-        launch_baseconv(c, B.kQA, B.rQA, src + (size_t)p * L * N, e + ((size_t)p * T2 + L) * N, nb, ss, s_e, s);
-    }
-    launch_ntt(c, e, e, nb, s_e, 2 * T2, fold_on ? B.rmAux : B.rmT, false, s);
-}
-
-// d [3][T2][N] (NTT domain) -> o3 = t * round(d / Q) [3][L][N]: bfv_mult's tail
-void bfv_dot_tail(Context& c, const BfvDotBasis& B, bool fold_on, u64* d, u64* ext, u64* o3, long long so, int nb, hipStream_t s) {
-    const long long N = c.n;
-    const int L = B.L, M = B.M, T2 = B.T2;
-    const long long s_d = 3LL * T2 * N, s_x = 3LL * M * N;
-    launch_ntt(c, d, d, nb, s_d, 3 * T2, B.rmT, true, s);
-    for (int k = 0; k < 3; k++) launch_baseconv(c, B.kQA, B.rQA, d + (size_t)k * T2 * N, ext + (size_t)k * M * N, nb, s_d, s_x, s);
-    if (fold_on) {
-        for (int k = 0; k < 3; k++)
-            launch_baseconv(c, B.kAQf, B.rAQ, d + ((size_t)k * T2 + L) * N, o3 + (size_t)k * L * N, nb, s_d, so, s, ext + (size_t)k * M * N,
-                            s_x, B.sub_rows.data());
-        return;
-    }
-    launch_sub_mul_general(c, 3, M, B.lmA, B.kQinv, d + (size_t)L * N, s_d, T2, ext, s_x, M, nullptr, 0, 0, 0, d + (size_t)L * N, s_d,
-                           T2, nb, s);
-    for (int k = 0; k < 3; k++) launch_baseconv(c, B.kAQ, B.rAQ, d + ((size_t)k * T2 + L) * N, o3 + (size_t)k * L * N, nb, s_d, so, s);
-    launch_sub_mul_general(c, 3, L, B.lmQ, B.kT, o3, so, L, nullptr, 0, 0, nullptr, 0, 0, 0, o3, so, L, nb, s);
-}
-
 // every argument error of the two entry points, before anything is queued; false: nothing to do (batch <= 0)
 bool bfv_dot_check(const Context& c, int level, const DotTerms& t, const Key* rlk, bool with_relin, const u64* out, long long so,
                    int out_polys, int batch) {
@@ -1137,81 +1139,11 @@ bool bfv_dot_check(const Context& c, int level, const DotTerms& t, const Key* rl
     if (t.addend) ck.apart(sp_out, ck.operand(t.addend, t.s_addend, w, "the addend", true), "the addend");
     return true;
 }
-
-void bfv_mult_sum_run(Context& c, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s0) {
-    const long long N = c.n;
-    const int L = level + 1;
-    const BfvDotPlan plan = bfv_dot_plan(c.T.mod.data(), c.nq, level, c.logn, t.n);
-    const bool fold_on = sw::bfv_fold();
-    // the groups' bases: a full group's and, where it differs, the shorter last group's
-    std::vector<BfvDotBasis> bases;
-    auto basis_of = [&](int m) -> const BfvDotBasis& {
-        const int M = bfv_dot_aux_count(c.T.mod.data(), L, c.logn, m);
-        for (const auto& B : bases)
-            if (B.M == M) return B;
-        bases.push_back(bfv_dot_basis(c, level, M, fold_on));
-        return bases.back();
-    };
-    bases.reserve(2);
-    const int Mx = basis_of(std::min(t.n, plan.max_terms)).M, Tx = L + Mx;
-    if (plan.n_groups > 1 && t.n % plan.max_terms) basis_of(t.n % plan.max_terms);
-    // pairs per launch: the setting, at most one launch's and one group's terms, and no more than leaves the tile bfv_mult gets
-    auto rows_of = [&](int g) { return 4 * (size_t)g * Tx + 3 * (size_t)Tx + 3 * (size_t)Mx; };
-    int g = std::min({c.bfv_dot_chunk > 0 ? c.bfv_dot_chunk : LSA_BFV_DOT_CHUNK, LSA_DOT_MAX_TERMS, t.n, plan.max_terms});
-    {
-        const int M1 = bfv_aux_limbs(c, level);
-        const int tile1 = pick_tile(c, 7 * (size_t)(L + M1) + 3 * (size_t)M1, batch);
-        while (g > 1 && pick_tile(c, rows_of(g), batch) < tile1) g--;
-    }
-    for_tiles(c, rows_of(g), batch, s0, [&](int nb, int b0, u64* ws, int tb, hipStream_t s) {
-        u64* o3 = d3 + (size_t)b0 * sd;
-        for (int gi = 0, i0 = 0; gi < plan.n_groups; gi++) {
-            const int m = std::min(plan.max_terms, t.n - i0);
-            const BfvDotBasis& B = basis_of(m);
-            const int T2 = B.T2;
-            const long long s_e = 2LL * T2 * N, s_d = 3LL * T2 * N;
-            const size_t slot = (size_t)tb * s_e;
-            u64* e = ws;
-            u64* d = e + 2 * (size_t)g * slot;
-            u64* ext = d + (size_t)tb * s_d;
-            for (int j0 = 0; j0 < m; j0 += g) {
-                const int mm = std::min(g, m - j0);
-                const u64 *pa[LSA_DOT_MAX_TERMS], *pb[LSA_DOT_MAX_TERMS];
-                long long sa[LSA_DOT_MAX_TERMS], sb[LSA_DOT_MAX_TERMS];
-                for (int j = 0; j < mm; j++) {
-                    const int i = i0 + j0 + j;
-                    // an operand shared by the batch (stride 0) is extended once and read by every item of the tensor
-                    u64* ea = e + (size_t)(2 * j) * slot;
-                    bfv_dot_extend(c, B, fold_on, t.as[i] + (size_t)b0 * t.sas[i], t.sas[i], ea, t.sas[i] ? nb : 1, s);
-                    pa[j] = ea, sa[j] = t.sas[i] ? s_e : 0;
-                    if (t.as[i] == t.bs[i] && t.sas[i] == t.sbs[i]) {   // a square
-                        pb[j] = pa[j], sb[j] = sa[j];
-                        continue;
-                    }
-                    u64* eb = e + (size_t)(2 * j + 1) * slot;
-                    bfv_dot_extend(c, B, fold_on, t.bs[i] + (size_t)b0 * t.sbs[i], t.sbs[i], eb, t.sbs[i] ? nb : 1, s);
-                    pb[j] = eb, sb[j] = t.sbs[i] ? s_e : 0;
-                }
-                launch_tensor_sum(c, mm, pa, sa, nullptr, pb, sb, nullptr, nullptr, 0, j0 > 0, d, s_d, nb, T2, B.rmT, s);
-            }
-            if (gi == 0) {
-                bfv_dot_tail(c, B, fold_on, d, ext, o3, sd, nb, s);
-            } else {   // a later group: scaled down on its own into the (now free) extension slots, then added in Q
-                const long long st = 3LL * L * N;
-                bfv_dot_tail(c, B, fold_on, d, ext, e, st, nb, s);
-                launch_elementwise(c, EW_ADD, o3, e, o3, nb, sd, st, sd, 3 * L, rm_seq(L), s);
-            }
-            i0 += m;
-        }
-        if (t.addend)
-            launch_elementwise(c, EW_ADD, o3, t.addend + (size_t)b0 * t.s_addend, o3, nb, sd, t.s_addend, sd, 2 * L, rm_seq(L), s);
-    });
-}
 }  // namespace
 
 void bfv_mult_sum(Context& c, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s) {
     if (!bfv_dot_check(c, level, t, nullptr, false, d3, sd, 3, batch)) return;
-    bfv_mult_sum_run(c, level, t, d3, batch, sd, s);
+    bfv_mult_sum_run(c, "bfv_dot", level, t, d3, batch, sd, s);
 }
 
 // the summed, scaled-down tensor lives in the second arena, as in bfv_mult_relin
@@ -1219,7 +1151,7 @@ void bfv_dot(Context& c, int level, const DotTerms& t, const Key* rlk, u64* out,
     if (!bfv_dot_check(c, level, t, rlk, true, out, so, 2, batch)) return;
     const long long sd = 3LL * (level + 1) * c.n;
     u64* d3 = c.workspace2((size_t)sd * batch, s);
-    bfv_mult_sum_run(c, level, t, d3, batch, sd, s);
+    bfv_mult_sum_run(c, "bfv_dot", level, t, d3, batch, sd, s);
     bfv_relin(c, level, d3, *rlk, out, batch, sd, so, s);
 }
 

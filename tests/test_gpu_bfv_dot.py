@@ -128,6 +128,65 @@ def test_small_ring_levels_terms_tiles_and_streams():
         rig.close()
 
 
+def test_one_context_runs_a_level_over_two_auxiliary_bases():
+    """bfv_mult and bfv_mult_sum share one basis builder whose cached constants and conversion plans are keyed by (L, M).  N = 2^12,
+    level 1, batch 3 (items 0 and 2 equal), ONE context: n = 3 builds the M(3) = 3 basis first, then bfv_mult and n = 1 run the same
+    level over M(1) = 2, then n = 3 again -- folded, then with LSA_BFV_FOLD=0 (read per call: both sets of constants sit in the
+    cache).  The three pairs are a plain one, one whose b is shared by the batch (stride 0) and a square: bfv_mult on each is the
+    oracle's on item 1 and mult_sum(n = 1) on the whole batch, and both sums of the three are the model's.
+    A second context takes the other order -- unfolded before folded, bfv_mult and n = 1 (M = 2) before n = 3 (M = 3), then M = 2
+    again: the M = 3 vector of Q^-1 begins with the M = 2 one, so only the short vector cached first shows a name without M"""
+    need_gpu()
+    from lattisense_amd._native import check, lib
+    P = params.BFV_DEFAULT[8192]
+    n, lvl, batch = 1 << 12, 1, 3
+    w2, w3 = 2 * (lvl + 1) * n, 3 * (lvl + 1) * n
+    assert [model.aux_limbs(n, P["q"], lvl, m) for m in (1, 3)] == [2, 3]
+    want3 = want1 = None
+    for sum_first, folds, seed in ((True, (None, "0"), 1207), (False, ("0", None), 1208)):
+        rig = Rig(n, P["q"], P["p"], P["t"], 2, seed)
+        ctx = rig.ctx
+
+        def mult(a, b, sb):
+            out = ctx.alloc(batch * w3)
+            check(lib().lsa_bfv_mult(ctx.h, lvl, a.ptr, b.ptr, out.ptr, batch, w2, sb, w3, ctx.stream))
+            return ctx.download(out, (batch, 3, lvl + 1, n))
+
+        try:
+            if want3 is None:   # the operands and their references, once
+                hA, hB, hW = [rig.ct(lvl, batch) for _ in range(3)], rig.ct(lvl, batch), rig.ct(lvl, 1)
+                for x in hA + [hB]:
+                    x[2] = x[0]
+
+                def host(i):   # item i of the three pairs
+                    return [hA[0][i], hA[1][i], hA[2][i]], [hB[i], hW[0], hA[2][i]]
+
+                want3 = {i: model.mult_sum(rig.o, lvl, *host(i)) for i in (0, 1)}
+                want1 = [rig.o.bfv_mult(lvl, a, b) for a, b in zip(*host(1))]
+            dA, dB, dW = [ctx.upload(x) for x in hA], ctx.upload(hB), ctx.upload(hW)
+            pairs = [("plain", dA[0], dB, w2), ("b shared by the batch", dA[1], dW, 0), ("square", dA[2], dA[2], w2)]
+
+            def three(tag):
+                got = mult_sum(rig, lvl, dA, [dB, dW, dA[2]], batch, sbs=[w2, 0, w2])
+                assert np.array_equal(got[0], want3[0]) and np.array_equal(got[1], want3[1]), ("n = 3 against the model", tag)
+                assert np.array_equal(got[2], got[0]) and not np.array_equal(got[1], got[0]), tag
+
+            def ones(tag):
+                for k, (what, a, b, sb) in enumerate(pairs):
+                    got = mult(a, b, sb)
+                    assert np.array_equal(got[1], want1[k]), ("bfv_mult against the oracle", what, tag)
+                    assert np.array_equal(got, mult_sum(rig, lvl, [a], [b], batch, sbs=[sb])), ("n == 1 is bfv_mult", what, tag)
+                    assert np.array_equal(got[2], got[0]) and not np.array_equal(got[1], got[0]), (what, tag)
+
+            for fold in folds:
+                with env(LSA_BFV_FOLD=fold):
+                    tag = (sum_first, fold)
+                    for step in (three, ones, three) if sum_first else (ones, three, ones):
+                        step(tag)
+        finally:
+            rig.close()
+
+
 def test_tight_chain_three_groups():
     """a chain whose top level leaves G = 1 spare bit: max_terms = 2, so n = 5 runs as groups of 2, 2 and 1, each scaled down on
     its own and added in Q"""
