@@ -426,6 +426,46 @@ int lsa_slot_sum_set_multi_mac(lsa_slot_sum plan, int enable);
 int lsa_ckks_slot_sum(lsa_context ctx, lsa_slot_sum plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
                       long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
 
+/* ---- BFV slot sum: out = sum_{i<count} rot_cols(y, i*step), y = ct + rot_rows(ct) if rows != 0, else ct -- the sum over slots
+ * that finishes a packed BFV inner product (lsa_bfv_dot).  BFV slots form a 2 x N/2 matrix: the column rotation r is the Galois
+ * element 5^(r mod N/2) mod 2N, the row swap is 2N-1; count = N/2 with rows = 1 leaves the total in every slot.  ct and out are
+ * [2][level+1][N] in the coefficient domain.  The plan is the one of the CKKS slot sum above -- state (x, s, n, tail), radix 2 or
+ * 4, TAIL and NEXT keys, at most four keys per step -- started at x = y; with rows != 0 one more step runs before the column
+ * steps, one decomposition of ct's c1 with one NEXT key, the key of 2N-1.  count == 1, rows == 0 is a copy and needs no key;
+ * count == 1, rows != 0 is the row step alone.
+ * The words: every limb of ct transformed to the NTT domain, the steps run as tests/bfv_slot_sum_model.py states them on
+ * oracle/ckks_bootstrap.py's rotate_ext, add_ext, moddown and add (the row step is rotate_ext with g = 2N-1), the result transformed
+ * back.  One step is x <- x + ModDown(sum of the NEXT extended rotations of x): the sum is formed over Q_level u P and divided by P
+ * ONCE; the TAIL rotations join an accumulator that is divided once, after the last step.  These words DIFFER from the chain of
+ * lsa_bfv_rotate + lsa_poly_addsub, which divides (and rounds) once per rotation; both decrypt to the same slot sum mod t.
+ * radix: 2, 4 or 0 = the default, 4.  Errors are LSA_ERR_ARG before anything is queued, with a message that begins
+ * "lsa_bfv_slot_sum" and names the argument: a CKKS context, a level out of range, count < 1, count > N/2, radix not 0 / 2 / 4, a
+ * planned rotation that is a multiple of N/2, a missing key (the message names the element), a key below the plan's level, a plan
+ * of another context, lsa_bfv_slot_sum_set_gather(plan, 1) on a ring above 2^14. */
+/* (the handle cannot be called lsa_bfv_slot_sum: C keeps typedef and function names in one name space) */
+typedef struct lsa_bfv_slot_sum_st* lsa_bfv_slot_sum_handle;
+/* host only, needs no device and no context: the counts of the plan (steps = decompositions, key MACs, divisions by P) and the
+ * Galois elements a run needs a key for (ascending, distinct).  Any output pointer may be null; n_galois receives their number;
+ * LSA_ERR_ARG if `galois_elements` is given and capacity is less. */
+int lsa_bfv_slot_sum_plan(int n_ring, long long step, int count, int radix, int rows, int* n_steps, int* n_keyswitch, int* n_moddown,
+                          uint64_t* galois_elements, int capacity, int* n_galois);
+int lsa_bfv_slot_sum_create(lsa_context ctx, int level, long long step, int count, int radix, int rows, lsa_bfv_slot_sum_handle* out);
+void lsa_bfv_slot_sum_destroy(lsa_bfv_slot_sum_handle plan);
+/* radix: the one in force (never 0); rows: 0 or 1; gather: the tail in force (below); any output pointer may be null */
+int lsa_bfv_slot_sum_info(lsa_bfv_slot_sum_handle plan, int* level, int* count, int* radix, int* rows, int* n_steps, int* n_keyswitch,
+                          int* n_moddown, int* n_galois, int* gather);
+int lsa_bfv_slot_sum_galois_elements(lsa_bfv_slot_sum_handle plan, uint64_t* out, int capacity);   /* ascending */
+/* 1 (the default where N <= 2^14): the rotated c0 terms never enter the NTT domain -- the division by P is exact on a multiple
+ * of P, ModDown(P z + a) = z + ModDown(a) residue for residue, so the ModDown tail gathers them in the coefficient domain from
+ * the c0 row staged in LDS (k_bfv_slot_tail).  0 (the only form above 2^14, selectable everywhere for A/B): c0 is transformed as
+ * well and rides through the key MAC and the division as P c0, the CKKS form.  The same words either way. */
+int lsa_bfv_slot_sum_set_gather(lsa_bfv_slot_sum_handle plan, int enable);
+/* in [batch][2][level+1][N] (coefficient domain) -> out, the same shape; batch strides sin / sout in words, even, pointers
+ * 16-byte aligned.  out may be in itself (same pointer, same stride) and otherwise may not overlap it; batch <= 0 is a no-op.
+ * galois_elements / keys: n_keys Galois keys at the plan's level or above, in any order and possibly more than needed. */
+int lsa_bfv_slot_sum(lsa_context ctx, lsa_bfv_slot_sum_handle plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                     long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
+
 /* ---- CKKS polynomial evaluation: p(x) = sum_k coef[k] B_k(x) on a ciphertext, B_k the Chebyshev polynomial T_k (basis 0) or
  * the monomial x^k (basis 1), by a baby-step / giant-step (Paterson-Stockmeyer) plan of depth k = ceil(log2(n_coef)), k >= 1:
  * the powers P_j for j < 2^log_baby and P_(2^j) above them (P_j from P_ceil(j/2) and P_floor(j/2); only those that are used),

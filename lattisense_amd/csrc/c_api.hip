@@ -828,6 +828,82 @@ int lsa_ckks_slot_sum(lsa_context ctx, lsa_slot_sum plan, const uint64_t* in, ui
     });
 }
 
+// ---- BFV slot sum (slot_sum.h, ops.hip bfv_slot_sum_run)
+struct lsa_bfv_slot_sum_st {
+    BfvSlotSum* p;
+    Context* c;
+};
+int lsa_bfv_slot_sum_plan(int n_ring, long long step, int count, int radix, int rows, int* n_steps, int* n_keyswitch, int* n_moddown,
+                          uint64_t* galois_elements, int capacity, int* n_galois) {
+    return guard([&] {
+        const BfvSlotSumPlanHost p = bfv_slot_sum_plan_checked(n_ring, step, count, radix, rows);
+        if (n_steps) *n_steps = (int)p.steps.size();
+        if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
+        if (n_moddown) *n_moddown = p.n_moddown;
+        if (n_galois) *n_galois = (int)p.galois.size();
+        LSA_REQUIRE(galois_elements == nullptr || (int)p.galois.size() <= capacity,
+                    "lsa_bfv_slot_sum_plan: capacity: buffer too small for the Galois elements");
+        if (galois_elements) std::copy(p.galois.begin(), p.galois.end(), galois_elements);
+    });
+}
+int lsa_bfv_slot_sum_create(lsa_context ctx, int level, long long step, int count, int radix, int rows, lsa_bfv_slot_sum_handle* out) {
+    return guard([&] {
+        LSA_REQUIRE(out != nullptr, "lsa_bfv_slot_sum_create: null argument");
+        auto h = std::make_unique<lsa_bfv_slot_sum_st>();
+        h->c = &C(ctx);
+        h->p = bfv_slot_sum_create(*h->c, level, step, count, radix, rows);
+        *out = h.release();
+    });
+}
+void lsa_bfv_slot_sum_destroy(lsa_bfv_slot_sum_handle plan) {
+    if (!plan) return;
+    delete plan->p;
+    delete plan;
+}
+int lsa_bfv_slot_sum_info(lsa_bfv_slot_sum_handle plan, int* level, int* count, int* radix, int* rows, int* n_steps, int* n_keyswitch,
+                          int* n_moddown, int* n_galois, int* gather) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr, "lsa_bfv_slot_sum_info: null plan handle");
+        const BfvSlotSumPlanHost& p = plan->p->plan;
+        if (level) *level = plan->p->level;
+        if (count) *count = p.count;
+        if (radix) *radix = p.radix;
+        if (rows) *rows = p.rows;
+        if (n_steps) *n_steps = (int)p.steps.size();
+        if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
+        if (n_moddown) *n_moddown = p.n_moddown;
+        if (n_galois) *n_galois = (int)p.galois.size();
+        if (gather) *gather = plan->p->gather ? 1 : 0;
+    });
+}
+int lsa_bfv_slot_sum_galois_elements(lsa_bfv_slot_sum_handle plan, uint64_t* out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr && out != nullptr, "lsa_bfv_slot_sum_galois_elements: null argument");
+        const auto& g = plan->p->plan.galois;
+        LSA_REQUIRE((int)g.size() <= capacity, "lsa_bfv_slot_sum_galois_elements: capacity: buffer too small");
+        std::copy(g.begin(), g.end(), out);
+    });
+}
+int lsa_bfv_slot_sum_set_gather(lsa_bfv_slot_sum_handle plan, int enable) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr, "lsa_bfv_slot_sum_set_gather: null plan handle");
+        LSA_REQUIRE(!enable || plan->c->logn <= LSA_PERM_LDS_MAX_LOGN,
+                    "lsa_bfv_slot_sum_set_gather: enable: the gathering tail stages a limb in LDS and needs N <= 2^14");
+        plan->p->gather = enable != 0;
+    });
+}
+int lsa_bfv_slot_sum(lsa_context ctx, lsa_bfv_slot_sum_handle plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                     long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr, "lsa_bfv_slot_sum: null plan handle");
+        LSA_REQUIRE(plan->c == &C(ctx), "lsa_bfv_slot_sum: the plan belongs to another context");
+        LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "lsa_bfv_slot_sum: null key argument");
+        std::map<u64, const Key*> g;
+        for (int i = 0; i < n_keys; i++) g[galois_elements[i]] = &K(keys[i], "lsa_bfv_slot_sum");
+        bfv_slot_sum_run(*plan->p, in, sin, out, sout, batch, g, S(stream));
+    });
+}
+
 // ---- CKKS polynomial evaluation (poly_eval.hip)
 struct lsa_polynomial_st {
     Polynomial* p;

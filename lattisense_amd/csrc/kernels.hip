@@ -1748,7 +1748,7 @@ __global__ __launch_bounds__(TPB) void k_ks_mac(KsMacArgs g) {
             }
         }
         if constexpr (EXT) {
-            if (tl < g.L) {
+            if (g.base && tl < g.L) {   // (no base: the caller adds the rotated c0 itself, the BFV slot sum's gathering tail)
                 const ulonglong2 c0 = ld2(g.base + b * g.sbase + tl * N + x);
                 const u64 k = g.pm[tl];
                 r00 = add_mod(r00, mont_mul(c0.x, k, m.q, m.qinv), m.q);
@@ -1792,14 +1792,15 @@ static void launch_ks_mac_kb(int beta, dim3 grid, hipStream_t s, const KsMacArgs
 }
 
 // scatter (with engine < 0): the result is written as the rotated extended ciphertext perm(acc + P * c0) -- scatter = the index
-// map of the rotation's inverse element, base = the ciphertext whose c0 enters (see KsMacArgs)
+// map of the rotation's inverse element, base = the ciphertext whose c0 enters (see KsMacArgs); base == nullptr: no P * c0 is
+// added, the result is perm(acc)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, const Key& key,
                    u64* acc, long long sacc, int batch, hipStream_t s, bool unfused_only, const u32* scatter, const u64* base, long long sbase,
                    const TensorFold* fold, bool accumulate) {
     if (batch <= 0) return;
     KsMacArgs g{};
     LSA_REQUIRE(!accumulate || scatter, "key MAC: only the extended output accumulates");
-    LSA_REQUIRE(!scatter || (!unfused_only && base), "key MAC: the extended output covers every target limb and needs the ciphertext");
+    LSA_REQUIRE(!scatter || !unfused_only, "key MAC: the extended output covers every target limb");
     LSA_REQUIRE(!(scatter && fold), "key MAC: the tensor fold has no extended output");
     if (fold) {
         g.fa = fold->a;
@@ -1843,7 +1844,7 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
     const double T = targets;
     int q_targets = 0;   // (tensor fold: the own digit of a Q target reads a0, a1, b0, b1 instead of cx)
     for (int i = 0; i < targets; i++) q_targets += (g.n_tl ? g.tl_list[i] : i) < g.L;
-    ProfScope ps(c, PROF_KSMAC, 8.0 * c.n * (batch * (g.beta * T + 2 * T * (accumulate ? 2 : 1) + (scatter ? g.L : 0) + (fold ? 3.0 * q_targets : 0.0)) +
+    ProfScope ps(c, PROF_KSMAC, 8.0 * c.n * (batch * (g.beta * T + 2 * T * (accumulate ? 2 : 1) + (scatter && base ? g.L : 0) + (fold ? 3.0 * q_targets : 0.0)) +
                                              2.0 * g.beta * T), s);
     // enough workgroups to fill the chip, as few key re-reads as possible
     const dim3 grid1 = ew_grid(c, targets, 1);

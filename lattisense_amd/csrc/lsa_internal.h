@@ -324,8 +324,8 @@ void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows
 // key-switch inner product: acc[h][tl] = sum_d ext(d,tl) * key[d][h][tl];  ext(d,tl) = cx[tl] when tl is in digit d
 // unfused_only: only the target limbs that do not take the fused kernel (ks_fused_limb; k_ntt_r16_ksmac did the others)
 // scatter (every target limb only): the result leaves as the ROTATED EXTENDED ciphertext acc[h][tl][scatter[x]] = sum(x) + (h == 0, tl < L:
-// P * base[tl][x]) -- gadget product, c0 * P and the automorphism of a baby-step rotation in one pass; accumulate: added to
-// what acc holds there (a giant-step rotation joining a running sum)
+// P * base[tl][x]) -- gadget product, c0 * P and the automorphism of a baby-step rotation in one pass (base == nullptr: no P * c0);
+// accumulate: added to what acc holds there (a giant-step rotation joining a running sum)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext,
                    const Key& key, u64* acc, long long sacc, int batch, hipStream_t s, bool unfused_only = false,
                    const u32* scatter = nullptr, const u64* base = nullptr, long long sbase = 0,
@@ -516,6 +516,40 @@ SlotSumPlanHost slot_sum_plan_checked(int n_ring, long long step, int count, int
 SlotSum* slot_sum_create(Context& c, int level, long long step, int count, int radix);
 void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
                   const std::map<u64, const Key*>& glk, hipStream_t s);
+// BFV slot sum  out = sum_{i<count} rot_cols(y, i*step), y = in + rot_rows(in) if rows (lsa_bfv_slot_sum_*; plan: slot_sum.h).
+// Ciphertexts are in the coefficient domain.  gather: the rotated c0 terms never enter the NTT domain -- the key MAC adds no
+// P * c0 and the ModDown tail gathers them from the c0 row staged in LDS (slot_sum.hip k_bfv_slot_tail; N <= 2^14); plain: c0 is
+// transformed too and rides through the division as P * c0 (the CKKS form).  The same words, since ModDown(P z + a) = z + ModDown(a).
+struct BfvSlotSum {
+    Context& c;
+    int level;
+    BfvSlotSumPlanHost plan;
+    bool gather;
+    BfvSlotSum(Context& ctx, int level_) : c(ctx), level(level_), gather(ctx.logn <= LSA_PERM_LDS_MAX_LOGN) {}
+};
+#define LSA_BFV_SLOTSUM_DEFAULT_RADIX 4   // what radix 0 stands for
+BfvSlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count, int radix, int rows);
+BfvSlotSum* bfv_slot_sum_create(Context& c, int level, long long step, int count, int radix, int rows);
+void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
+                      const std::map<u64, const Key*>& glk, hipStream_t s);
+// the coefficient-domain ModDown tail of one step of the BFV slot sum (k_bfv_slot_tail), x and out [2][L][N]:
+//   out[0][j][y] = x0[j][y] + sum_{r<n_next} sign_r(y) x0[j][pi_r(y)] + (addend ? addend[j][y] : 0) + (acc[0][j][y] - conv[0][j][y]) Pinv_j
+//   out[1][j][y] = x1[j][y] + (acc[1][j][y] - conv[1][j][y]) Pinv_j
+//   tail_c0[j][y] (+)= sign_t(y) x0[j][pi_t(y)]                       when `tail` is given
+// next / tail: Context::coeff_perm tables.  out may be x itself: a row is read and written by one workgroup, reads first.
+struct BfvSlotTail {
+    int n_next = 0;
+    const u32* next[3] = {nullptr, nullptr, nullptr};
+    const u32* tail = nullptr;
+    u64* tail_c0 = nullptr;   // [L][N] per batch item
+    long long s_tail = 0;
+    bool tail_accumulate = false;
+    const u64* addend = nullptr;   // [L][N] per batch item
+    long long s_addend = 0;
+};
+void launch_bfv_slot_tail(Context& c, int level, const BfvSlotTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
+                          const u64* conv, long long sconv, const u64* x, long long sx, u64* out, long long sout, int batch,
+                          hipStream_t s);
 void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                 hipStream_t s);
 void poly_addsub(Context& c, int op, int level, int polys, const u64* a, const u64* b, u64* out, int batch, long long sa,

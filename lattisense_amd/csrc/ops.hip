@@ -50,7 +50,9 @@ struct RotMacTerm {   // the pt_mul factor of one rotate-and-MAC term (fz_epi = 
 //            added to p instead (p[row][y] (+)= value * pt[limb][y] * 2^-64, y = scatter[x]): one term of a BFV rotate-and-MAC
 //   RESCALE  NTT domain, fused tails: p is scratch of the same shape and rs.out receives rescale(p)
 //   COEFF    coefficient domain, `base` given there (BFV).  coeff_gather: the coefficient-domain automorphism of a BFV rotation,
-//            Context::coeff_perm(g), applied by the tail's loads (k_sub_mul_perm): p[row][x] = sign_x * value(pi_x)
+//            Context::coeff_perm(g), applied by the tail's loads (k_sub_mul_perm): p[row][x] = sign_x * value(pi_x).
+//            slot_tail (base = x, both polynomials): one step of the BFV slot sum, the rotated c0 terms gathered by the tail
+//            (k_bfv_slot_tail)
 struct KsOut {
     enum Form { NTT, RESCALE, COEFF };
     u64* p;
@@ -63,6 +65,7 @@ struct KsOut {
     const u32* scatter = nullptr;
     const u32* coeff_gather = nullptr;
     const RotMacTerm* rmac = nullptr;
+    const BfvSlotTail* slot_tail = nullptr;
 };
 
 // step 5, the division by P of a polynomial pair over Q_level u P (acc: [2][L+k][N] per batch item, NTT domain; its P rows --
@@ -71,6 +74,8 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
     LSA_REQUIRE(!o.scatter || (c.fuse_tails && o.form == KsOut::NTT), "scattered ModDown store: fused tails, NTT-domain output");
     LSA_REQUIRE(!o.rmac || o.scatter, "rotate-and-MAC tail: needs the rotation's index map");
     LSA_REQUIRE(!o.coeff_gather || o.form == KsOut::COEFF, "gathered ModDown tail: coefficient-domain output");
+    LSA_REQUIRE(!o.slot_tail || (o.form == KsOut::COEFF && !o.coeff_gather && o.base && o.base_polys == 2 && o.base_rpp == level + 1),
+                "slot-sum ModDown tail: coefficient-domain output on a whole ciphertext");
     LSA_REQUIRE(o.form != KsOut::RESCALE || (c.fuse_tails && level >= 1 && ((o.base && o.base_polys == 2) || (!o.base && o.base_polys == 0))),
                 "merged ModDown+rescale: unsupported shape");
     const bool coeff_out = o.form == KsOut::COEFF, rs = o.form == KsOut::RESCALE;
@@ -107,7 +112,9 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
             launch_baseconv(c, k, rows, acc + (size_t)h * T * N, conv + (size_t)h * L * N, nb, s_acc, s_conv, s);
     }
     if (coeff_out) {
-        if (o.coeff_gather)
+        if (o.slot_tail)
+            launch_bfv_slot_tail(c, level, *o.slot_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
+        else if (o.coeff_gather)
             launch_moddown_final_perm(c, level, o.coeff_gather, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp,
                                       o.base_polys, o.p, o.sp, nb, s);
         else
@@ -1657,14 +1664,6 @@ SlotSumPlanHost slot_sum_plan_checked(int n_ring, long long step, int count, int
     }
 }
 
-static u64 galois_of_rotation(int r, int n_ring) {   // 5^r mod 2N
-    const u64 mask = 2 * (u64)n_ring - 1;
-    u64 e = 1, b = 5;
-    for (; r; r >>= 1, b = b * b & mask)
-        if (r & 1) e = e * b & mask;
-    return e;
-}
-
 SlotSum* slot_sum_create(Context& c, int level, long long step, int count, int radix) {
     LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, "slot sum: context is not CKKS");
     LSA_REQUIRE(level >= 0 && level < c.nq, "slot sum: level out of range");
@@ -1769,6 +1768,122 @@ void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long 
             sx = sout;
         }
         if (tail_live) ks_moddown(c, level, tail, s_ext2, t.conv, {.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2}, nb, st);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ BFV slot sum
+// out = sum_{i<count} rot_cols(y, i*step), y = in + rot_rows(in) if rows, by the plan of slot_sum.h on coefficient-domain
+// ciphertexts.  Per tile and step, as bfv_rotate_many: c1 of x into the NTT domain once (the MAC's own-digit operand), the
+// decomposition from the coefficients, one launch_ks_mac per key with the rotation's NTT-domain scatter -- the first NEXT key
+// writes the tile's acc, later ones add to it, the TAIL key writes or adds to the extended tail accumulator -- then the
+// coefficient-domain ModDown of the NEXT sum.  gather: the MACs add no P * c0; the tail (k_bfv_slot_tail) adds x and the rotated
+// c0 terms, gathered from the c0 row in LDS, and collects the TAIL rotation's c0 term in tail_c0 [L][N]; after the last step
+// out = x + (tail_c0, 0) + ModDown(tail).  plain: c0 is transformed too and enters the MACs as `base` (the CKKS form), the tails are
+// launch_moddown_final with base = x.  ModDown(P z + a) = z + ModDown(a) residue for residue, so both give the same words.  x
+// lives in `out` from the second step on and is updated in place.
+BfvSlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count, int radix, int rows) {
+    try {
+        return bfv_slot_sum_plan(n_ring, step, count, radix, rows, LSA_BFV_SLOTSUM_DEFAULT_RADIX);
+    } catch (const std::invalid_argument& e) {
+        throw Error(LSA_ERR_ARG, e.what());
+    }
+}
+
+BfvSlotSum* bfv_slot_sum_create(Context& c, int level, long long step, int count, int radix, int rows) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "lsa_bfv_slot_sum_create: context is not BFV");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "lsa_bfv_slot_sum_create: level out of range (0.." + std::to_string(c.nq - 1) + ")");
+    auto p = std::make_unique<BfvSlotSum>(c, level);
+    p->plan = bfv_slot_sum_plan_checked(c.n, step, count, radix, rows);
+    LSA_REQUIRE(p->plan.steps.empty() || c.np >= 1, "lsa_bfv_slot_sum_create: key switching needs at least one special prime");
+    return p.release();
+}
+
+void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
+                      const std::map<u64, const Key*>& glk, hipStream_t s) {
+    Context& c = p.c;
+    const int level = p.level;
+    const EntryCheck ck(c, "lsa_bfv_slot_sum", LSA_ALGO_BFV, level, 0, batch);
+    std::map<u64, const Key*> key_of;   // every key is looked up before anything is queued
+    for (u64 e : p.plan.galois) {
+        auto it = glk.find(e);
+        LSA_REQUIRE(it != glk.end() && it->second, ck.who + ": Galois key for element " + std::to_string(e) + " missing");
+        ck.key(*it->second, "a Galois key");
+        key_of[e] = it->second;
+    }
+    if (batch <= 0) return;
+    const long long N = c.n;
+    const int L = level + 1, T = L + c.np;
+    const size_t w = 2 * (size_t)L * N;
+    const Span sp_in = ck.operand(in, sin, w, "in", false), sp_out = ck.output(out, sout, w);
+    ck.same_or_apart(sp_out, sp_in, "in");
+    if (p.plan.steps.empty()) {   // count == 1, no rows: a copy
+        if (layout::same(sp_out, sp_in)) return;
+        std::vector<int> rows(2 * L);
+        for (int i = 0; i < 2 * L; i++) rows[i] = i;
+        launch_copy_rows(c, in, sin, out, sout, 2 * L, rows.data(), batch, s);
+        return;
+    }
+    const bool gather = p.gather;
+    LSA_REQUIRE(!gather || c.logn <= LSA_PERM_LDS_MAX_LOGN, ck.who + ": the gathering tail needs N <= 2^14");
+    std::map<u64, const u32*> scatter_of, perm_of;   // (table look-ups upload on first use: only after every argument is accepted)
+    for (u64 e : p.plan.galois) {
+        scatter_of[e] = inverse_perm(c, e);
+        if (gather) perm_of[e] = c.coeff_perm(e);
+    }
+    const bool has_tail = p.plan.has_tail;
+    const size_t ks_rows = KsTile::rows(c, level);
+    // per batch item: NTT(c1) | the KsTile rows | the extended tail accumulator | tail_c0 (gather) or NTT(c0) (plain)
+    const size_t r_tail = has_tail ? 2 * (size_t)T : 0, r_last = gather ? (has_tail ? (size_t)L : 0) : (size_t)L;
+    const long long sL = (long long)L * N;
+    for_tiles(c, (size_t)L + ks_rows + r_tail + r_last, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
+        u64* cxn = ws;
+        u64* ks_ws = cxn + (size_t)L * N * tb;
+        u64* tail = ks_ws + ks_rows * N * tb;
+        u64* last = tail + r_tail * N * tb;   // tail_c0 or NTT(c0)
+        KsTile t(c, level, nb, ks_ws, st);
+        const long long s_ext2 = t.s_acc;   // [2][T][N] per batch item, like t.acc
+        const u64* x = in + (size_t)b0 * sin;
+        long long sx = sin;
+        u64* o = out + (size_t)b0 * sout;
+        bool tail_live = false;
+        for (const BfvSlotSumStep& step : p.plan.steps) {
+            const u64* c1 = x + sL;
+            launch_ntt(c, c1, cxn, nb, sx, sL, L, rm_seq(L), false, st);
+            if (!gather) launch_ntt(c, x, last, nb, sx, sL, L, rm_seq(L), false, st);
+            t.decompose(cxn, sL, c1, sx);
+            BfvSlotTail bt;
+            bool next_live = false;
+            for (const BfvSlotSumKey& k : step.keys) {
+                const bool add_to = k.tail ? tail_live : next_live;
+                launch_ks_mac(c, level, cxn, sL, t.ext, t.s_ext, *key_of.at(k.g), k.tail ? tail : t.acc, s_ext2, nb, st, false,
+                              scatter_of.at(k.g), gather ? nullptr : last, sL, nullptr, add_to);
+                if (k.tail) {
+                    if (gather) {
+                        bt.tail = perm_of.at(k.g);
+                        bt.tail_c0 = last;
+                        bt.s_tail = sL;
+                        bt.tail_accumulate = tail_live;
+                    }
+                    tail_live = true;
+                } else {
+                    if (gather) bt.next[bt.n_next++] = perm_of.at(k.g);
+                    next_live = true;
+                }
+            }
+            t.moddown({.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2, .form = KsOut::COEFF,
+                       .slot_tail = gather ? &bt : nullptr});
+            x = o;
+            sx = sout;
+        }
+        if (tail_live) {
+            BfvSlotTail bt;
+            bt.addend = last;
+            bt.s_addend = sL;
+            ks_moddown(c, level, tail, s_ext2, t.conv,
+                       {.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2, .form = KsOut::COEFF,
+                        .slot_tail = gather ? &bt : nullptr},
+                       nb, st);
+        }
     });
 }
 

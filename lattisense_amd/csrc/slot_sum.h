@@ -89,4 +89,63 @@ inline SlotSumPlanHost slot_sum_plan(int n_ring, long long step, int count, int 
     return p;
 }
 
+inline unsigned long long galois_of_rotation(int r, int n_ring) {   // 5^r mod 2N
+    const unsigned long long mask = 2 * (unsigned long long)n_ring - 1;
+    unsigned long long e = 1, b = 5;
+    for (; r; r >>= 1, b = b * b & mask)
+        if (r & 1) e = e * b & mask;
+    return e;
+}
+
+// ---- the BFV slot sum  out = sum_{i<count} rot_cols(y, i*step),  y = ct + rot_rows(ct) if rows != 0, else ct.  BFV slots form a
+// 2 x N/2 matrix: the column rotation r is the Galois element 5^(r mod N/2) mod 2N, the row swap is 2N-1.  The plan is the one
+// above, started at x = y; with rows != 0 one more step runs first, one decomposition of ct's c1 with one NEXT key, the key of
+// 2N-1.  Keys are named by their Galois element.
+struct BfvSlotSumKey {
+    unsigned long long g;
+    bool tail;
+};
+struct BfvSlotSumStep {
+    std::vector<BfvSlotSumKey> keys;   // the TAIL key, if any, first
+};
+struct BfvSlotSumPlanHost {
+    int n_ring = 0, count = 0, radix = 4, rows = 0;
+    long long step = 0;
+    std::vector<BfvSlotSumStep> steps;
+    bool has_tail = false;
+    int n_keyswitch = 0, n_moddown = 0;
+    std::vector<unsigned long long> galois;   // ascending, distinct
+};
+
+// Throws std::invalid_argument; the message begins "lsa_bfv_slot_sum" and names the argument.
+inline BfvSlotSumPlanHost bfv_slot_sum_plan(int n_ring, long long step, int count, int radix, int rows, int dflt_radix = 4) {
+    SlotSumPlanHost cols;
+    try {
+        cols = slot_sum_plan(n_ring, step, count, radix, dflt_radix);
+    } catch (const std::invalid_argument& e) {
+        const std::string m = e.what(), pre = "slot sum: ";
+        throw std::invalid_argument("lsa_bfv_slot_sum: " + (m.compare(0, pre.size(), pre) == 0 ? m.substr(pre.size()) : m));
+    }
+    BfvSlotSumPlanHost p;
+    p.n_ring = n_ring;
+    p.count = count;
+    p.step = step;
+    p.radix = cols.radix;
+    p.rows = rows ? 1 : 0;
+    p.has_tail = cols.has_tail;
+    if (p.rows) p.steps.push_back({{{2 * (unsigned long long)n_ring - 1, false}}});
+    for (const SlotSumStep& st : cols.steps) {
+        BfvSlotSumStep b;
+        for (const SlotSumKey& k : st.keys) b.keys.push_back({galois_of_rotation(k.rot, n_ring), k.tail});
+        p.steps.push_back(b);
+    }
+    p.n_keyswitch = cols.n_keyswitch + p.rows;
+    p.n_moddown = cols.n_moddown + p.rows;
+    for (const auto& st : p.steps)
+        for (const auto& k : st.keys) p.galois.push_back(k.g);
+    std::sort(p.galois.begin(), p.galois.end());
+    p.galois.erase(std::unique(p.galois.begin(), p.galois.end()), p.galois.end());
+    return p;
+}
+
 }  // namespace lsa

@@ -1,11 +1,15 @@
-// slot_sum.hip — the device kernels of the CKKS slot sum (ops.hip slot_sum_run; plan: slot_sum.h):
+// slot_sum.hip — the device kernels of the slot sums (ops.hip slot_sum_run, bfv_slot_sum_run; plan: slot_sum.h).  CKKS:
 //   k_ks_mac_multi<KB, K>  the gadget inner product of ONE decomposition with K = 2..4 keys ("a MAC kernel that reads the
 //                          decomposed digits once for all keys of a hoisted group"), each key's product leaving
 //                          as that key's rotated extended ciphertext in that key's own buffer;
 //   k_ext_sum              out (+)= sum of up to three extended ciphertexts: joins the per-key buffers.
 // The per-point arithmetic is ks_mac_multi.h's, which the host compiles too (tests/cpp/test_ks_mac_multi.cpp).  k_ks_mac
 // (kernels.hip) stays the single-key kernel: SlotSum::multi_mac = false runs it once per key, each launch adding to its
-// destination, and that form measured faster at every bench shape, so it is the default.
+// destination, and that form measured faster at every bench shape, so it is the default.  BFV:
+//   k_bfv_slot_tail        the coefficient-domain ModDown tail of one step: x + (acc - conv) / P plus the step's rotated c0 terms,
+//                          gathered from the c0 row staged in LDS.
+#include <atomic>
+
 #include "ks_mac_multi.h"
 #include "lsa_internal.h"
 
@@ -207,6 +211,87 @@ __global__ __launch_bounds__(TPB) void k_ext_sum(ExtSumArgs g) {
     st2(po, ext_sum_point(r.x, vx, LSA_KSM_MAX_KEYS - 1, q), ext_sum_point(r.y, vy, LSA_KSM_MAX_KEYS - 1, q));
 }
 
+struct BfvSlotTailArgs {
+    const u64* x;             // [2][L][N], coefficient domain
+    const u64* acc;           // [2][acc_rpp][N], out of the NTT domain
+    const u64* conv;          // [2][L][N]
+    const u64* addend;        // [L][N] or null: one more addend of polynomial 0
+    u64* out;                 // [2][L][N]; may be x
+    u64* tail_c0;             // [L][N] or null
+    const u32* next[LSA_KSM_MAX_KEYS - 1];   // coeff_perm tables of the NEXT rotations
+    const u32* tail;          // coeff_perm table of the TAIL rotation (with tail_c0)
+    const u64* kvec;          // [L] P^-1 mod q_j, Montgomery form
+    const ModDev* mods;
+    long long sx, sacc, sconv, sadd, so, stail;
+    int n_next, tail_acc, acc_rpp, limbs, logn;
+};
+
+#define LSA_SLOT_TAIL_THREADS 1024
+// grid: x = 2*limbs, y = batch; dynamic LDS: 8N bytes when the launch gathers, else none.  One workgroup per row: a c0 row is
+// loaded once (coalesced, into LDS) and serves the row's own term, up to three NEXT gathers and the TAIL gather; every word of x is
+// read before the barrier and every word of out is stored after it by the same workgroup, so out == x is safe.  The c1 rows are
+// plain element-wise work.
+__global__ __launch_bounds__(LSA_SLOT_TAIL_THREADS) void k_bfv_slot_tail(BfvSlotTailArgs g) {
+    extern __shared__ __attribute__((aligned(16))) u64 lds[];
+    const int n = 1 << g.logn;
+    const int row = blockIdx.x;
+    const int poly = row / g.limbs, limb = row % g.limbs;
+    const ModDev m = g.mods[limb];
+    const u64 k = g.kvec[limb];
+    const long long b = blockIdx.y;
+    const long long ro = ((long long)poly * g.limbs + limb) << g.logn;
+    const u64* xr = g.x + b * g.sx + ro;
+    const u64* a = g.acc + b * g.sacc + (((long long)poly * g.acc_rpp + limb) << g.logn);
+    const u64* v = g.conv + b * g.sconv + ro;
+    u64* o = g.out + b * g.so + ro;
+    const bool gather = poly == 0 && (g.n_next > 0 || g.tail != nullptr);   // uniform over the workgroup
+    if (gather) {
+        for (int x = threadIdx.x * 2; x < n; x += 2 * LSA_SLOT_TAIL_THREADS) *reinterpret_cast<ulonglong2*>(lds + x) = ld2(xr + x);
+        __syncthreads();
+    }
+    const u64* ad = poly == 0 && g.addend ? g.addend + b * g.sadd + ((long long)limb << g.logn) : nullptr;
+    u64* tc = gather && g.tail ? g.tail_c0 + b * g.stail + ((long long)limb << g.logn) : nullptr;
+    for (int x = threadIdx.x * 2; x < n; x += 2 * LSA_SLOT_TAIL_THREADS) {
+        const ulonglong2 va = ld2(a + x), vv = ld2(v + x);
+        const ulonglong2 c = gather ? *reinterpret_cast<const ulonglong2*>(lds + x) : ld2(xr + x);
+        u64 r0 = add_mod(mont_mul(sub_mod(va.x, vv.x, m.q), k, m.q, m.qinv), c.x, m.q);
+        u64 r1 = add_mod(mont_mul(sub_mod(va.y, vv.y, m.q), k, m.q, m.qinv), c.y, m.q);
+        if (ad) {
+            const ulonglong2 w = ld2(ad + x);
+            r0 = add_mod(r0, w.x, m.q);
+            r1 = add_mod(r1, w.y, m.q);
+        }
+        if (gather) {
+            auto rotated = [&](const u32* perm, u64& t0, u64& t1) {
+                const uint2 p = *reinterpret_cast<const uint2*>(perm + x);
+                t0 = lds[p.x & 0x7fffffffu];
+                t1 = lds[p.y & 0x7fffffffu];
+                if (p.x >> 31) t0 = neg_mod(t0, m.q);
+                if (p.y >> 31) t1 = neg_mod(t1, m.q);
+            };
+#pragma unroll
+            for (int i = 0; i < LSA_KSM_MAX_KEYS - 1; i++)
+                if (i < g.n_next) {
+                    u64 t0, t1;
+                    rotated(g.next[i], t0, t1);
+                    r0 = add_mod(r0, t0, m.q);
+                    r1 = add_mod(r1, t1, m.q);
+                }
+            if (tc) {
+                u64 t0, t1;
+                rotated(g.tail, t0, t1);
+                if (g.tail_acc) {
+                    const ulonglong2 w = ld2(tc + x);
+                    t0 = add_mod(t0, w.x, m.q);
+                    t1 = add_mod(t1, w.y, m.q);
+                }
+                st2(tc + x, t0, t1);
+            }
+        }
+        st2(o + x, r0, r1);
+    }
+}
+
 }  // namespace
 
 void launch_ks_mac_multi(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, int n_keys,
@@ -279,6 +364,63 @@ void launch_ext_sum(Context& c, int level, int n_in, const u64* const* in, long 
     for (int tl = 0; tl < T; tl++) g.mod_of[tl] = (unsigned char)c.qp_mod(L, tl);
     ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * 2.0 * T * (n_in + (accumulate ? 2.0 : 1.0)) * batch, s);
     hipLaunchKernelGGL(k_ext_sum, dim3((unsigned)(2 * T * (c.n / (2 * TPB))), (unsigned)batch), dim3(TPB), 0, s, g);
+    LSA_HIP(hipGetLastError());
+}
+
+void launch_bfv_slot_tail(Context& c, int level, const BfvSlotTail& t, const u64* acc, long long sacc, int acc_rpp, const u64* conv,
+                          long long sconv, const u64* x, long long sx, u64* out, long long sout, int batch, hipStream_t s) {
+    if (batch <= 0) return;
+    const int L = level + 1;
+    LSA_REQUIRE(level >= 0 && L <= c.nq, "BFV slot tail: level out of range");
+    LSA_REQUIRE(acc && conv && x && out && acc_rpp >= L, "BFV slot tail: null or short operand");
+    LSA_REQUIRE(t.n_next >= 0 && t.n_next <= LSA_KSM_MAX_KEYS - 1, "BFV slot tail: at most three NEXT rotations");
+    LSA_REQUIRE((t.tail != nullptr) == (t.tail_c0 != nullptr), "BFV slot tail: the TAIL rotation and its accumulator come together");
+    const bool gathers = t.n_next > 0 || t.tail;
+    LSA_REQUIRE(!gathers || c.logn <= LSA_PERM_LDS_MAX_LOGN, "BFV slot tail: the ring's limbs do not fit in LDS");
+    LSA_REQUIRE(c.n >= 2, "BFV slot tail: ring degree too small");
+    BfvSlotTailArgs g{};
+    g.x = x;
+    g.acc = acc;
+    g.conv = conv;
+    g.addend = t.addend;
+    g.out = out;
+    g.tail_c0 = t.tail_c0;
+    for (int i = 0; i < t.n_next; i++) {
+        LSA_REQUIRE(t.next[i] != nullptr, "BFV slot tail: permutation missing");
+        g.next[i] = t.next[i];
+    }
+    g.tail = t.tail;
+    g.kvec = c.pinv_vec(level);
+    g.mods = c.d_mods;
+    g.sx = sx;
+    g.sacc = sacc;
+    g.sconv = sconv;
+    g.sadd = t.s_addend;
+    g.so = sout;
+    g.stail = t.s_tail;
+    g.n_next = t.n_next;
+    g.tail_acc = t.tail_accumulate ? 1 : 0;
+    g.acc_rpp = acc_rpp;
+    g.limbs = L;
+    g.logn = c.logn;
+    // x, acc, conv and out for both polynomials; per c0 row the addend, the tail (read if it accumulates) and 4 bytes per point and table
+    ProfScope ps(c, PROF_ELEMWISE,
+                 8.0 * c.n * batch * L * (8.0 + (t.addend ? 1 : 0) + (t.tail ? (t.tail_accumulate ? 2 : 1) : 0)) +
+                     4.0 * c.n * batch * L * (t.n_next + (t.tail ? 1 : 0)),
+                 s);
+    const size_t lds_bytes = gathers ? (size_t)c.n * sizeof(u64) : 0;
+    if (lds_bytes > 65536) {   // opt in to more than 64 KiB of dynamic LDS, once per device (the attribute is per device)
+        static std::atomic<unsigned long long> raised{0};
+        int dev = 0;
+        LSA_HIP(hipGetDevice(&dev));
+        const unsigned long long bit = 1ull << (dev & 63);
+        if (!(raised.load(std::memory_order_acquire) & bit)) {
+            LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bfv_slot_tail), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024));
+            raised.fetch_or(bit, std::memory_order_release);
+        }
+    }
+    hipLaunchKernelGGL(k_bfv_slot_tail, dim3((unsigned)(2 * L), (unsigned)batch), dim3(LSA_SLOT_TAIL_THREADS), lds_bytes, s, g);
     LSA_HIP(hipGetLastError());
 }
 

@@ -657,6 +657,75 @@ class SlotSumPlan:
         return out
 
 
+def bfv_slot_sum_plan(n, step, count, radix=0, rows=0):
+    """{steps, keyswitches, moddowns, galois_elements} of the BFV slot sum sum_{i<count} rot_cols(y, i*step), y = ct + rot_rows(ct)
+    if rows -- host only (include/lattisense_amd.h: lsa_bfv_slot_sum_plan).  radix: 2, 4 or 0 = the default; elements ascending."""
+    ns, nk, nm, cnt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    args = (int(n), int(step), int(count), int(radix), int(bool(rows)), ctypes.byref(ns), ctypes.byref(nk), ctypes.byref(nm))
+    check(lib().lsa_bfv_slot_sum_plan(*args, None, 0, ctypes.byref(cnt)))
+    g = (ctypes.c_uint64 * max(cnt.value, 1))()
+    check(lib().lsa_bfv_slot_sum_plan(*args, g, cnt.value, ctypes.byref(cnt)))
+    return {"steps": ns.value, "keyswitches": nk.value, "moddowns": nm.value, "galois_elements": [int(e) for e in g[: cnt.value]]}
+
+
+class BfvSlotSumPlan:
+    """out = sum_{i<count} rot_cols(y, i*step), y = ct + rot_rows(ct) if rows, on coefficient-domain BFV ciphertexts at `level`
+    (include/lattisense_amd.h: lsa_bfv_slot_sum_*).  Planning needs no GPU (`.galois_elements`, the counts); the device plan is
+    made by the first run.  gather: None = the library's default, else the tail to run (False: the plain form)."""
+
+    def __init__(self, ctx, level, step, count, radix=0, rows=0):
+        self.ctx, self.level, self.step, self.count, self.rows = ctx, int(level), int(step), int(count), int(bool(rows))
+        self.h = None
+        self.gather = None
+        info = bfv_slot_sum_plan(ctx.n, step, count, radix, rows)
+        self.steps, self.keyswitches, self.moddowns = info["steps"], info["keyswitches"], info["moddowns"]
+        self.galois_elements = info["galois_elements"]
+        self.radix = int(radix)
+
+    def _handle(self):
+        if self.h is None:
+            h = ctypes.c_void_p()   # (a context without a device has no handle: the library refuses, there is no CPU path)
+            check(lib().lsa_bfv_slot_sum_create(self.ctx.h, self.level, self.step, self.count, self.radix, self.rows, ctypes.byref(h)))
+            self.h = h
+            rx, ng = ctypes.c_int(), ctypes.c_int()
+            check(lib().lsa_bfv_slot_sum_info(self.h, None, None, ctypes.byref(rx), None, None, None, None, ctypes.byref(ng), None))
+            g = (ctypes.c_uint64 * max(ng.value, 1))()
+            check(lib().lsa_bfv_slot_sum_galois_elements(self.h, g, ng.value))
+            assert [int(x) for x in g[: ng.value]] == self.galois_elements
+            self.radix = rx.value
+        return self.h
+
+    def gather_in_force(self):
+        ga = ctypes.c_int()
+        check(lib().lsa_bfv_slot_sum_info(self._handle(), None, None, None, None, None, None, None, None, ctypes.byref(ga)))
+        return bool(ga.value)
+
+    def close(self):
+        if self.h:
+            lib().lsa_bfv_slot_sum_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, in_buf, batch, glk, out=None):
+        """in_buf: device [batch][2][level+1][N], coefficient domain; glk: {galois element: key handle}; returns device
+        [batch][2][level+1][N] (out may be in_buf)"""
+        h = self._handle()
+        words = 2 * (self.level + 1) * self.ctx.n
+        if self.gather is not None:
+            check(lib().lsa_bfv_slot_sum_set_gather(h, int(bool(self.gather))))
+        if out is None:
+            out = self.ctx.alloc(max(batch, 1) * words)
+        elts = (ctypes.c_uint64 * max(len(glk), 1))(*glk.keys())
+        keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
+        check(lib().lsa_bfv_slot_sum(self.ctx.h, h, in_buf.ptr, out.ptr, batch, words, words, len(glk), elts, keys, self.ctx.stream))
+        return out
+
+
 BASES = {"chebyshev": 0, "monomial": 1}
 
 
