@@ -466,6 +466,57 @@ int lsa_bfv_slot_sum_set_gather(lsa_bfv_slot_sum_handle plan, int enable);
 int lsa_bfv_slot_sum(lsa_context ctx, lsa_bfv_slot_sum_handle plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
                      long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
 
+/* ---- BFV slot encoder: `batch` host vectors of N integers in [0, t) -- row 0 of the 2 x N/2 slot matrix, then row 1 -- to device
+ * plaintexts, the BFV counterpart of lsa_ckks_encode.  The coefficients are oracle/client.py Client.bfv_encode(values): the values
+ * placed through Lattigo's batching index matrix, then the inverse negacyclic transform mod t.  The lift to the chain is the
+ * pt_mul convention: the coefficient in [0, t) is used as it is at every modulus (t is below every q_j and p_i).
+ * form: 0 = ring-t coefficients [N], words in [0, t): the operand of the plaintext add / sub / multiply entry points that lift;
+ *       1 = pt_mul [level+1][N]: NTT domain, Montgomery form, the operand of lsa_bfv_mult_plain_mul / _mac_plain_mul /
+ *           _rotate_mac_plain_mul;
+ *       2 = extended [level+1+k][N] over Q_level u P: NTT domain, plain residues, the operand of lsa_bfv_linear_transform.
+ * The transform mod t runs on the device, one workgroup per plaintext with the whole plaintext in LDS (k_bfv_encode_t), up to
+ * N = 2^15; above that the image does not fit, the transform runs on the host and the device takes over from the coefficient
+ * row.  out_dev: [batch][rows][N], batch stride sout words (even, at least rows * N), 16-byte aligned.  batch <= 0 is a no-op;
+ * the call returns when the plaintexts are complete on `stream` (the lsa_ckks_encode contract).  Errors are LSA_ERR_ARG before
+ * anything is queued, with a message that begins "lsa_bfv_encode": a CKKS context, level or form out of range, a value >= t,
+ * t >= 2^32 or t not a prime that is 1 mod 2N, a null pointer, out_dev off the 16-byte grid, a short or odd stride. */
+int lsa_bfv_encode(lsa_context ctx, int level, int form, const uint64_t* values, uint64_t* out_dev, long long sout, int batch,
+                   void* stream);
+
+/* ---- BFV linear transform: plaintext matrix x encrypted vector in diagonal form, baby-step / giant-step with double hoisting.
+ * The matrix acts on both rows of the 2 x N/2 slot matrix at once.  period: a power of two that divides N/2; rotations are column
+ * rotations (Galois element 5^r mod 2N).  Diagonal k (taken mod period; negative indices allowed; no two equal mod period) holds one
+ * vector per slot row, values[i][row][period] < t, tiled over that row's N/2 columns:
+ *     out_row[c] = sum_k d_k,row[c mod period] * x_row[(c + k) mod N/2]  mod t,     row = 0, 1
+ * (Lattigo's BGV/BFV LinearTransform).  Terms that mix the two rows (the row swap, element 2N-1) are out of scope: run a second plan on
+ * lsa_bfv_rotate(ct, 2N-1) and add.  The split n1 is lsa_lt_plan_rotations(period, ...)'s; n1 = 0 (fewer than three diagonals) means
+ * every diagonal is a baby step of the single giant step 0.  The plaintext of diagonal k = giant + baby is lsa_bfv_encode form 2 of
+ * rot_{-giant}(d_k) (lsa_bfv_lt_plaintext reads it back).
+ * The words, as tests/bfv_lt_model.py states them on oracle/ckks_bootstrap.py's rotate_ext / lift_ext, mul_plain_ext, add_ext and
+ * moddown: (1) every limb of ct into the NTT domain; (2) baby_b = rotate_ext(x, b) for every baby step, lift_ext for b = 0;
+ * (3) inner_g = sum_b pt_{g+b} . baby_b over Q_level u P; (4) the accumulator starts as inner_0 and every other giant step adds
+ * rotate_ext(moddown(inner_g), g); (5) out = moddown(accumulator), transformed back.  That is (giant steps other than 0) + 1
+ * divisions by P; for three or more diagonals the words of oracle linear_transform(double_hoist=True, rescale=False, plains=...).
+ * They DIFFER from lsa_bfv_rotate_mac_plain_mul on the same diagonals, which divides once per rotation; both decrypt to the same slots.
+ * ct and out are [2][level+1][N] in the coefficient domain; out may not overlap in; batch <= 0 is a no-op.  Errors are LSA_ERR_ARG
+ * before anything is queued, messages beginning "lsa_bfv_lt_create" / "lsa_bfv_linear_transform": a CKKS context, level out of
+ * range, no special prime, a bad period, two indices equal mod period, a value >= t, a missing key (the message names the element),
+ * a key below the plan's level, a plan of another context, out overlapping in, a bad alignment or stride. */
+typedef struct lsa_bfv_lt_st* lsa_bfv_lt;
+int lsa_bfv_lt_create(lsa_context ctx, int level, int period, int n_diag, const int* diag_index, const uint64_t* values,
+                      double bsgs_ratio, void* stream, lsa_bfv_lt* out);
+void lsa_bfv_lt_destroy(lsa_bfv_lt lt);
+/* n1: 0 or the split; n_baby / n_giant: distinct baby and giant steps, step 0 included; rows = level + 1 + k; any pointer may be null */
+int lsa_bfv_lt_info(lsa_bfv_lt lt, int* level, int* period, int* n_diag, int* n1, int* n_baby, int* n_giant, int* rows,
+                    int* n_galois, int* n_moddown);
+int lsa_bfv_lt_diagonals(lsa_bfv_lt lt, int* index_out, int capacity);           /* ascending, reduced mod period */
+int lsa_bfv_lt_galois_elements(lsa_bfv_lt lt, uint64_t* out, int capacity);       /* ascending */
+/* the encoded diagonal at position diag_pos of lsa_bfv_lt_diagonals' order: rows * N words */
+int lsa_bfv_lt_plaintext(lsa_bfv_lt lt, int diag_pos, uint64_t* host_out, long long capacity_words);
+/* galois_elements / keys: n_keys Galois keys at the plan's level or above, in any order and possibly more than needed */
+int lsa_bfv_linear_transform(lsa_context ctx, lsa_bfv_lt lt, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                             long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
+
 /* ---- CKKS polynomial evaluation: p(x) = sum_k coef[k] B_k(x) on a ciphertext, B_k the Chebyshev polynomial T_k (basis 0) or
  * the monomial x^k (basis 1), by a baby-step / giant-step (Paterson-Stockmeyer) plan of depth k = ceil(log2(n_coef)), k >= 1:
  * the powers P_j for j < 2^log_baby and P_(2^j) above them (P_j from P_ceil(j/2) and P_floor(j/2); only those that are used),

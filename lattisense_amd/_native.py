@@ -159,6 +159,14 @@ SIGNATURES = {
     "lsa_bfv_slot_sum_galois_elements": (c_int, [c_vp, c_u64p, c_int]),
     "lsa_bfv_slot_sum_set_gather": (c_int, [c_vp, c_int]),
     "lsa_bfv_slot_sum": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_int, c_u64p, ctypes.POINTER(c_vp), c_vp]),
+    "lsa_bfv_encode": (c_int, [c_vp, c_int, c_int, c_u64p, c_vp, c_ll, c_int, c_vp]),
+    "lsa_bfv_lt_create": (c_int, [c_vp, c_int, c_int, c_int, ctypes.POINTER(c_int), c_u64p, ctypes.c_double, c_vp, ctypes.POINTER(c_vp)]),
+    "lsa_bfv_lt_destroy": (None, [c_vp]),
+    "lsa_bfv_lt_info": (c_int, [c_vp] + [ctypes.POINTER(c_int)] * 9),
+    "lsa_bfv_lt_diagonals": (c_int, [c_vp, ctypes.POINTER(c_int), c_int]),
+    "lsa_bfv_lt_galois_elements": (c_int, [c_vp, c_u64p, c_int]),
+    "lsa_bfv_lt_plaintext": (c_int, [c_vp, c_int, c_u64p, c_ll]),
+    "lsa_bfv_linear_transform": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_int, c_u64p, ctypes.POINTER(c_vp), c_vp]),
     "lsa_lt_plan_rotations": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.c_double, ctypes.POINTER(c_int),
                                       ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int)]),
     "lsa_poly_plan": (c_int, [c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int, c_int, c_int, ctypes.POINTER(c_int),

@@ -1,5 +1,6 @@
 // c_api.hip — extern "C" operator layer (include/lattisense_amd.h).  Every entry point converts C++ exceptions into
 // error codes: nothing throws across the C boundary (the reference does, SURVEY §8b "Errors").
+#include "bfv_encode.h"
 #include "build_flags.h"
 #include "linear_transform.h"
 #include "poly_eval.h"
@@ -754,6 +755,88 @@ int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double 
         if (count) *count = (int)rot.size();
         LSA_REQUIRE(rotations == nullptr || (int)rot.size() <= capacity, "buffer too small");
         if (rotations) std::copy(rot.begin(), rot.end(), rotations);
+    });
+}
+
+// ---- BFV slot encoder and linear transform (bfv_encode.h, linear_transform.h)
+int lsa_bfv_encode(lsa_context ctx, int level, int form, const uint64_t* values, uint64_t* out_dev, long long sout, int batch,
+                   void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(ctx != nullptr, "lsa_bfv_encode: null context");
+        bfv_encode(C(ctx), level, form, values, out_dev, sout, batch, S(stream));
+    });
+}
+struct lsa_bfv_lt_st {
+    BfvLinearTransform* lt;
+    Context* c;
+};
+int lsa_bfv_lt_create(lsa_context ctx, int level, int period, int n_diag, const int* diag_index, const uint64_t* values,
+                      double bsgs_ratio, void* stream, lsa_bfv_lt* out) {
+    return guard([&] {
+        LSA_REQUIRE(ctx != nullptr && out != nullptr, "lsa_bfv_lt_create: null argument");
+        auto h = std::make_unique<lsa_bfv_lt_st>();
+        h->c = &C(ctx);
+        h->lt = bfv_lt_create(*h->c, level, period, n_diag, diag_index, values, bsgs_ratio, S(stream));
+        *out = h.release();
+    });
+}
+void lsa_bfv_lt_destroy(lsa_bfv_lt lt) {
+    if (!lt) return;
+    delete lt->lt;
+    delete lt;
+}
+int lsa_bfv_lt_info(lsa_bfv_lt lt, int* level, int* period, int* n_diag, int* n1, int* n_baby, int* n_giant, int* rows,
+                    int* n_galois, int* n_moddown) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr, "lsa_bfv_lt_info: null plan handle");
+        const BtMatrix& m = lt->lt->m;
+        if (level) *level = m.level;
+        if (period) *period = m.period;
+        if (n_diag) *n_diag = (int)m.ks.size();
+        if (n1) *n1 = m.naive ? 0 : m.n1;
+        if (n_baby) *n_baby = lt->lt->n_baby;
+        if (n_giant) *n_giant = lt->lt->n_giant;
+        if (rows) *rows = m.rows;
+        if (n_galois) *n_galois = (int)lt->lt->galois.size();
+        if (n_moddown) *n_moddown = lt->lt->n_moddown;
+    });
+}
+int lsa_bfv_lt_diagonals(lsa_bfv_lt lt, int* index_out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr && index_out != nullptr, "lsa_bfv_lt_diagonals: null argument");
+        const auto& ks = lt->lt->m.ks;
+        LSA_REQUIRE((int)ks.size() <= capacity, "lsa_bfv_lt_diagonals: capacity: buffer too small");
+        std::copy(ks.begin(), ks.end(), index_out);
+    });
+}
+int lsa_bfv_lt_galois_elements(lsa_bfv_lt lt, uint64_t* out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr && out != nullptr, "lsa_bfv_lt_galois_elements: null argument");
+        const auto& g = lt->lt->galois;
+        LSA_REQUIRE((int)g.size() <= capacity, "lsa_bfv_lt_galois_elements: capacity: buffer too small");
+        std::copy(g.begin(), g.end(), out);
+    });
+}
+int lsa_bfv_lt_plaintext(lsa_bfv_lt lt, int diag_pos, uint64_t* host_out, long long capacity_words) {
+    return guard([&] {
+        LSA_REQUIRE(lt != nullptr && host_out != nullptr, "lsa_bfv_lt_plaintext: null argument");
+        const BtMatrix& m = lt->lt->m;
+        LSA_REQUIRE(diag_pos >= 0 && diag_pos < (int)m.plains.size(), "lsa_bfv_lt_plaintext: diagonal position out of range");
+        LSA_REQUIRE(capacity_words >= (long long)m.rows * lt->c->n, "lsa_bfv_lt_plaintext: capacity: buffer too small for the plaintext's rows");
+        lt->c->use_device();
+        LSA_HIP(hipMemcpy(host_out, m.plains[diag_pos], (size_t)m.rows * lt->c->n * sizeof(u64), hipMemcpyDeviceToHost));
+    });
+}
+int lsa_bfv_linear_transform(lsa_context ctx, lsa_bfv_lt lt, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                             long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(ctx != nullptr, "lsa_bfv_linear_transform: null context");
+        LSA_REQUIRE(lt != nullptr, "lsa_bfv_linear_transform: null plan handle");
+        LSA_REQUIRE(lt->c == &C(ctx), "lsa_bfv_linear_transform: the plan belongs to another context");
+        LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "lsa_bfv_linear_transform: null key argument");
+        std::map<u64, const Key*> g;
+        for (int i = 0; i < n_keys; i++) g[galois_elements[i]] = &K(keys[i], "lsa_bfv_linear_transform");
+        bfv_lt_run(*lt->lt, in, sin, out, sout, batch, g, S(stream));
     });
 }
 

@@ -84,6 +84,13 @@ struct LtEval {
     long long N;
     std::string who;              // prefix of error messages
     bool giant_scatter = false;   // giant-step rotations through the accumulating scatter of the key MAC (ckks_rotate_ext)
+    // BFV (bfv_lt_run): the ciphertext a double-hoisted transform is applied to is held in the coefficient domain as well.
+    // Entrance: its baby-step decomposition reads c1's coefficients (no inverse transform).  Exit: the final division by P
+    // writes coefficients straight to coeff_out (no NTT-domain ModDown followed by inverse transforms).  Both null: CKKS.
+    const u64* c1_coef = nullptr;
+    long long s_coef = 0;
+    u64* coeff_out = nullptr;
+    long long s_coeff_out = 0;
 
     LtEval(Context& c_, DevPool& p, hipStream_t s_, int m_, const std::map<u64, const Key*>& g, const char* who_)
         : c(c_), pool(p), s(s_), m(m_), glk(g), N(c_.n), who(who_) {}
@@ -176,5 +183,27 @@ LinearTransform* lt_create(Context& c, int level, int log_slots, int n_diag, con
                            double pt_scale, double bsgs_ratio, bool double_hoist, hipStream_t s);
 void lt_run(LinearTransform& lt, const u64* in, long long sin, u64* out, long long sout, int batch, bool rescale,
             const std::map<u64, const Key*>& glk, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------ BFV operator plan
+// lsa_bfv_lt_* / lsa_bfv_linear_transform (include/lattisense_amd.h).  The matrix acts on both rows of the 2 x N/2
+// slot matrix at once: diagonal k holds one vector of `period` values per slot row.  Always double-hoisted: the plaintexts are the
+// encoder's extended form (bfv_encode.h, BFV_PT_EXT) of rot_{-giant}(d_k), one allocation for all diagonals.  Fewer than three
+// diagonals: m.naive, m.n1 = period -- every diagonal a baby step of the single giant step 0, the same loop.
+struct BfvLinearTransform {
+    Context& c;
+    BtMatrix m;
+    int n_baby = 0, n_giant = 0, n_moddown = 0;   // distinct baby steps (0 included), giant steps (0 included), divisions by P
+    std::vector<u64> galois;                      // elements of the non-zero rotations, ascending
+    u64* plains_dev = nullptr;                    // [n_diag][m.rows][N]
+    DevPool pool;
+    explicit BfvLinearTransform(Context& ctx) : c(ctx) {}
+    ~BfvLinearTransform();
+};
+// values: host [n_diag][2][period], every word < t
+BfvLinearTransform* bfv_lt_create(Context& c, int level, int period, int n_diag, const int* diag_index, const u64* values,
+                                  double bsgs_ratio, hipStream_t s);
+// in / out [batch][2][level+1][N], coefficient domain; out overlaps no word of in
+void bfv_lt_run(BfvLinearTransform& lt, const u64* in, long long sin, u64* out, long long sout, int batch,
+                const std::map<u64, const Key*>& glk, hipStream_t s);
 
 }  // namespace lsa

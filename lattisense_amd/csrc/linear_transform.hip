@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "bfv_encode.h"
 #include "layout_check.h"
 #include "linear_transform.h"
 
@@ -287,7 +288,7 @@ std::map<int, DCt> LtEval::rotate_many_ext(const DCt& a, const std::vector<int>&
         ptrs.push_back(o.data());
     }
     ckks_rotate_many_ext(c, a.level, a.data(), (int)els.size(), els.data(), keys.data(), ptrs.data(), m, stride(a.level),
-                         stride_ext(a.level), s);
+                         stride_ext(a.level), s, c1_coef, s_coef);
     return out;
 }
 
@@ -399,6 +400,11 @@ DCt LtEval::linear_transform_dh(const DCt& ct, const BtMatrix& mt, bool do_resca
         const u64 e = galois_of(r);
         ckks_rotate_ext(c, ct.level, iq.data(), e, gkey(e), acc.data(), have, m, stride(ct.level), stride_ext(ct.level), s, giant_scatter);
         have = true;
+    }
+    if (coeff_out) {   // BFV exit: the last division leaves in the coefficient domain, in the caller's buffer
+        LSA_REQUIRE(!do_rescale, who + ": a coefficient-domain exit takes no rescale");
+        ckks_moddown_ext(c, ct.level, acc.data(), coeff_out, m, stride_ext(ct.level), s_coeff_out, s, /*coeff_out=*/true);
+        return wrap(coeff_out, ct.level, ct.scale * pt_scale);
     }
     DCt res = moddown(acc);
     return do_rescale ? rescale(res) : res;
@@ -562,6 +568,110 @@ void lt_run(LinearTransform& lt, const u64* in, long long sin, u64* out, long lo
     std::vector<int> all(2 * (y.level + 1));
     for (size_t i = 0; i < all.size(); i++) all[i] = (int)i;
     launch_copy_rows(c, y.data(), ev.stride(y.level), out, sout, (int)all.size(), all.data(), batch, s);
+}
+
+// ------------------------------------------------------------------------------------------------ BFV operator
+BfvLinearTransform::~BfvLinearTransform() {
+    (void)hipSetDevice(c.device);
+    (void)hipDeviceSynchronize();
+    if (plains_dev) (void)hipFree(plains_dev);
+    pool.release();
+}
+
+BfvLinearTransform* bfv_lt_create(Context& c, int level, int period, int n_diag, const int* diag_index, const u64* values,
+                                  double bsgs_ratio, hipStream_t s) {
+    const std::string who = "lsa_bfv_lt_create";
+    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, who + ": context is not BFV");
+    LSA_REQUIRE(level >= 0 && level < c.nq, who + ": level out of range (0.." + std::to_string(c.nq - 1) + ")");
+    LSA_REQUIRE(c.np >= 1, who + ": double hoisting needs a special prime");
+    const int n = c.n / 2;
+    LSA_REQUIRE(period >= 1 && (period & (period - 1)) == 0 && period <= n, who + ": period must be a power of two that divides N/2");
+    LSA_REQUIRE(n_diag >= 1 && diag_index && values, who + ": at least one diagonal");
+    LSA_REQUIRE(bsgs_ratio >= 0, who + ": negative bsgs_ratio");
+    (void)bfv_encode_tables(c, who.c_str());   // refuses a t that has no slots
+    std::map<int, const u64*> mat;   // reduced index -> the caller's [2][period]
+    for (int i = 0; i < n_diag; i++) {
+        const int k = ((diag_index[i] % period) + period) % period;
+        LSA_REQUIRE(!mat.count(k), who + ": diagonal index " + std::to_string(diag_index[i]) + " repeats another modulo the period");
+        const u64* v = values + (size_t)i * 2 * period;
+        for (int x = 0; x < 2 * period; x++)
+            LSA_REQUIRE(v[x] < c.t, who + ": value " + std::to_string(v[x]) + " of diagonal " + std::to_string(diag_index[i]) + " is not below t");
+        mat[k] = v;
+    }
+    auto lt = std::make_unique<BfvLinearTransform>(c);
+    BtMatrix& bm = lt->m;
+    bm.level = level;
+    bm.period = period;
+    bm.pt_scale = 1.0;
+    for (auto& kv : mat) bm.ks.push_back(kv.first);
+    bm.naive = bm.ks.size() < 3;
+    bm.n1 = bm.naive ? period : bsgs_split(bm.ks, period, bsgs_ratio > 0 ? bsgs_ratio : 2.0);
+    bm.rows = bfv_pt_rows(c, level, BFV_PT_EXT);
+    const size_t N = (size_t)c.n, D = bm.ks.size();
+    std::map<int, bool> babies, giants;
+    std::vector<u64> rolled(D * N);   // rot_{-giant}(d_k) of both slot rows, tiled over the N/2 columns
+    for (size_t i = 0; i < D; i++) {
+        const int k = bm.ks[i], giant = (k / bm.n1) * bm.n1;
+        babies[k - giant] = true;
+        giants[giant] = true;
+        const u64* d = mat.at(k);
+        for (int row = 0; row < 2; row++)
+            for (int col = 0; col < n; col++)
+                rolled[i * N + (size_t)row * n + col] = d[(size_t)row * period + (((col - giant) % period) + period) % period];
+    }
+    lt->n_baby = (int)babies.size();
+    lt->n_giant = (int)giants.size();
+    lt->n_moddown = lt->n_giant - (giants.count(0) ? 1 : 0) + 1;
+    std::map<u64, bool> gal;
+    auto gel = [&](int rot) {
+        u64 e = 1;
+        for (int i = 0; i < rot % n; i++) e = e * 5 % (2ULL * c.n);
+        return e;
+    };
+    for (auto& kv : babies)
+        if (kv.first % n) gal[gel(kv.first)] = true;
+    for (auto& kv : giants)
+        if (kv.first % n) gal[gel(kv.first)] = true;
+    for (auto& kv : gal) lt->galois.push_back(kv.first);
+    // nothing has touched the device so far
+    c.use_device();
+    const long long spt = (long long)bm.rows * (long long)N;
+    LSA_HIP(hipMalloc((void**)&lt->plains_dev, D * (size_t)spt * sizeof(u64)));
+    bfv_encode_rows(c, level, BFV_PT_EXT, rolled.data(), lt->plains_dev, spt, (int)D, s);   // the public encoder's path
+    for (size_t i = 0; i < D; i++) bm.plains.push_back(lt->plains_dev + i * (size_t)spt);
+    return lt.release();
+}
+
+void bfv_lt_run(BfvLinearTransform& lt, const u64* in, long long sin, u64* out, long long sout, int batch,
+                const std::map<u64, const Key*>& glk, hipStream_t s) {
+    const std::string who = "lsa_bfv_linear_transform";
+    Context& c = lt.c;
+    const int level = lt.m.level, L = level + 1;
+    const long long N = c.n;
+    for (u64 e : lt.galois) {   // every key before anything is queued
+        auto it = glk.find(e);
+        LSA_REQUIRE(it != glk.end() && it->second && it->second->data, who + ": Galois key for element " + std::to_string(e) + " missing");
+        LSA_REQUIRE(it->second->level >= level, who + ": the Galois key for element " + std::to_string(e) +
+                                                    " was exported at a lower level than the plan");
+    }
+    if (batch <= 0) return;
+    LSA_REQUIRE(in && out, who + ": null argument");
+    const size_t w = 2 * (size_t)L * N;
+    const layout::Span sp_in = layout::span_of(in, sin, w), sp_out = layout::span_of(out, sout, w);
+    LSA_REQUIRE(layout::stride_ok(sp_in, false), who + ": batch stride of in below one ciphertext");
+    LSA_REQUIRE(layout::stride_ok(sp_out, false), who + ": batch stride of out below one ciphertext");
+    LSA_REQUIRE(layout::aligned16(sp_in) && layout::aligned16(sp_out), who + ": in and out must be 16-byte aligned with even batch strides");
+    LSA_REQUIRE(layout::apart(sp_out, sp_in, batch), who + ": out overlaps in");
+    LtEval ev(c, lt.pool, s, batch, glk, who.c_str());
+    ev.giant_scatter = lt_giant_scatter();
+    // entrance: c0 and c1 into the NTT domain once; the decomposition reads c1's coefficients where they lie
+    DCt x = ev.alloc(level, 1.0);
+    launch_ntt(c, in, x.data(), batch, sin, ev.stride(level), 2 * L, ev.rm2(level), false, s);
+    ev.c1_coef = in + (size_t)L * N;
+    ev.s_coef = sin;
+    ev.coeff_out = out;
+    ev.s_coeff_out = sout;
+    (void)ev.linear_transform_dh(x, lt.m, false);
 }
 
 }  // namespace lsa

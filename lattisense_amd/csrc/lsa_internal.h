@@ -146,6 +146,8 @@ struct Context {
         std::vector<u64> I;   // [nq] psi_j^(N/2)
     } cconst;
 
+    std::shared_ptr<const BfvEncodeTables> bfv_enc;   // the slot encoder's host tables (bfv_encode.h), built on first use
+
     // workspace arena: grows on demand, reused across calls (single in-flight operator per context)
     u64* ws = nullptr;
     size_t ws_words = 0;
@@ -493,11 +495,16 @@ void ckks_add_const(Context& c, int level, const u64* ct, long long sct, double 
 void ckks_affine_const(Context& c, int level, const u64* ct, long long sct, double re, double im, double const_scale, double add_re,
                        double add_im, double ct_scale, u64* out, long long so, int batch, bool rescale, hipStream_t s);
 void ckks_lift_ext(Context& c, int level, const u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
+// c1_coef (BFV: the caller holds the ciphertext in the coefficient domain as well): c1's coefficients, read by the decomposition
+// in place of an inverse transform of in's c1 (KsTile::decompose); the same words
 void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
-                          int batch, long long sin, long long sout, hipStream_t s);
+                          int batch, long long sin, long long sout, hipStream_t s, const u64* c1_coef = nullptr, long long s_coef = 0);
 void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, bool accumulate, int batch,
                      long long sin, long long sout, hipStream_t s, bool scatter_mac = false);
-void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
+// coeff_out: the result leaves in the coefficient domain (ks_moddown's COEFF form: every row of `in` leaves the NTT domain once
+// and the tail runs there) -- INTT of the NTT-domain result, residue for residue
+void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s,
+                      bool coeff_out = false);
 // CKKS slot sum  out = sum_{i<count} rot(in, i*step)  (lsa_slot_sum_* / lsa_ckks_slot_sum; plan rule: slot_sum.h).  Every step is one
 // decomposition whose 1..4 rotations stay over Q_level u P (the words of ckks_rotate_ext); the NEXT group is divided by P once with
 // x riding on the ModDown tail's base, the TAIL rotations gather in an extended accumulator divided once at the end.

@@ -638,7 +638,7 @@ void ckks_lift_ext(Context& c, int level, const u64* in, u64* out, int batch, lo
 
 // outs[i] = automorphism_g[i]( (P c0 + ks0, ks1) ), ks = gadget product of c1 with glk[i]; one decomposition for all
 void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
-                          int batch, long long sin, long long sout, hipStream_t s) {
+                          int batch, long long sin, long long sout, hipStream_t s, const u64* c1_coef, long long s_coef) {
     if (n_rot <= 0) return;
     const long long N = c.n;
     const int L = level + 1;
@@ -648,7 +648,7 @@ void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const
     for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* ct = in + (size_t)b0 * sin;
         KsTile t(c, level, nb, ws, st);
-        t.decompose(ct + (long long)L * N, sin);
+        t.decompose(ct + (long long)L * N, sin, c1_coef ? c1_coef + (size_t)b0 * s_coef : nullptr, s_coef);
         for (int i = 0; i < n_rot; i++) {
             if (one_pass) {
                 launch_ks_mac(c, level, ct + (long long)L * N, sin, t.ext, t.s_ext, *glk[i], outs[i] + (size_t)b0 * sout, sout, nb, st,
@@ -692,10 +692,12 @@ void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk
 }
 
 // the rounded division by P: extended ciphertext -> ciphertext [2][L][N].  `in` is clobbered (its P rows leave the NTT domain).
-void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s) {
+void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s,
+                      bool coeff_out) {
     const int L = level + 1;
     for_tiles(c, 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
-        ks_moddown(c, level, in + (size_t)b0 * sin, sin, ws, {.p = out + (size_t)b0 * sout, .sp = sout}, nb, st);
+        ks_moddown(c, level, in + (size_t)b0 * sin, sin, ws,
+                   {.p = out + (size_t)b0 * sout, .sp = sout, .form = coeff_out ? KsOut::COEFF : KsOut::NTT}, nb, st);
     });
 }
 

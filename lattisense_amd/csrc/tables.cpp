@@ -224,4 +224,53 @@ void HostTables::build(int n_, const std::vector<u64>& moduli) {
     }
 }
 
+void BfvEncodeTables::build(int n_, u64 t_) {
+    n = n_;
+    t = t_;
+    logn = 0;
+    while ((1 << logn) < n) logn++;
+    if (n < 2 || (1 << logn) != n) throw std::invalid_argument("ring degree must be a power of two");
+    if (t >> 32) throw std::invalid_argument("plaintext modulus t must be below 2^32 (the encoder's words are 32-bit)");
+    if (t < 3 || (t - 1) % (2 * (u64)n) != 0) throw std::invalid_argument("plaintext modulus t must be 1 mod 2N for slot encoding");
+    if (!is_prime64(t)) throw std::invalid_argument("plaintext modulus t must be prime for slot encoding");
+    const u64 m = 2 * (u64)n;
+    index.assign(n, 0);
+    u64 pos = 1;
+    for (int i = 0; i < n / 2; i++) {
+        index[i] = bit_reverse((unsigned)((pos - 1) >> 1), logn);
+        index[i | (n >> 1)] = bit_reverse((unsigned)((m - pos - 1) >> 1), logn);
+        pos = pos * 5 % m;
+    }
+    const u64 psi_inv = inv_mod(pow_mod(smallest_primitive_root(t), (t - 1) / m, t), t);
+    psiinv.assign(2 * (size_t)n, 0);
+    u64 pw = 1;
+    for (int j = 0; j < n; j++) {
+        const unsigned x = bit_reverse((unsigned)j, logn);
+        psiinv[2 * x] = (uint32_t)pw;
+        psiinv[2 * x + 1] = (uint32_t)((pw << 32) / t);
+        pw = mul_mod_host(pw, psi_inv, t);
+    }
+    const u64 ni = inv_mod((u64)n % t, t);
+    ninv = (uint32_t)ni;
+    ninv_shoup = (uint32_t)((ni << 32) / t);
+}
+
+void BfvEncodeTables::encode(const u64* values, u64* coef) const {
+    for (int i = 0; i < n; i++) coef[index[i]] = values[i];
+    int tt = 1;
+    for (int mm = n; mm > 1; mm >>= 1) {   // Gentleman-Sande, bit-reversed in, natural out (Lattigo ring/ntt.go InvNTT)
+        const int h = mm >> 1;
+        for (int i = 0, j1 = 0; i < h; i++, j1 += 2 * tt) {
+            const u64 f = psiinv[2 * (size_t)(h + i)];
+            for (int j = j1; j < j1 + tt; j++) {
+                const u64 u = coef[j], v = coef[j + tt];
+                coef[j] = (u + v) % t;
+                coef[j + tt] = mul_mod_host((u + t - v) % t, f, t);
+            }
+        }
+        tt <<= 1;
+    }
+    for (int j = 0; j < n; j++) coef[j] = mul_mod_host(coef[j], ninv, t);
+}
+
 }  // namespace lsa

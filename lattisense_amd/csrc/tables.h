@@ -43,6 +43,23 @@ struct HostTables {
     void build(int n_, const std::vector<u64>& moduli);
 };
 
+// BFV slot encoder (bfv_encode.h): the tables of the inverse negacyclic transform mod the plaintext modulus t, 32-bit words.
+// index: Lattigo's batching index matrix -- slot i of the 2 x N/2 slot matrix (row 0 first) is evaluation point index[i] of the
+// transform.  psiinv: {w, floor(w 2^32 / t)} with w = psi^-brv(x), psi = g^((t-1)/2N) for the smallest generator g of Z_t^* (the
+// choice HostTables::build makes for the chain primes); ninv = N^-1 mod t the same way.
+struct BfvEncodeTables {
+    int n = 0, logn = 0;
+    u64 t = 0;
+    std::vector<uint32_t> index;    // [n]
+    std::vector<uint32_t> psiinv;   // [n][2]
+    uint32_t ninv = 0, ninv_shoup = 0;
+    // throws std::invalid_argument (the message names what is wrong with t): t >= 2^32, t not 1 mod 2N, t not prime
+    void build(int n_, u64 t_);
+    // coef[x] in [0, t): the inverse transform of the N slot values (each < t) placed through `index` -- the host twin of
+    // k_bfv_encode_t, used above its LDS limit and by the tests of the tables
+    void encode(const u64* values, u64* coef) const;
+};
+
 inline u64 to_mont_host(u64 a, u64 q) { return (u64)(((unsigned __int128)a << 64) % q); }
 inline u64 shoup_quotient_host(u64 a, u64 q) { return (u64)(((unsigned __int128)a << 64) / q); }
 

@@ -246,6 +246,22 @@ class DeviceContext:
                                     float(scale), out.ptr, w, batch, self.stream))
         return out
 
+    def bfv_pt_rows(self, level, form):
+        """rows of a BFV plaintext: form 0 ring-t coefficients (1), 1 pt_mul (level+1), 2 extended over Q_level u P (level+1+k)"""
+        return {0: 1, 1: level + 1, 2: level + 1 + len(self.p)}[form]
+
+    def bfv_encode(self, level, form, values, out=None, sout=None):
+        """values: [batch][N] integers in [0, t), row 0 of the 2 x N/2 slot matrix then row 1 -> device plaintexts
+        [batch][rows][N] (include/lattisense_amd.h: lsa_bfv_encode); sout: batch stride in words (default: compact)"""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1, self.n))
+        batch = v.shape[0]
+        w = self.bfv_pt_rows(level, form) * self.n
+        sout = w if sout is None else sout
+        if out is None:
+            out = self.alloc(max(batch, 1) * max(sout, w))
+        check(lib().lsa_bfv_encode(self.h, level, form, v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), out.ptr, sout, batch, self.stream))
+        return out
+
     def ckks_mult_plain(self, level, ct, pt, batch, rescale=False, out=None, spt=None):
         """ct x pt on both polynomials (then rescaled); spt: the plaintexts' batch stride in words (0: one for the whole batch)"""
         out, so = self._plain_out(level, batch, rescale, out)
@@ -589,6 +605,105 @@ class LinearTransformPlan:
         keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
         check(lib().lsa_ckks_linear_transform(self.ctx.h, self.h, in_buf.ptr, out.ptr, batch, 2 * (self.level + 1) * n, 2 * lo * n,
                                               int(bool(rescale)), len(glk), elts, keys, self.ctx.stream))
+        return out
+
+
+def bfv_lt_plan(n, period, diag_index, ratio=0.0):
+    """{n1, rotations, galois_elements, babies, giants, moddowns} of the BFV linear transform over these diagonals at ring degree
+    n -- host only: the split of plan_rotations (lsa_lt_plan_rotations), n1 = 0 meaning every diagonal is a baby step of giant 0"""
+    assert period >= 1 and period & (period - 1) == 0 and (n // 2) % period == 0, "period: a power of two that divides N/2"
+    n1, rot = plan_rotations(period, diag_index, ratio)
+    ks = sorted({int(k) % period for k in diag_index})
+    split = n1 if n1 else period
+    giants = sorted({(k // split) * split for k in ks})
+    babies = sorted({k % split for k in ks})
+    return {"n1": n1, "rotations": rot, "galois_elements": sorted(pow(5, r, 2 * n) for r in rot), "babies": babies, "giants": giants,
+            "moddowns": len([g for g in giants if g]) + 1}
+
+
+class BfvLinearTransformPlan:
+    """A plaintext matrix in diagonal form over both rows of the BFV slot matrix, encoded for ciphertexts at `level`
+    (include/lattisense_amd.h: lsa_bfv_lt_*).  diags: {k: integer array [2][period] (one vector per slot row) or [period] (the
+    same vector on both rows)}, values in [0, t): out_row[c] = sum_k d_k,row[c mod period] * x_row[(c + k) mod N/2] mod t.
+    Planning needs no GPU (`.n1`, `.rotations`, `.galois_elements`); the device plan is created on first use."""
+
+    def __init__(self, ctx, level, diags, period=None, ratio=0.0):
+        self.ctx, self.level, self.ratio = ctx, level, ratio
+        self.h = None
+        ks = list(diags)
+        assert ks, "at least one diagonal"
+        first = np.asarray(diags[ks[0]])
+        self.period = int(first.shape[-1]) if period is None else int(period)
+        vals = np.empty((len(ks), 2, self.period), dtype=np.uint64)
+        for i, k in enumerate(ks):
+            d = np.asarray(diags[k], dtype=np.uint64)
+            assert d.shape in ((self.period,), (2, self.period)), "a diagonal is [period] or [2][period]"
+            vals[i] = d
+        self._index, self._values = [int(k) for k in ks], vals
+        info = bfv_lt_plan(ctx.n, self.period, self._index, ratio)
+        self.n1, self.rotations, self.galois_elements = info["n1"], info["rotations"], info["galois_elements"]
+        self.babies, self.giants, self.moddowns = info["babies"], info["giants"], info["moddowns"]
+        self.diagonals = sorted(k % self.period for k in self._index)
+
+    def _handle(self):
+        if self.h is None:
+            idx = (ctypes.c_int * len(self._index))(*self._index)
+            h = ctypes.c_void_p()
+            check(lib().lsa_bfv_lt_create(self.ctx.h, self.level, self.period, len(self._index), idx,
+                                          self._values.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(self.ratio), self.ctx.stream,
+                                          ctypes.byref(h)))
+            self.h = h
+            rows = ctypes.c_int()
+            check(lib().lsa_bfv_lt_info(self.h, None, None, None, None, None, None, ctypes.byref(rows), None, None))
+            self.rows = rows.value
+        return self.h
+
+    def info(self):
+        """the device plan's own counts (lsa_bfv_lt_info) and lists"""
+        h = self._handle()
+        v = [ctypes.c_int() for _ in range(9)]
+        check(lib().lsa_bfv_lt_info(h, *[ctypes.byref(x) for x in v]))
+        names = ("level", "period", "n_diag", "n1", "n_baby", "n_giant", "rows", "n_galois", "n_moddown")
+        out = {k: x.value for k, x in zip(names, v)}
+        kk = (ctypes.c_int * out["n_diag"])()
+        check(lib().lsa_bfv_lt_diagonals(h, kk, out["n_diag"]))
+        g = (ctypes.c_uint64 * max(out["n_galois"], 1))()
+        check(lib().lsa_bfv_lt_galois_elements(h, g, out["n_galois"]))
+        out["diagonals"], out["galois_elements"] = [int(k) for k in kk], [int(x) for x in g[: out["n_galois"]]]
+        return out
+
+    def close(self):
+        if self.h:
+            lib().lsa_bfv_lt_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def oracle_plains(self):
+        """{k (reduced mod period): extended plaintext [rows][N]}: what tests/bfv_lt_model.py linear_transform takes as `plains`"""
+        h = self._handle()
+        out = {}
+        for i, k in enumerate(self.diagonals):
+            pt = np.empty((self.rows, self.ctx.n), dtype=np.uint64)
+            check(lib().lsa_bfv_lt_plaintext(h, i, pt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), pt.size))
+            out[k] = pt
+        return out
+
+    def run(self, in_buf, batch, glk, out=None, sin=None, sout=None):
+        """in_buf: device [batch][2][level+1][N], coefficient domain; glk: {galois element: key handle}; returns the device
+        output, the same shape (sin / sout: batch strides in words, default compact)"""
+        w = 2 * (self.level + 1) * self.ctx.n
+        sin, sout = (w if sin is None else sin), (w if sout is None else sout)
+        h = self._handle()
+        if out is None:
+            out = self.ctx.alloc(max(batch, 1) * max(sout, w))
+        elts = (ctypes.c_uint64 * max(len(glk), 1))(*glk.keys())
+        keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
+        check(lib().lsa_bfv_linear_transform(self.ctx.h, h, in_buf.ptr, out.ptr, batch, sin, sout, len(glk), elts, keys, self.ctx.stream))
         return out
 
 
