@@ -284,12 +284,6 @@ struct Bootstrap {
             natural_scale = out_scale;
         }
         std::map<u64, bool> gal;
-        auto gel = [&](int rot) {
-            u64 e = 1;
-            const u64 m = 2ULL * c.n;
-            for (int i = 0; i < rot % n; i++) e = e * 5 % m;
-            return e;
-        };
         // one matrix -> plaintexts (diagonals of period `period`, tiled over the N/2 slots) + the rotations it needs
         auto make_one = [&](const Diags& mat, int level, int period) {
             return lt_make_matrix(c, mat, level, period, (double)c.T.mod[level], 2.0, double_hoist, s, owned, gal, "bootstrap");
@@ -298,7 +292,7 @@ struct Bootstrap {
         if (sparse) {
             p1 = make_one(dp1, top_level - (int)mc.size(), 2 * ns);
             p2 = make_one(dp2, top_level - (int)mc.size(), 2 * ns);
-            for (int i = log_slots; i < logn_ring - 1; i++) gal[gel(1 << i)] = true;   // SubSum
+            for (int i = log_slots; i < logn_ring - 1; i++) gal[galois_of_rotation(1 << i, c.n)] = true;   // SubSum: 2^i < N/2
         }
         for (size_t i = 0; i < ms.size(); i++) stc.push_back(make_one(ms[i], stc_level - (int)i, sparse && i == 0 ? 2 * ns : ns));
         gal[2ULL * c.n - 1] = true;
@@ -347,7 +341,7 @@ namespace {
 struct Eval : CtEval {
     Bootstrap& bt;
 
-    Eval(Context& c_, Bootstrap& b, hipStream_t s_, int m_, const Key& rlk_, const std::map<u64, const Key*>& g)
+    Eval(Context& c_, Bootstrap& b, hipStream_t s_, int m_, const Key& rlk_, const GaloisKeys& g)
         : CtEval(c_, b.pool, s_, m_, rlk_, g, "bootstrap"), bt(b) {}
     DCt conj(const DCt& a) {
         const u64 e = 2ULL * c.n - 1;
@@ -480,7 +474,7 @@ void bootstrap_destroy(Bootstrap* b) { delete b; }
 
 // in: [batch][2][1][N] level-0 ciphertexts at the plan's input scale; out: [batch][2][out_level+1][N]
 void bootstrap_run(Bootstrap& bt, const u64* in, long long sin, u64* out, long long sout, int batch, const Key& rlk,
-                   const std::map<u64, const Key*>& glk, const Key* swk_dts, const Key* swk_std, hipStream_t s) {
+                   const GaloisKeys& glk, const Key* swk_dts, const Key* swk_std, hipStream_t s) {
     Context& c = bt.c;
     c.use_device();
     Eval ev(c, bt, s, batch, rlk, glk);

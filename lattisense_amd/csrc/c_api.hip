@@ -51,6 +51,43 @@ static const Key& K(lsa_key k, const char* who = nullptr) {
 }
 static hipStream_t S(void* s) { return (hipStream_t)s; }
 
+// ---- plan handles.  The operators that work through a plan (bootstrap, the two linear transforms, the two slot sums, polynomial
+// evaluation) hand out one kind of handle: the plan with its deleter and the context it was made on.  The public header keeps a
+// distinct opaque type per operator; each derives from PlanHandle.  Every entry point keeps its own message texts.
+template <typename T>
+struct PlanHandle {
+    std::unique_ptr<T, void (*)(T*)> plan;
+    Context* c;
+};
+template <typename T>
+static void plan_delete(T* p) {
+    delete p;
+}
+template <typename H, typename T>
+static void make_plan(H** out, Context& c, T* plan, void (*destroy)(T*) = plan_delete<T>) {
+    std::unique_ptr<T, void (*)(T*)> owned(plan, destroy);
+    *out = new H{{std::move(owned), &c}};
+}
+template <typename H>
+static auto& P(H* h, const char* null_msg) {   // the plan of a handle
+    LSA_REQUIRE(h != nullptr, null_msg);
+    return *h->plan;
+}
+template <typename H>
+static auto& P(H* h, lsa_context ctx, const char* null_msg, const char* other_ctx_msg) {   // ... that an operator runs on ctx
+    LSA_REQUIRE(h != nullptr, null_msg);
+    LSA_REQUIRE(h->c == &C(ctx), other_ctx_msg);
+    return *h->plan;
+}
+template <typename V, typename O>
+static void copy_out(const V& v, O* out, int capacity, const char* too_small) {
+    LSA_REQUIRE((int)v.size() <= capacity, too_small);
+    std::copy(v.begin(), v.end(), out);
+}
+static GaloisKeys G(int n, const uint64_t* elements, const lsa_key* keys, const char* who = nullptr) {
+    return GaloisKeys(n, elements, keys, [&](lsa_key k) { return &K(k, who); });
+}
+
 extern "C" {
 
 const char* lsa_last_error(void) { return last_error().c_str(); }
@@ -168,8 +205,6 @@ int lsa_event_destroy(lsa_context ctx, void* ev) {
 size_t lsa_key_bytes(lsa_context ctx, int key_level) {
     return ctx ? key_layout(ctx->ctx, key_level).words * sizeof(u64) : 0;
 }
-
-struct lsa_key_fp_owner;   // (see lsa_key_st::fp_owned)
 
 int lsa_key_upload(lsa_context ctx, const uint64_t* compact_host, int key_level, void* stream, lsa_key* out) {
     return guard([&] {
@@ -528,23 +563,19 @@ int lsa_bfv_rotate_mac_plain_mul(lsa_context ctx, int level, const uint64_t* in,
     });
 }
 
+
 // ---- CKKS bootstrapping
-struct lsa_bootstrap_st {
-    Bootstrap* b;
-    Context* c;
-};
+struct lsa_bootstrap_st : PlanHandle<Bootstrap> {};
 int lsa_bootstrap_create_ex(lsa_context ctx, int cts_depth, int stc_depth, int k, int double_angle, double message_ratio,
                             double in_scale, double out_scale, int log_slots, int sine_deg, int arcsine_deg, void* stream,
                             lsa_bootstrap* out) {
     return guard([&] {
         LSA_REQUIRE(out != nullptr, "null argument");
         LSA_REQUIRE(k >= 1 && double_angle >= 0 && double_angle <= 8 && message_ratio > 0 && in_scale > 0, "bad bootstrap parameters");
-        auto h = std::make_unique<lsa_bootstrap_st>();
-        h->c = &C(ctx);
-        LSA_REQUIRE(log_slots >= 0 && (log_slots == 0 || (2 << log_slots) <= C(ctx).n), "bad slot count");
-        h->b = bootstrap_create(C(ctx), cts_depth, stc_depth, k, double_angle, message_ratio, in_scale, out_scale, log_slots, S(stream),
-                                sine_deg, arcsine_deg);
-        *out = h.release();
+        Context& c = C(ctx);
+        LSA_REQUIRE(log_slots >= 0 && (log_slots == 0 || (2 << log_slots) <= c.n), "bad slot count");
+        make_plan(out, c, bootstrap_create(c, cts_depth, stc_depth, k, double_angle, message_ratio, in_scale, out_scale, log_slots, S(stream),
+                                           sine_deg, arcsine_deg), bootstrap_destroy);
     });
 }
 int lsa_bootstrap_create(lsa_context ctx, int cts_depth, int stc_depth, int k, int double_angle, double message_ratio,
@@ -556,62 +587,52 @@ int lsa_bootstrap_create(lsa_context ctx, int cts_depth, int stc_depth, int k, i
 // correction (0: none); either output pointer may be null to query the counts
 int lsa_bootstrap_evalmod_constants(lsa_bootstrap b, int* n_cheb, double* cheb, int* n_asin, double* asin_coef) {
     return guard([&] {
-        LSA_REQUIRE(b != nullptr, "null bootstrap handle");
-        const auto& c = bootstrap_chebyshev(*b->b);
-        const auto& a = bootstrap_arcsine(*b->b);
+        const Bootstrap& bt = P(b, "null bootstrap handle");
+        const auto& c = bootstrap_chebyshev(bt);
+        const auto& a = bootstrap_arcsine(bt);
         if (n_cheb) *n_cheb = (int)c.size();
         if (n_asin) *n_asin = (int)a.size();
         if (cheb) std::copy(c.begin(), c.end(), cheb);
         if (asin_coef) std::copy(a.begin(), a.end(), asin_coef);
     });
 }
-void lsa_bootstrap_destroy(lsa_bootstrap b) {
-    if (!b) return;
-    bootstrap_destroy(b->b);
-    delete b;
-}
+void lsa_bootstrap_destroy(lsa_bootstrap b) { delete b; }
 int lsa_bootstrap_info(lsa_bootstrap b, int* out_level, double* out_scale, int* n_galois, int* n_matrices, int* n_cts,
                        int* sparse) {
     return guard([&] {
-        LSA_REQUIRE(b != nullptr, "null bootstrap handle");
-        if (out_level) *out_level = bootstrap_out_level(*b->b);
-        if (out_scale) *out_scale = bootstrap_out_scale(*b->b);
-        if (n_galois) *n_galois = (int)bootstrap_galois(*b->b).size();
-        if (n_matrices) *n_matrices = bootstrap_matrices(*b->b);
-        if (n_cts) *n_cts = bootstrap_cts_matrices(*b->b);
-        if (sparse) *sparse = bootstrap_is_sparse(*b->b) ? 1 : 0;
+        const Bootstrap& bt = P(b, "null bootstrap handle");
+        if (out_level) *out_level = bootstrap_out_level(bt);
+        if (out_scale) *out_scale = bootstrap_out_scale(bt);
+        if (n_galois) *n_galois = (int)bootstrap_galois(bt).size();
+        if (n_matrices) *n_matrices = bootstrap_matrices(bt);
+        if (n_cts) *n_cts = bootstrap_cts_matrices(bt);
+        if (sparse) *sparse = bootstrap_is_sparse(bt) ? 1 : 0;
     });
 }
 int lsa_bootstrap_galois_elements(lsa_bootstrap b, uint64_t* out, int capacity) {
     return guard([&] {
         LSA_REQUIRE(b != nullptr && out != nullptr, "null argument");
-        const auto& g = bootstrap_galois(*b->b);
-        LSA_REQUIRE((int)g.size() <= capacity, "buffer too small");
-        for (size_t i = 0; i < g.size(); i++) out[i] = g[i];
+        copy_out(bootstrap_galois(*b->plan), out, capacity, "buffer too small");
     });
 }
 int lsa_bootstrap_chebyshev(lsa_bootstrap b, double* out32) {
     return guard([&] {
         LSA_REQUIRE(b != nullptr && out32 != nullptr, "null argument");
-        const auto& cf = bootstrap_chebyshev(*b->b);
+        const auto& cf = bootstrap_chebyshev(*b->plan);
         LSA_REQUIRE(cf.size() <= 32, "more than 32 Chebyshev coefficients: use lsa_bootstrap_evalmod_constants");
         for (size_t i = 0; i < 32; i++) out32[i] = i < cf.size() ? cf[i] : 0.0;
     });
 }
 int lsa_bootstrap_matrix_info(lsa_bootstrap b, int index, int* level, int* n1, int* n_diagonals, int* diagonals, int capacity) {
     return guard([&] {
-        LSA_REQUIRE(b != nullptr, "null bootstrap handle");
         int lv, n1v;
         const std::vector<int>* ks;
         const std::vector<u64*>* pl;
-        bootstrap_matrix(*b->b, index, &lv, &n1v, &ks, &pl);
+        bootstrap_matrix(P(b, "null bootstrap handle"), index, &lv, &n1v, &ks, &pl);
         if (level) *level = lv;
         if (n1) *n1 = n1v;
         if (n_diagonals) *n_diagonals = (int)ks->size();
-        if (diagonals) {
-            LSA_REQUIRE((int)ks->size() <= capacity, "buffer too small");
-            for (size_t i = 0; i < ks->size(); i++) diagonals[i] = (*ks)[i];
-        }
+        if (diagonals) copy_out(*ks, diagonals, capacity, "buffer too small");
     });
 }
 int lsa_bootstrap_plaintext(lsa_bootstrap b, int matrix, int diag_pos, uint64_t* host_out) {
@@ -620,7 +641,7 @@ int lsa_bootstrap_plaintext(lsa_bootstrap b, int matrix, int diag_pos, uint64_t*
         int lv, n1v;
         const std::vector<int>* ks;
         const std::vector<u64*>* pl;
-        bootstrap_matrix(*b->b, matrix, &lv, &n1v, &ks, &pl);
+        bootstrap_matrix(*b->plan, matrix, &lv, &n1v, &ks, &pl);
         LSA_REQUIRE(diag_pos >= 0 && diag_pos < (int)pl->size(), "diagonal position out of range");
         b->c->use_device();
         // the rows at q_0..q_level only, whatever the plan keeps behind them: what this entry point has always written
@@ -633,7 +654,7 @@ int lsa_bootstrap_plaintext_ext(lsa_bootstrap b, int matrix, int diag_pos, uint6
         int lv, n1v, rows = 0;
         const std::vector<int>* ks;
         const std::vector<u64*>* pl;
-        bootstrap_matrix(*b->b, matrix, &lv, &n1v, &ks, &pl, &rows);
+        bootstrap_matrix(*b->plan, matrix, &lv, &n1v, &ks, &pl, &rows);
         LSA_REQUIRE(diag_pos >= 0 && diag_pos < (int)pl->size(), "diagonal position out of range");
         LSA_REQUIRE(capacity_words >= (long long)rows * b->c->n, "buffer too small for the plaintext's rows (lsa_bootstrap_plaintext_rows)");
         b->c->use_device();
@@ -646,7 +667,7 @@ int lsa_bootstrap_plaintext_rows(lsa_bootstrap b, int matrix, int* rows) {
         int lv, n1v;
         const std::vector<int>* ks;
         const std::vector<u64*>* pl;
-        bootstrap_matrix(*b->b, matrix, &lv, &n1v, &ks, &pl, rows);
+        bootstrap_matrix(*b->plan, matrix, &lv, &n1v, &ks, &pl, rows);
     });
 }
 int lsa_ckks_bootstrap(lsa_context ctx, lsa_bootstrap b, const uint64_t* in, uint64_t* out, int batch, long long sin, long long sout,
@@ -654,70 +675,56 @@ int lsa_ckks_bootstrap(lsa_context ctx, lsa_bootstrap b, const uint64_t* in, uin
                        void* stream) {
     return guard([&] {
         LSA_REQUIRE(b != nullptr && in != nullptr && out != nullptr && rlk != nullptr, "null argument");
-        LSA_REQUIRE(b->c == &C(ctx), "bootstrap plan belongs to another context");
+        Bootstrap& bt = P(b, ctx, "null argument", "bootstrap plan belongs to another context");
         LSA_REQUIRE((swk_dts == nullptr) == (swk_std == nullptr), "swk_dts and swk_std come as a pair");
-        std::map<u64, const Key*> g;
-        for (int i = 0; i < n_glk; i++) g[glk_elements[i]] = &K(glk[i]);
-        bootstrap_run(*b->b, in, sin, out, sout, batch, K(rlk), g, swk_dts ? &K(swk_dts) : nullptr,
-                      swk_std ? &K(swk_std) : nullptr, S(stream));
+        const GaloisKeys g = G(n_glk, glk_elements, glk);
+        bootstrap_run(bt, in, sin, out, sout, batch, K(rlk), g, swk_dts ? &K(swk_dts) : nullptr, swk_std ? &K(swk_std) : nullptr,
+                      S(stream));
     });
 }
 
 // ---- CKKS linear transform (linear_transform.hip)
-struct lsa_linear_transform_st {
-    LinearTransform* lt;
-    Context* c;
-};
+struct lsa_linear_transform_st : PlanHandle<LinearTransform> {};
 int lsa_lt_create(lsa_context ctx, int level, int log_slots, int n_diag, const int* diag_index, const double* values,
                   double pt_scale, double bsgs_ratio, int double_hoist, void* stream, lsa_linear_transform* out) {
     return guard([&] {
         LSA_REQUIRE(out != nullptr, "null argument");
-        auto h = std::make_unique<lsa_linear_transform_st>();
-        h->c = &C(ctx);
-        h->lt = lt_create(*h->c, level, log_slots, n_diag, diag_index, values, pt_scale, bsgs_ratio, double_hoist != 0, S(stream));
-        *out = h.release();
+        Context& c = C(ctx);
+        make_plan(out, c, lt_create(c, level, log_slots, n_diag, diag_index, values, pt_scale, bsgs_ratio, double_hoist != 0, S(stream)));
     });
 }
-void lsa_lt_destroy(lsa_linear_transform lt) {
-    if (!lt) return;
-    delete lt->lt;
-    delete lt;
-}
+void lsa_lt_destroy(lsa_linear_transform lt) { delete lt; }
 int lsa_lt_info(lsa_linear_transform lt, int* level, int* period, int* n_diag, int* n1, int* rows, int* n_galois,
                 int* double_hoist, double* pt_scale) {
     return guard([&] {
-        LSA_REQUIRE(lt != nullptr, "null linear-transform handle");
-        const BtMatrix& m = lt->lt->m;
+        const LinearTransform& p = P(lt, "null linear-transform handle");
+        const BtMatrix& m = p.m;
         if (level) *level = m.level;
         if (period) *period = m.period;
         if (n_diag) *n_diag = (int)m.ks.size();
         if (n1) *n1 = m.naive ? 0 : m.n1;
         if (rows) *rows = m.rows;
-        if (n_galois) *n_galois = (int)lt->lt->galois.size();
-        if (double_hoist) *double_hoist = lt->lt->double_hoist ? 1 : 0;
+        if (n_galois) *n_galois = (int)p.galois.size();
+        if (double_hoist) *double_hoist = p.double_hoist ? 1 : 0;
         if (pt_scale) *pt_scale = m.pt_scale;
     });
 }
 int lsa_lt_diagonals(lsa_linear_transform lt, int* index_out, int capacity) {
     return guard([&] {
         LSA_REQUIRE(lt != nullptr && index_out != nullptr, "null argument");
-        const auto& ks = lt->lt->m.ks;
-        LSA_REQUIRE((int)ks.size() <= capacity, "buffer too small");
-        std::copy(ks.begin(), ks.end(), index_out);
+        copy_out(lt->plan->m.ks, index_out, capacity, "buffer too small");
     });
 }
 int lsa_lt_galois_elements(lsa_linear_transform lt, uint64_t* out, int capacity) {
     return guard([&] {
         LSA_REQUIRE(lt != nullptr && out != nullptr, "null argument");
-        const auto& g = lt->lt->galois;
-        LSA_REQUIRE((int)g.size() <= capacity, "buffer too small");
-        std::copy(g.begin(), g.end(), out);
+        copy_out(lt->plan->galois, out, capacity, "buffer too small");
     });
 }
 int lsa_lt_plaintext(lsa_linear_transform lt, int diag_pos, uint64_t* host_out, long long capacity_words) {
     return guard([&] {
         LSA_REQUIRE(lt != nullptr && host_out != nullptr, "null argument");
-        const BtMatrix& m = lt->lt->m;
+        const BtMatrix& m = lt->plan->m;
         LSA_REQUIRE(diag_pos >= 0 && diag_pos < (int)m.plains.size(), "diagonal position out of range");
         LSA_REQUIRE(capacity_words >= (long long)m.rows * lt->c->n, "buffer too small for the plaintext's rows (lsa_lt_info)");
         lt->c->use_device();
@@ -728,13 +735,10 @@ int lsa_ckks_linear_transform(lsa_context ctx, lsa_linear_transform lt, const ui
                               long long sin, long long sout, int rescale, int n_glk, const uint64_t* glk_elements,
                               const lsa_key* glk, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(lt != nullptr, "null linear-transform handle");
-        LSA_REQUIRE(lt->c == &C(ctx), "linear-transform plan belongs to another context");
+        LinearTransform& p = P(lt, ctx, "null linear-transform handle", "linear-transform plan belongs to another context");
         if (batch <= 0) return;
         LSA_REQUIRE(in != nullptr && out != nullptr && n_glk >= 0 && (n_glk == 0 || (glk_elements && glk)), "null argument");
-        std::map<u64, const Key*> g;
-        for (int i = 0; i < n_glk; i++) g[glk_elements[i]] = &K(glk[i]);
-        lt_run(*lt->lt, in, sin, out, sout, batch, rescale != 0, g, S(stream));
+        lt_run(p, in, sin, out, sout, batch, rescale != 0, G(n_glk, glk_elements, glk), S(stream));
     });
 }
 int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double bsgs_ratio, int* n1, int* rotations,
@@ -753,8 +757,7 @@ int lsa_lt_plan_rotations(int period, int n_diag, const int* diag_index, double 
         const int split = lt_plan(ks, period, bsgs_ratio > 0 ? bsgs_ratio : 2.0, rot);
         if (n1) *n1 = split;
         if (count) *count = (int)rot.size();
-        LSA_REQUIRE(rotations == nullptr || (int)rot.size() <= capacity, "buffer too small");
-        if (rotations) std::copy(rot.begin(), rot.end(), rotations);
+        if (rotations) copy_out(rot, rotations, capacity, "buffer too small");
     });
 }
 
@@ -766,61 +769,48 @@ int lsa_bfv_encode(lsa_context ctx, int level, int form, const uint64_t* values,
         bfv_encode(C(ctx), level, form, values, out_dev, sout, batch, S(stream));
     });
 }
-struct lsa_bfv_lt_st {
-    BfvLinearTransform* lt;
-    Context* c;
-};
+struct lsa_bfv_lt_st : PlanHandle<BfvLinearTransform> {};
 int lsa_bfv_lt_create(lsa_context ctx, int level, int period, int n_diag, const int* diag_index, const uint64_t* values,
                       double bsgs_ratio, void* stream, lsa_bfv_lt* out) {
     return guard([&] {
         LSA_REQUIRE(ctx != nullptr && out != nullptr, "lsa_bfv_lt_create: null argument");
-        auto h = std::make_unique<lsa_bfv_lt_st>();
-        h->c = &C(ctx);
-        h->lt = bfv_lt_create(*h->c, level, period, n_diag, diag_index, values, bsgs_ratio, S(stream));
-        *out = h.release();
+        Context& c = C(ctx);
+        make_plan(out, c, bfv_lt_create(c, level, period, n_diag, diag_index, values, bsgs_ratio, S(stream)));
     });
 }
-void lsa_bfv_lt_destroy(lsa_bfv_lt lt) {
-    if (!lt) return;
-    delete lt->lt;
-    delete lt;
-}
+void lsa_bfv_lt_destroy(lsa_bfv_lt lt) { delete lt; }
 int lsa_bfv_lt_info(lsa_bfv_lt lt, int* level, int* period, int* n_diag, int* n1, int* n_baby, int* n_giant, int* rows,
                     int* n_galois, int* n_moddown) {
     return guard([&] {
-        LSA_REQUIRE(lt != nullptr, "lsa_bfv_lt_info: null plan handle");
-        const BtMatrix& m = lt->lt->m;
+        const BfvLinearTransform& p = P(lt, "lsa_bfv_lt_info: null plan handle");
+        const BtMatrix& m = p.m;
         if (level) *level = m.level;
         if (period) *period = m.period;
         if (n_diag) *n_diag = (int)m.ks.size();
         if (n1) *n1 = m.naive ? 0 : m.n1;
-        if (n_baby) *n_baby = lt->lt->n_baby;
-        if (n_giant) *n_giant = lt->lt->n_giant;
+        if (n_baby) *n_baby = p.n_baby;
+        if (n_giant) *n_giant = p.n_giant;
         if (rows) *rows = m.rows;
-        if (n_galois) *n_galois = (int)lt->lt->galois.size();
-        if (n_moddown) *n_moddown = lt->lt->n_moddown;
+        if (n_galois) *n_galois = (int)p.galois.size();
+        if (n_moddown) *n_moddown = p.n_moddown;
     });
 }
 int lsa_bfv_lt_diagonals(lsa_bfv_lt lt, int* index_out, int capacity) {
     return guard([&] {
         LSA_REQUIRE(lt != nullptr && index_out != nullptr, "lsa_bfv_lt_diagonals: null argument");
-        const auto& ks = lt->lt->m.ks;
-        LSA_REQUIRE((int)ks.size() <= capacity, "lsa_bfv_lt_diagonals: capacity: buffer too small");
-        std::copy(ks.begin(), ks.end(), index_out);
+        copy_out(lt->plan->m.ks, index_out, capacity, "lsa_bfv_lt_diagonals: capacity: buffer too small");
     });
 }
 int lsa_bfv_lt_galois_elements(lsa_bfv_lt lt, uint64_t* out, int capacity) {
     return guard([&] {
         LSA_REQUIRE(lt != nullptr && out != nullptr, "lsa_bfv_lt_galois_elements: null argument");
-        const auto& g = lt->lt->galois;
-        LSA_REQUIRE((int)g.size() <= capacity, "lsa_bfv_lt_galois_elements: capacity: buffer too small");
-        std::copy(g.begin(), g.end(), out);
+        copy_out(lt->plan->galois, out, capacity, "lsa_bfv_lt_galois_elements: capacity: buffer too small");
     });
 }
 int lsa_bfv_lt_plaintext(lsa_bfv_lt lt, int diag_pos, uint64_t* host_out, long long capacity_words) {
     return guard([&] {
         LSA_REQUIRE(lt != nullptr && host_out != nullptr, "lsa_bfv_lt_plaintext: null argument");
-        const BtMatrix& m = lt->lt->m;
+        const BtMatrix& m = lt->plan->m;
         LSA_REQUIRE(diag_pos >= 0 && diag_pos < (int)m.plains.size(), "lsa_bfv_lt_plaintext: diagonal position out of range");
         LSA_REQUIRE(capacity_words >= (long long)m.rows * lt->c->n, "lsa_bfv_lt_plaintext: capacity: buffer too small for the plaintext's rows");
         lt->c->use_device();
@@ -831,167 +821,120 @@ int lsa_bfv_linear_transform(lsa_context ctx, lsa_bfv_lt lt, const uint64_t* in,
                              long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream) {
     return guard([&] {
         LSA_REQUIRE(ctx != nullptr, "lsa_bfv_linear_transform: null context");
-        LSA_REQUIRE(lt != nullptr, "lsa_bfv_linear_transform: null plan handle");
-        LSA_REQUIRE(lt->c == &C(ctx), "lsa_bfv_linear_transform: the plan belongs to another context");
+        BfvLinearTransform& p = P(lt, ctx, "lsa_bfv_linear_transform: null plan handle", "lsa_bfv_linear_transform: the plan belongs to another context");
         LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "lsa_bfv_linear_transform: null key argument");
-        std::map<u64, const Key*> g;
-        for (int i = 0; i < n_keys; i++) g[galois_elements[i]] = &K(keys[i], "lsa_bfv_linear_transform");
-        bfv_lt_run(*lt->lt, in, sin, out, sout, batch, g, S(stream));
+        bfv_lt_run(p, in, sin, out, sout, batch, G(n_keys, galois_elements, keys, "lsa_bfv_linear_transform"), S(stream));
     });
 }
 
 // ---- CKKS slot sum (slot_sum.h, ops.hip slot_sum_run)
-struct lsa_slot_sum_st {
-    SlotSum* p;
-    Context* c;
-};
+struct lsa_slot_sum_st : PlanHandle<SlotSum> {};
+// the counts the plan and info entry points of both slot sums report (null: not asked for)
+static void slot_sum_counts(const SlotSumPlanHost& p, int* count, int* radix, int* n_steps, int* n_keyswitch, int* n_moddown,
+                            int* n_galois) {
+    if (count) *count = p.count;
+    if (radix) *radix = p.radix;
+    if (n_steps) *n_steps = (int)p.steps.size();
+    if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
+    if (n_moddown) *n_moddown = p.n_moddown;
+    if (n_galois) *n_galois = (int)p.galois.size();
+}
 int lsa_slot_sum_plan(int n_ring, long long step, int count, int radix, int* n_steps, int* n_keyswitch, int* n_moddown,
                       int* rotations, int capacity, int* n_rot) {
     return guard([&] {
         const SlotSumPlanHost p = slot_sum_plan_checked(n_ring, step, count, radix);
-        if (n_steps) *n_steps = (int)p.steps.size();
-        if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
-        if (n_moddown) *n_moddown = p.n_moddown;
-        if (n_rot) *n_rot = (int)p.rotations.size();
-        LSA_REQUIRE(rotations == nullptr || (int)p.rotations.size() <= capacity, "slot sum: buffer too small for the rotations");
-        if (rotations) std::copy(p.rotations.begin(), p.rotations.end(), rotations);
+        slot_sum_counts(p, nullptr, nullptr, n_steps, n_keyswitch, n_moddown, n_rot);   // (as many rotations as elements)
+        if (rotations) copy_out(p.rotations, rotations, capacity, "slot sum: buffer too small for the rotations");
     });
 }
 int lsa_slot_sum_create(lsa_context ctx, int level, long long step, int count, int radix, lsa_slot_sum* out) {
     return guard([&] {
         LSA_REQUIRE(out != nullptr, "null argument");
-        auto h = std::make_unique<lsa_slot_sum_st>();
-        h->c = &C(ctx);
-        h->p = slot_sum_create(*h->c, level, step, count, radix);
-        *out = h.release();
+        Context& c = C(ctx);
+        make_plan(out, c, slot_sum_create(c, level, step, count, radix));
     });
 }
-void lsa_slot_sum_destroy(lsa_slot_sum plan) {
-    if (!plan) return;
-    delete plan->p;
-    delete plan;
-}
+void lsa_slot_sum_destroy(lsa_slot_sum plan) { delete plan; }
 int lsa_slot_sum_info(lsa_slot_sum plan, int* level, int* count, int* radix, int* n_steps, int* n_keyswitch, int* n_moddown,
                       int* n_galois) {
     return guard([&] {
-        LSA_REQUIRE(plan != nullptr, "null slot-sum handle");
-        const SlotSumPlanHost& p = plan->p->plan;
-        if (level) *level = plan->p->level;
-        if (count) *count = p.count;
-        if (radix) *radix = p.radix;
-        if (n_steps) *n_steps = (int)p.steps.size();
-        if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
-        if (n_moddown) *n_moddown = p.n_moddown;
-        if (n_galois) *n_galois = (int)plan->p->galois.size();
+        const SlotSum& p = P(plan, "null slot-sum handle");
+        if (level) *level = p.level;
+        slot_sum_counts(p.plan, count, radix, n_steps, n_keyswitch, n_moddown, n_galois);
     });
 }
 int lsa_slot_sum_galois_elements(lsa_slot_sum plan, uint64_t* out, int capacity) {
     return guard([&] {
         LSA_REQUIRE(plan != nullptr && out != nullptr, "null argument");
-        const auto& g = plan->p->galois;
-        LSA_REQUIRE((int)g.size() <= capacity, "buffer too small");
-        std::copy(g.begin(), g.end(), out);
+        copy_out(plan->plan->plan.galois, out, capacity, "buffer too small");
     });
 }
 int lsa_slot_sum_set_multi_mac(lsa_slot_sum plan, int enable) {
-    return guard([&] {
-        LSA_REQUIRE(plan != nullptr, "null slot-sum handle");
-        plan->p->multi_mac = enable != 0;
-    });
+    return guard([&] { P(plan, "null slot-sum handle").multi_mac = enable != 0; });
 }
 int lsa_ckks_slot_sum(lsa_context ctx, lsa_slot_sum plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
                       long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(plan != nullptr, "null slot-sum handle");
-        LSA_REQUIRE(plan->c == &C(ctx), "slot sum: the plan belongs to another context");
+        SlotSum& p = P(plan, ctx, "null slot-sum handle", "slot sum: the plan belongs to another context");
         LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "slot sum: null argument");
-        std::map<u64, const Key*> g;
-        for (int i = 0; i < n_keys; i++) g[galois_elements[i]] = &K(keys[i], "lsa_ckks_slot_sum");
-        slot_sum_run(*plan->p, in, sin, out, sout, batch, g, S(stream));
+        slot_sum_run(p, in, sin, out, sout, batch, G(n_keys, galois_elements, keys, "lsa_ckks_slot_sum"), S(stream));
     });
 }
 
 // ---- BFV slot sum (slot_sum.h, ops.hip bfv_slot_sum_run)
-struct lsa_bfv_slot_sum_st {
-    BfvSlotSum* p;
-    Context* c;
-};
+struct lsa_bfv_slot_sum_st : PlanHandle<BfvSlotSum> {};
 int lsa_bfv_slot_sum_plan(int n_ring, long long step, int count, int radix, int rows, int* n_steps, int* n_keyswitch, int* n_moddown,
                           uint64_t* galois_elements, int capacity, int* n_galois) {
     return guard([&] {
-        const BfvSlotSumPlanHost p = bfv_slot_sum_plan_checked(n_ring, step, count, radix, rows);
-        if (n_steps) *n_steps = (int)p.steps.size();
-        if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
-        if (n_moddown) *n_moddown = p.n_moddown;
-        if (n_galois) *n_galois = (int)p.galois.size();
-        LSA_REQUIRE(galois_elements == nullptr || (int)p.galois.size() <= capacity,
-                    "lsa_bfv_slot_sum_plan: capacity: buffer too small for the Galois elements");
-        if (galois_elements) std::copy(p.galois.begin(), p.galois.end(), galois_elements);
+        const SlotSumPlanHost p = bfv_slot_sum_plan_checked(n_ring, step, count, radix, rows);
+        slot_sum_counts(p, nullptr, nullptr, n_steps, n_keyswitch, n_moddown, n_galois);
+        if (galois_elements)
+            copy_out(p.galois, galois_elements, capacity, "lsa_bfv_slot_sum_plan: capacity: buffer too small for the Galois elements");
     });
 }
 int lsa_bfv_slot_sum_create(lsa_context ctx, int level, long long step, int count, int radix, int rows, lsa_bfv_slot_sum_handle* out) {
     return guard([&] {
         LSA_REQUIRE(out != nullptr, "lsa_bfv_slot_sum_create: null argument");
-        auto h = std::make_unique<lsa_bfv_slot_sum_st>();
-        h->c = &C(ctx);
-        h->p = bfv_slot_sum_create(*h->c, level, step, count, radix, rows);
-        *out = h.release();
+        Context& c = C(ctx);
+        make_plan(out, c, bfv_slot_sum_create(c, level, step, count, radix, rows));
     });
 }
-void lsa_bfv_slot_sum_destroy(lsa_bfv_slot_sum_handle plan) {
-    if (!plan) return;
-    delete plan->p;
-    delete plan;
-}
+void lsa_bfv_slot_sum_destroy(lsa_bfv_slot_sum_handle plan) { delete plan; }
 int lsa_bfv_slot_sum_info(lsa_bfv_slot_sum_handle plan, int* level, int* count, int* radix, int* rows, int* n_steps, int* n_keyswitch,
                           int* n_moddown, int* n_galois, int* gather) {
     return guard([&] {
-        LSA_REQUIRE(plan != nullptr, "lsa_bfv_slot_sum_info: null plan handle");
-        const BfvSlotSumPlanHost& p = plan->p->plan;
-        if (level) *level = plan->p->level;
-        if (count) *count = p.count;
-        if (radix) *radix = p.radix;
-        if (rows) *rows = p.rows;
-        if (n_steps) *n_steps = (int)p.steps.size();
-        if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
-        if (n_moddown) *n_moddown = p.n_moddown;
-        if (n_galois) *n_galois = (int)p.galois.size();
-        if (gather) *gather = plan->p->gather ? 1 : 0;
+        const BfvSlotSum& p = P(plan, "lsa_bfv_slot_sum_info: null plan handle");
+        if (level) *level = p.level;
+        if (rows) *rows = p.plan.rows;
+        slot_sum_counts(p.plan, count, radix, n_steps, n_keyswitch, n_moddown, n_galois);
+        if (gather) *gather = p.gather ? 1 : 0;
     });
 }
 int lsa_bfv_slot_sum_galois_elements(lsa_bfv_slot_sum_handle plan, uint64_t* out, int capacity) {
     return guard([&] {
         LSA_REQUIRE(plan != nullptr && out != nullptr, "lsa_bfv_slot_sum_galois_elements: null argument");
-        const auto& g = plan->p->plan.galois;
-        LSA_REQUIRE((int)g.size() <= capacity, "lsa_bfv_slot_sum_galois_elements: capacity: buffer too small");
-        std::copy(g.begin(), g.end(), out);
+        copy_out(plan->plan->plan.galois, out, capacity, "lsa_bfv_slot_sum_galois_elements: capacity: buffer too small");
     });
 }
 int lsa_bfv_slot_sum_set_gather(lsa_bfv_slot_sum_handle plan, int enable) {
     return guard([&] {
-        LSA_REQUIRE(plan != nullptr, "lsa_bfv_slot_sum_set_gather: null plan handle");
-        LSA_REQUIRE(!enable || plan->c->logn <= LSA_PERM_LDS_MAX_LOGN,
+        BfvSlotSum& p = P(plan, "lsa_bfv_slot_sum_set_gather: null plan handle");
+        LSA_REQUIRE(!enable || p.c.logn <= LSA_PERM_LDS_MAX_LOGN,
                     "lsa_bfv_slot_sum_set_gather: enable: the gathering tail stages a limb in LDS and needs N <= 2^14");
-        plan->p->gather = enable != 0;
+        p.gather = enable != 0;
     });
 }
 int lsa_bfv_slot_sum(lsa_context ctx, lsa_bfv_slot_sum_handle plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
                      long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(plan != nullptr, "lsa_bfv_slot_sum: null plan handle");
-        LSA_REQUIRE(plan->c == &C(ctx), "lsa_bfv_slot_sum: the plan belongs to another context");
+        BfvSlotSum& p = P(plan, ctx, "lsa_bfv_slot_sum: null plan handle", "lsa_bfv_slot_sum: the plan belongs to another context");
         LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "lsa_bfv_slot_sum: null key argument");
-        std::map<u64, const Key*> g;
-        for (int i = 0; i < n_keys; i++) g[galois_elements[i]] = &K(keys[i], "lsa_bfv_slot_sum");
-        bfv_slot_sum_run(*plan->p, in, sin, out, sout, batch, g, S(stream));
+        bfv_slot_sum_run(p, in, sin, out, sout, batch, G(n_keys, galois_elements, keys, "lsa_bfv_slot_sum"), S(stream));
     });
 }
 
 // ---- CKKS polynomial evaluation (poly_eval.hip)
-struct lsa_polynomial_st {
-    Polynomial* p;
-    Context* c;
-};
+struct lsa_polynomial_st : PlanHandle<Polynomial> {};
 int lsa_poly_plan(int basis, int n_coef, const double* coef, int log_baby, int level_in, int with_interval, int* depth,
                   int* log_baby_out, int* n_mult, int* n_leaves, int* n_leaf_launches) {
     return guard([&] { poly_plan(basis, n_coef, coef, log_baby, level_in, with_interval != 0, depth, log_baby_out, n_mult, n_leaves, n_leaf_launches); });
@@ -1000,50 +943,40 @@ int lsa_poly_create(lsa_context ctx, int basis, int n_coef, const double* coef, 
                     double scale_out, int log_baby, lsa_polynomial* out) {
     return guard([&] {
         LSA_REQUIRE(out != nullptr, "null argument");
-        auto h = std::make_unique<lsa_polynomial_st>();
-        h->c = &C(ctx);
-        h->p = poly_create(*h->c, basis, n_coef, coef, a, b, level_in, scale_in, scale_out, log_baby, nullptr);
-        *out = h.release();
+        Context& c = C(ctx);
+        make_plan(out, c, poly_create(c, basis, n_coef, coef, a, b, level_in, scale_in, scale_out, log_baby, nullptr));
     });
 }
-void lsa_poly_destroy(lsa_polynomial p) {
-    if (!p) return;
-    delete p->p;
-    delete p;
-}
+void lsa_poly_destroy(lsa_polynomial p) { delete p; }
 int lsa_poly_info(lsa_polynomial p, int* level_in, int* level_out, double* scale_out, int* depth, int* log_baby, int* n_mult,
                   int* n_leaves, int* n_leaf_launches, int* n_constants) {
     return guard([&] {
-        LSA_REQUIRE(p != nullptr, "null polynomial handle");
-        const Polynomial& P = *p->p;
-        if (level_in) *level_in = P.level_in;
-        if (level_out) *level_out = P.level_out;
-        if (scale_out) *scale_out = P.scale_out;
-        if (depth) *depth = P.depth;
-        if (log_baby) *log_baby = P.st.log_baby;
-        if (n_mult) *n_mult = P.st.mults;
-        if (n_leaves) *n_leaves = (int)P.st.jobs.size();
-        if (n_leaf_launches) *n_leaf_launches = (int)P.st.groups.size();
-        if (n_constants) *n_constants = (int)P.constants.size();
+        const Polynomial& poly = P(p, "null polynomial handle");
+        if (level_in) *level_in = poly.level_in;
+        if (level_out) *level_out = poly.level_out;
+        if (scale_out) *scale_out = poly.scale_out;
+        if (depth) *depth = poly.depth;
+        if (log_baby) *log_baby = poly.st.log_baby;
+        if (n_mult) *n_mult = poly.st.mults;
+        if (n_leaves) *n_leaves = (int)poly.st.jobs.size();
+        if (n_leaf_launches) *n_leaf_launches = (int)poly.st.groups.size();
+        if (n_constants) *n_constants = (int)poly.constants.size();
     });
 }
 int lsa_poly_constants(lsa_polynomial p, long long* out, int capacity) {
     return guard([&] {
         LSA_REQUIRE(p != nullptr && out != nullptr, "null argument");
-        const auto& k = p->p->constants;
-        LSA_REQUIRE((int)k.size() <= capacity, "buffer too small");
-        std::copy(k.begin(), k.end(), out);
+        copy_out(p->plan->constants, out, capacity, "buffer too small");
     });
 }
 int lsa_ckks_poly_eval(lsa_context ctx, lsa_polynomial p, const uint64_t* in, uint64_t* out, int batch, long long sin,
                        long long sout, lsa_key rlk, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(p != nullptr, "null polynomial handle");
-        LSA_REQUIRE(p->c == &C(ctx), "poly: the plan belongs to another context");
+        Polynomial& poly = P(p, ctx, "null polynomial handle", "poly: the plan belongs to another context");
         if (batch <= 0) return;
         LSA_REQUIRE(in != nullptr && out != nullptr, "null argument");
         LSA_REQUIRE(rlk != nullptr && rlk->key.data != nullptr, "poly: the relinearisation key is missing");
-        poly_run(*p->p, in, sin, out, sout, batch, K(rlk), S(stream));
+        poly_run(poly, in, sin, out, sout, batch, K(rlk), S(stream));
     });
 }
 

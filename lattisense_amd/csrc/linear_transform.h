@@ -80,7 +80,7 @@ struct LtEval {
     DevPool& pool;   // released device buffers (single in-order stream: reuse is ordered)
     hipStream_t s;
     int m;   // batch
-    const std::map<u64, const Key*>& glk;
+    const GaloisKeys& glk;
     long long N;
     std::string who;              // prefix of error messages
     bool giant_scatter = false;   // giant-step rotations through the accumulating scatter of the key MAC (ckks_rotate_ext)
@@ -92,7 +92,7 @@ struct LtEval {
     u64* coeff_out = nullptr;
     long long s_coeff_out = 0;
 
-    LtEval(Context& c_, DevPool& p, hipStream_t s_, int m_, const std::map<u64, const Key*>& g, const char* who_)
+    LtEval(Context& c_, DevPool& p, hipStream_t s_, int m_, const GaloisKeys& g, const char* who_)
         : c(c_), pool(p), s(s_), m(m_), glk(g), N(c_.n), who(who_) {}
     long long stride(int level) const { return 2LL * (level + 1) * N; }
     DCt alloc(int level, double scale) {
@@ -145,16 +145,8 @@ struct LtEval {
         ckks_rescale(c, a.level, 2, a.data(), o.data(), m, stride(a.level), stride(a.level - 1), s);
         return o;
     }
-    const Key& gkey(u64 e) const {
-        auto it = glk.find(e);
-        LSA_REQUIRE(it != glk.end(), who + ": Galois key for element " + std::to_string(e) + " missing");
-        return *it->second;
-    }
-    u64 galois_of(int r) const {
-        u64 e = 1;
-        for (int i = 0; i < r; i++) e = e * 5 % (2ULL * c.n);
-        return e;
-    }
+    const Key& gkey(u64 e) const { return glk.require(e, who); }
+    u64 galois_of(int r) const { return galois_of_rotation(r, c.n); }   // r in [0, N/2)
     DCt rotate(const DCt& a, int r);
     // rotations of one ciphertext by several steps with a single decomposition (hoisted); same residues as rotate()
     std::map<int, DCt> rotate_many(const DCt& a, const std::vector<int>& steps);
@@ -182,7 +174,7 @@ struct LinearTransform {
 LinearTransform* lt_create(Context& c, int level, int log_slots, int n_diag, const int* diag_index, const double* values,
                            double pt_scale, double bsgs_ratio, bool double_hoist, hipStream_t s);
 void lt_run(LinearTransform& lt, const u64* in, long long sin, u64* out, long long sout, int batch, bool rescale,
-            const std::map<u64, const Key*>& glk, hipStream_t s);
+            const GaloisKeys& glk, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ BFV operator plan
 // lsa_bfv_lt_* / lsa_bfv_linear_transform (include/lattisense_amd.h).  The matrix acts on both rows of the 2 x N/2
@@ -204,6 +196,6 @@ BfvLinearTransform* bfv_lt_create(Context& c, int level, int period, int n_diag,
                                   double bsgs_ratio, hipStream_t s);
 // in / out [batch][2][level+1][N], coefficient domain; out overlaps no word of in
 void bfv_lt_run(BfvLinearTransform& lt, const u64* in, long long sin, u64* out, long long sout, int batch,
-                const std::map<u64, const Key*>& glk, hipStream_t s);
+                const GaloisKeys& glk, hipStream_t s);
 
 }  // namespace lsa

@@ -175,12 +175,7 @@ BtMatrix lt_make_matrix(Context& c, const Diags& mat, int level, int period, dou
                         hipStream_t s, std::vector<u64*>& owned, std::map<u64, bool>& gal, const char* who) {
     const int n = c.n / 2;
     const std::vector<int> rg = rot_group(n);
-    auto gel = [&](int rot) {
-        u64 e = 1;
-        const u64 m = 2ULL * c.n;
-        for (int i = 0; i < rot % n; i++) e = e * 5 % m;
-        return e;
-    };
+    auto gel = [&](int rot) { return galois_of_rotation(rot % n, c.n); };   // rot in [0, period], period <= N/2
     BtMatrix bm;
     bm.level = level;
     bm.period = period;
@@ -544,7 +539,7 @@ LinearTransform* lt_create(Context& c, int level, int log_slots, int n_diag, con
 }
 
 void lt_run(LinearTransform& lt, const u64* in, long long sin, u64* out, long long sout, int batch, bool rescale,
-            const std::map<u64, const Key*>& glk, hipStream_t s) {
+            const GaloisKeys& glk, hipStream_t s) {
     if (batch <= 0) return;
     Context& c = lt.c;
     const long long N = c.n;
@@ -623,15 +618,10 @@ BfvLinearTransform* bfv_lt_create(Context& c, int level, int period, int n_diag,
     lt->n_giant = (int)giants.size();
     lt->n_moddown = lt->n_giant - (giants.count(0) ? 1 : 0) + 1;
     std::map<u64, bool> gal;
-    auto gel = [&](int rot) {
-        u64 e = 1;
-        for (int i = 0; i < rot % n; i++) e = e * 5 % (2ULL * c.n);
-        return e;
-    };
     for (auto& kv : babies)
-        if (kv.first % n) gal[gel(kv.first)] = true;
+        if (kv.first % n) gal[galois_of_rotation(kv.first % n, c.n)] = true;
     for (auto& kv : giants)
-        if (kv.first % n) gal[gel(kv.first)] = true;
+        if (kv.first % n) gal[galois_of_rotation(kv.first % n, c.n)] = true;
     for (auto& kv : gal) lt->galois.push_back(kv.first);
     // nothing has touched the device so far
     c.use_device();
@@ -643,17 +633,14 @@ BfvLinearTransform* bfv_lt_create(Context& c, int level, int period, int n_diag,
 }
 
 void bfv_lt_run(BfvLinearTransform& lt, const u64* in, long long sin, u64* out, long long sout, int batch,
-                const std::map<u64, const Key*>& glk, hipStream_t s) {
+                const GaloisKeys& glk, hipStream_t s) {
     const std::string who = "lsa_bfv_linear_transform";
     Context& c = lt.c;
     const int level = lt.m.level, L = level + 1;
     const long long N = c.n;
-    for (u64 e : lt.galois) {   // every key before anything is queued
-        auto it = glk.find(e);
-        LSA_REQUIRE(it != glk.end() && it->second && it->second->data, who + ": Galois key for element " + std::to_string(e) + " missing");
-        LSA_REQUIRE(it->second->level >= level, who + ": the Galois key for element " + std::to_string(e) +
-                                                    " was exported at a lower level than the plan");
-    }
+    (void)glk.resolve(lt.galois, who, [&](u64 e, const Key& k) {   // every key before anything is queued
+        LSA_REQUIRE(k.level >= level, who + ": the Galois key for element " + std::to_string(e) + " was exported at a lower level than the plan");
+    });
     if (batch <= 0) return;
     LSA_REQUIRE(in && out, who + ": null argument");
     const size_t w = 2 * (size_t)L * N;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/lattisense_amd.h"
+#include "galois_keys.h"
 #include "ntt_plan.h"
 #include "ntt_chunk.h"
 #include "plain_ops.h"
@@ -18,11 +19,6 @@
 #include "tables.h"
 
 namespace lsa {
-
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 void set_last_error(const std::string& m);
 
@@ -87,6 +83,8 @@ struct Key {
     // (that path is then not taken).  Lives and dies with `data` (same allocation, or owned by the key's holder).
     const double* fp = nullptr;
 };
+
+using GaloisKeys = GaloisKeySet<Key>;   // the Galois keys of one call (galois_keys.h)
 
 struct Context {
     int algo, n, logn, nq, np, nmul, nmod, device;
@@ -432,7 +430,7 @@ int bootstrap_cts_matrices(const Bootstrap& bt);
 void bootstrap_matrix(const Bootstrap& bt, int i, int* level, int* n1, const std::vector<int>** ks, const std::vector<u64*>** plains,
                       int* rows = nullptr);
 void bootstrap_run(Bootstrap& bt, const u64* in, long long sin, u64* out, long long sout, int batch, const Key& rlk,
-                   const std::map<u64, const Key*>& glk, const Key* swk_dts, const Key* swk_std, hipStream_t s);
+                   const GaloisKeys& glk, const Key* swk_dts, const Key* swk_std, hipStream_t s);
 
 // ---------------------------------------------------------------- operator pipelines (ops.hip)
 const std::string& last_error();
@@ -512,7 +510,6 @@ struct SlotSum {
     Context& c;
     int level;
     SlotSumPlanHost plan;
-    std::vector<u64> galois;    // elements of plan.rotations, ascending
     // steps with 2..4 keys: true = one k_ks_mac_multi launch + k_ext_sum; false = one launch_ks_mac per key, each adding to its
     // destination.  The same words; the default is the faster form on the MI355X (the multi-key launch lost 6-10 %)
     bool multi_mac = false;
@@ -522,7 +519,7 @@ struct SlotSum {
 SlotSumPlanHost slot_sum_plan_checked(int n_ring, long long step, int count, int radix);   // slot_sum_plan, refusals as LSA_ERR_ARG
 SlotSum* slot_sum_create(Context& c, int level, long long step, int count, int radix);
 void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
-                  const std::map<u64, const Key*>& glk, hipStream_t s);
+                  const GaloisKeys& glk, hipStream_t s);
 // BFV slot sum  out = sum_{i<count} rot_cols(y, i*step), y = in + rot_rows(in) if rows (lsa_bfv_slot_sum_*; plan: slot_sum.h).
 // Ciphertexts are in the coefficient domain.  gather: the rotated c0 terms never enter the NTT domain -- the key MAC adds no
 // P * c0 and the ModDown tail gathers them from the c0 row staged in LDS (slot_sum.hip k_bfv_slot_tail; N <= 2^14); plain: c0 is
@@ -530,15 +527,15 @@ void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long 
 struct BfvSlotSum {
     Context& c;
     int level;
-    BfvSlotSumPlanHost plan;
+    SlotSumPlanHost plan;
     bool gather;
     BfvSlotSum(Context& ctx, int level_) : c(ctx), level(level_), gather(ctx.logn <= LSA_PERM_LDS_MAX_LOGN) {}
 };
 #define LSA_BFV_SLOTSUM_DEFAULT_RADIX 4   // what radix 0 stands for
-BfvSlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count, int radix, int rows);
+SlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count, int radix, int rows);
 BfvSlotSum* bfv_slot_sum_create(Context& c, int level, long long step, int count, int radix, int rows);
 void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
-                      const std::map<u64, const Key*>& glk, hipStream_t s);
+                      const GaloisKeys& glk, hipStream_t s);
 // the coefficient-domain ModDown tail of one step of the BFV slot sum (k_bfv_slot_tail), x and out [2][L][N]:
 //   out[0][j][y] = x0[j][y] + sum_{r<n_next} sign_r(y) x0[j][pi_r(y)] + (addend ? addend[j][y] : 0) + (acc[0][j][y] - conv[0][j][y]) Pinv_j
 //   out[1][j][y] = x1[j][y] + (acc[1][j][y] - conv[1][j][y]) Pinv_j

@@ -1672,39 +1672,59 @@ SlotSum* slot_sum_create(Context& c, int level, long long step, int count, int r
     auto p = std::make_unique<SlotSum>(c, level);
     p->plan = slot_sum_plan_checked(c.n, step, count, radix);
     LSA_REQUIRE(p->plan.steps.empty() || c.np >= 1, "slot sum: key switching needs at least one special prime");
-    for (int r : p->plan.rotations) p->galois.push_back(galois_of_rotation(r, c.n));
-    std::sort(p->galois.begin(), p->galois.end());
     return p.release();
 }
 
-void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
-                  const std::map<u64, const Key*>& glk, hipStream_t s) {
-    Context& c = p.c;
-    const int level = p.level;
-    const EntryCheck ck(c, "lsa_ckks_slot_sum", LSA_ALGO_CKKS, level, 0, batch);
-    std::map<int, const Key*> key_of;   // every key is looked up before anything is queued
-    for (int r : p.plan.rotations) {
-        const u64 e = galois_of_rotation(r, c.n);
-        auto it = glk.find(e);
-        LSA_REQUIRE(it != glk.end() && it->second, ck.who + ": Galois key for element " + std::to_string(e) + " missing");
-        ck.key(*it->second, "a Galois key");
-        key_of[r] = it->second;
-    }
-    if (batch <= 0) return;
-    const long long N = c.n;
-    const int L = level + 1, T = L + c.np;
-    const size_t w = 2 * (size_t)L * N;
+// What both slot-sum runners do before their tiles.  Every key of `elements` (the plan's, in the order a missing one is reported)
+// is looked up and checked before anything is queued; then the operands; a plan without steps (count == 1, no row fold) is a
+// copy; last the rotations' tables, element by element (table look-ups upload on first use: only after every argument is
+// accepted): the NTT-domain scatter and, for the BFV gathering tail, the coefficient-domain permutation.
+// run == false: nothing is left to do.
+struct SlotSumCall {
+    bool run = false;
+    GaloisKeys key_of;   // the plan's keys alone, all present
+    std::map<u64, const u32*> scatter_of, perm_of;
+};
+static SlotSumCall slot_sum_prologue(Context& c, const EntryCheck& ck, const SlotSumPlanHost& plan, const std::vector<u64>& elements,
+                                     const GaloisKeys& glk, const u64* in, long long sin, u64* out, long long sout, int batch,
+                                     bool gather, hipStream_t s) {
+    SlotSumCall call;
+    const std::vector<const Key*> keys = glk.resolve(elements, ck.who, [&](u64, const Key& k) { ck.key(k, "a Galois key"); });
+    for (size_t i = 0; i < elements.size(); i++) call.key_of.insert(elements[i], keys[i]);
+    if (batch <= 0) return call;
+    const int L = ck.level + 1;
+    const size_t w = 2 * (size_t)L * c.n;
     const Span sp_in = ck.operand(in, sin, w, "in", false), sp_out = ck.output(out, sout, w);
     ck.same_or_apart(sp_out, sp_in, "in");
-    if (p.plan.steps.empty()) {   // count == 1: a copy
-        if (layout::same(sp_out, sp_in)) return;
+    if (plan.steps.empty()) {
+        if (layout::same(sp_out, sp_in)) return call;
         std::vector<int> rows(2 * L);
         for (int i = 0; i < 2 * L; i++) rows[i] = i;
         launch_copy_rows(c, in, sin, out, sout, 2 * L, rows.data(), batch, s);
-        return;
+        return call;
     }
-    std::map<int, const u32*> scatter_of;   // (table look-ups upload on first use: only after every argument is accepted)
-    for (int r : p.plan.rotations) scatter_of[r] = inverse_perm(c, galois_of_rotation(r, c.n));
+    LSA_REQUIRE(!gather || c.logn <= LSA_PERM_LDS_MAX_LOGN, ck.who + ": the gathering tail needs N <= 2^14");
+    for (u64 e : elements) {
+        call.scatter_of[e] = inverse_perm(c, e);
+        if (gather) call.perm_of[e] = c.coeff_perm(e);
+    }
+    call.run = true;
+    return call;
+}
+
+void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
+                  const GaloisKeys& glk, hipStream_t s) {
+    Context& c = p.c;
+    const int level = p.level;
+    const EntryCheck ck(c, "lsa_ckks_slot_sum", LSA_ALGO_CKKS, level, 0, batch);
+    std::vector<u64> by_rotation;   // a missing key is reported in the order of the plan's rotations
+    for (int r : p.plan.rotations) by_rotation.push_back(galois_of_rotation(r, c.n));
+    const SlotSumCall call = slot_sum_prologue(c, ck, p.plan, by_rotation, glk, in, sin, out, sout, batch, false, s);
+    if (!call.run) return;
+    const auto& key_of = call.key_of;
+    const auto& scatter_of = call.scatter_of;
+    const long long N = c.n;
+    const int L = level + 1, T = L + c.np;
     const size_t ks_rows = KsTile::rows(c, level);
     const bool multi = p.multi_mac;
     // extended buffers beyond KsTile's acc: one per key of a multi-key launch that is neither the first NEXT key nor the first
@@ -1753,7 +1773,7 @@ void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long 
                     if (dst != t.acc) next_more[n_sum++] = dst;
                     n_next++;
                 }
-                mk[i] = {key_of.at(k.rot), scatter_of.at(k.rot), dst};
+                mk[i] = {key_of.at(k.g), scatter_of.at(k.g), dst};
             }
             if (one_launch) {
                 launch_ks_mac_multi(c, level, cx, sx, t.ext, t.s_ext, nk, mk, s_ext2, x, sx, nb, st);
@@ -1783,7 +1803,7 @@ void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long 
 // out = x + (tail_c0, 0) + ModDown(tail).  plain: c0 is transformed too and enters the MACs as `base` (the CKKS form), the tails are
 // launch_moddown_final with base = x.  ModDown(P z + a) = z + ModDown(a) residue for residue, so both give the same words.  x
 // lives in `out` from the second step on and is updated in place.
-BfvSlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count, int radix, int rows) {
+SlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count, int radix, int rows) {
     try {
         return bfv_slot_sum_plan(n_ring, step, count, radix, rows, LSA_BFV_SLOTSUM_DEFAULT_RADIX);
     } catch (const std::invalid_argument& e) {
@@ -1801,37 +1821,18 @@ BfvSlotSum* bfv_slot_sum_create(Context& c, int level, long long step, int count
 }
 
 void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
-                      const std::map<u64, const Key*>& glk, hipStream_t s) {
+                      const GaloisKeys& glk, hipStream_t s) {
     Context& c = p.c;
     const int level = p.level;
     const EntryCheck ck(c, "lsa_bfv_slot_sum", LSA_ALGO_BFV, level, 0, batch);
-    std::map<u64, const Key*> key_of;   // every key is looked up before anything is queued
-    for (u64 e : p.plan.galois) {
-        auto it = glk.find(e);
-        LSA_REQUIRE(it != glk.end() && it->second, ck.who + ": Galois key for element " + std::to_string(e) + " missing");
-        ck.key(*it->second, "a Galois key");
-        key_of[e] = it->second;
-    }
-    if (batch <= 0) return;
+    const bool gather = p.gather;
+    const SlotSumCall call = slot_sum_prologue(c, ck, p.plan, p.plan.galois, glk, in, sin, out, sout, batch, gather, s);
+    if (!call.run) return;
+    const auto& key_of = call.key_of;
+    const auto& scatter_of = call.scatter_of;
+    const auto& perm_of = call.perm_of;
     const long long N = c.n;
     const int L = level + 1, T = L + c.np;
-    const size_t w = 2 * (size_t)L * N;
-    const Span sp_in = ck.operand(in, sin, w, "in", false), sp_out = ck.output(out, sout, w);
-    ck.same_or_apart(sp_out, sp_in, "in");
-    if (p.plan.steps.empty()) {   // count == 1, no rows: a copy
-        if (layout::same(sp_out, sp_in)) return;
-        std::vector<int> rows(2 * L);
-        for (int i = 0; i < 2 * L; i++) rows[i] = i;
-        launch_copy_rows(c, in, sin, out, sout, 2 * L, rows.data(), batch, s);
-        return;
-    }
-    const bool gather = p.gather;
-    LSA_REQUIRE(!gather || c.logn <= LSA_PERM_LDS_MAX_LOGN, ck.who + ": the gathering tail needs N <= 2^14");
-    std::map<u64, const u32*> scatter_of, perm_of;   // (table look-ups upload on first use: only after every argument is accepted)
-    for (u64 e : p.plan.galois) {
-        scatter_of[e] = inverse_perm(c, e);
-        if (gather) perm_of[e] = c.coeff_perm(e);
-    }
     const bool has_tail = p.plan.has_tail;
     const size_t ks_rows = KsTile::rows(c, level);
     // per batch item: NTT(c1) | the KsTile rows | the extended tail accumulator | tail_c0 (gather) or NTT(c0) (plain)
@@ -1848,14 +1849,14 @@ void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, lon
         long long sx = sin;
         u64* o = out + (size_t)b0 * sout;
         bool tail_live = false;
-        for (const BfvSlotSumStep& step : p.plan.steps) {
+        for (const SlotSumStep& step : p.plan.steps) {
             const u64* c1 = x + sL;
             launch_ntt(c, c1, cxn, nb, sx, sL, L, rm_seq(L), false, st);
             if (!gather) launch_ntt(c, x, last, nb, sx, sL, L, rm_seq(L), false, st);
             t.decompose(cxn, sL, c1, sx);
             BfvSlotTail bt;
             bool next_live = false;
-            for (const BfvSlotSumKey& k : step.keys) {
+            for (const SlotSumKey& k : step.keys) {
                 const bool add_to = k.tail ? tail_live : next_live;
                 launch_ks_mac(c, level, cxn, sL, t.ext, t.s_ext, *key_of.at(k.g), k.tail ? tail : t.acc, s_ext2, nb, st, false,
                               scatter_of.at(k.g), gather ? nullptr : last, sL, nullptr, add_to);

@@ -13,7 +13,7 @@ namespace lsa {
 // ------------------------------------------------------------------------------------------------ shared ciphertext helpers
 struct CtEval : LtEval {
     const Key& rlk;
-    CtEval(Context& c_, DevPool& p, hipStream_t s_, int m_, const Key& rlk_, const std::map<u64, const Key*>& g, const char* who_)
+    CtEval(Context& c_, DevPool& p, hipStream_t s_, int m_, const Key& rlk_, const GaloisKeys& g, const char* who_)
         : LtEval(c_, p, s_, m_, g, who_), rlk(rlk_) {}
     DCt mul(const DCt& a0, const DCt& b0) {
         // operands at different levels: the leading rows of each polynomial of the higher one ARE it at the lower level, the

@@ -345,7 +345,7 @@ void poly_run(Polynomial& p, const u64* in, long long sin, u64* out, long long s
     LSA_REQUIRE(sin >= 2LL * (p.level_in + 1) * N && sout >= 2LL * (p.level_out + 1) * N, "poly: batch stride shorter than a ciphertext");
     LSA_REQUIRE(layout::apart(out, sout, 2 * (size_t)(p.level_out + 1) * N, in, sin, 2 * (size_t)(p.level_in + 1) * N, batch),
                 "poly: out overlaps in");
-    static const std::map<u64, const Key*> no_glk;
+    static const GaloisKeys no_glk;
     CtEval ev(c, p.pool, s, batch, rlk, no_glk, "poly");
     const int m = batch;
     DCt u;

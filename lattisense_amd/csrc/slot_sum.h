@@ -13,36 +13,45 @@
 // At n == 1: out = x + ModDown(tail) if a tail exists, else x.  Every rotation is reduced mod N/2.  A step carries at most four
 // keys.  Radix 2 asks for the keys of Lattigo's InnerSumLog: 2^i * step for i < floor(log2 count), and for every set bit k of
 // count but the highest the offset (count with its low k+1 bits cleared) * step.
+//
+// The BFV slot sum  out = sum_{i<count} rot_cols(y, i*step),  y = ct + rot_rows(ct) if rows != 0, else ct, is the same plan: BFV
+// slots form a 2 x N/2 matrix, the column rotation r is the Galois element 5^(r mod N/2) mod 2N, the row swap is 2N-1.  The plan
+// starts at x = y; with rows != 0 one more step runs first, one decomposition of ct's c1 with one NEXT key, the key of 2N-1.
+// Every key is named by its Galois element (galois_keys.h); rows = 0 is the CKKS plan.
 #pragma once
 #include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "galois_keys.h"
+
 namespace lsa {
 
 #define LSA_SLOTSUM_MAX_KEYS 4   // keys of one step (one decomposition): 3 NEXT + 1 TAIL at radix 4
 
 struct SlotSumKey {
-    int rot;     // reduced mod N/2, never 0
-    bool tail;   // destination: the extended tail accumulator (else the step's NEXT sum)
+    uint64_t g;   // the key's Galois element
+    int rot;      // the rotation, reduced mod N/2, never 0; 0: the row swap
+    bool tail;    // destination: the extended tail accumulator (else the step's NEXT sum)
 };
 struct SlotSumStep {
     std::vector<SlotSumKey> keys;   // the TAIL key, if any, first; then the NEXT keys by ascending multiple of s
 };
 struct SlotSumPlanHost {
-    int n_ring = 0, count = 0, radix = 2;
+    int n_ring = 0, count = 0, radix = 2, rows = 0;
     long long step = 0;
     std::vector<SlotSumStep> steps;
     bool has_tail = false;
-    int n_keyswitch = 0;          // key MACs (one per key of every step)
-    int n_moddown = 0;            // divisions by P: one per step + one for the tail
-    std::vector<int> rotations;   // ascending, distinct, reduced mod N/2
+    int n_keyswitch = 0;            // key MACs (one per key of every step)
+    int n_moddown = 0;              // divisions by P: one per step + one for the tail
+    std::vector<int> rotations;     // ascending, distinct, reduced mod N/2 (the row swap is not among them)
+    std::vector<uint64_t> galois;   // ascending, distinct: the element of every key
 };
 
 // dflt_radix: what radix 0 stands for (the measured default).  Throws std::invalid_argument with a message that names
 // the argument.
-inline SlotSumPlanHost slot_sum_plan(int n_ring, long long step, int count, int radix, int dflt_radix = 2) {
+inline SlotSumPlanHost slot_sum_plan(int n_ring, long long step, int count, int radix, int dflt_radix = 2, int rows = 0) {
     if (n_ring < 4 || (n_ring & (n_ring - 1))) throw std::invalid_argument("slot sum: n_ring must be a power of two >= 4");
     const long long h = n_ring / 2;
     if (count < 1) throw std::invalid_argument("slot sum: count must be >= 1");
@@ -53,6 +62,7 @@ inline SlotSumPlanHost slot_sum_plan(int n_ring, long long step, int count, int 
     p.count = count;
     p.step = step;
     p.radix = radix ? radix : dflt_radix;
+    p.rows = rows ? 1 : 0;
     long long s = ((step % h) + h) % h;
     int n = count;
     auto add = [&](SlotSumStep& st, long long mult, bool tail) {
@@ -60,9 +70,9 @@ inline SlotSumPlanHost slot_sum_plan(int n_ring, long long step, int count, int 
         if (r == 0)
             throw std::invalid_argument("slot sum: step " + std::to_string(step) + " makes a planned rotation a multiple of N/2 (count " +
                                         std::to_string(count) + ")");
-        st.keys.push_back({r, tail});
-        p.n_keyswitch++;
+        st.keys.push_back({galois_of_rotation(r, n_ring), r, tail});
     };
+    if (p.rows) p.steps.push_back({{{2 * (uint64_t)n_ring - 1, 0, false}}});
     while (n > 1) {
         SlotSumStep st;
         if (n & 1) {
@@ -83,69 +93,26 @@ inline SlotSumPlanHost slot_sum_plan(int n_ring, long long step, int count, int 
     }
     p.n_moddown = (int)p.steps.size() + (p.has_tail ? 1 : 0);
     for (const auto& st : p.steps)
-        for (const auto& k : st.keys) p.rotations.push_back(k.rot);
+        for (const auto& k : st.keys) {
+            p.n_keyswitch++;
+            if (k.rot) p.rotations.push_back(k.rot);
+            p.galois.push_back(k.g);
+        }
     std::sort(p.rotations.begin(), p.rotations.end());
     p.rotations.erase(std::unique(p.rotations.begin(), p.rotations.end()), p.rotations.end());
+    std::sort(p.galois.begin(), p.galois.end());
+    p.galois.erase(std::unique(p.galois.begin(), p.galois.end()), p.galois.end());
     return p;
 }
 
-inline unsigned long long galois_of_rotation(int r, int n_ring) {   // 5^r mod 2N
-    const unsigned long long mask = 2 * (unsigned long long)n_ring - 1;
-    unsigned long long e = 1, b = 5;
-    for (; r; r >>= 1, b = b * b & mask)
-        if (r & 1) e = e * b & mask;
-    return e;
-}
-
-// ---- the BFV slot sum  out = sum_{i<count} rot_cols(y, i*step),  y = ct + rot_rows(ct) if rows != 0, else ct.  BFV slots form a
-// 2 x N/2 matrix: the column rotation r is the Galois element 5^(r mod N/2) mod 2N, the row swap is 2N-1.  The plan is the one
-// above, started at x = y; with rows != 0 one more step runs first, one decomposition of ct's c1 with one NEXT key, the key of
-// 2N-1.  Keys are named by their Galois element.
-struct BfvSlotSumKey {
-    unsigned long long g;
-    bool tail;
-};
-struct BfvSlotSumStep {
-    std::vector<BfvSlotSumKey> keys;   // the TAIL key, if any, first
-};
-struct BfvSlotSumPlanHost {
-    int n_ring = 0, count = 0, radix = 4, rows = 0;
-    long long step = 0;
-    std::vector<BfvSlotSumStep> steps;
-    bool has_tail = false;
-    int n_keyswitch = 0, n_moddown = 0;
-    std::vector<unsigned long long> galois;   // ascending, distinct
-};
-
-// Throws std::invalid_argument; the message begins "lsa_bfv_slot_sum" and names the argument.
-inline BfvSlotSumPlanHost bfv_slot_sum_plan(int n_ring, long long step, int count, int radix, int rows, int dflt_radix = 4) {
-    SlotSumPlanHost cols;
+// The BFV entry points' planner.  Throws std::invalid_argument; the message begins "lsa_bfv_slot_sum" and names the argument.
+inline SlotSumPlanHost bfv_slot_sum_plan(int n_ring, long long step, int count, int radix, int rows, int dflt_radix = 4) {
     try {
-        cols = slot_sum_plan(n_ring, step, count, radix, dflt_radix);
+        return slot_sum_plan(n_ring, step, count, radix, dflt_radix, rows);
     } catch (const std::invalid_argument& e) {
         const std::string m = e.what(), pre = "slot sum: ";
         throw std::invalid_argument("lsa_bfv_slot_sum: " + (m.compare(0, pre.size(), pre) == 0 ? m.substr(pre.size()) : m));
     }
-    BfvSlotSumPlanHost p;
-    p.n_ring = n_ring;
-    p.count = count;
-    p.step = step;
-    p.radix = cols.radix;
-    p.rows = rows ? 1 : 0;
-    p.has_tail = cols.has_tail;
-    if (p.rows) p.steps.push_back({{{2 * (unsigned long long)n_ring - 1, false}}});
-    for (const SlotSumStep& st : cols.steps) {
-        BfvSlotSumStep b;
-        for (const SlotSumKey& k : st.keys) b.keys.push_back({galois_of_rotation(k.rot, n_ring), k.tail});
-        p.steps.push_back(b);
-    }
-    p.n_keyswitch = cols.n_keyswitch + p.rows;
-    p.n_moddown = cols.n_moddown + p.rows;
-    for (const auto& st : p.steps)
-        for (const auto& k : st.keys) p.galois.push_back(k.g);
-    std::sort(p.galois.begin(), p.galois.end());
-    p.galois.erase(std::unique(p.galois.begin(), p.galois.end()), p.galois.end());
-    return p;
 }
 
 }  // namespace lsa

@@ -311,13 +311,13 @@ void Dispatcher::run_gpu_bucket(Lane& ln, const std::vector<ComputeNode*>& nodes
             LSA_REQUIRE(!bfv && polys_in == 2 && lvl == 0, "bootstrap expects a degree-1 CKKS ciphertext at level 0");
             Bootstrap& plan = bootstrap_plan(ln);
             LSA_REQUIRE(out_lvl == bootstrap_out_level(plan), "bootstrap: output datum is not at the bootstrap output level");
-            std::map<u64, const Key*> glk;
+            GaloisKeys glk;
             std::vector<const Key*> swk;
             for (size_t i = 2; i < n0->input_nodes.size(); i++) {
                 const DatumNode* kd = n0->input_nodes[i];
                 if (kd->datum_type == TYPE_GALOIS_KEY) {
                     LSA_REQUIRE(kd->fhe_prop && kd->fhe_prop->p, "Galois element missing on the key datum");
-                    glk[kd->fhe_prop->p->galois_element] = &key_of((int)i);
+                    glk.insert(kd->fhe_prop->p->galois_element, &key_of((int)i));
                 } else if (kd->datum_type == TYPE_SWITCH_KEY) {
                     swk.push_back(&key_of((int)i));
                 }

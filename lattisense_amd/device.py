@@ -442,24 +442,58 @@ def bfv_dot_plan(n, q, level, terms):
     return {"max_terms": mt.value, "groups": ng.value, "aux_limbs": al.value}
 
 
-class BootstrapPlan:
+def _key_arrays(glk):
+    """{galois element: key handle} -> (count, elements, handles) as an operator's three key arguments"""
+    n = len(glk)
+    return n, (ctypes.c_uint64 * max(n, 1))(*glk.keys()), (ctypes.c_void_p * max(n, 1))(*[k.value for k in glk.values()])
+
+
+def _fetch(ctype, count, fill):
+    """the list an entry point writes into a caller's array of `count` elements: fill(array, count)"""
+    a = (ctype * max(count, 1))()
+    check(fill(a, count))
+    return [int(x) for x in a[:count]]
+
+
+class _Plan:
+    """The handle of a device plan: `h` (None until the plan exists), released by close() or with the object.  A subclass
+    names its destroy entry point; one that plans on the host makes the handle in _handle(), on first use."""
+    _destroy = None
+
+    def _adopt(self, create):
+        """create(byref(handle)) -> status: the handle becomes self.h"""
+        h = ctypes.c_void_p()
+        check(create(ctypes.byref(h)))
+        self.h = h
+        return h
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(lib(), self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BootstrapPlan(_Plan):
     """Device-side CKKS bootstrapping plan (include/lattisense_amd.h: lsa_bootstrap_*)."""
+    _destroy = "lsa_bootstrap_destroy"
 
     def __init__(self, ctx, cts_depth=4, stc_depth=3, k=16, double_angle=3, message_ratio=256.0, in_scale=2.0 ** 40,
                  out_scale=0.0, log_slots=0, sine_deg=30, arcsine_deg=0):
         self.ctx = ctx
-        h = ctypes.c_void_p()
-        check(lib().lsa_bootstrap_create_ex(ctx.h, cts_depth, stc_depth, k, double_angle, message_ratio, in_scale, out_scale,
-                                            log_slots, sine_deg, arcsine_deg, ctx.stream, ctypes.byref(h)))
-        self.h = h
+        self._adopt(lambda h: lib().lsa_bootstrap_create_ex(ctx.h, cts_depth, stc_depth, k, double_angle, message_ratio, in_scale,
+                                                            out_scale, log_slots, sine_deg, arcsine_deg, ctx.stream, h))
         lv, sc, ng, nm, nc, sp = ctypes.c_int(), ctypes.c_double(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(lib().lsa_bootstrap_info(self.h, ctypes.byref(lv), ctypes.byref(sc), ctypes.byref(ng), ctypes.byref(nm),
                                        ctypes.byref(nc), ctypes.byref(sp)))
         self.out_level, self.out_scale, self.n_matrices = lv.value, sc.value, nm.value
         self.sparse, self.n_cts = bool(sp.value), nc.value
-        g = (ctypes.c_uint64 * ng.value)()
-        check(lib().lsa_bootstrap_galois_elements(self.h, g, ng.value))
-        self.galois_elements = [int(x) for x in g]
+        self.galois_elements = _fetch(ctypes.c_uint64, ng.value, lambda a, n: lib().lsa_bootstrap_galois_elements(self.h, a, n))
         # double hoisting (the default): baby-step / giant-step matrices carry plaintext rows for the special primes too
         self.double_hoist = False
         for i in range(self.n_matrices):
@@ -468,10 +502,8 @@ class BootstrapPlan:
             check(lib().lsa_bootstrap_plaintext_rows(self.h, i, ctypes.byref(rows)))
             self.double_hoist = self.double_hoist or rows.value > lvl.value + 1
 
-    def close(self):
-        if self.h:
-            lib().lsa_bootstrap_destroy(self.h)
-            self.h = None
+    def __del__(self):   # a bootstrap plan is released by close() alone, as it has always been
+        pass
 
     def chebyshev(self):
         return self.evalmod_constants()[0]
@@ -490,25 +522,22 @@ class BootstrapPlan:
         (residues at the special primes too) for a baby-step / giant-step matrix of a double-hoisting plan"""
         lv, n1, nd = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(lib().lsa_bootstrap_matrix_info(self.h, index, ctypes.byref(lv), ctypes.byref(n1), ctypes.byref(nd), None, 0))
-        ks = (ctypes.c_int * nd.value)()
-        check(lib().lsa_bootstrap_matrix_info(self.h, index, None, None, None, ks, nd.value))
+        ks = _fetch(ctypes.c_int, nd.value, lambda a, n: lib().lsa_bootstrap_matrix_info(self.h, index, None, None, None, a, n))
         plains = {}
         rows = ctypes.c_int()
         check(lib().lsa_bootstrap_plaintext_rows(self.h, index, ctypes.byref(rows)))
         for i, k in enumerate(ks):
             pt = np.empty((rows.value, self.ctx.n), dtype=np.uint64)
             check(lib().lsa_bootstrap_plaintext_ext(self.h, index, i, pt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), pt.size))
-            plains[int(k)] = pt
-        return lv.value, n1.value, [int(k) for k in ks], plains
+            plains[k] = pt
+        return lv.value, n1.value, ks, plains
 
     def run(self, in_buf, batch, rlk, glk, swk_dts=None, swk_std=None):
         """in_buf: device [batch][2][1][N]; glk: {galois element: key handle}; returns device [batch][2][out_level+1][N]"""
         n = self.ctx.n
         out = self.ctx.alloc(batch * 2 * (self.out_level + 1) * n)
-        elts = (ctypes.c_uint64 * len(glk))(*glk.keys())
-        keys = (ctypes.c_void_p * len(glk))(*[k.value for k in glk.values()])
         check(lib().lsa_ckks_bootstrap(self.ctx.h, self.h, in_buf.ptr, out.ptr, batch, 2 * n, 2 * (self.out_level + 1) * n, rlk,
-                                       len(glk), elts, keys, swk_dts, swk_std, self.ctx.stream))
+                                       *_key_arrays(glk), swk_dts, swk_std, self.ctx.stream))
         return out
 
     def oracle_plains(self):
@@ -534,15 +563,15 @@ def plan_rotations(period, diag_index, ratio=0.0):
     idx = (ctypes.c_int * len(diag_index))(*[int(k) for k in diag_index])
     n1, cnt = ctypes.c_int(), ctypes.c_int()
     check(lib().lsa_lt_plan_rotations(period, len(diag_index), idx, ratio, ctypes.byref(n1), None, 0, ctypes.byref(cnt)))
-    rot = (ctypes.c_int * max(cnt.value, 1))()
-    check(lib().lsa_lt_plan_rotations(period, len(diag_index), idx, ratio, ctypes.byref(n1), rot, cnt.value, ctypes.byref(cnt)))
-    return n1.value, [int(r) for r in rot[: cnt.value]]
+    rot = _fetch(ctypes.c_int, cnt.value, lambda a, n: lib().lsa_lt_plan_rotations(period, len(diag_index), idx, ratio, ctypes.byref(n1), a, n, None))
+    return n1.value, rot
 
 
-class LinearTransformPlan:
+class LinearTransformPlan(_Plan):
     """A plaintext matrix in diagonal form, encoded for ciphertexts at `level` (include/lattisense_amd.h: lsa_lt_*).
     diags: {k: complex array of length period}, d_k[t] multiplies x[(t + k) mod period], period = 2^log_slots (default: the
     arrays' length)."""
+    _destroy = "lsa_lt_destroy"
 
     def __init__(self, ctx, level, diags, log_slots=None, pt_scale=0, ratio=0, double_hoist=True):
         self.ctx = ctx
@@ -556,34 +585,17 @@ class LinearTransformPlan:
             d = np.asarray(diags[k], dtype=np.complex128)
             vals[i, :, 0], vals[i, :, 1] = d.real, d.imag
         idx = (ctypes.c_int * len(ks))(*[int(k) for k in ks])
-        h = ctypes.c_void_p()
-        check(lib().lsa_lt_create(ctx.h, level, period.bit_length() - 1, len(ks), idx,
-                                  vals.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(pt_scale), float(ratio),
-                                  int(bool(double_hoist)), ctx.stream, ctypes.byref(h)))
-        self.h = h
+        self._adopt(lambda h: lib().lsa_lt_create(ctx.h, level, period.bit_length() - 1, len(ks), idx,
+                                                  vals.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(pt_scale), float(ratio),
+                                                  int(bool(double_hoist)), ctx.stream, h))
         lv, pe, nd, n1, rows, ng, dh, sc = (ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(),
                                             ctypes.c_int(), ctypes.c_int(), ctypes.c_double())
         check(lib().lsa_lt_info(self.h, ctypes.byref(lv), ctypes.byref(pe), ctypes.byref(nd), ctypes.byref(n1), ctypes.byref(rows),
                                 ctypes.byref(ng), ctypes.byref(dh), ctypes.byref(sc)))
         self.level, self.period, self.n1, self.rows = lv.value, pe.value, n1.value, rows.value
         self.double_hoist, self.pt_scale = bool(dh.value), sc.value
-        kk = (ctypes.c_int * nd.value)()
-        check(lib().lsa_lt_diagonals(self.h, kk, nd.value))
-        self.diagonals = [int(k) for k in kk]
-        g = (ctypes.c_uint64 * max(ng.value, 1))()
-        check(lib().lsa_lt_galois_elements(self.h, g, ng.value))
-        self.galois_elements = [int(x) for x in g[: ng.value]]
-
-    def close(self):
-        if self.h:
-            lib().lsa_lt_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.diagonals = _fetch(ctypes.c_int, nd.value, lambda a, n: lib().lsa_lt_diagonals(self.h, a, n))
+        self.galois_elements = _fetch(ctypes.c_uint64, ng.value, lambda a, n: lib().lsa_lt_galois_elements(self.h, a, n))
 
     def oracle_plains(self):
         """{k (reduced mod period): plaintext [rows][N]}: what oracle/ckks_bootstrap.py linear_transform takes as `plains`"""
@@ -601,10 +613,8 @@ class LinearTransformPlan:
         lo = self.level if rescale else self.level + 1
         if out is None:
             out = self.ctx.alloc(max(batch, 1) * 2 * lo * n)
-        elts = (ctypes.c_uint64 * max(len(glk), 1))(*glk.keys())
-        keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
         check(lib().lsa_ckks_linear_transform(self.ctx.h, self.h, in_buf.ptr, out.ptr, batch, 2 * (self.level + 1) * n, 2 * lo * n,
-                                              int(bool(rescale)), len(glk), elts, keys, self.ctx.stream))
+                                              int(bool(rescale)), *_key_arrays(glk), self.ctx.stream))
         return out
 
 
@@ -621,11 +631,12 @@ def bfv_lt_plan(n, period, diag_index, ratio=0.0):
             "moddowns": len([g for g in giants if g]) + 1}
 
 
-class BfvLinearTransformPlan:
+class BfvLinearTransformPlan(_Plan):
     """A plaintext matrix in diagonal form over both rows of the BFV slot matrix, encoded for ciphertexts at `level`
     (include/lattisense_amd.h: lsa_bfv_lt_*).  diags: {k: integer array [2][period] (one vector per slot row) or [period] (the
     same vector on both rows)}, values in [0, t): out_row[c] = sum_k d_k,row[c mod period] * x_row[(c + k) mod N/2] mod t.
     Planning needs no GPU (`.n1`, `.rotations`, `.galois_elements`); the device plan is created on first use."""
+    _destroy = "lsa_bfv_lt_destroy"
 
     def __init__(self, ctx, level, diags, period=None, ratio=0.0):
         self.ctx, self.level, self.ratio = ctx, level, ratio
@@ -648,11 +659,9 @@ class BfvLinearTransformPlan:
     def _handle(self):
         if self.h is None:
             idx = (ctypes.c_int * len(self._index))(*self._index)
-            h = ctypes.c_void_p()
-            check(lib().lsa_bfv_lt_create(self.ctx.h, self.level, self.period, len(self._index), idx,
-                                          self._values.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(self.ratio), self.ctx.stream,
-                                          ctypes.byref(h)))
-            self.h = h
+            self._adopt(lambda h: lib().lsa_bfv_lt_create(self.ctx.h, self.level, self.period, len(self._index), idx,
+                                                          self._values.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), float(self.ratio),
+                                                          self.ctx.stream, h))
             rows = ctypes.c_int()
             check(lib().lsa_bfv_lt_info(self.h, None, None, None, None, None, None, ctypes.byref(rows), None, None))
             self.rows = rows.value
@@ -665,23 +674,9 @@ class BfvLinearTransformPlan:
         check(lib().lsa_bfv_lt_info(h, *[ctypes.byref(x) for x in v]))
         names = ("level", "period", "n_diag", "n1", "n_baby", "n_giant", "rows", "n_galois", "n_moddown")
         out = {k: x.value for k, x in zip(names, v)}
-        kk = (ctypes.c_int * out["n_diag"])()
-        check(lib().lsa_bfv_lt_diagonals(h, kk, out["n_diag"]))
-        g = (ctypes.c_uint64 * max(out["n_galois"], 1))()
-        check(lib().lsa_bfv_lt_galois_elements(h, g, out["n_galois"]))
-        out["diagonals"], out["galois_elements"] = [int(k) for k in kk], [int(x) for x in g[: out["n_galois"]]]
+        out["diagonals"] = _fetch(ctypes.c_int, out["n_diag"], lambda a, n: lib().lsa_bfv_lt_diagonals(h, a, n))
+        out["galois_elements"] = _fetch(ctypes.c_uint64, out["n_galois"], lambda a, n: lib().lsa_bfv_lt_galois_elements(h, a, n))
         return out
-
-    def close(self):
-        if self.h:
-            lib().lsa_bfv_lt_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def oracle_plains(self):
         """{k (reduced mod period): extended plaintext [rows][N]}: what tests/bfv_lt_model.py linear_transform takes as `plains`"""
@@ -701,9 +696,7 @@ class BfvLinearTransformPlan:
         h = self._handle()
         if out is None:
             out = self.ctx.alloc(max(batch, 1) * max(sout, w))
-        elts = (ctypes.c_uint64 * max(len(glk), 1))(*glk.keys())
-        keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
-        check(lib().lsa_bfv_linear_transform(self.ctx.h, h, in_buf.ptr, out.ptr, batch, sin, sout, len(glk), elts, keys, self.ctx.stream))
+        check(lib().lsa_bfv_linear_transform(self.ctx.h, h, in_buf.ptr, out.ptr, batch, sin, sout, *_key_arrays(glk), self.ctx.stream))
         return out
 
 
@@ -713,15 +706,15 @@ def plan_slot_sum(n, step, count, radix=0):
     ns, nk, nm, cnt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     args = (int(n), int(step), int(count), int(radix), ctypes.byref(ns), ctypes.byref(nk), ctypes.byref(nm))
     check(lib().lsa_slot_sum_plan(*args, None, 0, ctypes.byref(cnt)))
-    rot = (ctypes.c_int * max(cnt.value, 1))()
-    check(lib().lsa_slot_sum_plan(*args, rot, cnt.value, ctypes.byref(cnt)))
-    return {"steps": ns.value, "keyswitches": nk.value, "moddowns": nm.value, "rotations": [int(r) for r in rot[: cnt.value]]}
+    rot = _fetch(ctypes.c_int, cnt.value, lambda a, n: lib().lsa_slot_sum_plan(*args, a, n, None))
+    return {"steps": ns.value, "keyswitches": nk.value, "moddowns": nm.value, "rotations": rot}
 
 
-class SlotSumPlan:
+class SlotSumPlan(_Plan):
     """out = sum_{i<count} rot(ct, i*step) on ciphertexts at `level` (include/lattisense_amd.h: lsa_slot_sum_*); Replicate is
     step = -batch_size.  Planning needs no GPU (`.rotations`, `.galois_elements`, the counts); the device plan is made by the
     first run."""
+    _destroy = "lsa_slot_sum_destroy"
 
     def __init__(self, ctx, level, step, count, radix=0):
         self.ctx, self.level, self.step, self.count = ctx, int(level), int(step), int(count)
@@ -735,27 +728,13 @@ class SlotSumPlan:
 
     def _handle(self):
         if self.h is None:
-            h = ctypes.c_void_p()   # (a context without a device has no handle: the library refuses, there is no CPU path)
-            check(lib().lsa_slot_sum_create(self.ctx.h, self.level, self.step, self.count, self.radix, ctypes.byref(h)))
-            self.h = h
+            # (a context without a device has no handle: the library refuses, there is no CPU path)
+            self._adopt(lambda h: lib().lsa_slot_sum_create(self.ctx.h, self.level, self.step, self.count, self.radix, h))
             rx, ng = ctypes.c_int(), ctypes.c_int()
             check(lib().lsa_slot_sum_info(self.h, None, None, ctypes.byref(rx), None, None, None, ctypes.byref(ng)))
-            g = (ctypes.c_uint64 * max(ng.value, 1))()
-            check(lib().lsa_slot_sum_galois_elements(self.h, g, ng.value))
-            assert [int(x) for x in g[: ng.value]] == self.galois_elements
+            assert _fetch(ctypes.c_uint64, ng.value, lambda a, n: lib().lsa_slot_sum_galois_elements(self.h, a, n)) == self.galois_elements
             self.radix = rx.value
         return self.h
-
-    def close(self):
-        if self.h:
-            lib().lsa_slot_sum_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, in_buf, batch, glk, out=None):
         """in_buf: device [batch][2][level+1][N]; glk: {galois element: key handle}; returns device [batch][2][level+1][N]
@@ -766,9 +745,7 @@ class SlotSumPlan:
         if out is None:
             out = self.ctx.alloc(max(batch, 1) * words)
         check(lib().lsa_slot_sum_set_multi_mac(h, int(bool(self.multi_mac))))
-        elts = (ctypes.c_uint64 * max(len(glk), 1))(*glk.keys())
-        keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
-        check(lib().lsa_ckks_slot_sum(self.ctx.h, h, in_buf.ptr, out.ptr, batch, words, words, len(glk), elts, keys, self.ctx.stream))
+        check(lib().lsa_ckks_slot_sum(self.ctx.h, h, in_buf.ptr, out.ptr, batch, words, words, *_key_arrays(glk), self.ctx.stream))
         return out
 
 
@@ -778,15 +755,15 @@ def bfv_slot_sum_plan(n, step, count, radix=0, rows=0):
     ns, nk, nm, cnt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     args = (int(n), int(step), int(count), int(radix), int(bool(rows)), ctypes.byref(ns), ctypes.byref(nk), ctypes.byref(nm))
     check(lib().lsa_bfv_slot_sum_plan(*args, None, 0, ctypes.byref(cnt)))
-    g = (ctypes.c_uint64 * max(cnt.value, 1))()
-    check(lib().lsa_bfv_slot_sum_plan(*args, g, cnt.value, ctypes.byref(cnt)))
-    return {"steps": ns.value, "keyswitches": nk.value, "moddowns": nm.value, "galois_elements": [int(e) for e in g[: cnt.value]]}
+    g = _fetch(ctypes.c_uint64, cnt.value, lambda a, n: lib().lsa_bfv_slot_sum_plan(*args, a, n, None))
+    return {"steps": ns.value, "keyswitches": nk.value, "moddowns": nm.value, "galois_elements": g}
 
 
-class BfvSlotSumPlan:
+class BfvSlotSumPlan(_Plan):
     """out = sum_{i<count} rot_cols(y, i*step), y = ct + rot_rows(ct) if rows, on coefficient-domain BFV ciphertexts at `level`
     (include/lattisense_amd.h: lsa_bfv_slot_sum_*).  Planning needs no GPU (`.galois_elements`, the counts); the device plan is
     made by the first run.  gather: None = the library's default, else the tail to run (False: the plain form)."""
+    _destroy = "lsa_bfv_slot_sum_destroy"
 
     def __init__(self, ctx, level, step, count, radix=0, rows=0):
         self.ctx, self.level, self.step, self.count, self.rows = ctx, int(level), int(step), int(count), int(bool(rows))
@@ -799,14 +776,11 @@ class BfvSlotSumPlan:
 
     def _handle(self):
         if self.h is None:
-            h = ctypes.c_void_p()   # (a context without a device has no handle: the library refuses, there is no CPU path)
-            check(lib().lsa_bfv_slot_sum_create(self.ctx.h, self.level, self.step, self.count, self.radix, self.rows, ctypes.byref(h)))
-            self.h = h
+            # (a context without a device has no handle: the library refuses, there is no CPU path)
+            self._adopt(lambda h: lib().lsa_bfv_slot_sum_create(self.ctx.h, self.level, self.step, self.count, self.radix, self.rows, h))
             rx, ng = ctypes.c_int(), ctypes.c_int()
             check(lib().lsa_bfv_slot_sum_info(self.h, None, None, ctypes.byref(rx), None, None, None, None, ctypes.byref(ng), None))
-            g = (ctypes.c_uint64 * max(ng.value, 1))()
-            check(lib().lsa_bfv_slot_sum_galois_elements(self.h, g, ng.value))
-            assert [int(x) for x in g[: ng.value]] == self.galois_elements
+            assert _fetch(ctypes.c_uint64, ng.value, lambda a, n: lib().lsa_bfv_slot_sum_galois_elements(self.h, a, n)) == self.galois_elements
             self.radix = rx.value
         return self.h
 
@@ -814,17 +788,6 @@ class BfvSlotSumPlan:
         ga = ctypes.c_int()
         check(lib().lsa_bfv_slot_sum_info(self._handle(), None, None, None, None, None, None, None, None, ctypes.byref(ga)))
         return bool(ga.value)
-
-    def close(self):
-        if self.h:
-            lib().lsa_bfv_slot_sum_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, in_buf, batch, glk, out=None):
         """in_buf: device [batch][2][level+1][N], coefficient domain; glk: {galois element: key handle}; returns device
@@ -835,9 +798,7 @@ class BfvSlotSumPlan:
             check(lib().lsa_bfv_slot_sum_set_gather(h, int(bool(self.gather))))
         if out is None:
             out = self.ctx.alloc(max(batch, 1) * words)
-        elts = (ctypes.c_uint64 * max(len(glk), 1))(*glk.keys())
-        keys = (ctypes.c_void_p * max(len(glk), 1))(*[k.value for k in glk.values()])
-        check(lib().lsa_bfv_slot_sum(self.ctx.h, h, in_buf.ptr, out.ptr, batch, words, words, len(glk), elts, keys, self.ctx.stream))
+        check(lib().lsa_bfv_slot_sum(self.ctx.h, h, in_buf.ptr, out.ptr, batch, words, words, *_key_arrays(glk), self.ctx.stream))
         return out
 
 
@@ -853,18 +814,17 @@ def plan_polynomial(coeffs, level, basis="chebyshev", log_baby=0, interval=False
     return {"depth": d.value, "log_baby": b.value, "mults": mu.value, "leaves": lv.value, "leaf_launches": la.value}
 
 
-class PolynomialPlan:
+class PolynomialPlan(_Plan):
     """sum_k coeffs[k] T_k(u) (basis "chebyshev") or sum_k coeffs[k] u^k ("monomial") on ciphertexts at `level` and scale
     `scale_in`, u = x mapped from `interval` to [-1, 1] (include/lattisense_amd.h: lsa_poly_*)."""
+    _destroy = "lsa_poly_destroy"
 
     def __init__(self, ctx, coeffs, level, scale_in, basis="chebyshev", interval=(-1, 1), scale_out=None, log_baby=0):
         self.ctx = ctx
         self.h = None
         cf = (ctypes.c_double * len(coeffs))(*[float(x) for x in coeffs])
-        h = ctypes.c_void_p()
-        check(lib().lsa_poly_create(ctx.h, BASES[basis], len(coeffs), cf, float(interval[0]), float(interval[1]), int(level),
-                                    float(scale_in), float(scale_out or 0.0), int(log_baby), ctypes.byref(h)))
-        self.h = h
+        self._adopt(lambda h: lib().lsa_poly_create(ctx.h, BASES[basis], len(coeffs), cf, float(interval[0]), float(interval[1]), int(level),
+                                                    float(scale_in), float(scale_out or 0.0), int(log_baby), h))
         li, lo, d, b, mu, lv, la, nc = (ctypes.c_int() for _ in range(8))
         sc = ctypes.c_double()
         check(lib().lsa_poly_info(self.h, ctypes.byref(li), ctypes.byref(lo), ctypes.byref(sc), ctypes.byref(d), ctypes.byref(b),
@@ -873,22 +833,9 @@ class PolynomialPlan:
         self.mults, self.leaves, self.leaf_launches, self.n_constants = mu.value, lv.value, la.value, nc.value
         self.basis, self.scale_in = basis, float(scale_in)
 
-    def close(self):
-        if self.h:
-            lib().lsa_poly_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def constants(self):
         """every integer constant of the plan, in the planner's order (what tests/poly_model.py consumes)"""
-        k = (ctypes.c_longlong * max(self.n_constants, 1))()
-        check(lib().lsa_poly_constants(self.h, k, self.n_constants))
-        return [int(x) for x in k[: self.n_constants]]
+        return _fetch(ctypes.c_longlong, self.n_constants, lambda a, n: lib().lsa_poly_constants(self.h, a, n))
 
     def run(self, in_buf, batch, rlk, out=None):
         """in_buf: device [batch][2][level_in+1][N]; rlk: relinearisation key handle; returns device [batch][2][level_out+1][N]"""
