@@ -827,7 +827,7 @@ int lsa_bfv_linear_transform(lsa_context ctx, lsa_bfv_lt lt, const uint64_t* in,
     });
 }
 
-// ---- CKKS slot sum (slot_sum.h, ops.hip slot_sum_run)
+// ---- CKKS slot sum (slot_sum.h, slot_sum.hip slot_sum_run)
 struct lsa_slot_sum_st : PlanHandle<SlotSum> {};
 // the counts the plan and info entry points of both slot sums report (null: not asked for)
 static void slot_sum_counts(const SlotSumPlanHost& p, int* count, int* radix, int* n_steps, int* n_keyswitch, int* n_moddown,
@@ -881,7 +881,7 @@ int lsa_ckks_slot_sum(lsa_context ctx, lsa_slot_sum plan, const uint64_t* in, ui
     });
 }
 
-// ---- BFV slot sum (slot_sum.h, ops.hip bfv_slot_sum_run)
+// ---- BFV slot sum (slot_sum.h, slot_sum.hip bfv_slot_sum_run)
 struct lsa_bfv_slot_sum_st : PlanHandle<BfvSlotSum> {};
 int lsa_bfv_slot_sum_plan(int n_ring, long long step, int count, int radix, int rows, int* n_steps, int* n_keyswitch, int* n_moddown,
                           uint64_t* galois_elements, int capacity, int* n_galois) {

@@ -1795,9 +1795,11 @@ static void launch_ks_mac_kb(int beta, dim3 grid, hipStream_t s, const KsMacArgs
 // map of the rotation's inverse element, base = the ciphertext whose c0 enters (see KsMacArgs); base == nullptr: no P * c0 is
 // added, the result is perm(acc)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, const Key& key,
-                   u64* acc, long long sacc, int batch, hipStream_t s, bool unfused_only, const u32* scatter, const u64* base, long long sbase,
-                   const TensorFold* fold, bool accumulate) {
+                   const KsMacDst& dst, int batch, hipStream_t s, bool unfused_only, const TensorFold* fold) {
     if (batch <= 0) return;
+    const u32* scatter = dst.scatter;
+    const u64* base = dst.base;
+    const bool accumulate = dst.accumulate;
     KsMacArgs g{};
     LSA_REQUIRE(!accumulate || scatter, "key MAC: only the extended output accumulates");
     LSA_REQUIRE(!scatter || !unfused_only, "key MAC: the extended output covers every target limb");
@@ -1815,15 +1817,15 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
         g.pm = c.pmodq_vec(level);
         g.scatter = scatter;
         g.base = base;
-        g.sbase = sbase;
+        g.sbase = dst.sbase;
     }
     g.cx = cx;
     g.ext = ext;
     g.key = key.data;
-    g.acc = acc;
+    g.acc = dst.out;
     g.scx = scx;
     g.sext = sext;
-    g.sacc = sacc;
+    g.sacc = dst.sout;
     g.mods = c.d_mods;
     g.logn = c.logn;
     g.L = level + 1;

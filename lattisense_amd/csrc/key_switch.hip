@@ -1,0 +1,388 @@
+// key_switch.hip — the key switch (key_switch.h): the tile's decomposition, key MACs and ModDown, the rescale, the rotations'
+// index maps and the tiling, built from the kernels in kernels.hip.  Algorithms follow the CPU path the results must agree with
+// (Lattigo v4, restated in oracle/ls_oracle.c).
+#include "key_switch.h"
+
+namespace lsa {
+
+RowMap rm_seq(int count, int first) {
+    RowMap r;
+    LSA_REQUIRE(count >= 1 && count <= LSA_MAX_PERIOD, "row map too long");
+    r.period = count;
+    for (int i = 0; i < count; i++) r.mod_of[i] = (unsigned char)(first + i);
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------ key switch
+// step 5, the division by P of a polynomial pair over Q_level u P (acc: [2][L+k][N] per batch item, NTT domain; its P rows --
+// and, for the merged rescale, its last Q row -- are transformed in place), conv: 2L rows of scratch per batch item
+static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
+    LSA_REQUIRE(!o.scatter || (c.fuse_tails && o.form == KsOut::NTT), "scattered ModDown store: fused tails, NTT-domain output");
+    LSA_REQUIRE(!o.rmac || o.scatter, "rotate-and-MAC tail: needs the rotation's index map");
+    LSA_REQUIRE(!o.coeff_gather || o.form == KsOut::COEFF, "gathered ModDown tail: coefficient-domain output");
+    LSA_REQUIRE(!o.slot_tail || (o.form == KsOut::COEFF && !o.coeff_gather && o.base && o.base_polys == 2 && o.base_rpp == level + 1),
+                "slot-sum ModDown tail: coefficient-domain output on a whole ciphertext");
+    LSA_REQUIRE(o.form != KsOut::RESCALE || (c.fuse_tails && level >= 1 && ((o.base && o.base_polys == 2) || (!o.base && o.base_polys == 0))),
+                "merged ModDown+rescale: unsupported shape");
+    const bool coeff_out = o.form == KsOut::COEFF, rs = o.form == KsOut::RESCALE;
+    const long long N = c.n;
+    const int L = level + 1, np = c.np, T = L + np;
+    const long long s_conv = 2LL * L * N;
+    // 5. ModDown: P-part out of NTT, centred exact conversion P -> Q, back to NTT, (accQ - conv) * P^-1 (+ base).
+    //    coeff_out (BFV: the result is wanted in the coefficient domain and `base` is given there): every row of acc leaves
+    //    the NTT domain once and the tail runs on coefficients -- INTT((acc - NTT(conv)) * P^-1) == (INTT(acc) - conv) * P^-1
+    //    residue for residue, 2(L+k) transforms instead of 2k + 2L + 2L.
+    {
+        RowMap rm;
+        rm.period = 2 * T;
+        for (int h = 0; h < 2; h++)
+            for (int tl = 0; tl < T; tl++)
+                rm.mod_of[h * T + tl] = tl >= L ? (unsigned char)c.p_mod(tl - L)
+                                                : (coeff_out ? (unsigned char)tl
+                                                             : (rs && tl == level ? (unsigned char)level : LSA_ROW_SKIP));
+        launch_ntt(c, acc, acc, nb, s_acc, 2 * T, rm, true, s);
+    }
+    {
+        std::vector<int> src, dst;
+        BaseConvRows rows{};
+        for (int i = 0; i < np; i++) {
+            rows.src_row[i] = L + i;
+            src.push_back(c.p_mod(i));
+        }
+        for (int j = 0; j < L; j++) {
+            rows.dst_row[j] = j;
+            dst.push_back(j);
+        }
+        const BaseConvPlan* k = c.baseconv(src, dst, true, rs);
+        for (int h = 0; h < 2; h++)
+            launch_baseconv(c, k, rows, acc + (size_t)h * T * N, conv + (size_t)h * L * N, nb, s_acc, s_conv, s);
+    }
+    if (coeff_out) {
+        if (o.slot_tail)
+            launch_bfv_slot_tail(c, level, *o.slot_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
+        else if (o.coeff_gather)
+            launch_moddown_final_perm(c, level, o.coeff_gather, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp,
+                                      o.base_polys, o.p, o.sp, nb, s);
+        else
+            launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp, o.base_polys, o.p, o.sp, nb, s);
+        return;
+    }
+    if (rs) {
+        // base_polys == 0: the tensor fold -- P * base is already in acc's Q rows (TensorFold), so INTT(acc_l) * P^-1 carries
+        // INTT(base_l) and the tails below run without base
+        const int l = level;
+        // t[h] = (INTT(acc[h][l]) - conv[h][l]) * P^-1 + INTT(base[h][l]) -> p[h][l].  base is the caller's scratch here
+        // (the tensor output): its last limbs are transformed in place, nothing reads them in NTT form afterwards.
+        if (o.base) {
+            u64* base_rw = const_cast<u64*>(o.base);
+            RowMap rb;
+            rb.period = 1;
+            rb.mod_of[0] = (unsigned char)l;
+            rb.row0 = l;
+            rb.row_step = o.base_rpp;
+            launch_ntt(c, base_rw, base_rw, nb, o.sbase, o.sbase, 2, rb, true, s);
+        }
+        const unsigned char lm[1] = {(unsigned char)l};
+        launch_sub_mul_general(c, 2, 1, lm, c.pinv_vec(level) + l, acc + (long long)l * N, s_acc, T, conv + (long long)l * N,
+                               s_conv, L, o.base ? o.base + (long long)l * N : nullptr, o.sbase, o.base_rpp, o.base_polys,
+                               o.p + (long long)l * N, o.sp, L, nb, s);
+        // every other limb: in = conv_j*P^-1 + lift_j(t), out = (acc_j*P^-1 - NTT(in) + base_j) * q_l^-1
+        RowMap rmo;
+        rmo.period = 2 * L;
+        for (int h = 0; h < 2; h++)
+            for (int j = 0; j < L; j++) rmo.mod_of[h * L + j] = j == l ? LSA_ROW_SKIP : (unsigned char)j;
+        NttFusion fb;
+        fb.pro = 2;
+        fb.epi = 2;
+        fb.limbs = L;
+        fb.ql_mod = l;
+        fb.last = o.p + (long long)l * N;
+        fb.last_stride = o.sp;
+        fb.last_rpp = L;
+        fb.a = acc;
+        fb.a_stride = s_acc;
+        fb.a_rpp = T;
+        fb.base = o.base;
+        fb.base_stride = o.sbase;
+        fb.base_rpp = o.base_rpp;
+        fb.base_polys = o.base_polys;
+        fb.k = c.pinv_vec(level);
+        fb.k2 = c.qlinv_vec(level);
+        fb.out = o.rs.out;
+        fb.out_stride = o.rs.sout;
+        fb.out_rpp = level;
+        launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rmo, false, s, &fb);
+    } else if (c.fuse_tails) {
+        // forward NTT of conv with the ModDown tail fused into its last-pass store: the transformed conv is consumed in
+        // registers ((acc_Q - conv) * P^-1 + base) and never written
+        NttFusion fz;
+        fz.epi = 1;
+        fz.limbs = L;
+        fz.a = acc;
+        fz.a_stride = s_acc;
+        fz.a_rpp = T;
+        fz.base = o.base;
+        fz.base_stride = o.sbase;
+        fz.base_rpp = o.base_rpp;
+        fz.base_polys = o.base_polys;
+        fz.k = c.pinv_vec(level);
+        fz.out = o.p;
+        fz.out_stride = o.sp;
+        fz.out_rpp = L;
+        fz.scatter = o.scatter;
+        if (o.rmac) {
+            fz.epi = 4;
+            fz.pt = o.rmac->pt;
+            fz.pt_stride = o.rmac->spt;
+            fz.accumulate = o.rmac->accumulate;
+        }
+        launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rm_seq(L), false, s, &fz);
+    } else {
+        launch_ntt(c, conv, conv, nb, s_conv, 2 * L, rm_seq(L), false, s);
+        launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp, o.base_polys, o.p, o.sp, nb, s);
+    }
+}
+
+// one key per decomposition (relinearisation, a single rotation, a generic switch): the extension transform's second pass
+// and the key MAC run as one kernel where the shape allows (k_ntt_r16_ksmac) and some target limb takes it
+bool ks_fuse_mac(const Context& c, int level, const Key& key) {
+    const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
+    if (!ks_fused_enabled(c) || !ks_fused_engines(c) || (c.fp64_ntt && !key.fp) || beta * T > LSA_MAX_PERIOD || T > 64) return false;
+    for (int tl = 0; tl < T; tl++)
+        if (ks_fused_limb(c, L, tl)) return true;
+    return false;
+}
+
+size_t KsTile::rows(const Context& c, int level, KsSource::Form form) {
+    LSA_REQUIRE(c.np >= 1, "key switching needs at least one special prime");
+    const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
+    return (form == KsSource::COEFF ? (size_t)L : 0) + (size_t)L + (size_t)beta * T + 2 * (size_t)T + 2 * (size_t)L;
+}
+
+KsTile::KsTile(Context& c_, int level_, int nb_, u64* ws, hipStream_t s_, const Key* single_key, KsSource::Form form, int tb)
+    : c(c_), level(level_), nb(nb_), s(s_), key(single_key) {
+    LSA_REQUIRE(c.np >= 1, "key switching needs at least one special prime");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    const long long N = c.n;
+    L = level + 1;
+    T = L + c.np;
+    beta = ceil_div(L, c.np);
+    fused = key && ks_fuse_mac(c, level, *key);
+    s_cxi = (long long)L * N;
+    s_ext = (long long)beta * T * N;
+    s_acc = 2LL * T * N;
+    s_conv = 2LL * L * N;
+    cxn = form == KsSource::COEFF ? ws : nullptr;
+    cxi = cxn ? ws + (size_t)(tb ? tb : nb) * s_cxi : ws;
+    ext = cxi + (size_t)nb * s_cxi;
+    acc = ext + (size_t)nb * s_ext;
+    conv = acc + (size_t)nb * s_acc;
+}
+
+void KsTile::decompose(const KsSource& source) {
+    LSA_REQUIRE((source.form == KsSource::COEFF) == (cxn != nullptr), "key switch: the tile was laid out for another form of source");
+    src = source;
+    const long long N = c.n;
+    const int np = c.np;
+    if (src.form == KsSource::COEFF) {   // the MAC's own-digit operand, into the tile's own rows
+        launch_ntt(c, src.coef, cxn, nb, src.s_coef, s_cxi, L, rm_seq(L), false, s);
+        src.ntt = cxn;
+        src.s_ntt = s_cxi;
+    } else if (src.form == KsSource::PRODUCT) {   // (the MAC takes the own digit from a and b: its cx is not read)
+        src.ntt = cxi;
+        src.s_ntt = s_cxi;
+    }
+    const u64* cx_coef = src.coef;
+    // 1. cx out of the NTT domain
+    if (src.prod) {
+        LSA_REQUIRE(!cx_coef, "key switch: a product source has no coefficient-domain copy");
+        const TensorFold* prod = src.prod;
+        NttFusion fz;
+        fz.pro = 3;
+        fz.limbs = L;
+        fz.a = prod->a + prod->pa;   // the second polynomials a1, b1
+        fz.a_stride = prod->sa;
+        fz.a_rpp = (int)(prod->pa >> c.logn);
+        fz.b = prod->b + prod->pb;
+        fz.b_stride = prod->sb;
+        fz.b_rpp = (int)(prod->pb >> c.logn);
+        launch_ntt(c, cxi, cxi, nb, s_cxi, s_cxi, L, rm_seq(L), true, s, &fz);
+    } else if (!cx_coef) {
+        launch_ntt(c, src.ntt, cxi, nb, src.s_ntt, s_cxi, L, rm_seq(L), true, s);
+    }
+    const u64* conv_src = cx_coef ? cx_coef : cxi;
+    const long long s_src = cx_coef ? src.s_coef : s_cxi;
+    // 2. per digit: exact conversion of the digit's limbs to every other limb of Q u P.  A digit with ONE source limb q_s
+    //    needs none: (Q_d/q_s)^-1 = 1, y = x, v = 0, every target row is x mod p_t -- the load of its extension transform
+    //    lifts it (fz_pro = 4) and the rows are never stored in the coefficient domain (lsa_set_modup_lift(ctx, 0): converted as the others).
+    //    v = 0 holds for the conversion as it is computed -- v = (int)RN(double(y) / double(q_s)) -- while q_s < 2^53: y and q_s
+    //    are exact doubles and y / q_s <= 1 - 1/q_s < 1 - 2^-53 rounds below 1.  A larger q_s has residues next to q_s whose
+    //    quotient rounds to 1.0 (the conversion then yields y - q_s): such a digit keeps the conversion kernel, residue for residue.
+    const bool lift_on = c.modup_lift != 0;
+    auto lifted = [&](int d) { return lift_on && std::min(d * np + np, L) - d * np == 1 && (c.T.mods[d * np].q >> 53) == 0; };
+    bool any_lift = false, any_conv = false;
+    for (int d = 0; d < beta; d++) {
+        if (lifted(d)) {
+            any_lift = true;
+            continue;
+        }
+        any_conv = true;
+        const int d0 = d * np, d1 = std::min(d0 + np, L);
+        std::vector<int> from, dst;
+        BaseConvRows rows{};
+        for (int i = d0; i < d1; i++) {
+            rows.src_row[i - d0] = i;
+            from.push_back(i);
+        }
+        for (int tl = 0; tl < T; tl++) {
+            if (tl >= d0 && tl < d1) continue;
+            rows.dst_row[dst.size()] = d * T + tl;
+            dst.push_back(c.qp_mod(L, tl));
+        }
+        launch_baseconv(c, c.baseconv(from, dst, false), rows, conv_src, ext, nb, s_src, s_ext, s);
+    }
+    // 3. extended limbs into the NTT domain (the digit's own limbs are taken from cx directly by the MAC)
+    auto own = [&](int d, int tl) { return tl >= d * np && tl < std::min((d + 1) * np, L); };
+    NttFusion lf;   // the lifted digits: digit d reads row d * np of conv_src (only read), modulus index d * np
+    lf.pro = 4;
+    lf.limbs = T;
+    lf.last = conv_src;
+    lf.last_stride = s_src;
+    lf.last_rpp = np;
+    lf.ql_mod = 0;
+    if (beta * T <= LSA_MAX_PERIOD) {
+        RowMap rm, rl;
+        rm.period = rl.period = beta * T;
+        for (int d = 0; d < beta; d++)
+            for (int tl = 0; tl < T; tl++) {
+                const unsigned char m = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
+                rm.mod_of[d * T + tl] = lifted(d) ? LSA_ROW_SKIP : m;
+                rl.mod_of[d * T + tl] = lifted(d) ? m : LSA_ROW_SKIP;
+            }
+        if (any_conv) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, fused ? 1 : 3);
+        if (any_lift) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rl, false, s, &lf, fused ? 1 : 3);
+        if (!fused) return;
+        // the target limbs that do not take the fused kernel get their second pass here (stand-alone MAC later)
+        bool any = false;
+        for (int i = 0; i < beta * T; i++) {
+            rm.mod_of[i] = own(i / T, i % T) || ks_fused_limb(c, L, i % T) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, i % T);
+            any |= rm.mod_of[i] != LSA_ROW_SKIP;
+        }
+        if (any) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, 2);
+        return;
+    }
+    for (int d = 0; d < beta; d++) {   // (never fused: ks_fuse_mac needs beta * T <= LSA_MAX_PERIOD)
+        RowMap rm;
+        rm.period = T;
+        for (int tl = 0; tl < T; tl++) rm.mod_of[tl] = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
+        lf.last = conv_src + (size_t)d * np * N;   // (one digit per launch: polynomial 0 of the launch is digit d)
+        lf.ql_mod = d * np;
+        launch_ntt(c, ext + (size_t)d * T * N, ext + (size_t)d * T * N, nb, s_ext, s_ext, T, rm, false, s, lifted(d) ? &lf : nullptr);
+    }
+}
+
+void KsTile::mac(const Key& k) {
+    LSA_REQUIRE(src.ntt, "key MAC: decompose() has not run on this tile");
+    const TensorFold* fold = src.prod;
+    if (!fused) {
+        launch_ks_mac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, {acc, s_acc}, nb, s, false, fold);
+        return;
+    }
+    LSA_REQUIRE(&k == key, "fused key MAC: the tile was planned for another key");
+    LSA_REQUIRE(launch_ntt_ksmac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, acc, s_acc, nb, s, fold), "fused key MAC: shape not covered");
+    launch_ks_mac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, {acc, s_acc}, nb, s, true, fold);
+}
+
+void KsTile::mac_ext(const Key& k, const KsMacDst& dst) {
+    LSA_REQUIRE(src.ntt && !fused && dst.scatter, "extended key MAC: a decomposed, unfused tile and the rotation's index map");
+    launch_ks_mac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, dst, nb, s);
+}
+
+void KsTile::mac_ext_multi(int n_keys, const KsMacMultiKey* keys, long long sout, const u64* base, long long sbase) {
+    LSA_REQUIRE(src.ntt && !fused, "extended key MAC: a decomposed, unfused tile");
+    launch_ks_mac_multi(c, level, src.ntt, src.s_ntt, ext, s_ext, n_keys, keys, sout, base, sbase, nb, s);
+}
+
+void KsTile::moddown_of(u64* ext_acc, long long s_ext_acc, const KsOut& o) { ks_moddown(c, level, ext_acc, s_ext_acc, conv, o, nb, s); }
+
+void KsTile::moddown_ext(Context& c, int level, u64* ext_acc, long long s_ext_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
+    ks_moddown(c, level, ext_acc, s_ext_acc, conv, o, nb, s);
+}
+
+void key_switch(Context& c, int level, const KsSource& src, const Key& key, const KsOut& o, int nb, u64* ws, hipStream_t s) {
+    KsTile t(c, level, nb, ws, s, &key, src.form);
+    t.decompose(src);
+    t.mac(key);
+    t.moddown(o);
+}
+
+const u32* inverse_perm(Context& c, u64 g) {
+    const u64 mask = 2 * (u64)c.n - 1;
+    u64 inv = g;   // Newton iteration for the inverse modulo a power of two: doubles the correct low bits each step
+    for (int i = 0; i < 6; i++) inv = (inv * (2 - g * inv)) & mask;
+    LSA_REQUIRE(((inv * g) & mask) == 1, "Galois element without an inverse");
+    return c.ntt_perm(inv);
+}
+const u32* rotation_scatter(Context& c, u64 g) {
+    return sw::rot_scatter() && c.fuse_tails ? inverse_perm(c, g) : nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------ rescale
+void rescale(Context& c, int level, int polys, const u64* in, long long sin, u64* out, long long sout, int nb,
+             bool ntt_domain, u64* ws, hipStream_t s) {
+    LSA_REQUIRE(level >= 1 && level < c.nq, "rescale needs level >= 1");
+    const long long N = c.n;
+    const int L = level + 1;
+    u64* last = ws;
+    u64* tmp = last + (size_t)nb * polys * N;
+    const long long s_last = (long long)polys * N, s_tmp = (long long)polys * level * N;
+    std::vector<int> rows(polys);
+    for (int p = 0; p < polys; p++) rows[p] = p * L + level;
+    launch_copy_rows(c, in, sin, last, s_last, polys, rows.data(), nb, s);
+    if (ntt_domain) {
+        RowMap rm;
+        rm.period = 1;
+        rm.mod_of[0] = (unsigned char)level;
+        launch_ntt(c, last, last, nb, s_last, polys, rm, true, s);
+    }
+    if (ntt_domain && c.fuse_tails) {
+        // one forward NTT over the level limbs of every polynomial: its first-pass load derives the tile from the last limb
+        // (centred remainder, reduced to the target prime), its last-pass store applies (c - t) * q_l^-1 -> out
+        NttFusion fz;
+        fz.pro = 1;
+        fz.epi = 1;
+        fz.limbs = level;
+        fz.ql_mod = level;
+        fz.last = last;
+        fz.last_stride = s_last;
+        fz.a = in;
+        fz.a_stride = sin;
+        fz.a_rpp = L;
+        fz.k = c.qlinv_vec(level);
+        fz.out = out;
+        fz.out_stride = sout;
+        fz.out_rpp = level;
+        launch_ntt(c, tmp, tmp, nb, s_tmp, s_tmp, polys * level, rm_seq(level), false, s, &fz);
+        return;
+    }
+    launch_rescale_prep(c, level, polys, last, s_last, tmp, s_tmp, nb, s);
+    if (ntt_domain) launch_ntt(c, tmp, tmp, nb, s_tmp, polys * level, rm_seq(level), false, s);
+    launch_rescale_final(c, level, polys, in, sin, tmp, s_tmp, out, sout, nb, s);
+}
+
+// ------------------------------------------------------------------------------------------------ tiling
+int pick_tile(const Context& c, size_t rows_per_ct, int batch) {
+    if (c.tile_batch > 0) return std::min(c.tile_batch, batch);
+    // measured on MI355X (profiles/r01/tile_sweep*.log): launches need >= ~2k workgroups each to fill 256 CUs (~16
+    // ciphertexts per wave at N=2^16); past that the gain is the shrinking tail of each launch: +3 % (HMult) / +8 %
+    // (rotate) from 19 to 64 ciphertexts, for 6.6 GiB of workspace out of 288.
+    const size_t bytes_per_ct = rows_per_ct * (size_t)c.n * sizeof(u64);
+    size_t tb = (8ull << 30) / std::max<size_t>(bytes_per_ct, 1);
+    if (tb < 1) tb = 1;
+    // the cap scales with 1/N (same work per launch): 64 at N=2^16, 256 at N=2^14 (BFV mult+relin +12 % over 64)
+    const size_t cap = std::min<size_t>(512, std::max<size_t>(64, (64ull << 16) / (size_t)c.n));
+    if (tb > cap) tb = cap;
+    return (int)std::min<size_t>(tb, (size_t)batch);
+}
+
+}  // namespace lsa

@@ -1,5 +1,5 @@
 // layout_check.h — where a batched operand lives in memory, and whether two of them may be used together.  Plain C++, host only:
-// the argument checks of every operator (ops.hip, linear_transform.hip, poly_eval.hip) go through these functions, and
+// the argument checks of every operator (entry_check.h for ops.hip and slot_sum.hip, linear_transform.hip, poly_eval.hip) go through these functions, and
 // tests/cpp/test_layout_check.cpp compares them with a word-by-word model.
 //
 // An operand is `batch` items of `words` 64-bit words, item b at base + b * stride (stride in words).  stride == 0 means ONE item

@@ -107,7 +107,7 @@ struct LtEval {
         b->p = p;
         return DCt{b, level, scale};
     }
-    // extended ciphertext [2][level+1+k][N] over Q_level u P (ops.hip, ckks_rotate_many_ext); `level` and `scale` as for the
+    // extended ciphertext [2][level+1+k][N] over Q_level u P (ops.hip ckks_rotate_many_ext, on key_switch.h KsTile::mac_ext); `level` and `scale` as for the
     // ciphertext it will be divided down to
     long long stride_ext(int level) const { return 2LL * (level + 1 + c.np) * N; }
     DCt alloc_ext(int level, double scale) {

@@ -107,7 +107,7 @@ struct Context {
     int fp64_ntt = 1;               // use the FP64 butterfly engine for limbs with q < 2^47
     int tile_batch = 0;
     int fp_raw = 1;                 // FP64-engine limbs cross between the two NTT passes as doubles (LSA_NTT_FP_RAW=0: canonical u64)
-    int modup_lift = 1;             // single-limb key-switch digits lifted by the extension transform's load (ops.hip KsTile::decompose)
+    int modup_lift = 1;             // single-limb key-switch digits lifted by the extension transform's load (key_switch.hip KsTile::decompose)
     int fuse_tails = 1;             // ModDown / rescale element-wise tails fused into the NTT load/store phases
     int dual_stream = 0;            // 1: overlap alternate tiles of an operator on an auxiliary stream (+5% throughput,
                                     // but per-kernel timings then include the co-running kernel; off for clean accounting)
@@ -321,15 +321,21 @@ struct BaseConvRows {
 void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows, const u64* src, u64* dst, int batch,
                      long long ssrc, long long sdst, hipStream_t s, const u64* sub = nullptr, long long ssub = 0,
                      const int* sub_row = nullptr);
-// key-switch inner product: acc[h][tl] = sum_d ext(d,tl) * key[d][h][tl];  ext(d,tl) = cx[tl] when tl is in digit d
-// unfused_only: only the target limbs that do not take the fused kernel (ks_fused_limb; k_ntt_r16_ksmac did the others)
-// scatter (every target limb only): the result leaves as the ROTATED EXTENDED ciphertext acc[h][tl][scatter[x]] = sum(x) + (h == 0, tl < L:
+// key-switch inner product: out[h][tl] = sum_d ext(d,tl) * key[d][h][tl];  ext(d,tl) = cx[tl] when tl is in digit d
+// scatter (every target limb only): the result leaves as the ROTATED EXTENDED ciphertext out[h][tl][scatter[x]] = sum(x) + (h == 0, tl < L:
 // P * base[tl][x]) -- gadget product, c0 * P and the automorphism of a baby-step rotation in one pass (base == nullptr: no P * c0);
-// accumulate: added to what acc holds there (a giant-step rotation joining a running sum)
-void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext,
-                   const Key& key, u64* acc, long long sacc, int batch, hipStream_t s, bool unfused_only = false,
-                   const u32* scatter = nullptr, const u64* base = nullptr, long long sbase = 0,
-                   const TensorFold* fold = nullptr, bool accumulate = false);
+// accumulate: added to what out holds there (a giant-step rotation joining a running sum)
+struct KsMacDst {
+    u64* out;   // [2][L+k][N] per batch item
+    long long sout;
+    const u32* scatter = nullptr;
+    const u64* base = nullptr;
+    long long sbase = 0;
+    bool accumulate = false;
+};
+// unfused_only: only the target limbs that do not take the fused kernel (ks_fused_limb; k_ntt_r16_ksmac did the others)
+void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, const Key& key,
+                   const KsMacDst& dst, int batch, hipStream_t s, bool unfused_only = false, const TensorFold* fold = nullptr);
 // out[h][i] = base[h][i] + (acc[h][i] - conv[h][i]) * Pinv_i       (base may be null)
 void launch_moddown_final(Context& c, int level, const u64* acc, long long sacc, int acc_rows_per_poly, const u64* conv,
                           long long sconv, const u64* base, long long sbase, int base_rows_per_poly, int base_polys,
@@ -394,7 +400,7 @@ void key_prepare(Context& c, Key& key, u64* data, int key_level, double* fp, hip
 bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* ext, long long sext, const Key& key, u64* acc,
                       long long sacc, int batch, hipStream_t s, const TensorFold* fold = nullptr);
 int ks_fused_engines(const Context& c);   // which engines' target limbs take the fused kernel (LSA_KS_FUSED_ENGINES, default FP64 only)
-bool ks_fuse_mac(const Context& c, int level, const Key& key);   // a single-key switch at this level runs k_ntt_r16_ksmac (ops.hip)
+bool ks_fuse_mac(const Context& c, int level, const Key& key);   // a single-key switch at this level runs k_ntt_r16_ksmac (key_switch.hip)
 bool ks_fused_limb(const Context& c, int L, int tl);   // target limb tl of Q_level u P takes it (by its engine)
 // out = (a - b) * k_i  with per-row constant (Montgomery form) ; out = a * k_i
 void launch_sub_mul_const(Context& c, const u64* a, long long sa, const u64* b, long long sb, const u64* kvec, u64* out,
@@ -494,15 +500,16 @@ void ckks_affine_const(Context& c, int level, const u64* ct, long long sct, doub
                        double add_im, double ct_scale, u64* out, long long so, int batch, bool rescale, hipStream_t s);
 void ckks_lift_ext(Context& c, int level, const u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s);
 // c1_coef (BFV: the caller holds the ciphertext in the coefficient domain as well): c1's coefficients, read by the decomposition
-// in place of an inverse transform of in's c1 (KsTile::decompose); the same words
+// in place of an inverse transform of in's c1 (key_switch.h KsSource::BOTH); the same words
 void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
                           int batch, long long sin, long long sout, hipStream_t s, const u64* c1_coef = nullptr, long long s_coef = 0);
 void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, bool accumulate, int batch,
                      long long sin, long long sout, hipStream_t s, bool scatter_mac = false);
-// coeff_out: the result leaves in the coefficient domain (ks_moddown's COEFF form: every row of `in` leaves the NTT domain once
+// coeff_out: the result leaves in the coefficient domain (key_switch.h KsOut::COEFF: every row of `in` leaves the NTT domain once
 // and the tail runs there) -- INTT of the NTT-domain result, residue for residue
 void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s,
                       bool coeff_out = false);
+// ---- the slot sums (slot_sum.hip: kernels and runners, on the key-switch tile of key_switch.h)
 // CKKS slot sum  out = sum_{i<count} rot(in, i*step)  (lsa_slot_sum_* / lsa_ckks_slot_sum; plan rule: slot_sum.h).  Every step is one
 // decomposition whose 1..4 rotations stay over Q_level u P (the words of ckks_rotate_ext); the NEXT group is divided by P once with
 // x riding on the ModDown tail's base, the TAIL rotations gather in an extended accumulator divided once at the end.
@@ -554,6 +561,7 @@ struct BfvSlotTail {
 void launch_bfv_slot_tail(Context& c, int level, const BfvSlotTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
                           const u64* conv, long long sconv, const u64* x, long long sx, u64* out, long long sout, int batch,
                           hipStream_t s);
+// ---- (ops.hip again)
 void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                 hipStream_t s);
 void poly_addsub(Context& c, int op, int level, int polys, const u64* a, const u64* b, u64* out, int batch, long long sa,

@@ -2,509 +2,21 @@
 // (mega_ag_runners/gpu/mega_ag_executors_gpu.cu:71-426), built from the kernels in kernels.hip.
 //
 // Algorithms follow the CPU path the results must agree with (Lattigo v4, restated in oracle/ls_oracle.c):
-//   key-switch  = per-digit exact ModUp (DecomposeSingleNTT) + gadget MAC + centred ModDown (ModDownQPtoQNTT)
+//   key-switch  = key_switch.h: the tile (decomposition, key MACs, ModDown), the rescale and the tiling of a batch
 //   CKKS rescale = divide-and-round by the last prime (DivRoundByLastModulusNTT)
 //   rotate      = key-switch c1, add c0, then apply the automorphism (Evaluator.Automorphism)
 //   BFV mult    = centred extension Q->QMul, tensor in Q u QMul, round(./Q), centred return to Q, times t
-#include "layout_check.h"
+// The argument checks of the first-generation entry points are entry_check.h's; the slot sums' runners live in slot_sum.hip.
+#include "entry_check.h"
+#include "key_switch.h"
 #include "linear_transform.h"
-#include "lsa_internal.h"
 #include "plain_ops.h"
 #include "tensor_sum.h"
 
 namespace lsa {
-
-static RowMap rm_seq(int count, int first = 0) {
-    RowMap r;
-    LSA_REQUIRE(count >= 1 && count <= LSA_MAX_PERIOD, "row map too long");
-    r.period = count;
-    for (int i = 0; i < count; i++) r.mod_of[i] = (unsigned char)(first + i);
-    return r;
-}
-
-static int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-// ------------------------------------------------------------------------------------------------ key switch
-// Merged tail: the key-switch result is rescaled straight away (CKKS HMult+relin+rescale).  ModDown ends with
-// c_j = (acc_j - NTT(conv_j)) * P^-1 + base_j and the rescale continues with (c_j - NTT(lift_j(t))) * q_l^-1, t = INTT(c_l).
-// Modular arithmetic being exact and the transforms linear, residue for residue
-//   t   = (INTT(acc_l) - conv_l) * P^-1 + INTT(base_l)                      (two extra rows in transforms that run anyway)
-//   out = (acc_j * P^-1 - NTT(conv_j * P^-1 + lift_j(t)) + base_j) * q_l^-1  (ONE forward transform per remaining limb; the
-//                                                                            base conversion emits conv_j * P^-1 directly)
-// 104 limb transforms per operation instead of 128, and 4 fewer launches.
-struct KsRescale {
-    u64* out;          // [2][level][N], level - 1 result
-    long long sout;
-};
-
-struct RotMacTerm {   // the pt_mul factor of one rotate-and-MAC term (fz_epi = 4): p[scatter[x]] (+)= value(x) * pt[scatter[x]]
-    const u64* pt;
-    long long spt;
-    bool accumulate;
-};
-
-// What ModDown writes: p[h][i] = (h < base_polys ? base[h][i] : 0) + ModDown(acc)[h][i], base row h * base_rpp + i.
-//   NTT      NTT domain.  scatter (fused tails only): every result row is written through the index map, p[row][scatter[x]] =
-//            value(x) -- the NTT-domain automorphism of a rotation applied by the last pass's store instead of a permutation
-//            kernel afterwards.  rmac (with scatter): the scattered result is multiplied by a pt_mul plaintext and written or
-//            added to p instead (p[row][y] (+)= value * pt[limb][y] * 2^-64, y = scatter[x]): one term of a BFV rotate-and-MAC
-//   RESCALE  NTT domain, fused tails: p is scratch of the same shape and rs.out receives rescale(p)
-//   COEFF    coefficient domain, `base` given there (BFV).  coeff_gather: the coefficient-domain automorphism of a BFV rotation,
-//            Context::coeff_perm(g), applied by the tail's loads (k_sub_mul_perm): p[row][x] = sign_x * value(pi_x).
-//            slot_tail (base = x, both polynomials): one step of the BFV slot sum, the rotated c0 terms gathered by the tail
-//            (k_bfv_slot_tail)
-struct KsOut {
-    enum Form { NTT, RESCALE, COEFF };
-    u64* p;
-    long long sp;
-    const u64* base = nullptr;
-    long long sbase = 0;
-    int base_rpp = 0, base_polys = 0;
-    Form form = NTT;
-    KsRescale rs = {nullptr, 0};
-    const u32* scatter = nullptr;
-    const u32* coeff_gather = nullptr;
-    const RotMacTerm* rmac = nullptr;
-    const BfvSlotTail* slot_tail = nullptr;
-};
-
-// step 5, the division by P of a polynomial pair over Q_level u P (acc: [2][L+k][N] per batch item, NTT domain; its P rows --
-// and, for the merged rescale, its last Q row -- are transformed in place), conv: 2L rows of scratch per batch item
-static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
-    LSA_REQUIRE(!o.scatter || (c.fuse_tails && o.form == KsOut::NTT), "scattered ModDown store: fused tails, NTT-domain output");
-    LSA_REQUIRE(!o.rmac || o.scatter, "rotate-and-MAC tail: needs the rotation's index map");
-    LSA_REQUIRE(!o.coeff_gather || o.form == KsOut::COEFF, "gathered ModDown tail: coefficient-domain output");
-    LSA_REQUIRE(!o.slot_tail || (o.form == KsOut::COEFF && !o.coeff_gather && o.base && o.base_polys == 2 && o.base_rpp == level + 1),
-                "slot-sum ModDown tail: coefficient-domain output on a whole ciphertext");
-    LSA_REQUIRE(o.form != KsOut::RESCALE || (c.fuse_tails && level >= 1 && ((o.base && o.base_polys == 2) || (!o.base && o.base_polys == 0))),
-                "merged ModDown+rescale: unsupported shape");
-    const bool coeff_out = o.form == KsOut::COEFF, rs = o.form == KsOut::RESCALE;
-    const long long N = c.n;
-    const int L = level + 1, np = c.np, T = L + np;
-    const long long s_conv = 2LL * L * N;
-    // 5. ModDown: P-part out of NTT, centred exact conversion P -> Q, back to NTT, (accQ - conv) * P^-1 (+ base).
-    //    coeff_out (BFV: the result is wanted in the coefficient domain and `base` is given there): every row of acc leaves
-    //    the NTT domain once and the tail runs on coefficients -- INTT((acc - NTT(conv)) * P^-1) == (INTT(acc) - conv) * P^-1
-    //    residue for residue, 2(L+k) transforms instead of 2k + 2L + 2L.
-    {
-        RowMap rm;
-        rm.period = 2 * T;
-        for (int h = 0; h < 2; h++)
-            for (int tl = 0; tl < T; tl++)
-                rm.mod_of[h * T + tl] = tl >= L ? (unsigned char)c.p_mod(tl - L)
-                                                : (coeff_out ? (unsigned char)tl
-                                                             : (rs && tl == level ? (unsigned char)level : LSA_ROW_SKIP));
-        launch_ntt(c, acc, acc, nb, s_acc, 2 * T, rm, true, s);
-    }
-    {
-        std::vector<int> src, dst;
-        BaseConvRows rows{};
-        for (int i = 0; i < np; i++) {
-            rows.src_row[i] = L + i;
-            src.push_back(c.p_mod(i));
-        }
-        for (int j = 0; j < L; j++) {
-            rows.dst_row[j] = j;
-            dst.push_back(j);
-        }
-        const BaseConvPlan* k = c.baseconv(src, dst, true, rs);
-        for (int h = 0; h < 2; h++)
-            launch_baseconv(c, k, rows, acc + (size_t)h * T * N, conv + (size_t)h * L * N, nb, s_acc, s_conv, s);
-    }
-    if (coeff_out) {
-        if (o.slot_tail)
-            launch_bfv_slot_tail(c, level, *o.slot_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
-        else if (o.coeff_gather)
-            launch_moddown_final_perm(c, level, o.coeff_gather, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp,
-                                      o.base_polys, o.p, o.sp, nb, s);
-        else
-            launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp, o.base_polys, o.p, o.sp, nb, s);
-        return;
-    }
-    if (rs) {
-        // base_polys == 0: the tensor fold -- P * base is already in acc's Q rows (TensorFold), so INTT(acc_l) * P^-1 carries
-        // INTT(base_l) and the tails below run without base
-        const int l = level;
-        // t[h] = (INTT(acc[h][l]) - conv[h][l]) * P^-1 + INTT(base[h][l]) -> p[h][l].  base is the caller's scratch here
-        // (the tensor output): its last limbs are transformed in place, nothing reads them in NTT form afterwards.
-        if (o.base) {
-            u64* base_rw = const_cast<u64*>(o.base);
-            RowMap rb;
-            rb.period = 1;
-            rb.mod_of[0] = (unsigned char)l;
-            rb.row0 = l;
-            rb.row_step = o.base_rpp;
-            launch_ntt(c, base_rw, base_rw, nb, o.sbase, o.sbase, 2, rb, true, s);
-        }
-        const unsigned char lm[1] = {(unsigned char)l};
-        launch_sub_mul_general(c, 2, 1, lm, c.pinv_vec(level) + l, acc + (long long)l * N, s_acc, T, conv + (long long)l * N,
-                               s_conv, L, o.base ? o.base + (long long)l * N : nullptr, o.sbase, o.base_rpp, o.base_polys,
-                               o.p + (long long)l * N, o.sp, L, nb, s);
-        // every other limb: in = conv_j*P^-1 + lift_j(t), out = (acc_j*P^-1 - NTT(in) + base_j) * q_l^-1
-        RowMap rmo;
-        rmo.period = 2 * L;
-        for (int h = 0; h < 2; h++)
-            for (int j = 0; j < L; j++) rmo.mod_of[h * L + j] = j == l ? LSA_ROW_SKIP : (unsigned char)j;
-        NttFusion fb;
-        fb.pro = 2;
-        fb.epi = 2;
-        fb.limbs = L;
-        fb.ql_mod = l;
-        fb.last = o.p + (long long)l * N;
-        fb.last_stride = o.sp;
-        fb.last_rpp = L;
-        fb.a = acc;
-        fb.a_stride = s_acc;
-        fb.a_rpp = T;
-        fb.base = o.base;
-        fb.base_stride = o.sbase;
-        fb.base_rpp = o.base_rpp;
-        fb.base_polys = o.base_polys;
-        fb.k = c.pinv_vec(level);
-        fb.k2 = c.qlinv_vec(level);
-        fb.out = o.rs.out;
-        fb.out_stride = o.rs.sout;
-        fb.out_rpp = level;
-        launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rmo, false, s, &fb);
-    } else if (c.fuse_tails) {
-        // forward NTT of conv with the ModDown tail fused into its last-pass store: the transformed conv is consumed in
-        // registers ((acc_Q - conv) * P^-1 + base) and never written
-        NttFusion fz;
-        fz.epi = 1;
-        fz.limbs = L;
-        fz.a = acc;
-        fz.a_stride = s_acc;
-        fz.a_rpp = T;
-        fz.base = o.base;
-        fz.base_stride = o.sbase;
-        fz.base_rpp = o.base_rpp;
-        fz.base_polys = o.base_polys;
-        fz.k = c.pinv_vec(level);
-        fz.out = o.p;
-        fz.out_stride = o.sp;
-        fz.out_rpp = L;
-        fz.scatter = o.scatter;
-        if (o.rmac) {
-            fz.epi = 4;
-            fz.pt = o.rmac->pt;
-            fz.pt_stride = o.rmac->spt;
-            fz.accumulate = o.rmac->accumulate;
-        }
-        launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rm_seq(L), false, s, &fz);
-    } else {
-        launch_ntt(c, conv, conv, nb, s_conv, 2 * L, rm_seq(L), false, s);
-        launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp, o.base_polys, o.p, o.sp, nb, s);
-    }
-}
-
-// one key per decomposition (relinearisation, a single rotation, a generic switch): the extension transform's second pass
-// and the key MAC run as one kernel where the shape allows (k_ntt_r16_ksmac) and some target limb takes it
-bool ks_fuse_mac(const Context& c, int level, const Key& key) {
-    const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
-    if (!ks_fused_enabled(c) || !ks_fused_engines(c) || (c.fp64_ntt && !key.fp) || beta * T > LSA_MAX_PERIOD || T > 64) return false;
-    for (int tl = 0; tl < T; tl++)
-        if (ks_fused_limb(c, L, tl)) return true;
-    return false;
-}
-
-// One tile of a key switch: nb batch items on stream s, with the workspace laid out per batch item as
-// cxi [L] | ext [beta][L+k] | acc [2][L+k] | conv [2][L] rows.  Whether the extension transform's second pass runs fused with
-// the key MAC is decided here, once, so decompose() leaves the extended limbs in the state mac() reads them in.  Only a switch
-// with one key per decomposition fuses (single_key); hoisted rotations -- several keys on one decomposition, whose
-// residues are the same as if each rotation had been computed on its own -- pass none and keep the two steps apart.
-struct KsTile {
-    Context& c;
-    int level, L, T, beta, nb;
-    hipStream_t s;
-    const Key* key;   // fused: the one key mac() accepts
-    bool fused;
-    u64 *cxi, *ext, *acc, *conv;
-    long long s_cxi, s_ext, s_acc, s_conv;
-
-    static size_t rows(const Context& c, int level) {   // workspace rows per batch item
-        LSA_REQUIRE(c.np >= 1, "key switching needs at least one special prime");
-        const int L = level + 1, T = L + c.np, beta = ceil_div(L, c.np);
-        return (size_t)L + (size_t)beta * T + 2 * (size_t)T + 2 * (size_t)L;
-    }
-    KsTile(Context& c_, int level_, int nb_, u64* ws, hipStream_t s_, const Key* single_key = nullptr)
-        : c(c_), level(level_), nb(nb_), s(s_), key(single_key) {
-        LSA_REQUIRE(c.np >= 1, "key switching needs at least one special prime");
-        LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
-        const long long N = c.n;
-        L = level + 1;
-        T = L + c.np;
-        beta = ceil_div(L, c.np);
-        fused = key && ks_fuse_mac(c, level, *key);
-        s_cxi = (long long)L * N;
-        s_ext = (long long)beta * T * N;
-        s_acc = 2LL * T * N;
-        s_conv = 2LL * L * N;
-        cxi = ws;
-        ext = cxi + (size_t)nb * s_cxi;
-        acc = ext + (size_t)nb * s_ext;
-        conv = acc + (size_t)nb * s_acc;
-    }
-
-    // steps 1-3: cx out of the NTT domain, every digit converted to the other limbs of Q u P, extended limbs back into the NTT
-    // domain.  cx_coef: the same polynomial in the coefficient domain if the caller has it (BFV): the inverse transform is
-    // skipped.  prod (tensor fold, cx unused): cx = a1 * b1 is never stored, the inverse transform forms it as it loads (the
-    // product prologue).  Fused: the limbs that take the fused kernel are left after the first pass (mac() runs the second).
-    void decompose(const u64* cx, long long scx, const u64* cx_coef = nullptr, long long s_coef = 0, const TensorFold* prod = nullptr) {
-        const long long N = c.n;
-        const int np = c.np;
-        // 1. cx out of the NTT domain
-        if (prod) {
-            LSA_REQUIRE(!cx_coef, "key switch: a product source has no coefficient-domain copy");
-            NttFusion fz;
-            fz.pro = 3;
-            fz.limbs = L;
-            fz.a = prod->a + prod->pa;   // the second polynomials a1, b1
-            fz.a_stride = prod->sa;
-            fz.a_rpp = (int)(prod->pa >> c.logn);
-            fz.b = prod->b + prod->pb;
-            fz.b_stride = prod->sb;
-            fz.b_rpp = (int)(prod->pb >> c.logn);
-            launch_ntt(c, cxi, cxi, nb, s_cxi, s_cxi, L, rm_seq(L), true, s, &fz);
-        } else if (!cx_coef) {
-            launch_ntt(c, cx, cxi, nb, scx, s_cxi, L, rm_seq(L), true, s);
-        }
-        const u64* conv_src = cx_coef ? cx_coef : cxi;
-        const long long s_src = cx_coef ? s_coef : s_cxi;
-        // 2. per digit: exact conversion of the digit's limbs to every other limb of Q u P.  A digit with ONE source limb q_s
-        //    needs none: (Q_d/q_s)^-1 = 1, y = x, v = 0, every target row is x mod p_t -- the load of its extension transform
-        //    lifts it (fz_pro = 4) and the rows are never stored in the coefficient domain (lsa_set_modup_lift(ctx, 0): converted as the others).
-        //    v = 0 holds for the conversion as it is computed -- v = (int)RN(double(y) / double(q_s)) -- while q_s < 2^53: y and q_s
-        //    are exact doubles and y / q_s <= 1 - 1/q_s < 1 - 2^-53 rounds below 1.  A larger q_s has residues next to q_s whose
-        //    quotient rounds to 1.0 (the conversion then yields y - q_s): such a digit keeps the conversion kernel, residue for residue.
-        const bool lift_on = c.modup_lift != 0;
-        auto lifted = [&](int d) { return lift_on && std::min(d * np + np, L) - d * np == 1 && (c.T.mods[d * np].q >> 53) == 0; };
-        bool any_lift = false, any_conv = false;
-        for (int d = 0; d < beta; d++) {
-            if (lifted(d)) {
-                any_lift = true;
-                continue;
-            }
-            any_conv = true;
-            const int d0 = d * np, d1 = std::min(d0 + np, L);
-            std::vector<int> src, dst;
-            BaseConvRows rows{};
-            for (int i = d0; i < d1; i++) {
-                rows.src_row[i - d0] = i;
-                src.push_back(i);
-            }
-            for (int tl = 0; tl < T; tl++) {
-                if (tl >= d0 && tl < d1) continue;
-                rows.dst_row[dst.size()] = d * T + tl;
-                dst.push_back(c.qp_mod(L, tl));
-            }
-            launch_baseconv(c, c.baseconv(src, dst, false), rows, conv_src, ext, nb, s_src, s_ext, s);
-        }
-        // 3. extended limbs into the NTT domain (the digit's own limbs are taken from cx directly by the MAC)
-        auto own = [&](int d, int tl) { return tl >= d * np && tl < std::min((d + 1) * np, L); };
-        NttFusion lf;   // the lifted digits: digit d reads row d * np of conv_src (only read), modulus index d * np
-        lf.pro = 4;
-        lf.limbs = T;
-        lf.last = conv_src;
-        lf.last_stride = s_src;
-        lf.last_rpp = np;
-        lf.ql_mod = 0;
-        if (beta * T <= LSA_MAX_PERIOD) {
-            RowMap rm, rl;
-            rm.period = rl.period = beta * T;
-            for (int d = 0; d < beta; d++)
-                for (int tl = 0; tl < T; tl++) {
-                    const unsigned char m = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
-                    rm.mod_of[d * T + tl] = lifted(d) ? LSA_ROW_SKIP : m;
-                    rl.mod_of[d * T + tl] = lifted(d) ? m : LSA_ROW_SKIP;
-                }
-            if (any_conv) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, fused ? 1 : 3);
-            if (any_lift) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rl, false, s, &lf, fused ? 1 : 3);
-            if (!fused) return;
-            // the target limbs that do not take the fused kernel get their second pass here (stand-alone MAC later)
-            bool any = false;
-            for (int i = 0; i < beta * T; i++) {
-                rm.mod_of[i] = own(i / T, i % T) || ks_fused_limb(c, L, i % T) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, i % T);
-                any |= rm.mod_of[i] != LSA_ROW_SKIP;
-            }
-            if (any) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, 2);
-            return;
-        }
-        for (int d = 0; d < beta; d++) {   // (never fused: ks_fuse_mac needs beta * T <= LSA_MAX_PERIOD)
-            RowMap rm;
-            rm.period = T;
-            for (int tl = 0; tl < T; tl++) rm.mod_of[tl] = own(d, tl) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, tl);
-            lf.last = conv_src + (size_t)d * np * N;   // (one digit per launch: polynomial 0 of the launch is digit d)
-            lf.ql_mod = d * np;
-            launch_ntt(c, ext + (size_t)d * T * N, ext + (size_t)d * T * N, nb, s_ext, s_ext, T, rm, false, s, lifted(d) ? &lf : nullptr);
-        }
-    }
-
-    // step 4: the gadget inner product of the digits with key k (both halves) -> acc, [2][L+k][N] over Q_level u P, NTT
-    // domain; fused with the extension transform's second pass where decompose() stopped after the first one.
-    // fold: the tensor product folded into the MAC (TensorFold; the own digits come from its operands, cx is not read)
-    void mac(const u64* cx, long long scx, const Key& k, const TensorFold* fold = nullptr) {
-        if (!fused) {
-            launch_ks_mac(c, level, cx, scx, ext, s_ext, k, acc, s_acc, nb, s, false, nullptr, nullptr, 0, fold);
-            return;
-        }
-        LSA_REQUIRE(&k == key, "fused key MAC: the tile was planned for another key");
-        LSA_REQUIRE(launch_ntt_ksmac(c, level, cx, scx, ext, s_ext, k, acc, s_acc, nb, s, fold), "fused key MAC: shape not covered");
-        launch_ks_mac(c, level, cx, scx, ext, s_ext, k, acc, s_acc, nb, s, true, nullptr, nullptr, 0, fold);
-    }
-
-    void moddown(const KsOut& o) { ks_moddown(c, level, acc, s_acc, conv, o, nb, s); }   // step 5
-};
-
-// a key switch of cx (NTT domain) with one key
-static void key_switch(Context& c, int level, const u64* cx, long long scx, const Key& key, const KsOut& o, int nb, u64* ws,
-                       hipStream_t s) {
-    KsTile t(c, level, nb, ws, s, &key);
-    t.decompose(cx, scx);
-    t.mac(cx, scx, key);
-    t.moddown(o);
-}
-
-// the automorphism X -> X^g of a rotation as the SCATTER map of the key switch's last store: out[i] = in[perm_g[i]] is
-// out[perm_{g^-1}[x]] = in[x] (the maps of g and g^-1 are inverse permutations).  Null when the store cannot take it
-// (unfused tails, LSA_ROT_SCATTER=0): the caller then permutes afterwards.
-static const u32* inverse_perm(Context& c, u64 g) {
-    const u64 mask = 2 * (u64)c.n - 1;
-    u64 inv = g;   // Newton iteration for the inverse modulo a power of two: doubles the correct low bits each step
-    for (int i = 0; i < 6; i++) inv = (inv * (2 - g * inv)) & mask;
-    LSA_REQUIRE(((inv * g) & mask) == 1, "Galois element without an inverse");
-    return c.ntt_perm(inv);
-}
-static const u32* rotation_scatter(Context& c, u64 g) {
-    return sw::rot_scatter() && c.fuse_tails ? inverse_perm(c, g) : nullptr;
-}
-
-// ------------------------------------------------------------------------------------------------ rescale
-static size_t rescale_ws_rows(int level, int polys) { return (size_t)polys * (1 + level); }
-
-static void rescale(Context& c, int level, int polys, const u64* in, long long sin, u64* out, long long sout, int nb,
-                    bool ntt_domain, u64* ws, hipStream_t s) {
-    LSA_REQUIRE(level >= 1 && level < c.nq, "rescale needs level >= 1");
-    const long long N = c.n;
-    const int L = level + 1;
-    u64* last = ws;
-    u64* tmp = last + (size_t)nb * polys * N;
-    const long long s_last = (long long)polys * N, s_tmp = (long long)polys * level * N;
-    std::vector<int> rows(polys);
-    for (int p = 0; p < polys; p++) rows[p] = p * L + level;
-    launch_copy_rows(c, in, sin, last, s_last, polys, rows.data(), nb, s);
-    if (ntt_domain) {
-        RowMap rm;
-        rm.period = 1;
-        rm.mod_of[0] = (unsigned char)level;
-        launch_ntt(c, last, last, nb, s_last, polys, rm, true, s);
-    }
-    if (ntt_domain && c.fuse_tails) {
-        // one forward NTT over the level limbs of every polynomial: its first-pass load derives the tile from the last limb
-        // (centred remainder, reduced to the target prime), its last-pass store applies (c - t) * q_l^-1 -> out
-        NttFusion fz;
-        fz.pro = 1;
-        fz.epi = 1;
-        fz.limbs = level;
-        fz.ql_mod = level;
-        fz.last = last;
-        fz.last_stride = s_last;
-        fz.a = in;
-        fz.a_stride = sin;
-        fz.a_rpp = L;
-        fz.k = c.qlinv_vec(level);
-        fz.out = out;
-        fz.out_stride = sout;
-        fz.out_rpp = level;
-        launch_ntt(c, tmp, tmp, nb, s_tmp, s_tmp, polys * level, rm_seq(level), false, s, &fz);
-        return;
-    }
-    launch_rescale_prep(c, level, polys, last, s_last, tmp, s_tmp, nb, s);
-    if (ntt_domain) launch_ntt(c, tmp, tmp, nb, s_tmp, polys * level, rm_seq(level), false, s);
-    launch_rescale_final(c, level, polys, in, sin, tmp, s_tmp, out, sout, nb, s);
-}
-
-// ------------------------------------------------------------------------------------------------ tiling
-static int pick_tile(const Context& c, size_t rows_per_ct, int batch) {
-    if (c.tile_batch > 0) return std::min(c.tile_batch, batch);
-    // measured on MI355X (profiles/r01/tile_sweep*.log): launches need >= ~2k workgroups each to fill 256 CUs (~16
-    // ciphertexts per wave at N=2^16); past that the gain is the shrinking tail of each launch: +3 % (HMult) / +8 %
-    // (rotate) from 19 to 64 ciphertexts, for 6.6 GiB of workspace out of 288.
-    const size_t bytes_per_ct = rows_per_ct * (size_t)c.n * sizeof(u64);
-    size_t tb = (8ull << 30) / std::max<size_t>(bytes_per_ct, 1);
-    if (tb < 1) tb = 1;
-    // the cap scales with 1/N (same work per launch): 64 at N=2^16, 256 at N=2^14 (BFV mult+relin +12 % over 64)
-    const size_t cap = std::min<size_t>(512, std::max<size_t>(64, (64ull << 16) / (size_t)c.n));
-    if (tb > cap) tb = cap;
-    return (int)std::min<size_t>(tb, (size_t)batch);
-}
-
-// Runs fn(nb, b0, ws, tb, stream) for every tile of `tb` ciphertexts.  Tiles alternate between the caller's stream and
-// the context's auxiliary stream (each with its own workspace half): every kernel of the pipeline uses only part of the
-// chip's VALU / HBM / latency budget, so two independent tiles in flight fill each other's gaps.
-template <typename F>
-static void for_tiles(Context& c, size_t rows_per_ct, int batch, hipStream_t s, F&& fn) {
-    if (batch <= 0) return;
-    const int tb = pick_tile(c, rows_per_ct, batch);
-    const int ntiles = ceil_div(batch, tb);
-    const bool dual = c.dual_stream && ntiles >= 2;
-    const size_t words = rows_per_ct * (size_t)c.n * tb;
-    u64* ws = c.workspace(words * (dual ? 2 : 1), s);
-    if (dual) c.fork_aux(s);
-    for (int t = 0; t < ntiles; t++) {
-        const int b0 = t * tb, nb = std::min(tb, batch - b0);
-        const bool on_aux = dual && (t & 1);
-        fn(nb, b0, ws + (on_aux ? words : 0), tb, on_aux ? c.aux_stream : s);
-    }
-    if (dual) c.join_aux(s);
-}
-
-// ------------------------------------------------------------------------------------------------ argument checks
-// The layout, overlap and argument contract of the first-generation entry points (include/lattisense_amd.h, "Layout and
-// aliasing"), checked in the operators themselves so that the task dispatcher and the plan runners get it too.  Everything is
-// decided on the host before a kernel or a copy is queued; every refusal is LSA_ERR_ARG with a message that begins with the entry
-// point's name.  The span arithmetic is layout_check.h's.
 namespace {
 using layout::Span;
-
-struct EntryCheck {
-    const Context& c;
-    std::string who;
-    int level, batch;
-    size_t N;
-    // algo: LSA_ALGO_BFV / LSA_ALGO_CKKS, or -1 for an operator both schemes use; min_level: 1 for the operators that drop a limb
-    EntryCheck(const Context& c_, const char* who_, int algo, int level_, int min_level, int batch_)
-        : c(c_), who(who_), level(level_), batch(batch_), N((size_t)c_.n) {
-        LSA_REQUIRE(algo < 0 || c.algo == algo, who + (algo == LSA_ALGO_BFV ? ": context is not BFV" : ": context is not CKKS"));
-        LSA_REQUIRE(level >= min_level && level < c.nq,
-                    who + ": level out of range (" + std::to_string(min_level) + ".." + std::to_string(c.nq - 1) + ")");
-    }
-    void polys(int polys) const {   // a plaintext or one polynomial, a ciphertext, a degree-2 ciphertext
-        LSA_REQUIRE(polys >= 1 && polys <= 3, who + ": polys must be 1, 2 or 3");
-    }
-    void key(const Key& k, const char* what) const {
-        LSA_REQUIRE(k.data != nullptr, who + ": " + what + " is null");
-        LSA_REQUIRE(k.level >= level, who + ": " + what + " was exported at a lower level than the ciphertext");
-    }
-    // an operand of `words` words per batch item; shared_ok: a batch stride of 0 (one operand for the whole batch) is accepted
-    Span operand(const u64* p, long long stride, size_t words, const char* what, bool shared_ok) const {
-        LSA_REQUIRE(p != nullptr, who + ": " + what + " is null");
-        const Span sp = layout::span_of(p, stride, words);
-        LSA_REQUIRE(layout::stride_ok(sp, shared_ok), who + ": batch stride of " + what +
-                                                          (shared_ok ? " below one operand (0: shared by the batch)" : " below one operand"));
-        // the element-wise kernels move 16 bytes per lane at base + item * stride
-        LSA_REQUIRE(layout::aligned16(sp), who + ": " + what + " must be 16-byte aligned with an even batch stride");
-        return sp;
-    }
-    Span output(const u64* p, long long stride, size_t words, const char* what = "out") const { return operand(p, stride, words, what, false); }
-    void apart(const Span& out, const Span& in, const char* what) const {
-        LSA_REQUIRE(layout::apart(out, in, batch), who + ": the output overlaps " + what);
-    }
-    void same_or_apart(const Span& out, const Span& in, const char* what) const {
-        LSA_REQUIRE(layout::same_or_apart(out, in, batch),
-                    who + ": the output must be " + what + " itself (same pointer, same stride) or not overlap it");
-    }
-};
-}  // namespace
+}
 
 // ================================================================================================ CKKS
 void ckks_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int batch, long long sa, long long sb,
@@ -528,8 +40,7 @@ void ckks_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, 
     ck.apart(ck.output(out, so, 2 * (size_t)L * N), ck.operand(d3, sd, 3 * (size_t)L * N, "d3", false), "d3");
     for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* d = d3 + (size_t)b0 * sd;
-        key_switch(c, level, d + 2LL * L * N, sd, rlk, {.p = out + (size_t)b0 * so, .sp = so, .base = d, .sbase = sd, .base_rpp = L, .base_polys = 2},
-                   nb, ws, st);
+        key_switch(c, level, KsSource::of_ntt(d + 2LL * L * N, sd), rlk, ks_onto_ct(out + (size_t)b0 * so, so, d, sd, L), nb, ws, st);
     });
 }
 
@@ -563,9 +74,8 @@ void ckks_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u6
         // the permutation rides on the ModDown tail's store: no intermediate, no permutation kernel (2L reads + 2L writes less)
         for_tiles(c, ks_rows, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
             const u64* ct = in + (size_t)b0 * sin;
-            key_switch(c, level, ct + (long long)L * N, sin, glk,
-                       {.p = out + (size_t)b0 * sout, .sp = sout, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1, .scatter = scatter},
-                       nb, ws, st);
+            key_switch(c, level, KsSource::of_ntt(ct + (long long)L * N, sin), glk,
+                       ks_onto_c0(out + (size_t)b0 * sout, sout, ct, sin, L, {.scatter = scatter}), nb, ws, st);
         });
         return;
     }
@@ -573,8 +83,7 @@ void ckks_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u6
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
-        key_switch(c, level, ct + (long long)L * N, sin, glk, {.p = p, .sp = sp, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1},
-                   nb, ws, st);
+        key_switch(c, level, KsSource::of_ntt(ct + (long long)L * N, sin), glk, ks_onto_c0(p, sp, ct, sin, L), nb, ws, st);
         launch_permute_ntt(c, perm, p, sp, out + (size_t)b0 * sout, sout, 2 * L, nb, st);
     });
 }
@@ -614,15 +123,14 @@ void ckks_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
         KsTile t(c, level, nb, ws, st);
-        t.decompose(ct + (long long)L * N, sin);
+        t.decompose(KsSource::of_ntt(ct + (long long)L * N, sin));
         for (int i : order) {
-            t.mac(ct + (long long)L * N, sin, *glk[i]);
+            t.mac(*glk[i]);
             if (scatters[i]) {   // the permutation rides on the ModDown tail's store
-                t.moddown({.p = outs[i] + (size_t)b0 * sout, .sp = sout, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1,
-                           .scatter = scatters[i]});
+                t.moddown(ks_onto_c0(outs[i] + (size_t)b0 * sout, sout, ct, sin, L, {.scatter = scatters[i]}));
                 continue;
             }
-            t.moddown({.p = p, .sp = sp, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1});
+            t.moddown(ks_onto_c0(p, sp, ct, sin, L));
             launch_permute_ntt(c, perms[i], p, sp, outs[i] + (size_t)b0 * sout, sout, 2 * L, nb, st);
         }
     });
@@ -648,14 +156,14 @@ void ckks_rotate_many_ext(Context& c, int level, const u64* in, int n_rot, const
     for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* ct = in + (size_t)b0 * sin;
         KsTile t(c, level, nb, ws, st);
-        t.decompose(ct + (long long)L * N, sin, c1_coef ? c1_coef + (size_t)b0 * s_coef : nullptr, s_coef);
+        const u64* c1 = ct + (long long)L * N;
+        t.decompose(c1_coef ? KsSource::of_both(c1, sin, c1_coef + (size_t)b0 * s_coef, s_coef) : KsSource::of_ntt(c1, sin));
         for (int i = 0; i < n_rot; i++) {
             if (one_pass) {
-                launch_ks_mac(c, level, ct + (long long)L * N, sin, t.ext, t.s_ext, *glk[i], outs[i] + (size_t)b0 * sout, sout, nb, st,
-                              false, perms[i], ct, sin);
+                t.mac_ext(*glk[i], {.out = outs[i] + (size_t)b0 * sout, .sout = sout, .scatter = perms[i], .base = ct, .sbase = sin});
                 continue;
             }
-            t.mac(ct + (long long)L * N, sin, *glk[i]);
+            t.mac(*glk[i]);
             launch_permute_ext(c, level, perms[i], t.acc, t.s_acc, ct, sin, 1, outs[i] + (size_t)b0 * sout, sout, false, nb, st);
         }
     });
@@ -675,9 +183,8 @@ void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk
         for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
             const u64* ct = in + (size_t)b0 * sin;
             KsTile t(c, level, nb, ws, st);
-            t.decompose(ct + (long long)L * N, sin);
-            launch_ks_mac(c, level, ct + (long long)L * N, sin, t.ext, t.s_ext, glk, out + (size_t)b0 * sout, sout, nb, st, false, scatter,
-                          ct, sin, nullptr, accumulate);
+            t.decompose(KsSource::of_ntt(ct + (long long)L * N, sin));
+            t.mac_ext(glk, {.out = out + (size_t)b0 * sout, .sout = sout, .scatter = scatter, .base = ct, .sbase = sin, .accumulate = accumulate});
         });
         return;
     }
@@ -685,8 +192,8 @@ void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk
     for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* ct = in + (size_t)b0 * sin;
         KsTile t(c, level, nb, ws, st, &glk);
-        t.decompose(ct + (long long)L * N, sin);
-        t.mac(ct + (long long)L * N, sin, glk);
+        t.decompose(KsSource::of_ntt(ct + (long long)L * N, sin));
+        t.mac(glk);
         launch_permute_ext(c, level, perm, t.acc, t.s_acc, ct, sin, 1, out + (size_t)b0 * sout, sout, accumulate, nb, st);
     });
 }
@@ -694,10 +201,9 @@ void ckks_rotate_ext(Context& c, int level, const u64* in, u64 g, const Key& glk
 // the rounded division by P: extended ciphertext -> ciphertext [2][L][N].  `in` is clobbered (its P rows leave the NTT domain).
 void ckks_moddown_ext(Context& c, int level, u64* in, u64* out, int batch, long long sin, long long sout, hipStream_t s,
                       bool coeff_out) {
-    const int L = level + 1;
-    for_tiles(c, 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
-        ks_moddown(c, level, in + (size_t)b0 * sin, sin, ws,
-                   {.p = out + (size_t)b0 * sout, .sp = sout, .form = coeff_out ? KsOut::COEFF : KsOut::NTT}, nb, st);
+    for_tiles(c, KsTile::moddown_rows(level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+        KsTile::moddown_ext(c, level, in + (size_t)b0 * sin, sin, ws,
+                            {.p = out + (size_t)b0 * sout, .sp = sout, .form = coeff_out ? KsOut::COEFF : KsOut::NTT}, nb, st);
     });
 }
 
@@ -709,8 +215,7 @@ void ckks_switch_key(Context& c, int level, const u64* in, const Key& swk, u64* 
     const int L = level + 1;
     for_tiles(c, KsTile::rows(c, level), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* ct = in + (size_t)b0 * sin;
-        key_switch(c, level, ct + (long long)L * N, sin, swk,
-                   {.p = out + (size_t)b0 * sout, .sp = sout, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1}, nb, ws, st);
+        key_switch(c, level, KsSource::of_ntt(ct + (long long)L * N, sin), swk, ks_onto_c0(out + (size_t)b0 * sout, sout, ct, sin, L), nb, ws, st);
     });
 }
 
@@ -722,7 +227,7 @@ static void ckks_relin_tail(Context& c, int level, const u64* d3, long long sd, 
     const int L = level + 1;
     const long long sr = 2LL * L * c.n;
     const u64* d2 = d3 + 2LL * L * c.n;
-    KsOut o{.p = r2, .sp = sr, .base = d3, .sbase = sd, .base_rpp = L, .base_polys = 2};
+    KsOut o = ks_onto_ct(r2, sr, d3, sd, L);
     const bool merged = with_rescale && c.fuse_tails;   // the merged ModDown + rescale tail
     if (!with_rescale) {
         o.p = out;
@@ -731,7 +236,7 @@ static void ckks_relin_tail(Context& c, int level, const u64* d3, long long sd, 
         o.form = KsOut::RESCALE;
         o.rs = {out, so};
     }
-    key_switch(c, level, d2, sd, rlk, o, nb, sub, s);
+    key_switch(c, level, KsSource::of_ntt(d2, sd), rlk, o, nb, sub, s);
     if (with_rescale && !merged) rescale(c, level, 2, r2, sr, out, so, nb, true, sub, s);
 }
 
@@ -773,10 +278,8 @@ void ckks_mult_relin_rescale_rpp(Context& c, int level, const u64* a, const u64*
             const u64* ta = a + (size_t)b0 * sa;
             const u64* bt = b + (size_t)b0 * sb;
             const TensorFold tf{ta, bt, sa, sb, (long long)(a_rpp ? a_rpp : L) * N, (long long)(b_rpp ? b_rpp : L) * N};
-            KsTile t(c, level, nb, sub, st, &rlk);
-            t.decompose(nullptr, 0, nullptr, 0, &tf);
-            t.mac(t.cxi, t.s_cxi, rlk, &tf);   // (the MAC takes the own digit from a and b: its cx is not read)
-            t.moddown({.p = r2, .sp = sr, .form = KsOut::RESCALE, .rs = {out + (size_t)b0 * so, so}});
+            key_switch(c, level, KsSource::of_product(tf), rlk, {.p = r2, .sp = sr, .form = KsOut::RESCALE, .rs = {out + (size_t)b0 * so, so}},
+                       nb, sub, st);
             return;
         }
         launch_tensor(c, a + (size_t)b0 * sa, b + (size_t)b0 * sb, d3, nb, sa, sb, sd, L, rm_seq(L), st, a_rpp, b_rpp);
@@ -1076,20 +579,6 @@ void bfv_mult(Context& c, int level, const u64* a, const u64* b, u64* d3, int ba
     bfv_mult_sum_run(c, "lsa_bfv_mult", level, one, d3, batch, sd, s);
 }
 
-// key switch of a coefficient-domain polynomial: NTT in, INTT out
-// cx in the coefficient domain; p[h] = (h < base_polys ? base[h] : 0) + KeySwitch(cx)[h], all in the coefficient domain.
-// Only the MAC's own-digit operand needs cx in the NTT domain; the decomposition starts from the coefficients the caller
-// already has and the ModDown tail runs on coefficients (KsOut::COEFF).  Workspace: NTT(cx) [L] rows, then the tile's.
-static void bfv_key_switch(Context& c, int level, const u64* cx, long long scx, const Key& key, const KsOut& o, int nb, u64* ws,
-                           hipStream_t s) {
-    const long long scxn = (long long)(level + 1) * c.n;
-    KsTile t(c, level, nb, ws + (size_t)nb * scxn, s, &key);
-    launch_ntt(c, cx, ws, nb, scx, scxn, level + 1, rm_seq(level + 1), false, s);
-    t.decompose(ws, scxn, cx, scx);
-    t.mac(ws, scxn, key);
-    t.moddown(o);
-}
-
 void bfv_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, int batch, long long sd, long long so,
                hipStream_t s) {
     const EntryCheck ck(c, "lsa_bfv_relin", LSA_ALGO_BFV, level, 0, batch);
@@ -1098,11 +587,11 @@ void bfv_relin(Context& c, int level, const u64* d3, const Key& rlk, u64* out, i
     const long long N = c.n;
     const int L = level + 1;
     ck.apart(ck.output(out, so, 2 * (size_t)L * N), ck.operand(d3, sd, 3 * (size_t)L * N, "d3", false), "d3");
-    for_tiles(c, KsTile::rows(c, level) + L, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
+    // the decomposition starts from the coefficients of d2 and the ModDown tail runs on coefficients (KsSource::COEFF, KsOut::COEFF)
+    for_tiles(c, KsTile::rows(c, level, KsSource::COEFF), batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         const u64* d = d3 + (size_t)b0 * sd;
-        bfv_key_switch(c, level, d + 2LL * L * N, sd, rlk,
-                       {.p = out + (size_t)b0 * so, .sp = so, .base = d, .sbase = sd, .base_rpp = L, .base_polys = 2, .form = KsOut::COEFF},
-                       nb, ws, st);
+        key_switch(c, level, KsSource::of_coeff(d + 2LL * L * N, sd), rlk,
+                   ks_onto_ct(out + (size_t)b0 * so, so, d, sd, L, {.form = KsOut::COEFF}), nb, ws, st);
     });
 }
 
@@ -1175,13 +664,13 @@ void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64
     // would let one tile store over what another still reads
     ck.same_or_apart(ck.output(out, sout, 2 * (size_t)L * N), ck.operand(in, sin, 2 * (size_t)L * N, "in", false), "in");
     const u32* perm = c.coeff_perm(g);
-    const size_t ks_rows = KsTile::rows(c, level) + L;
+    const size_t ks_rows = KsTile::rows(c, level, KsSource::COEFF);
     const long long sp = 2LL * L * N;
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
-        bfv_key_switch(c, level, ct + (long long)L * N, sin, glk,   // p0 = c0 + ks0
-                       {.p = p, .sp = sp, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1, .form = KsOut::COEFF}, nb, ws, st);
+        key_switch(c, level, KsSource::of_coeff(ct + (long long)L * N, sin), glk,   // p0 = c0 + ks0
+                   ks_onto_c0(p, sp, ct, sin, L, {.form = KsOut::COEFF}), nb, ws, st);
         launch_permute_coeff(c, perm, p, sp, out + (size_t)b0 * sout, sout, 2 * L, rm_seq(L), nb, st);
     });
 }
@@ -1203,7 +692,7 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
     LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
     const long long N = c.n;
     const int L = level + 1;
-    const size_t ks_rows = KsTile::rows(c, level) + L;
+    const size_t ks_rows = KsTile::rows(c, level, KsSource::COEFF);
     const long long sp = 2LL * L * N;
     // the one-pass tail stages a limb in LDS (N <= 2^14); larger rings keep the two steps, which measured faster than gathering
     // from global memory
@@ -1225,15 +714,13 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
     }
     if (overlapping >= 0) order.push_back(overlapping);
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
-        u64* cxn = ws;
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
-        KsTile t(c, level, nb, ws + (size_t)nb * L * N, st);
-        launch_ntt(c, ct + (long long)L * N, cxn, nb, sin, (long long)L * N, L, rm_seq(L), false, st);
-        t.decompose(cxn, (long long)L * N, ct + (long long)L * N, sin);
+        KsTile t(c, level, nb, ws, st, nullptr, KsSource::COEFF);
+        t.decompose(KsSource::of_coeff(ct + (long long)L * N, sin));
         for (int i : order) {
-            t.mac(cxn, (long long)L * N, *glk[i]);
-            KsOut o{.p = p, .sp = sp, .base = ct, .sbase = sin, .base_rpp = L, .base_polys = 1, .form = KsOut::COEFF};
+            t.mac(*glk[i]);
+            KsOut o = ks_onto_c0(p, sp, ct, sin, L, {.form = KsOut::COEFF});
             if (direct[i]) {   // p0 = c0 + ks0 and the automorphism in one tail, straight into the output
                 o.p = outs[i] + (size_t)b0 * sout;
                 o.sp = sout;
@@ -1371,7 +858,7 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
         u64* o = out + (size_t)b0 * sout;
         KsTile t(c, level, nb, sub, st);
         launch_ntt(c, ct, ctn, nb, sin, sct, 2 * L, rm_seq(L), false, st);
-        if (any_rot) t.decompose(ctn + L * N, sct, ct + (long long)L * N, sin);
+        if (any_rot) t.decompose(KsSource::of_both(ctn + L * N, sct, ct + (long long)L * N, sin));
         bool first = true;
         for (int i = 0; i < n; i++) {   // identity terms: no transform at all
             if (g[i] != 1) continue;
@@ -1382,13 +869,12 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
         for (int i = 0; i < n; i++) {
             if (g[i] == 1) continue;
             const u64* pt = pts[i] + (size_t)b0 * spts[i];
-            t.mac(ctn + L * N, sct, *glk[i]);
+            t.mac(*glk[i]);
             if (fused) {
                 const RotMacTerm term{pt, spts[i], !first};
-                t.moddown({.p = o, .sp = sout, .base = ctn, .sbase = sct, .base_rpp = L, .base_polys = 1, .scatter = scatters[i],
-                           .rmac = &term});
+                t.moddown(ks_onto_c0(o, sout, ctn, sct, L, {.scatter = scatters[i], .rmac = &term}));
             } else {
-                t.moddown({.p = p, .sp = sct, .base = ctn, .sbase = sct, .base_rpp = L, .base_polys = 1, .scatter = scatters[i]});
+                t.moddown(ks_onto_c0(p, sct, ctn, sct, L, {.scatter = scatters[i]}));
                 const u64* r = p;
                 if (perms[i]) {   // no scattered store: the automorphism as a separate pass (conv is free again)
                     launch_permute_ntt(c, perms[i], p, sct, t.conv, t.s_conv, 2 * L, nb, st);
@@ -1648,246 +1134,6 @@ void ckks_affine_const(Context& c, int level, const u64* ct, long long sct, doub
     pc.ciphertext(ct, sct, "ct");
     pc.output(out, so, rescale, ct, sct);
     cconst_run(c, pc, &alpha, &beta, ct, sct, out, so, rescale, s);
-}
-
-// ------------------------------------------------------------------------------------------------ CKKS slot sum
-// out = sum_{i<count} rot(in, i*step) by the plan of slot_sum.h.  Per tile the steps run back to back: one decomposition of x's c1,
-// the gadget products of the step's 1..4 keys written as rotated extended ciphertexts (launch_ks_mac with `scatter`: the words of
-// ckks_rotate_ext) -- several keys in ONE k_ks_mac_multi launch, each into its own buffer, k_ext_sum joining them -- then
-// x <- x + ModDown(NEXT sum) with x riding on the ModDown tail's base (base_polys = 2).  That store is index for index, so from
-// the second step on x lives in `out` and is updated in place, and out == in is allowed.  The TAIL rotations gather in an extended
-// accumulator that is divided once, after the last step.  All temporaries are the tile's workspace: the KsTile rows, up to three more
-// extended ciphertexts for the keys of a multi-key launch beyond the first, and one for the tail.
-SlotSumPlanHost slot_sum_plan_checked(int n_ring, long long step, int count, int radix) {
-    try {
-        return slot_sum_plan(n_ring, step, count, radix, LSA_SLOTSUM_DEFAULT_RADIX);
-    } catch (const std::invalid_argument& e) {
-        throw Error(LSA_ERR_ARG, e.what());
-    }
-}
-
-SlotSum* slot_sum_create(Context& c, int level, long long step, int count, int radix) {
-    LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, "slot sum: context is not CKKS");
-    LSA_REQUIRE(level >= 0 && level < c.nq, "slot sum: level out of range");
-    auto p = std::make_unique<SlotSum>(c, level);
-    p->plan = slot_sum_plan_checked(c.n, step, count, radix);
-    LSA_REQUIRE(p->plan.steps.empty() || c.np >= 1, "slot sum: key switching needs at least one special prime");
-    return p.release();
-}
-
-// What both slot-sum runners do before their tiles.  Every key of `elements` (the plan's, in the order a missing one is reported)
-// is looked up and checked before anything is queued; then the operands; a plan without steps (count == 1, no row fold) is a
-// copy; last the rotations' tables, element by element (table look-ups upload on first use: only after every argument is
-// accepted): the NTT-domain scatter and, for the BFV gathering tail, the coefficient-domain permutation.
-// run == false: nothing is left to do.
-struct SlotSumCall {
-    bool run = false;
-    GaloisKeys key_of;   // the plan's keys alone, all present
-    std::map<u64, const u32*> scatter_of, perm_of;
-};
-static SlotSumCall slot_sum_prologue(Context& c, const EntryCheck& ck, const SlotSumPlanHost& plan, const std::vector<u64>& elements,
-                                     const GaloisKeys& glk, const u64* in, long long sin, u64* out, long long sout, int batch,
-                                     bool gather, hipStream_t s) {
-    SlotSumCall call;
-    const std::vector<const Key*> keys = glk.resolve(elements, ck.who, [&](u64, const Key& k) { ck.key(k, "a Galois key"); });
-    for (size_t i = 0; i < elements.size(); i++) call.key_of.insert(elements[i], keys[i]);
-    if (batch <= 0) return call;
-    const int L = ck.level + 1;
-    const size_t w = 2 * (size_t)L * c.n;
-    const Span sp_in = ck.operand(in, sin, w, "in", false), sp_out = ck.output(out, sout, w);
-    ck.same_or_apart(sp_out, sp_in, "in");
-    if (plan.steps.empty()) {
-        if (layout::same(sp_out, sp_in)) return call;
-        std::vector<int> rows(2 * L);
-        for (int i = 0; i < 2 * L; i++) rows[i] = i;
-        launch_copy_rows(c, in, sin, out, sout, 2 * L, rows.data(), batch, s);
-        return call;
-    }
-    LSA_REQUIRE(!gather || c.logn <= LSA_PERM_LDS_MAX_LOGN, ck.who + ": the gathering tail needs N <= 2^14");
-    for (u64 e : elements) {
-        call.scatter_of[e] = inverse_perm(c, e);
-        if (gather) call.perm_of[e] = c.coeff_perm(e);
-    }
-    call.run = true;
-    return call;
-}
-
-void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
-                  const GaloisKeys& glk, hipStream_t s) {
-    Context& c = p.c;
-    const int level = p.level;
-    const EntryCheck ck(c, "lsa_ckks_slot_sum", LSA_ALGO_CKKS, level, 0, batch);
-    std::vector<u64> by_rotation;   // a missing key is reported in the order of the plan's rotations
-    for (int r : p.plan.rotations) by_rotation.push_back(galois_of_rotation(r, c.n));
-    const SlotSumCall call = slot_sum_prologue(c, ck, p.plan, by_rotation, glk, in, sin, out, sout, batch, false, s);
-    if (!call.run) return;
-    const auto& key_of = call.key_of;
-    const auto& scatter_of = call.scatter_of;
-    const long long N = c.n;
-    const int L = level + 1, T = L + c.np;
-    const size_t ks_rows = KsTile::rows(c, level);
-    const bool multi = p.multi_mac;
-    // extended buffers beyond KsTile's acc: one per key of a multi-key launch that is neither the first NEXT key nor the first
-    // TAIL key of the plan (the most any step needs), and the tail accumulator
-    int n_more = 0;
-    {
-        bool live = false;
-        for (const SlotSumStep& step : p.plan.steps) {
-            int more = 0, next = 0;
-            for (const SlotSumKey& k : step.keys) more += k.tail ? (live ? 1 : 0) : (next++ ? 1 : 0);
-            for (const SlotSumKey& k : step.keys) live = live || k.tail;
-            if (multi && step.keys.size() >= 2) n_more = std::max(n_more, more);
-        }
-    }
-    const int n_extra = n_more + (p.plan.has_tail ? 1 : 0);
-    for_tiles(c, ks_rows + (size_t)n_extra * 2 * T, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
-        KsTile t(c, level, nb, ws, st);
-        const long long s_ext2 = t.s_acc;   // [2][T][N] per batch item, like t.acc
-        u64* extra[LSA_SLOTSUM_MAX_KEYS];
-        for (int i = 0; i < n_extra; i++) extra[i] = ws + (ks_rows * tb + (size_t)i * 2 * T * tb) * N;
-        u64* tail = p.plan.has_tail ? extra[n_more] : nullptr;
-        const u64* x = in + (size_t)b0 * sin;
-        long long sx = sin;
-        u64* o = out + (size_t)b0 * sout;
-        bool tail_live = false;
-        for (const SlotSumStep& step : p.plan.steps) {
-            const u64* cx = x + (long long)L * N;
-            t.decompose(cx, sx);
-            const int nk = (int)step.keys.size();
-            const bool one_launch = multi && nk >= 2;
-            KsMacMultiKey mk[LSA_SLOTSUM_MAX_KEYS];
-            bool add_to[LSA_SLOTSUM_MAX_KEYS];   // sequential form: the key's product is added to its destination
-            const u64* next_more[LSA_SLOTSUM_MAX_KEYS];
-            const u64* tail_more = nullptr;
-            int n_next = 0, n_sum = 0, used = 0;
-            for (int i = 0; i < nk; i++) {
-                const SlotSumKey& k = step.keys[i];
-                u64* dst;
-                if (k.tail) {
-                    add_to[i] = tail_live;
-                    dst = !tail_live || !one_launch ? tail : extra[used++];
-                    if (dst != tail) tail_more = dst;
-                } else {
-                    add_to[i] = n_next > 0;
-                    dst = n_next == 0 || !one_launch ? t.acc : extra[used++];
-                    if (dst != t.acc) next_more[n_sum++] = dst;
-                    n_next++;
-                }
-                mk[i] = {key_of.at(k.g), scatter_of.at(k.g), dst};
-            }
-            if (one_launch) {
-                launch_ks_mac_multi(c, level, cx, sx, t.ext, t.s_ext, nk, mk, s_ext2, x, sx, nb, st);
-                if (n_sum) launch_ext_sum(c, level, n_sum, next_more, s_ext2, t.acc, s_ext2, true, nb, st);
-                if (tail_more) launch_ext_sum(c, level, 1, &tail_more, s_ext2, tail, s_ext2, true, nb, st);
-            } else {
-                for (int i = 0; i < nk; i++)
-                    launch_ks_mac(c, level, cx, sx, t.ext, t.s_ext, *mk[i].key, mk[i].out, s_ext2, nb, st, false, mk[i].scatter, x, sx, nullptr,
-                                  add_to[i]);
-            }
-            for (int i = 0; i < nk; i++) tail_live = tail_live || step.keys[i].tail;
-            t.moddown({.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2});
-            x = o;
-            sx = sout;
-        }
-        if (tail_live) ks_moddown(c, level, tail, s_ext2, t.conv, {.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2}, nb, st);
-    });
-}
-
-// ------------------------------------------------------------------------------------------------ BFV slot sum
-// out = sum_{i<count} rot_cols(y, i*step), y = in + rot_rows(in) if rows, by the plan of slot_sum.h on coefficient-domain
-// ciphertexts.  Per tile and step, as bfv_rotate_many: c1 of x into the NTT domain once (the MAC's own-digit operand), the
-// decomposition from the coefficients, one launch_ks_mac per key with the rotation's NTT-domain scatter -- the first NEXT key
-// writes the tile's acc, later ones add to it, the TAIL key writes or adds to the extended tail accumulator -- then the
-// coefficient-domain ModDown of the NEXT sum.  gather: the MACs add no P * c0; the tail (k_bfv_slot_tail) adds x and the rotated
-// c0 terms, gathered from the c0 row in LDS, and collects the TAIL rotation's c0 term in tail_c0 [L][N]; after the last step
-// out = x + (tail_c0, 0) + ModDown(tail).  plain: c0 is transformed too and enters the MACs as `base` (the CKKS form), the tails are
-// launch_moddown_final with base = x.  ModDown(P z + a) = z + ModDown(a) residue for residue, so both give the same words.  x
-// lives in `out` from the second step on and is updated in place.
-SlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count, int radix, int rows) {
-    try {
-        return bfv_slot_sum_plan(n_ring, step, count, radix, rows, LSA_BFV_SLOTSUM_DEFAULT_RADIX);
-    } catch (const std::invalid_argument& e) {
-        throw Error(LSA_ERR_ARG, e.what());
-    }
-}
-
-BfvSlotSum* bfv_slot_sum_create(Context& c, int level, long long step, int count, int radix, int rows) {
-    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "lsa_bfv_slot_sum_create: context is not BFV");
-    LSA_REQUIRE(level >= 0 && level < c.nq, "lsa_bfv_slot_sum_create: level out of range (0.." + std::to_string(c.nq - 1) + ")");
-    auto p = std::make_unique<BfvSlotSum>(c, level);
-    p->plan = bfv_slot_sum_plan_checked(c.n, step, count, radix, rows);
-    LSA_REQUIRE(p->plan.steps.empty() || c.np >= 1, "lsa_bfv_slot_sum_create: key switching needs at least one special prime");
-    return p.release();
-}
-
-void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
-                      const GaloisKeys& glk, hipStream_t s) {
-    Context& c = p.c;
-    const int level = p.level;
-    const EntryCheck ck(c, "lsa_bfv_slot_sum", LSA_ALGO_BFV, level, 0, batch);
-    const bool gather = p.gather;
-    const SlotSumCall call = slot_sum_prologue(c, ck, p.plan, p.plan.galois, glk, in, sin, out, sout, batch, gather, s);
-    if (!call.run) return;
-    const auto& key_of = call.key_of;
-    const auto& scatter_of = call.scatter_of;
-    const auto& perm_of = call.perm_of;
-    const long long N = c.n;
-    const int L = level + 1, T = L + c.np;
-    const bool has_tail = p.plan.has_tail;
-    const size_t ks_rows = KsTile::rows(c, level);
-    // per batch item: NTT(c1) | the KsTile rows | the extended tail accumulator | tail_c0 (gather) or NTT(c0) (plain)
-    const size_t r_tail = has_tail ? 2 * (size_t)T : 0, r_last = gather ? (has_tail ? (size_t)L : 0) : (size_t)L;
-    const long long sL = (long long)L * N;
-    for_tiles(c, (size_t)L + ks_rows + r_tail + r_last, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
-        u64* cxn = ws;
-        u64* ks_ws = cxn + (size_t)L * N * tb;
-        u64* tail = ks_ws + ks_rows * N * tb;
-        u64* last = tail + r_tail * N * tb;   // tail_c0 or NTT(c0)
-        KsTile t(c, level, nb, ks_ws, st);
-        const long long s_ext2 = t.s_acc;   // [2][T][N] per batch item, like t.acc
-        const u64* x = in + (size_t)b0 * sin;
-        long long sx = sin;
-        u64* o = out + (size_t)b0 * sout;
-        bool tail_live = false;
-        for (const SlotSumStep& step : p.plan.steps) {
-            const u64* c1 = x + sL;
-            launch_ntt(c, c1, cxn, nb, sx, sL, L, rm_seq(L), false, st);
-            if (!gather) launch_ntt(c, x, last, nb, sx, sL, L, rm_seq(L), false, st);
-            t.decompose(cxn, sL, c1, sx);
-            BfvSlotTail bt;
-            bool next_live = false;
-            for (const SlotSumKey& k : step.keys) {
-                const bool add_to = k.tail ? tail_live : next_live;
-                launch_ks_mac(c, level, cxn, sL, t.ext, t.s_ext, *key_of.at(k.g), k.tail ? tail : t.acc, s_ext2, nb, st, false,
-                              scatter_of.at(k.g), gather ? nullptr : last, sL, nullptr, add_to);
-                if (k.tail) {
-                    if (gather) {
-                        bt.tail = perm_of.at(k.g);
-                        bt.tail_c0 = last;
-                        bt.s_tail = sL;
-                        bt.tail_accumulate = tail_live;
-                    }
-                    tail_live = true;
-                } else {
-                    if (gather) bt.next[bt.n_next++] = perm_of.at(k.g);
-                    next_live = true;
-                }
-            }
-            t.moddown({.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2, .form = KsOut::COEFF,
-                       .slot_tail = gather ? &bt : nullptr});
-            x = o;
-            sx = sout;
-        }
-        if (tail_live) {
-            BfvSlotTail bt;
-            bt.addend = last;
-            bt.s_addend = sL;
-            ks_moddown(c, level, tail, s_ext2, t.conv,
-                       {.p = o, .sp = sout, .base = x, .sbase = sx, .base_rpp = L, .base_polys = 2, .form = KsOut::COEFF,
-                        .slot_tail = gather ? &bt : nullptr},
-                       nb, st);
-        }
-    });
 }
 
 }  // namespace lsa

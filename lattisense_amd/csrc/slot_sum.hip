@@ -1,4 +1,5 @@
-// slot_sum.hip — the device kernels of the slot sums (ops.hip slot_sum_run, bfv_slot_sum_run; plan: slot_sum.h).  CKKS:
+// slot_sum.hip — the slot sums: their device kernels and, below them, their runners on the key-switch tile of key_switch.h
+// (slot_sum_run, bfv_slot_sum_run; plan: slot_sum.h).  CKKS:
 //   k_ks_mac_multi<KB, K>  the gadget inner product of ONE decomposition with K = 2..4 keys ("a MAC kernel that reads the
 //                          decomposed digits once for all keys of a hoisted group"), each key's product leaving
 //                          as that key's rotated extended ciphertext in that key's own buffer;
@@ -10,8 +11,9 @@
 //                          gathered from the c0 row staged in LDS.
 #include <atomic>
 
+#include "entry_check.h"
+#include "key_switch.h"
 #include "ks_mac_multi.h"
-#include "lsa_internal.h"
 
 namespace lsa {
 
@@ -422,6 +424,238 @@ void launch_bfv_slot_tail(Context& c, int level, const BfvSlotTail& t, const u64
     }
     hipLaunchKernelGGL(k_bfv_slot_tail, dim3((unsigned)(2 * L), (unsigned)batch), dim3(LSA_SLOT_TAIL_THREADS), lds_bytes, s, g);
     LSA_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------ CKKS slot sum
+// out = sum_{i<count} rot(in, i*step) by the plan of slot_sum.h.  Per tile the steps run back to back: one decomposition of x's c1,
+// the gadget products of the step's 1..4 keys written as rotated extended ciphertexts (KsTile::mac_ext: the words of
+// ckks_rotate_ext) -- several keys in ONE k_ks_mac_multi launch, each into its own buffer, k_ext_sum joining them -- then
+// x <- x + ModDown(NEXT sum) with x riding on the ModDown tail's base (base_polys = 2).  That store is index for index, so from
+// the second step on x lives in `out` and is updated in place, and out == in is allowed.  The TAIL rotations gather in an extended
+// accumulator that is divided once, after the last step.  All temporaries are the tile's workspace: the KsTile rows, up to three more
+// extended ciphertexts for the keys of a multi-key launch beyond the first, and one for the tail.
+SlotSumPlanHost slot_sum_plan_checked(int n_ring, long long step, int count, int radix) {
+    try {
+        return slot_sum_plan(n_ring, step, count, radix, LSA_SLOTSUM_DEFAULT_RADIX);
+    } catch (const std::invalid_argument& e) {
+        throw Error(LSA_ERR_ARG, e.what());
+    }
+}
+
+SlotSum* slot_sum_create(Context& c, int level, long long step, int count, int radix) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_CKKS, "slot sum: context is not CKKS");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "slot sum: level out of range");
+    auto p = std::make_unique<SlotSum>(c, level);
+    p->plan = slot_sum_plan_checked(c.n, step, count, radix);
+    LSA_REQUIRE(p->plan.steps.empty() || c.np >= 1, "slot sum: key switching needs at least one special prime");
+    return p.release();
+}
+
+// What both slot-sum runners do before their tiles.  Every key of `elements` (the plan's, in the order a missing one is reported)
+// is looked up and checked before anything is queued; then the operands; a plan without steps (count == 1, no row fold) is a
+// copy; last the rotations' tables, element by element (table look-ups upload on first use: only after every argument is
+// accepted): the NTT-domain scatter and, for the BFV gathering tail, the coefficient-domain permutation.
+// run == false: nothing is left to do.
+struct SlotSumCall {
+    bool run = false;
+    GaloisKeys key_of;   // the plan's keys alone, all present
+    std::map<u64, const u32*> scatter_of, perm_of;
+};
+static SlotSumCall slot_sum_prologue(Context& c, const EntryCheck& ck, const SlotSumPlanHost& plan, const std::vector<u64>& elements,
+                                     const GaloisKeys& glk, const u64* in, long long sin, u64* out, long long sout, int batch,
+                                     bool gather, hipStream_t s) {
+    SlotSumCall call;
+    const std::vector<const Key*> keys = glk.resolve(elements, ck.who, [&](u64, const Key& k) { ck.key(k, "a Galois key"); });
+    for (size_t i = 0; i < elements.size(); i++) call.key_of.insert(elements[i], keys[i]);
+    if (batch <= 0) return call;
+    const int L = ck.level + 1;
+    const size_t w = 2 * (size_t)L * c.n;
+    const layout::Span sp_in = ck.operand(in, sin, w, "in", false), sp_out = ck.output(out, sout, w);
+    ck.same_or_apart(sp_out, sp_in, "in");
+    if (plan.steps.empty()) {
+        if (layout::same(sp_out, sp_in)) return call;
+        std::vector<int> rows(2 * L);
+        for (int i = 0; i < 2 * L; i++) rows[i] = i;
+        launch_copy_rows(c, in, sin, out, sout, 2 * L, rows.data(), batch, s);
+        return call;
+    }
+    LSA_REQUIRE(!gather || c.logn <= LSA_PERM_LDS_MAX_LOGN, ck.who + ": the gathering tail needs N <= 2^14");
+    for (u64 e : elements) {
+        call.scatter_of[e] = inverse_perm(c, e);
+        if (gather) call.perm_of[e] = c.coeff_perm(e);
+    }
+    call.run = true;
+    return call;
+}
+
+void slot_sum_run(SlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
+                  const GaloisKeys& glk, hipStream_t s) {
+    Context& c = p.c;
+    const int level = p.level;
+    const EntryCheck ck(c, "lsa_ckks_slot_sum", LSA_ALGO_CKKS, level, 0, batch);
+    std::vector<u64> by_rotation;   // a missing key is reported in the order of the plan's rotations
+    for (int r : p.plan.rotations) by_rotation.push_back(galois_of_rotation(r, c.n));
+    const SlotSumCall call = slot_sum_prologue(c, ck, p.plan, by_rotation, glk, in, sin, out, sout, batch, false, s);
+    if (!call.run) return;
+    const auto& key_of = call.key_of;
+    const auto& scatter_of = call.scatter_of;
+    const long long N = c.n;
+    const int L = level + 1, T = L + c.np;
+    const size_t ks_rows = KsTile::rows(c, level);
+    const bool multi = p.multi_mac;
+    // extended buffers beyond KsTile's acc: one per key of a multi-key launch that is neither the first NEXT key nor the first
+    // TAIL key of the plan (the most any step needs), and the tail accumulator
+    int n_more = 0;
+    {
+        bool live = false;
+        for (const SlotSumStep& step : p.plan.steps) {
+            int more = 0, next = 0;
+            for (const SlotSumKey& k : step.keys) more += k.tail ? (live ? 1 : 0) : (next++ ? 1 : 0);
+            for (const SlotSumKey& k : step.keys) live = live || k.tail;
+            if (multi && step.keys.size() >= 2) n_more = std::max(n_more, more);
+        }
+    }
+    const int n_extra = n_more + (p.plan.has_tail ? 1 : 0);
+    for_tiles(c, ks_rows + (size_t)n_extra * 2 * T, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
+        KsTile t(c, level, nb, ws, st);
+        const long long s_ext2 = t.s_acc;   // [2][T][N] per batch item, like t.acc
+        u64* extra[LSA_SLOTSUM_MAX_KEYS];
+        for (int i = 0; i < n_extra; i++) extra[i] = ws + (ks_rows * tb + (size_t)i * 2 * T * tb) * N;
+        u64* tail = p.plan.has_tail ? extra[n_more] : nullptr;
+        const u64* x = in + (size_t)b0 * sin;
+        long long sx = sin;
+        u64* o = out + (size_t)b0 * sout;
+        bool tail_live = false;
+        for (const SlotSumStep& step : p.plan.steps) {
+            t.decompose(KsSource::of_ntt(x + (long long)L * N, sx));
+            const int nk = (int)step.keys.size();
+            const bool one_launch = multi && nk >= 2;
+            KsMacMultiKey mk[LSA_SLOTSUM_MAX_KEYS];
+            bool add_to[LSA_SLOTSUM_MAX_KEYS];   // sequential form: the key's product is added to its destination
+            const u64* next_more[LSA_SLOTSUM_MAX_KEYS];
+            const u64* tail_more = nullptr;
+            int n_next = 0, n_sum = 0, used = 0;
+            for (int i = 0; i < nk; i++) {
+                const SlotSumKey& k = step.keys[i];
+                u64* dst;
+                if (k.tail) {
+                    add_to[i] = tail_live;
+                    dst = !tail_live || !one_launch ? tail : extra[used++];
+                    if (dst != tail) tail_more = dst;
+                } else {
+                    add_to[i] = n_next > 0;
+                    dst = n_next == 0 || !one_launch ? t.acc : extra[used++];
+                    if (dst != t.acc) next_more[n_sum++] = dst;
+                    n_next++;
+                }
+                mk[i] = {key_of.at(k.g), scatter_of.at(k.g), dst};
+            }
+            if (one_launch) {
+                t.mac_ext_multi(nk, mk, s_ext2, x, sx);
+                if (n_sum) launch_ext_sum(c, level, n_sum, next_more, s_ext2, t.acc, s_ext2, true, nb, st);
+                if (tail_more) launch_ext_sum(c, level, 1, &tail_more, s_ext2, tail, s_ext2, true, nb, st);
+            } else {
+                for (int i = 0; i < nk; i++)
+                    t.mac_ext(*mk[i].key, {.out = mk[i].out, .sout = s_ext2, .scatter = mk[i].scatter, .base = x, .sbase = sx, .accumulate = add_to[i]});
+            }
+            for (int i = 0; i < nk; i++) tail_live = tail_live || step.keys[i].tail;
+            t.moddown(ks_onto_ct(o, sout, x, sx, L));
+            x = o;
+            sx = sout;
+        }
+        if (tail_live) t.moddown_of(tail, s_ext2, ks_onto_ct(o, sout, x, sx, L));
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ BFV slot sum
+// out = sum_{i<count} rot_cols(y, i*step), y = in + rot_rows(in) if rows, by the plan of slot_sum.h on coefficient-domain
+// ciphertexts.  Per tile and step, as bfv_rotate_many: c1 of x into the NTT domain once (the MAC's own-digit operand, a COEFF
+// source of the tile), the decomposition from the coefficients, one extended MAC per key with the rotation's NTT-domain scatter
+// -- the first NEXT key writes the tile's acc, later ones add to it, the TAIL key writes or adds to the extended tail accumulator
+// -- then the coefficient-domain ModDown of the NEXT sum.  gather: the MACs add no P * c0; the tail (k_bfv_slot_tail) adds x and
+// the rotated c0 terms, gathered from the c0 row in LDS, and collects the TAIL rotation's c0 term in tail_c0 [L][N]; after the
+// last step out = x + (tail_c0, 0) + ModDown(tail).  plain: c0 is transformed too and enters the MACs as `base` (the CKKS form), the
+// tails are launch_moddown_final with base = x.  ModDown(P z + a) = z + ModDown(a) residue for residue, so both give the same
+// words.  x lives in `out` from the second step on and is updated in place.
+SlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count, int radix, int rows) {
+    try {
+        return bfv_slot_sum_plan(n_ring, step, count, radix, rows, LSA_BFV_SLOTSUM_DEFAULT_RADIX);
+    } catch (const std::invalid_argument& e) {
+        throw Error(LSA_ERR_ARG, e.what());
+    }
+}
+
+BfvSlotSum* bfv_slot_sum_create(Context& c, int level, long long step, int count, int radix, int rows) {
+    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "lsa_bfv_slot_sum_create: context is not BFV");
+    LSA_REQUIRE(level >= 0 && level < c.nq, "lsa_bfv_slot_sum_create: level out of range (0.." + std::to_string(c.nq - 1) + ")");
+    auto p = std::make_unique<BfvSlotSum>(c, level);
+    p->plan = bfv_slot_sum_plan_checked(c.n, step, count, radix, rows);
+    LSA_REQUIRE(p->plan.steps.empty() || c.np >= 1, "lsa_bfv_slot_sum_create: key switching needs at least one special prime");
+    return p.release();
+}
+
+void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
+                      const GaloisKeys& glk, hipStream_t s) {
+    Context& c = p.c;
+    const int level = p.level;
+    const EntryCheck ck(c, "lsa_bfv_slot_sum", LSA_ALGO_BFV, level, 0, batch);
+    const bool gather = p.gather;
+    const SlotSumCall call = slot_sum_prologue(c, ck, p.plan, p.plan.galois, glk, in, sin, out, sout, batch, gather, s);
+    if (!call.run) return;
+    const auto& key_of = call.key_of;
+    const auto& scatter_of = call.scatter_of;
+    const auto& perm_of = call.perm_of;
+    const long long N = c.n;
+    const int L = level + 1, T = L + c.np;
+    const bool has_tail = p.plan.has_tail;
+    const size_t ks_rows = KsTile::rows(c, level, KsSource::COEFF);   // NTT(c1) in front of the tile's own rows
+    // per batch item: the KsTile rows | the extended tail accumulator | tail_c0 (gather) or NTT(c0) (plain)
+    const size_t r_tail = has_tail ? 2 * (size_t)T : 0, r_last = gather ? (has_tail ? (size_t)L : 0) : (size_t)L;
+    const long long sL = (long long)L * N;
+    for_tiles(c, ks_rows + r_tail + r_last, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
+        u64* tail = ws + ks_rows * N * tb;
+        u64* last = tail + r_tail * N * tb;   // tail_c0 or NTT(c0)
+        // (tb: tail and last follow the tile's rows at offsets counted in tiles of tb items, so the tile's NTT(c1) block in front
+        // of its own rows spans tb items as well, a ragged last tile included)
+        KsTile t(c, level, nb, ws, st, nullptr, KsSource::COEFF, tb);
+        const long long s_ext2 = t.s_acc;   // [2][T][N] per batch item, like t.acc
+        const u64* x = in + (size_t)b0 * sin;
+        long long sx = sin;
+        u64* o = out + (size_t)b0 * sout;
+        bool tail_live = false;
+        for (const SlotSumStep& step : p.plan.steps) {
+            if (!gather) launch_ntt(c, x, last, nb, sx, sL, L, rm_seq(L), false, st);
+            t.decompose(KsSource::of_coeff(x + sL, sx));
+            BfvSlotTail bt;
+            bool next_live = false;
+            for (const SlotSumKey& k : step.keys) {
+                const bool add_to = k.tail ? tail_live : next_live;
+                t.mac_ext(*key_of.at(k.g), {.out = k.tail ? tail : t.acc, .sout = s_ext2, .scatter = scatter_of.at(k.g),
+                                            .base = gather ? nullptr : last, .sbase = sL, .accumulate = add_to});
+                if (k.tail) {
+                    if (gather) {
+                        bt.tail = perm_of.at(k.g);
+                        bt.tail_c0 = last;
+                        bt.s_tail = sL;
+                        bt.tail_accumulate = tail_live;
+                    }
+                    tail_live = true;
+                } else {
+                    if (gather) bt.next[bt.n_next++] = perm_of.at(k.g);
+                    next_live = true;
+                }
+            }
+            t.moddown(ks_onto_ct(o, sout, x, sx, L, {.form = KsOut::COEFF, .slot_tail = gather ? &bt : nullptr}));
+            x = o;
+            sx = sout;
+        }
+        if (tail_live) {
+            BfvSlotTail bt;
+            bt.addend = last;
+            bt.s_addend = sL;
+            t.moddown_of(tail, s_ext2, ks_onto_ct(o, sout, x, sx, L, {.form = KsOut::COEFF, .slot_tail = gather ? &bt : nullptr}));
+        }
+    });
 }
 
 }  // namespace lsa

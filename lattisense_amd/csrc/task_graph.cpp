@@ -327,7 +327,7 @@ void TaskGraph::validate_structure() const {
 // partial-sum input).  Modular addition is associative and commutative, so every residue of the result is unchanged; a
 // 72-term accumulation becomes 5 launches instead of 72 products + 71 dependent additions.
 // Peephole: CKKS mult(ct,ct) -> relin -> rescale whose intermediates have no other reader becomes one node that runs the
-// fused operator (merged ModDown+rescale tail, ops.hip): same residues, 104 instead of 128 limb transforms.
+// fused operator (merged ModDown+rescale tail, key_switch.hip): same residues, 104 instead of 128 limb transforms.
 void TaskGraph::fuse_mult_relin_rescale() {
     if (algo != ALGO_CKKS) return;
     auto private_to = [](const DatumNode* d) {

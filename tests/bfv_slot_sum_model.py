@@ -1,4 +1,4 @@
-"""CPU restatement of the BFV slot sum (lattisense_amd/csrc/slot_sum.h and ops.hip bfv_slot_sum_run), twice:
+"""CPU restatement of the BFV slot sum (lattisense_amd/csrc/slot_sum.h and slot_sum.hip bfv_slot_sum_run), twice:
 
 slot_sum        the words as include/lattisense_amd.h fixes them: every limb of the ciphertext into the NTT domain, the steps on
                 oracle/ckks_bootstrap.py's rotate_ext, add_ext, moddown and add exactly as tests/slot_sum_model.py slot_sum states

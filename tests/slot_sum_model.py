@@ -1,4 +1,4 @@
-"""CPU restatement of the CKKS slot sum (lattisense_amd/csrc/slot_sum.h and ops.hip slot_sum_run) over
+"""CPU restatement of the CKKS slot sum (lattisense_amd/csrc/slot_sum.h and slot_sum.hip slot_sum_run) over
 oracle/ckks_bootstrap.py's Evaluator: the plan rule written out again, and its steps replayed with rotate_ext, add_ext, moddown and
 add exactly as the operator states them.  The device gives these words."""
 

@@ -1,4 +1,4 @@
-"""BFV slot sum on the device (lsa_bfv_slot_sum_*; ops.hip bfv_slot_sum_run, slot_sum.hip k_bfv_slot_tail) against its CPU model
+"""BFV slot sum on the device (lsa_bfv_slot_sum_*; slot_sum.hip bfv_slot_sum_run and k_bfv_slot_tail) against its CPU model
 (tests/bfv_slot_sum_model.py slot_sum on oracle/ckks_bootstrap.py): identical word for word, for every batch item, on a one-pass
 ring (every count that takes another plan shape, both radices, with and without the row step, three steps), with keys above the
 plan's level, on 60/61-bit special primes (integer engine), on the full N = 2^14 ring (two-pass transforms, the 128 KiB LDS row) and

@@ -1,4 +1,4 @@
-"""CKKS slot sum on the device (lsa_slot_sum_* / lsa_ckks_slot_sum; ops.hip slot_sum_run, slot_sum.hip k_ks_mac_multi / k_ext_sum)
+"""CKKS slot sum on the device (lsa_slot_sum_* / lsa_ckks_slot_sum; slot_sum.hip slot_sum_run, k_ks_mac_multi / k_ext_sum)
 against its CPU model (tests/slot_sum_model.py on oracle/ckks_bootstrap.py): identical word for word, for every batch item, on a
 one-pass ring (every count that takes another plan shape, both radices, three steps), on 61-bit primes (integer engine, unfused
 MAC), with more than eight digits (the streaming instantiation), on a whole-limb ring with a partial last batch group and on a

@@ -1,5 +1,5 @@
 """Key switch with the ModUp of a single-limb digit lifted by the load of its extension transform (NttPassArgs::fz_pro == 4,
-ops.hip KsTile::decompose) instead of a base-conversion launch.  The lift changes which kernel produces the digit's extension
+key_switch.hip KsTile::decompose) instead of a base-conversion launch.  The lift changes which kernel produces the digit's extension
 rows, never a residue: every output is compared bit for bit with lsa_set_modup_lift(ctx, 0) (the conversion kernel, same context) and
 with the CPU oracle, at the smallest shapes that reach each kernel the prologue lives in -- the single-pass and the staged
 two-pass k_ntt_pass, the 7- and 8-stage k_ntt_r16 first passes, k_ntt_r8x3 behind a lifted first pass -- with the key MAC fused

@@ -13,7 +13,8 @@ from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_SOURCES = ["lattisense_amd/csrc/kernels.hip", "lattisense_amd/csrc/ntt_core.h", "lattisense_amd/csrc/ntt_r16.h",
-                  "lattisense_amd/csrc/modarith.h", "lattisense_amd/csrc/ops.hip"]
+                  "lattisense_amd/csrc/modarith.h", "lattisense_amd/csrc/ops.hip", "lattisense_amd/csrc/key_switch.hip",
+                  "lattisense_amd/csrc/slot_sum.hip"]
 NTT_KERNELS = ("k_ntt_r16", "k_ntt_r8x3", "k_ntt_pass")   # the limb-transform passes: radix-16-squared (8- / 7-stage), three radix-8 groups (9-stage), the staged kernel
 
 
