@@ -545,6 +545,56 @@ int lsa_poly_constants(lsa_polynomial p, long long* out, int capacity);
 int lsa_ckks_poly_eval(lsa_context ctx, lsa_polynomial p, const uint64_t* in, uint64_t* out, int batch, long long sin,
                        long long sout, lsa_key rlk, void* stream);
 
+/* ---- BFV polynomial evaluation: p(x) = sum_{k < n_coef} coef[k] x^k mod t, slot-wise on a ciphertext, by a FLAT baby-step /
+ * giant-step plan.  m = 2^log_baby, G = ceil(n_coef / m), the coefficients zero-padded to G * m:
+ *   baby powers   x^j = x^ceil(j/2) * x^floor(j/2) for 2 <= j < m, by lsa_bfv_mult_relin: only those a non-zero coefficient
+ *                 needs, or another needed power needs;
+ *   giant powers  y = x^m = x^(m/2) * x^(m/2) and y^g = y^ceil(g/2) * y^floor(g/2) for 2 <= g < G: only those a non-zero leaf needs,
+ *                 and their halves;
+ *   leaves        leaf_g = coef[g m] + sum_{1 <= j < m} coef[g m + j] x^j, up to 8 per launch of one kernel that reads every baby
+ *                 power once per launch; an all-zero leaf does not exist, a leaf that is only a constant is the trivial
+ *                 ciphertext (c1 = 0) and goes through the sum like any other;
+ *   sum           out = leaf_0 + sum_{g >= 1, leaf_g != 0} leaf_g * y^g by lsa_bfv_dot with leaf_0 as its addend: ONE scale-down
+ *                 by Q and ONE relinearisation for the whole sum.  With no term g >= 1, out is leaf_0 itself.
+ * Counts: n_mult = key switches = baby powers computed + giant powers computed (y included) + 1 if the sum has a term;
+ * n_pairs = terms of the sum; n_leaf_launches = ceil(n_leaves / 8); depth from d(x^j) = ceil(log2 j), d(y^g) = log_baby +
+ * ceil(log2 g), d(leaf) = the maximum over its used powers (0 for a constant): depth = max(d(leaf_0), max_g(max(d(leaf_g), d(y^g)) + 1)).
+ * depth is the multiplicative depth of the circuit, which is what the noise budget of a BFV parameter set runs out of: every
+ * level of it takes bits off the margin between the noise and Q/2t, and a plan one level deeper can fail to decrypt where the
+ * shallower one succeeds (DESIGN.md 4.15 has figures measured on the CPU oracle).  log_baby = 0 therefore asks for the least
+ * depth first, then the least n_mult, then the smaller value; 1..4 forces it.
+ * n_coef: 1..256; every coef[k] < t; a polynomial whose highest non-zero coefficient is coef[0] is refused.
+ * A coefficient enters a leaf centred into (-t/2, t/2]; the constant c of a leaf is Lattigo's scaleUp of the constant polynomial
+ * (c in every slot, one coefficient of c0), the words of lsa_bfv_affine_const below.  The words of the whole operator are those of
+ * the composition of lsa_bfv_mult_relin, lsa_bfv_affine_const, lsa_poly_addsub and lsa_bfv_dot (tests/bfv_poly_model.py).
+ * All ciphertexts are [2][level+1][N], coefficient domain, at the plan's ONE level (a BFV level change is no row prefix); the
+ * relinearisation key is the only key.  A run holds (m-1) + (G-1) + n_leaves ciphertexts per batch item at most, in ONE
+ * workspace of the plan, kept across runs (a plan runs on one stream at a time); a run at another batch size waits for `stream`,
+ * gives the workspace back and takes one of its own size.  out overlaps no input; pointers are 16-byte aligned and strides
+ * even; batch <= 0 is a no-op; everything runs on `stream`.  Errors are LSA_ERR_ARG before anything is queued, messages beginning
+ * "bfv_poly": a CKKS context, a level out of range, n_coef outside 1..256, a coefficient >= t, degree 0, log_baby outside 0..4, a
+ * null pointer, a missing key or one exported below `level`, a plan of another context, out overlapping in, a bad alignment or
+ * stride, and (at create) a level whose auxiliary basis the context cannot hold for one product or for the sum's largest group,
+ * which is what lsa_bfv_mult and lsa_bfv_dot would refuse in the middle of a run. */
+typedef struct lsa_bfv_polynomial_st* lsa_bfv_polynomial;
+/* host only, no context, no device; every output pointer nullable */
+int lsa_bfv_poly_plan(uint64_t t, int n_coef, const uint64_t* coef, int log_baby, int* log_baby_out, int* depth, int* n_mult,
+                      int* n_leaves, int* n_leaf_launches, int* n_pairs);
+int lsa_bfv_poly_create(lsa_context ctx, int level, int n_coef, const uint64_t* coef, int log_baby, void* stream,
+                        lsa_bfv_polynomial* out);
+void lsa_bfv_poly_destroy(lsa_bfv_polynomial p);
+int lsa_bfv_poly_info(lsa_bfv_polynomial p, int* level, int* n_coef, int* log_baby, int* depth, int* n_mult, int* n_leaves,
+                      int* n_leaf_launches, int* n_pairs);
+int lsa_bfv_poly_eval(lsa_context ctx, lsa_bfv_polynomial p, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                      long long sout, lsa_key rlk, void* stream);
+/* out = k * ct + c in every slot, k and c below t: the kernel with one source and one output; out may BE ct (same stride).
+ * Limb j of out is (k centred into (-t/2, t/2], mod q_j) * ct, plus on coefficient 0 of c0 the word of Lattigo's scaleUp of the
+ * constant polynomial c.  The 2 (level + 1) constant words travel in the launch's arguments: the call allocates nothing, copies
+ * nothing to the device and keeps nothing per (k, c), so any number of distinct constants costs the same; level + 1 <= 64.
+ * Errors are LSA_ERR_ARG, messages beginning "lsa_bfv_affine_const". */
+int lsa_bfv_affine_const(lsa_context ctx, int level, const uint64_t* ct, long long sct, uint64_t k, uint64_t c, uint64_t* out,
+                         long long sout, int batch, void* stream);
+
 /* diagnostic builds only (-DLSA_NTT_DIAG_STAMPS): device buffer of 8192*8 u64 receiving per-workgroup phase time stamps
  * of every following NTT launch; NULL turns it off.  Ignored by the normal build. */
 int lsa_debug_set_ntt_stamps(lsa_context ctx, void* device_buffer);

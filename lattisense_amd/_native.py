@@ -179,6 +179,12 @@ SIGNATURES = {
                               ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "lsa_poly_constants": (c_int, [c_vp, ctypes.POINTER(c_ll), c_int]),
     "lsa_ckks_poly_eval": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_vp, c_vp]),
+    "lsa_bfv_poly_plan": (c_int, [ctypes.c_uint64, c_int, c_u64p, c_int] + [ctypes.POINTER(c_int)] * 6),
+    "lsa_bfv_poly_create": (c_int, [c_vp, c_int, c_int, c_u64p, c_int, c_vp, ctypes.POINTER(c_vp)]),
+    "lsa_bfv_poly_destroy": (None, [c_vp]),
+    "lsa_bfv_poly_info": (c_int, [c_vp] + [ctypes.POINTER(c_int)] * 8),
+    "lsa_bfv_poly_eval": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_vp, c_vp]),
+    "lsa_bfv_affine_const": (c_int, [c_vp, c_int, c_vp, c_ll, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_ll, c_int, c_vp]),
     "lsa_profile_begin": (c_int, [c_vp, c_int]),
     "lsa_profile_end": (c_int, [c_vp]),
     "lsa_profile_read": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),

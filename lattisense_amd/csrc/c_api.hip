@@ -1,6 +1,7 @@
 // c_api.hip — extern "C" operator layer (include/lattisense_amd.h).  Every entry point converts C++ exceptions into
 // error codes: nothing throws across the C boundary (the reference does, SURVEY §8b "Errors").
 #include "bfv_encode.h"
+#include "bfv_poly.h"
 #include "build_flags.h"
 #include "linear_transform.h"
 #include "poly_eval.h"
@@ -51,8 +52,8 @@ static const Key& K(lsa_key k, const char* who = nullptr) {
 }
 static hipStream_t S(void* s) { return (hipStream_t)s; }
 
-// ---- plan handles.  The operators that work through a plan (bootstrap, the two linear transforms, the two slot sums, polynomial
-// evaluation) hand out one kind of handle: the plan with its deleter and the context it was made on.  The public header keeps a
+// ---- plan handles.  The operators that work through a plan (bootstrap, the two linear transforms, the two slot sums, the two polynomial
+// evaluators) hand out one kind of handle: the plan with its deleter and the context it was made on.  The public header keeps a
 // distinct opaque type per operator; each derives from PlanHandle.  Every entry point keeps its own message texts.
 template <typename T>
 struct PlanHandle {
@@ -977,6 +978,58 @@ int lsa_ckks_poly_eval(lsa_context ctx, lsa_polynomial p, const uint64_t* in, ui
         LSA_REQUIRE(in != nullptr && out != nullptr, "null argument");
         LSA_REQUIRE(rlk != nullptr && rlk->key.data != nullptr, "poly: the relinearisation key is missing");
         poly_run(poly, in, sin, out, sout, batch, K(rlk), S(stream));
+    });
+}
+
+// ---- BFV polynomial evaluation and constant operands (bfv_poly.hip; the planner is bfv_poly.h's and needs no device)
+struct lsa_bfv_polynomial_st : PlanHandle<BfvPolynomial> {};
+static void bfv_poly_counts(const BfvPolyPlan& p, int* log_baby, int* depth, int* n_mult, int* n_leaves, int* n_leaf_launches,
+                            int* n_pairs) {
+    if (log_baby) *log_baby = p.log_baby;
+    if (depth) *depth = p.depth;
+    if (n_mult) *n_mult = p.n_mult;
+    if (n_leaves) *n_leaves = p.n_leaves;
+    if (n_leaf_launches) *n_leaf_launches = p.n_leaf_launches;
+    if (n_pairs) *n_pairs = p.n_pairs;
+}
+int lsa_bfv_poly_plan(uint64_t t, int n_coef, const uint64_t* coef, int log_baby, int* log_baby_out, int* depth, int* n_mult,
+                      int* n_leaves, int* n_leaf_launches, int* n_pairs) {
+    return guard([&] {
+        bfv_poly_counts(bfv_poly_plan_checked(t, n_coef, coef, log_baby), log_baby_out, depth, n_mult, n_leaves, n_leaf_launches, n_pairs);
+    });
+}
+int lsa_bfv_poly_create(lsa_context ctx, int level, int n_coef, const uint64_t* coef, int log_baby, void* stream,
+                        lsa_bfv_polynomial* out) {
+    return guard([&] {
+        LSA_REQUIRE(out != nullptr, "bfv_poly: null argument (out)");
+        LSA_REQUIRE(ctx != nullptr, "bfv_poly: null context");
+        Context& c = C(ctx);
+        make_plan(out, c, bfv_poly_create(c, level, n_coef, coef, log_baby, S(stream)), bfv_poly_destroy);
+    });
+}
+void lsa_bfv_poly_destroy(lsa_bfv_polynomial p) { delete p; }
+int lsa_bfv_poly_info(lsa_bfv_polynomial p, int* level, int* n_coef, int* log_baby, int* depth, int* n_mult, int* n_leaves,
+                      int* n_leaf_launches, int* n_pairs) {
+    return guard([&] {
+        const BfvPolynomial& poly = P(p, "bfv_poly: null plan handle");
+        if (level) *level = bfv_poly_level(poly);
+        if (n_coef) *n_coef = bfv_poly_plan_of(poly).n_coef;
+        bfv_poly_counts(bfv_poly_plan_of(poly), log_baby, depth, n_mult, n_leaves, n_leaf_launches, n_pairs);
+    });
+}
+int lsa_bfv_poly_eval(lsa_context ctx, lsa_bfv_polynomial p, const uint64_t* in, uint64_t* out, int batch, long long sin,
+                      long long sout, lsa_key rlk, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(ctx != nullptr, "bfv_poly: null context");
+        BfvPolynomial& poly = P(p, ctx, "bfv_poly: null plan handle", "bfv_poly: the plan belongs to another context");
+        bfv_poly_run(poly, in, sin, out, sout, batch, rlk ? &rlk->key : nullptr, S(stream));
+    });
+}
+int lsa_bfv_affine_const(lsa_context ctx, int level, const uint64_t* ct, long long sct, uint64_t k, uint64_t c, uint64_t* out,
+                         long long sout, int batch, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(ctx != nullptr, "lsa_bfv_affine_const: null context");
+        bfv_affine_const(C(ctx), level, ct, sct, k, c, out, sout, batch, S(stream));
     });
 }
 

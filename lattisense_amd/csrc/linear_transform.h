@@ -75,6 +75,9 @@ struct DCt {
     u64* data() const { return buf->p + off; }
 };
 
+// `words` words from the pool (an exact-size free buffer, else a fresh allocation); they go back to it with the last copy
+DCt pool_alloc_words(DevPool& pool, size_t words);
+
 struct LtEval {
     Context& c;
     DevPool& pool;   // released device buffers (single in-order stream: reuse is ordered)

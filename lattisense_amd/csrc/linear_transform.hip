@@ -205,7 +205,9 @@ void DevPool::release() {
     free.clear();
 }
 
-DCt LtEval::alloc_words(size_t words) {
+DCt LtEval::alloc_words(size_t words) { return pool_alloc_words(pool, words); }
+
+DCt pool_alloc_words(DevPool& pool, size_t words) {
     auto b = std::make_shared<DBuf>();
     b->words = words;
     b->pool = &pool;

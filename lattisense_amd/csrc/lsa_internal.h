@@ -578,6 +578,20 @@ void bfv_mult_relin(Context& c, int level, const u64* a, const u64* b, const Key
 void bfv_mult_sum(Context& c, int level, const DotTerms& t, u64* d3, int batch, long long sd, hipStream_t s);
 // out = bfv_relin(d3 above): ONE scale-down per group of terms and ONE key switch for the whole sum
 void bfv_dot(Context& c, int level, const DotTerms& t, const Key* rlk, u64* out, int batch, long long so, hipStream_t s);
+// BFV polynomial evaluation and constant operands (bfv_poly.hip; planner and counts: bfv_poly.h; semantics:
+// include/lattisense_amd.h).  The plan is opaque outside its unit; ciphertexts are coefficient-domain [2][level+1][N].
+struct BfvPolyPlan;
+struct BfvPolynomial;
+BfvPolyPlan bfv_poly_plan_checked(u64 t, int n_coef, const u64* coef, int log_baby);   // the planner's refusals as LSA_ERR_ARG
+BfvPolynomial* bfv_poly_create(Context& c, int level, int n_coef, const u64* coef, int log_baby, hipStream_t s);
+void bfv_poly_destroy(BfvPolynomial* p);
+const BfvPolyPlan& bfv_poly_plan_of(const BfvPolynomial& p);
+int bfv_poly_level(const BfvPolynomial& p);
+// out = p(in) slot-wise; out overlaps no word of in; rlk null: refused
+void bfv_poly_run(BfvPolynomial& p, const u64* in, long long sin, u64* out, long long sout, int batch, const Key* rlk, hipStream_t s);
+// out = k * ct + c in every slot (k, c < t); out may be ct itself (same pointer, same stride)
+void bfv_affine_const(Context& c, int level, const u64* ct, long long sct, u64 k, u64 cst, u64* out, long long sout, int batch,
+                      hipStream_t s);
 void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64* out, int batch, long long sin,
                 long long sout, hipStream_t s);
 void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,

@@ -432,6 +432,14 @@ class DeviceContext:
                                 2 * L * self.n, self.stream))
         return out
 
+    def bfv_affine_const(self, level, ct, k, c, batch, out=None):
+        """k * ct + c in every slot, k and c in [0, t): [batch][2][level+1][N], coefficient domain; out=ct works in place"""
+        w = 2 * (level + 1) * self.n
+        if out is None:
+            out = self.alloc(max(batch, 1) * w)
+        check(lib().lsa_bfv_affine_const(self.h, level, ct.ptr, w, int(k), int(c), out.ptr, w, batch, self.stream))
+        return out
+
 
 def bfv_dot_plan(n, q, level, terms):
     """{max_terms, groups, aux_limbs} of the BFV inner product of `terms` pairs at `level` of the chain q at ring degree n -- host
@@ -844,4 +852,47 @@ class PolynomialPlan(_Plan):
             out = self.ctx.alloc(max(batch, 1) * 2 * (self.level_out + 1) * n)
         check(lib().lsa_ckks_poly_eval(self.ctx.h, self.h, in_buf.ptr, out.ptr, batch, 2 * (self.level_in + 1) * n,
                                        2 * (self.level_out + 1) * n, rlk, self.ctx.stream))
+        return out
+
+
+_BFV_POLY_COUNTS = ("log_baby", "depth", "n_mult", "n_leaves", "n_leaf_launches", "n_pairs")
+
+
+def _u64_array(values):
+    return (ctypes.c_uint64 * max(len(values), 1))(*[int(x) for x in values])
+
+
+def bfv_poly_plan(t, coeffs, log_baby=0):
+    """{log_baby, depth, n_mult, n_leaves, n_leaf_launches, n_pairs} of the flat baby-step / giant-step plan that
+    sum_k coeffs[k] x^k mod t gets -- host only (include/lattisense_amd.h: lsa_bfv_poly_plan); log_baby 0 = the planner's choice"""
+    v = [ctypes.c_int() for _ in _BFV_POLY_COUNTS]
+    check(lib().lsa_bfv_poly_plan(int(t), len(coeffs), _u64_array(coeffs), int(log_baby), *[ctypes.byref(x) for x in v]))
+    return {k: x.value for k, x in zip(_BFV_POLY_COUNTS, v)}
+
+
+class BfvPolynomialPlan(_Plan):
+    """sum_k coeffs[k] x^k mod t, slot-wise on coefficient-domain BFV ciphertexts at `level`, coeffs in [0, t)
+    (include/lattisense_amd.h: lsa_bfv_poly_*).  The only key is the relinearisation key."""
+    _destroy = "lsa_bfv_poly_destroy"
+
+    def __init__(self, ctx, coeffs, level, log_baby=0):
+        self.ctx, self.level = ctx, int(level)
+        self.h = None
+        self._adopt(lambda h: lib().lsa_bfv_poly_create(ctx.h, self.level, len(coeffs), _u64_array(coeffs), int(log_baby), ctx.stream, h))
+        for k, x in self.info().items():
+            setattr(self, k, x)
+
+    def info(self):
+        """the device plan's own counts (lsa_bfv_poly_info)"""
+        v = [ctypes.c_int() for _ in range(8)]
+        check(lib().lsa_bfv_poly_info(self.h, *[ctypes.byref(x) for x in v]))
+        return {k: x.value for k, x in zip(("level", "n_coef") + _BFV_POLY_COUNTS, v)}
+
+    def run(self, in_buf, batch, rlk, out=None):
+        """in_buf: device [batch][2][level+1][N]; rlk: relinearisation key handle; returns device [batch][2][level+1][N]
+        (out overlaps no word of in_buf)"""
+        w = 2 * (self.level + 1) * self.ctx.n
+        if out is None:
+            out = self.ctx.alloc(max(batch, 1) * w)
+        check(lib().lsa_bfv_poly_eval(self.ctx.h, self.h, in_buf.ptr, out.ptr, batch, w, w, rlk, self.ctx.stream))
         return out
