@@ -103,6 +103,67 @@ def ceiling_mixed_chain(n, np_):
     return {"n": n, "q": q, "p": p}
 
 
+# ---------------------------------------------------------------- BFV chains (tests/test_gpu_boundary.py, the operator-chain tests)
+
+def bfv_mixed_chain(n):
+    """FP64-size primes (46/47/48-bit) next to 57/58/59-bit ones: the narrow-split predicate of the base conversions is false
+    although some sources are below 2^58; P: two 61-bit primes"""
+    q = (params.ntt_primes_below(46, n, 1) + params.ntt_primes_below(59, n, 1) + params.ntt_primes_below(47, n, 1) +
+         primes_above(57, n, 1) + primes_above(47, n, 1) + params.ntt_primes_below(58, n, 1) + params.ntt_primes_below(57, n, 1) +
+         primes_above(46, n, 1))
+    return q, params.ntt_primes_below(61, n, 2)
+
+
+def bfv_fp_chain(n):
+    """every limb on the FP64 butterfly engine.  Q: the two largest NTT primes below 2^47, the largest below 2^46 and the smallest
+    above 2^45; P: the next two primes below 2^47"""
+    top = params.ntt_primes_below(47, n, 4)
+    q = top[:2] + params.ntt_primes_below(46, n, 1) + primes_above(45, n, 1)
+    p = top[2:]
+    assert len(set(q + p)) == 6 and all(fp_engine(m) and params._is_prime(m) and (m - 1) % (2 * n) == 0 for m in q + p), (q, p)
+    assert [m.bit_length() for m in q] == [47, 47, 46, 46] and all(m.bit_length() == 47 for m in p), (q, p)
+    return q, p
+
+
+BFV_OPERATOR_CHAINS = ("fp", "mixed", "ceiling")
+BFV_OPERATOR_T = 65537
+
+
+def bfv_operator_chain(kind, n):
+    """(q, p) of the three chains the BFV operators are held to (tests/test_gpu_bfv_operator_chains.py):
+    fp       bfv_fp_chain: 4 Q + 2 P, all six on the FP64 engine;
+    mixed    the first six Q limbs of bfv_mixed_chain (46, 59, 47, 58, 48 and 58 bits) with its two 61-bit P: both engines in
+             every launch over Q u P;
+    ceiling  ceiling_chain(n, 4, 2): six primes just below 2^61, none on the FP64 engine.
+    The special primes come in pairs, so a level with an odd number of limbs ends its decomposition in a digit of one limb."""
+    if kind == "fp":
+        return bfv_fp_chain(n)
+    if kind == "mixed":
+        q, p = bfv_mixed_chain(n)
+        q = q[:6]
+        assert any(fp_engine(m) for m in q) and any((1 << 47) < m < (1 << 48) for m in q)
+        assert any(m.bit_length() in (58, 59) for m in q) and all(m.bit_length() == 61 for m in p) and len(p) == 2
+        return q, p
+    assert kind == "ceiling", kind
+    C = ceiling_chain(n, 4, 2)
+    return C["q"], C["p"]
+
+
+def digit_sizes(level, np_):
+    """limbs per key-switch digit at `level` with np_ special primes"""
+    L = level + 1
+    return [min(np_, L - d) for d in range(0, L, np_)]
+
+
+def lift_level(q, p):
+    """the highest level below the top whose last digit is exactly one limb: the digit the ModUp lift applies to (when that limb
+    is below 2^53)"""
+    for level in range(len(q) - 2, -1, -1):
+        if digit_sizes(level, len(p))[-1] == 1:
+            return level
+    raise AssertionError("no level with a single-limb last digit")
+
+
 def pattern(name, q, n, rng):
     """one limb-polynomial of n residues modulo q"""
     q = int(q)

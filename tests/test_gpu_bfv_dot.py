@@ -300,7 +300,10 @@ def test_shared_operands_squares_and_chunk_sizes():
 
 @pytest.mark.parametrize("mode", ["LSA_BFV_FOLD=0", "fp64_off"])
 def test_switches(mode):
-    """the unfolded extension and tail (LSA_BFV_FOLD=0, read per call) and the integer NTT engine give the same words"""
+    """the unfolded extension and tail (LSA_BFV_FOLD=0, read per call) and a context with lsa_set_fp64_ntt(0) give the same
+    words.  This chain (54 / 55-bit Q, 55-bit P, 61-bit auxiliary primes) has no FP64-engine limb, so fp64_off runs the integer
+    engine on every row as the default does: it shows that the setting itself changes nothing.  The comparison of the two engines
+    lives in tests/test_gpu_bfv_operator_chains.py (test_dot_variants on the fp and mixed chains)."""
     need_gpu()
     P = params.BFV_DEFAULT[8192]
     n, lvl, batch, terms = 1 << 12, 1, 2, 5    # level 1, five terms: M(5) = M(1) + 1

@@ -103,6 +103,9 @@ def test_form1_is_the_pt_mul_helper_and_multiplies_messages(n, levels):
 
 
 def test_form2_is_a_forward_transform_per_row():
+    """N = 2^13 (54 / 55-bit Q, 55-bit P): no row of this chain is an FP64-engine limb, so the run after lsa_set_fp64_ntt(0)
+    ("integer engine") uses the engine the first run used and shows that the setting itself changes nothing.  The comparison of
+    the two engines on form 2 lives in tests/test_gpu_bfv_operator_chains.py (test_encode_variants on the fp and mixed chains)."""
     need_gpu()
     n, lvl = 8192, 2
     ctx, o, c, t = _rig(n)

@@ -182,7 +182,10 @@ def test_composition_of_public_entry_points(rig, inputs):
 
 
 def test_switches(rig, inputs):
-    """tile batch 0 / 1 / 2 and single / dual stream give the same words; so does the integer NTT engine on a fresh context"""
+    """tile batch 0 / 1 / 2 and single / dual stream give the same words; so does a fresh context with lsa_set_fp64_ntt(0).  This
+    chain (54 / 55-bit Q, 55-bit P, 61-bit auxiliary primes) has no FP64-engine limb, so both contexts run the integer engine on
+    every row: the run shows that the setting itself changes nothing.  The comparison of the two engines lives in
+    tests/test_gpu_bfv_operator_chains.py (test_poly_eval_variants on the fp and mixed chains)."""
     from lattisense_amd._native import check, lib
     ctx, lvl, batch = rig.ctx, 2, 3
     h, d = inputs[lvl]

@@ -2,9 +2,9 @@
 (tests/bfv_slot_sum_model.py slot_sum on oracle/ckks_bootstrap.py): identical word for word, for every batch item, on a one-pass
 ring (every count that takes another plan shape, both radices, with and without the row step, three steps), with keys above the
 plan's level, on 60/61-bit special primes (integer engine), on the full N = 2^14 ring (two-pass transforms, the 128 KiB LDS row) and
-above the LDS limit (the plain form); the same words with the gathering tail off, on the integer engine, with unfused tails, with
-the batch split into tiles, with chunked transforms and in place; the message by equality mod t; refusals that leave the context
-usable.
+above the LDS limit (the plain form); the same words with the gathering tail off, under lsa_set_fp64_ntt(0), with unfused tails,
+with the batch split into tiles, with chunked transforms and in place; the message by equality mod t; refusals that leave the
+context usable.  No chain here has an FP64-engine limb: the two engines are compared in tests/test_gpu_bfv_operator_chains.py.
 
 Each model walk is computed once per distinct ciphertext and case and shared by the variants."""
 import ctypes
@@ -170,7 +170,10 @@ def test_above_the_lds_limit_runs_the_plain_form():
 
 def test_same_words_across_variants():
     """count 21 at radix 4 with the row step (the second column step adds to a live tail) and count 7 at radix 2, batch 3: the
-    plain form, the integer engine, unfused tails, tiles of 2 + 1, chunked transforms, and out == in"""
+    plain form, lsa_set_fp64_ntt(0), unfused tails, tiles of 2 + 1, chunked transforms, and out == in.  This chain (54 / 55-bit Q,
+    55-bit P) has no FP64-engine limb, so "integer engine" below is the engine of every row already: the run shows that the
+    setting itself changes nothing.  The comparison of the two engines lives in tests/test_gpu_bfv_operator_chains.py
+    (test_slot_sum_variants on the fp and mixed chains)."""
     need_gpu()
     from lattisense_amd._native import check, lib
     rig = Rig(11, "d8192", 200)

@@ -24,7 +24,8 @@ import numpy as np
 import pytest
 
 from lattisense_amd import params
-from tests.boundary import ORDERS, PATTERNS, fp_engine, head_flags, pattern_ct, pattern_key, primes_above, straddle_chain
+from tests.boundary import (ORDERS, PATTERNS, bfv_mixed_chain, fp_engine, head_flags, pattern_ct, pattern_key, primes_above,
+                            straddle_chain)
 from tests.gpu_util import env, need_gpu
 
 pytestmark = pytest.mark.gpu
@@ -333,15 +334,6 @@ def test_bootstrap_chain_drops_n16():
 
 
 # ---------------------------------------------------------------- BFV
-
-def bfv_mixed_chain(n):
-    """FP64-size primes (46/47/48-bit) next to 57/58/59-bit ones: the narrow-split predicate of the base conversions is false
-    although some sources are below 2^58; P: two 61-bit primes"""
-    q = (params.ntt_primes_below(46, n, 1) + params.ntt_primes_below(59, n, 1) + params.ntt_primes_below(47, n, 1) +
-         primes_above(57, n, 1) + primes_above(47, n, 1) + params.ntt_primes_below(58, n, 1) + params.ntt_primes_below(57, n, 1) +
-         primes_above(46, n, 1))
-    return q, params.ntt_primes_below(61, n, 2)
-
 
 def bfv_small_chain(n):
     """every Q and P prime below 2^58, with the largest ones (57.99 bits) among them: the split predicate true at its edge"""
