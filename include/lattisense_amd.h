@@ -284,6 +284,11 @@ int lsa_set_fuse_tails(lsa_context ctx, int enable);
  * transform lifts it (x mod p_t); 0: the conversion kernel for those digits too (A/B measurement and parity; identical
  * results).  Read by every operator call. */
 int lsa_set_modup_lift(lsa_context ctx, int enable);
+/* CKKS HMult+relin+rescale with the tensor fold: the fused key MAC finishes the rescaled FP64-engine limbs from its running sums
+ * instead of writing the accumulator's Q rows for the epilogue pass to read back.  0: never; 1 (default): on rings whose second
+ * NTT pass has eight stages (N = 2^16, the measured shape); 2: wherever the shape allows (also seven-stage second passes,
+ * N = 2^14).  Identical results for every value; another value is refused (LSA_ERR_ARG).  Read by every operator call. */
+int lsa_set_ks_tail_in_mac(lsa_context ctx, int mode);
 /* Two-pass NTTs (N > 2^12) run both passes over a chunk of at most `mib` MiB of limbs before moving on, so that the
  * second pass is served by the 256 MiB Infinity Cache (0, the default = one launch per pass over the whole batch).  Results are
  * identical for every value: the setting only changes how many batch items one launch covers, and the operands of the fused

@@ -480,6 +480,12 @@ int lsa_set_fuse_tails(lsa_context ctx, int enable) {
 int lsa_set_modup_lift(lsa_context ctx, int enable) {
     return guard([&] { C(ctx).modup_lift = enable ? 1 : 0; });
 }
+int lsa_set_ks_tail_in_mac(lsa_context ctx, int mode) {
+    return guard([&] {
+        LSA_REQUIRE(mode >= 0 && mode <= 2, "lsa_set_ks_tail_in_mac: mode is 0, 1 or 2");
+        C(ctx).ks_tail_in_mac = mode;
+    });
+}
 int lsa_set_dual_stream(lsa_context ctx, int enable) {
     return guard([&] { C(ctx).dual_stream = enable ? 1 : 0; });
 }

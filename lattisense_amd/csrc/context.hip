@@ -2,6 +2,7 @@
 #include "build_flags.h"
 #include "lsa_internal.h"
 #include <cstdlib>
+#include <cstring>
 
 namespace lsa {
 
@@ -338,6 +339,26 @@ const u64* Context::pfold_vec(int level) {
         v[L + j] = pr;
     }
     return raw_vec("pfold" + std::to_string(L), v);
+}
+
+const u64* Context::tail_fp_vec(int level) {
+    const std::string name = "tailfp" + std::to_string(level);
+    {   // (on the launch path of every tile: the cached vector first, the modular inverses only when it has to be made)
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = consts.find(name);
+        if (it != consts.end()) return it->second;
+    }
+    std::vector<u64> v(2 * (size_t)level);
+    const u64 ql = T.mod[level];
+    for (int j = 0; j < level; j++) {
+        const u64 q = T.mod[j];
+        u64 pr = 1;
+        for (int l = 0; l < np; l++) pr = mul_mod_host(pr, T.mod[p_mod(l)] % q, q);
+        const double kd = (double)inv_mod(pr, q), k2d = (double)inv_mod(ql % q, q);   // (exact below 2^53; read for FP64-engine limbs only)
+        std::memcpy(&v[j], &kd, sizeof(double));
+        std::memcpy(&v[level + j], &k2d, sizeof(double));
+    }
+    return raw_vec(name, v);
 }
 
 const u64* Context::qlinv_vec(int level) {

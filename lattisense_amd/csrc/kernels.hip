@@ -224,8 +224,12 @@ static bool ntt_launch_r16(const NttPassArgs& a, int npass, bool fused, long lon
 #ifndef LSA_KSMAC_WAVES_FP
 #define LSA_KSMAC_WAVES_FP LSA_KSMAC_WAVES
 #endif
-template <int MU, bool FP>
+// TAIL (FP64-engine Q limbs of a merged ModDown + rescale): after the digits the workgroup transforms the hand-off of in_j for
+// both polynomials the same way and stores the rescaled limb from the running sums (KsFusedArgs::tconv, r16_mac_tail) -- two more
+// iterations of the digit loop's shape, no register a digit iteration does not hold
+template <int MU, bool FP, bool TAIL = false>
 __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMAC_WAVES) void k_ntt_r16_ksmac(KsFusedArgs g) {
+    static_assert(!TAIL || (FP && MU <= 8), "the tail runs on the FP64 engine's eight- and seven-stage passes");
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     const int tid = threadIdx.x;
     const int T = g.L + g.np;
@@ -307,6 +311,40 @@ __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMA
         r16_mac_digit<MU, FP>(g, a, bc, L, tid, d, kj, own, b, tl, lds, acc0, acc1);
         r16_sync<1>();   // the next digit's first exchange overwrites the tile image these lanes just read
     }
+    if constexpr (TAIL) {
+        a.src = g.tconv;
+        // the tail's addresses are derived from copies of the lane, limb and batch indices that the compiler cannot see through:
+        // from the originals it forms them ahead of the digit loop, next to the loop's own, and carries them through it in
+        // registers the loop needs (MU = 8: 14 VGPRs spilled around the whole loop, MU = 7: 34; none this way)
+        int tt = tid, ttl = tl;
+        long long tb = b;
+        asm volatile("" : "+v"(tt), "+s"(ttl), "+s"(tb));
+        int tk, ti;   // (the twiddle groups too: the per-lane table addresses formed from them are 64-bit values)
+        r16_lane<1, MU>(tt, tk, ti);
+        const unsigned T1 = r16_G1<1, MU>(bc, tk), T2 = (T1 << 4) + ((unsigned)ti << (8 - MU));
+        const double kd = g.tkd[ttl], k2d = g.tkd[g.L - 1 + ttl];   // P^-1 and q_l^-1 of this limb, the values the epilogue pass takes
+        // (a loop that is not unrolled, the second polynomial's sums moved into the first's registers for its turn: unrolled, the
+        // compiler starts the second polynomial's loads under the first one's tail and the kernel spills)
+#pragma unroll 1
+        for (int h = 0; h < 2; h++) {
+            bc.row = h * g.L + ttl;
+            bc.base_src = tb * g.stconv + ((long long)bc.row << g.logn);
+            u64 v[16];
+            r16_load_direct<1, false, 0, MU>(a, bc, tt, v);
+            r16_group<1, 0, MU>(v, a, bc, L, T1);
+            r16_lds_put<1, 0, MU>(tt, lds, v);
+            r16_sync<1>();
+            r16_lds_get<1, 1, MU>(tt, lds, v);
+            r16_group<1, 1, MU>(v, a, bc, L, T2);
+            r16_lds_put<1, 1, MU>(tt, lds, v);
+            r16_sync<1>();
+            r16_mac_tail<MU>(g, a, bc, L, tt, tb, ttl, h, kd, k2d, lds, acc0);
+            r16_sync<1>();
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc0[e] = acc1[e];
+        }
+        return;
+    }
     r16_mac_store<MU, FP>(g, a, bc, L, tid, b, tl, acc0, acc1);
 }
 
@@ -327,11 +365,20 @@ int ks_fused_engines(const Context& c) {
 bool ks_fused_limb(const Context& c, int L, int tl) { return (ks_fused_engines(c) >> (c.fp_engine(c.qp_mod(L, tl)) ? 1 : 0)) & 1; }
 
 bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* ext, long long sext, const Key& key, u64* acc,
-                      long long sacc, int batch, hipStream_t s, const TensorFold* fold) {
+                      long long sacc, int batch, hipStream_t s, const TensorFold* fold, KsFusedLimbs limbs, const KsTailOperands* tail) {
     if (batch <= 0) return true;
     if (!ks_fused_enabled(c) || (c.fp64_ntt && !key.fp)) return false;
     LSA_REQUIRE(key.level >= level, "key-switch key exported at a lower level than the ciphertext");
+    LSA_REQUIRE((limbs == KS_FUSED_Q_TAIL) == (tail != nullptr), "fused key MAC: the tail launch and its operands go together");
+    if (tail && (level < 1 || ks_fused_engines(c) != 2 || c.plan.pass[1].mu > 8)) return false;
     KsFusedArgs g{};
+    if (tail) {
+        g.tconv = tail->conv;
+        g.stconv = tail->sconv;
+        g.tout = tail->out;
+        g.stout = tail->sout;
+        g.tkd = reinterpret_cast<const double*>(c.tail_fp_vec(level));
+    }
     g.ext = ext;
     g.cx = cx;
     g.key = key.data;
@@ -372,6 +419,8 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
         int transforms = 0, q_targets = 0;
         for (int tl = 0; tl < T; tl++) {
             if (!ks_fused_limb(c, g.L, tl) || (int)c.fp_engine(c.qp_mod(g.L, tl)) != eng) continue;
+            if (limbs == KS_FUSED_P && tl < g.L) continue;
+            if (limbs == KS_FUSED_Q_TAIL && tl >= level) continue;
             g.tl_list[g.n_tl++] = (unsigned char)tl;
             transforms += g.beta - (tl < g.L ? 1 : 0);
             q_targets += tl < g.L;
@@ -381,13 +430,20 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
         LSA_REQUIRE(nblocks < (1LL << 31), "ntt: grid too large");
         // LSA_KSMAC_XCD=0: plain batch-fastest order (A/B: +0.45 % headline with the deal, ab_ksmac_xcd_deal.log)
         g.xcd_deal = sw::ksmac_xcd() && ((g.n_tl << (c.logn - 12)) % 8 == 0) ? 1 : 0;
+        // (the tail launch: the second pass of two more transforms per limb, as the epilogue pass it replaces counted them, and no
+        // accumulator rows: the MAC's two writes per limb are gone, and the epilogue never counted its reads of them)
+        if (tail) transforms += 2 * g.n_tl;
         const double ntt_bytes = 16.0 * c.n * transforms * batch / 2;
         // (tensor fold: the own digit of a Q target reads a0, a1, b0, b1 instead of cx)
         const double fold_bytes = fold ? 3.0 * 8 * c.n * q_targets * batch : 0.0;
-        ProfScope ps(c, PROF_NTT, ntt_bytes + fold_bytes + 8.0 * c.n * g.n_tl * (batch * ((double)g.beta + 2.0) + 2.0 * g.beta), s,
+        ProfScope ps(c, PROF_NTT, ntt_bytes + fold_bytes + 8.0 * c.n * g.n_tl * (batch * ((double)g.beta + (tail ? 0.0 : 2.0)) + 2.0 * g.beta), s,
                      ntt_bytes);
         const dim3 grid((unsigned)nblocks), block(LSA_R16_THREADS);
-        if (mu == 9 && eng) hipLaunchKernelGGL((k_ntt_r16_ksmac<9, true>), grid, block, lds_bytes, s, g);
+        if (tail) {
+            LSA_REQUIRE(eng == 1 && (mu == 8 || mu == 7), "fused key MAC: the tail runs on the FP64 engine's eight- and seven-stage passes");
+            if (mu == 8) hipLaunchKernelGGL((k_ntt_r16_ksmac<8, true, true>), grid, block, lds_bytes, s, g);
+            else hipLaunchKernelGGL((k_ntt_r16_ksmac<7, true, true>), grid, block, lds_bytes, s, g);
+        } else if (mu == 9 && eng) hipLaunchKernelGGL((k_ntt_r16_ksmac<9, true>), grid, block, lds_bytes, s, g);
         else if (mu == 9) hipLaunchKernelGGL((k_ntt_r16_ksmac<9, false>), grid, block, lds_bytes, s, g);
         else if (mu == 8 && eng) hipLaunchKernelGGL((k_ntt_r16_ksmac<8, true>), grid, block, lds_bytes, s, g);
         else if (mu == 8) hipLaunchKernelGGL((k_ntt_r16_ksmac<8, false>), grid, block, lds_bytes, s, g);
@@ -1795,7 +1851,7 @@ static void launch_ks_mac_kb(int beta, dim3 grid, hipStream_t s, const KsMacArgs
 // map of the rotation's inverse element, base = the ciphertext whose c0 enters (see KsMacArgs); base == nullptr: no P * c0 is
 // added, the result is perm(acc)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, const Key& key,
-                   const KsMacDst& dst, int batch, hipStream_t s, bool unfused_only, const TensorFold* fold) {
+                   const KsMacDst& dst, int batch, hipStream_t s, bool unfused_only, const TensorFold* fold, int extra_tl) {
     if (batch <= 0) return;
     const u32* scatter = dst.scatter;
     const u64* base = dst.base;
@@ -1839,7 +1895,7 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
     if (unfused_only) {   // the others went through the fused kernel
         LSA_REQUIRE(targets <= 64, "key MAC: too many target limbs for a subset launch");
         for (int tl = 0; tl < targets; tl++)
-            if (!ks_fused_limb(c, g.L, tl)) g.tl_list[g.n_tl++] = (unsigned char)tl;
+            if (!ks_fused_limb(c, g.L, tl) || tl == extra_tl) g.tl_list[g.n_tl++] = (unsigned char)tl;
         if (!g.n_tl) return;
         targets = g.n_tl;
     }

@@ -97,6 +97,7 @@ struct KsTile {
     hipStream_t s;
     const Key* key;   // fused: the one key mac() accepts
     bool fused;
+    bool tail = false;   // plan_tail() said yes: decompose() leaves limb `level` to the stand-alone MAC, mac_rescale() follows
     u64 *cxn, *cxi, *ext, *acc, *conv;   // cxn: the rows of a COEFF source
     long long s_cxi, s_ext, s_acc, s_conv;
     KsSource src;
@@ -120,6 +121,19 @@ struct KsTile {
     // the same for 2..4 keys in one launch, each into its own buffer (launch_ks_mac_multi)
     void mac_ext_multi(int n_keys, const KsMacMultiKey* keys, long long sout, const u64* base, long long sbase);
     void moddown(const KsOut& o) { moddown_of(acc, s_acc, o); }   // step 5
+    // Steps 4 and 5 as one sequence, the merged rescale tail finished inside the fused key MAC: the Q part of the accumulator that
+    // the fused kernel would write and the epilogue pass read back stays in registers.
+    //   1. (decompose) limb l = level counts as an unfused target: its extension rows get the stand-alone second pass
+    //   2. the fused P limbs (plain fused kernel) and k_ks_mac for the unfused targets and limb l -> acc's P rows, integer Q rows, row l
+    //   3. ModDown's head as ever: P rows and row l out of the NTT domain, the two conversions, t = (INTT(acc_l) - conv_l) * P^-1
+    //   4. the first pass of NTT(in_j), in_j = conv_j * P^-1 + lift_j(t), every limb j != l
+    //   5. the fused kernel's tail variant on the FP64-engine Q limbs j != l: the digits, then the second pass of in_j for both
+    //      polynomials, out_j = (sum * P^-1 - NTT(in_j)) * q_l^-1 straight into the rescaled ciphertext
+    //   6. the integer-engine Q limbs j != l keep the epilogue pass: the second pass alone, on their rows
+    // plan_tail(): the tile takes it -- fused, a tensor-fold product rescaled straight away (KsOut::RESCALE without base), FP64-engine
+    // limbs fused alone, some FP64-engine Q limb below l, and Context::ks_tail_in_mac allows the ring.  Call it before decompose().
+    bool plan_tail(const KsOut& o);
+    void mac_rescale(const Key& k, const KsOut& o);
     // step 5 on an extended accumulator the caller holds ([2][L+k][N] per item; its P rows leave the NTT domain)
     void moddown_of(u64* ext_acc, long long s_ext_acc, const KsOut& o);
     // step 5 without a tile: `conv` is moddown_rows(level) rows per item of scratch

@@ -16,7 +16,10 @@ RowMap rm_seq(int count, int first) {
 // ------------------------------------------------------------------------------------------------ key switch
 // step 5, the division by P of a polynomial pair over Q_level u P (acc: [2][L+k][N] per batch item, NTT domain; its P rows --
 // and, for the merged rescale, its last Q row -- are transformed in place), conv: 2L rows of scratch per batch item
-static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
+// Its head, ks_moddown_head -- the inverse transforms and the conversion -- is the same for every output.  The merged rescale goes
+// on with ks_rescale_head: t, then the fusion of the one forward transform of in_j that finishes it, which ks_moddown launches
+// whole and KsTile::mac_rescale pass by pass around the key MAC's tail variant.
+static void ks_moddown_head(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
     LSA_REQUIRE(!o.scatter || (c.fuse_tails && o.form == KsOut::NTT), "scattered ModDown store: fused tails, NTT-domain output");
     LSA_REQUIRE(!o.rmac || o.scatter, "rotate-and-MAC tail: needs the rotation's index map");
     LSA_REQUIRE(!o.coeff_gather || o.form == KsOut::COEFF, "gathered ModDown tail: coefficient-domain output");
@@ -57,6 +60,17 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
         for (int h = 0; h < 2; h++)
             launch_baseconv(c, k, rows, acc + (size_t)h * T * N, conv + (size_t)h * L * N, nb, s_acc, s_conv, s);
     }
+}
+
+static NttFusion ks_rescale_head(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s,
+                                 RowMap& rmo);
+
+static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
+    const bool coeff_out = o.form == KsOut::COEFF, rs = o.form == KsOut::RESCALE;
+    const long long N = c.n;
+    const int L = level + 1, T = L + c.np;
+    const long long s_conv = 2LL * L * N;
+    ks_moddown_head(c, level, acc, s_acc, conv, o, nb, s);
     if (coeff_out) {
         if (o.slot_tail)
             launch_bfv_slot_tail(c, level, *o.slot_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
@@ -68,49 +82,8 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
         return;
     }
     if (rs) {
-        // base_polys == 0: the tensor fold -- P * base is already in acc's Q rows (TensorFold), so INTT(acc_l) * P^-1 carries
-        // INTT(base_l) and the tails below run without base
-        const int l = level;
-        // t[h] = (INTT(acc[h][l]) - conv[h][l]) * P^-1 + INTT(base[h][l]) -> p[h][l].  base is the caller's scratch here
-        // (the tensor output): its last limbs are transformed in place, nothing reads them in NTT form afterwards.
-        if (o.base) {
-            u64* base_rw = const_cast<u64*>(o.base);
-            RowMap rb;
-            rb.period = 1;
-            rb.mod_of[0] = (unsigned char)l;
-            rb.row0 = l;
-            rb.row_step = o.base_rpp;
-            launch_ntt(c, base_rw, base_rw, nb, o.sbase, o.sbase, 2, rb, true, s);
-        }
-        const unsigned char lm[1] = {(unsigned char)l};
-        launch_sub_mul_general(c, 2, 1, lm, c.pinv_vec(level) + l, acc + (long long)l * N, s_acc, T, conv + (long long)l * N,
-                               s_conv, L, o.base ? o.base + (long long)l * N : nullptr, o.sbase, o.base_rpp, o.base_polys,
-                               o.p + (long long)l * N, o.sp, L, nb, s);
-        // every other limb: in = conv_j*P^-1 + lift_j(t), out = (acc_j*P^-1 - NTT(in) + base_j) * q_l^-1
         RowMap rmo;
-        rmo.period = 2 * L;
-        for (int h = 0; h < 2; h++)
-            for (int j = 0; j < L; j++) rmo.mod_of[h * L + j] = j == l ? LSA_ROW_SKIP : (unsigned char)j;
-        NttFusion fb;
-        fb.pro = 2;
-        fb.epi = 2;
-        fb.limbs = L;
-        fb.ql_mod = l;
-        fb.last = o.p + (long long)l * N;
-        fb.last_stride = o.sp;
-        fb.last_rpp = L;
-        fb.a = acc;
-        fb.a_stride = s_acc;
-        fb.a_rpp = T;
-        fb.base = o.base;
-        fb.base_stride = o.sbase;
-        fb.base_rpp = o.base_rpp;
-        fb.base_polys = o.base_polys;
-        fb.k = c.pinv_vec(level);
-        fb.k2 = c.qlinv_vec(level);
-        fb.out = o.rs.out;
-        fb.out_stride = o.rs.sout;
-        fb.out_rpp = level;
+        const NttFusion fb = ks_rescale_head(c, level, acc, s_acc, conv, o, nb, s, rmo);
         launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rmo, false, s, &fb);
     } else if (c.fuse_tails) {
         // forward NTT of conv with the ModDown tail fused into its last-pass store: the transformed conv is consumed in
@@ -141,6 +114,58 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
         launch_ntt(c, conv, conv, nb, s_conv, 2 * L, rm_seq(L), false, s);
         launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp, o.base_polys, o.p, o.sp, nb, s);
     }
+}
+
+// the merged rescale after the head: t into the last limbs of o.p, then the row map (rmo) and the fusion of the forward transform of
+// in_j over every other limb (prologue: in_j = conv_j * P^-1 + lift_j(t); epilogue: out_j)
+static NttFusion ks_rescale_head(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s,
+                                 RowMap& rmo) {
+    const long long N = c.n;
+    const int L = level + 1, T = L + c.np;
+    const long long s_conv = 2LL * L * N;
+    // base_polys == 0: the tensor fold -- P * base is already in acc's Q rows (TensorFold), so INTT(acc_l) * P^-1 carries
+    // INTT(base_l) and the tails below run without base
+    const int l = level;
+    // t[h] = (INTT(acc[h][l]) - conv[h][l]) * P^-1 + INTT(base[h][l]) -> p[h][l].  base is the caller's scratch here
+    // (the tensor output): its last limbs are transformed in place, nothing reads them in NTT form afterwards.
+    if (o.base) {
+        u64* base_rw = const_cast<u64*>(o.base);
+        RowMap rb;
+        rb.period = 1;
+        rb.mod_of[0] = (unsigned char)l;
+        rb.row0 = l;
+        rb.row_step = o.base_rpp;
+        launch_ntt(c, base_rw, base_rw, nb, o.sbase, o.sbase, 2, rb, true, s);
+    }
+    const unsigned char lm[1] = {(unsigned char)l};
+    launch_sub_mul_general(c, 2, 1, lm, c.pinv_vec(level) + l, acc + (long long)l * N, s_acc, T, conv + (long long)l * N,
+                           s_conv, L, o.base ? o.base + (long long)l * N : nullptr, o.sbase, o.base_rpp, o.base_polys,
+                           o.p + (long long)l * N, o.sp, L, nb, s);
+    // every other limb: in = conv_j*P^-1 + lift_j(t), out = (acc_j*P^-1 - NTT(in) + base_j) * q_l^-1
+    rmo.period = 2 * L;
+    for (int h = 0; h < 2; h++)
+        for (int j = 0; j < L; j++) rmo.mod_of[h * L + j] = j == l ? LSA_ROW_SKIP : (unsigned char)j;
+    NttFusion fb;
+    fb.pro = 2;
+    fb.epi = 2;
+    fb.limbs = L;
+    fb.ql_mod = l;
+    fb.last = o.p + (long long)l * N;
+    fb.last_stride = o.sp;
+    fb.last_rpp = L;
+    fb.a = acc;
+    fb.a_stride = s_acc;
+    fb.a_rpp = T;
+    fb.base = o.base;
+    fb.base_stride = o.sbase;
+    fb.base_rpp = o.base_rpp;
+    fb.base_polys = o.base_polys;
+    fb.k = c.pinv_vec(level);
+    fb.k2 = c.qlinv_vec(level);
+    fb.out = o.rs.out;
+    fb.out_stride = o.rs.sout;
+    fb.out_rpp = level;
+    return fb;
 }
 
 // one key per decomposition (relinearisation, a single rotation, a generic switch): the extension transform's second pass
@@ -265,7 +290,8 @@ void KsTile::decompose(const KsSource& source) {
         // the target limbs that do not take the fused kernel get their second pass here (stand-alone MAC later)
         bool any = false;
         for (int i = 0; i < beta * T; i++) {
-            rm.mod_of[i] = own(i / T, i % T) || ks_fused_limb(c, L, i % T) ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, i % T);
+            const bool in_mac = ks_fused_limb(c, L, i % T) && !(tail && i % T == level);   // (tail: limb l goes to the stand-alone MAC)
+            rm.mod_of[i] = own(i / T, i % T) || in_mac ? LSA_ROW_SKIP : (unsigned char)c.qp_mod(L, i % T);
             any |= rm.mod_of[i] != LSA_ROW_SKIP;
         }
         if (any) launch_ntt(c, ext, ext, nb, s_ext, s_ext, beta * T, rm, false, s, nullptr, 2);
@@ -288,7 +314,7 @@ void KsTile::mac(const Key& k) {
         launch_ks_mac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, {acc, s_acc}, nb, s, false, fold);
         return;
     }
-    LSA_REQUIRE(&k == key, "fused key MAC: the tile was planned for another key");
+    LSA_REQUIRE(&k == key && !tail, "fused key MAC: the tile was planned for another key or for mac_rescale()");
     LSA_REQUIRE(launch_ntt_ksmac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, acc, s_acc, nb, s, fold), "fused key MAC: shape not covered");
     launch_ks_mac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, {acc, s_acc}, nb, s, true, fold);
 }
@@ -309,9 +335,53 @@ void KsTile::moddown_ext(Context& c, int level, u64* ext_acc, long long s_ext_ac
     ks_moddown(c, level, ext_acc, s_ext_acc, conv, o, nb, s);
 }
 
+bool KsTile::plan_tail(const KsOut& o) {
+    const int mu = c.plan.pass[1].mu;   // (fused: a two-pass plan)
+    tail = fused && c.ks_tail_in_mac != 0 && c.fuse_tails && level >= 1 && o.form == KsOut::RESCALE && !o.base && o.base_polys == 0 &&
+           ks_fused_engines(c) == 2 && (mu == 8 || (mu == 7 && c.ks_tail_in_mac == 2));
+    if (!tail) return false;
+    tail = false;
+    for (int j = 0; j < level; j++) tail |= ks_fused_limb(c, L, j);   // (a tile whose only FP64-engine Q limb is l has nothing to gain)
+    return tail;
+}
+
+void KsTile::mac_rescale(const Key& k, const KsOut& o) {
+    LSA_REQUIRE(src.ntt && fused && tail && &k == key, "tail in the key MAC: a decomposed tile planned for it and for this key");
+    LSA_REQUIRE(o.form == KsOut::RESCALE && !o.base && o.base_polys == 0, "tail in the key MAC: a merged rescale without base");
+    const TensorFold* fold = src.prod;
+    // 2. the accumulator rows that ModDown's head reads
+    LSA_REQUIRE(launch_ntt_ksmac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, acc, s_acc, nb, s, fold, KS_FUSED_P), "fused key MAC: shape not covered");
+    launch_ks_mac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, {acc, s_acc}, nb, s, true, fold, level);
+    // 3. the head
+    ks_moddown_head(c, level, acc, s_acc, conv, o, nb, s);
+    RowMap rmo;
+    const NttFusion fb = ks_rescale_head(c, level, acc, s_acc, conv, o, nb, s, rmo);
+    // 4. the first pass with the prologue alone (the prologue belongs to the first executed pass, the epilogue to the pass that
+    //    stores final values: each transform launch here carries only the one its pass runs)
+    NttFusion fp = fb;
+    fp.epi = 0;
+    launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rmo, false, s, &fp, 1);
+    // 5. the digits and the tail of the FP64-engine Q limbs
+    const KsTailOperands kt{conv, s_conv, o.rs.out, o.rs.sout};
+    LSA_REQUIRE(launch_ntt_ksmac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, acc, s_acc, nb, s, fold, KS_FUSED_Q_TAIL, &kt),
+                "fused key MAC: tail shape not covered");
+    // 6. the integer-engine limbs: the second pass alone with the epilogue, every FP64-engine row skipped
+    for (int i = 0; i < 2 * L; i++)
+        if (rmo.mod_of[i] != LSA_ROW_SKIP && c.fp_engine(rmo.mod_of[i])) rmo.mod_of[i] = LSA_ROW_SKIP;
+    NttFusion fe = fb;
+    fe.pro = 0;
+    fe.last = nullptr;
+    launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rmo, false, s, &fe, 2);
+}
+
 void key_switch(Context& c, int level, const KsSource& src, const Key& key, const KsOut& o, int nb, u64* ws, hipStream_t s) {
     KsTile t(c, level, nb, ws, s, &key, src.form);
+    const bool tail = t.plan_tail(o);
     t.decompose(src);
+    if (tail) {
+        t.mac_rescale(key, o);
+        return;
+    }
     t.mac(key);
     t.moddown(o);
 }

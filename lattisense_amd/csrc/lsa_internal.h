@@ -109,6 +109,8 @@ struct Context {
     int fp_raw = 1;                 // FP64-engine limbs cross between the two NTT passes as doubles (LSA_NTT_FP_RAW=0: canonical u64)
     int modup_lift = 1;             // single-limb key-switch digits lifted by the extension transform's load (key_switch.hip KsTile::decompose)
     int fuse_tails = 1;             // ModDown / rescale element-wise tails fused into the NTT load/store phases
+    int ks_tail_in_mac = 1;         // merged rescale tail finished inside the fused key MAC (key_switch.h KsTile::plan_tail): 0 never,
+                                    // 1 where the second pass has eight stages (the measured shape), 2 wherever the shape allows
     int dual_stream = 0;            // 1: overlap alternate tiles of an operator on an auxiliary stream (+5% throughput,
                                     // but per-kernel timings then include the co-running kernel; off for clean accounting)
     hipStream_t aux_stream = nullptr;
@@ -177,6 +179,9 @@ struct Context {
     // (mont_mul(x, .) = x * P in Montgomery form), row 1 P mod q_j as a plain residue (the FP64 engine's double)
     const u64* pfold_vec(int level);
     const u64* qlinv_vec(int level);
+    // [2][level] the merged tail's factors of limb j < level as plain doubles' bits: row 0 P^-1 mod q_j, row 1 q_level^-1 mod q_j (the
+    // values of pinv_vec and qlinv_vec out of Montgomery form; the tail variant of the fused key MAC reads them)
+    const u64* tail_fp_vec(int level);
     const u32* ntt_perm(u64 g);
     const u32* coeff_perm(u64 g);
     // per-modulus constant vector on device, Montgomery form, built by `gen(mod_index)`
@@ -333,9 +338,11 @@ struct KsMacDst {
     long long sbase = 0;
     bool accumulate = false;
 };
-// unfused_only: only the target limbs that do not take the fused kernel (ks_fused_limb; k_ntt_r16_ksmac did the others)
+// unfused_only: only the target limbs that do not take the fused kernel (ks_fused_limb; k_ntt_r16_ksmac did the others), and
+// limb extra_tl with them whatever its engine (-1: none)
 void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u64* ext, long long sext, const Key& key,
-                   const KsMacDst& dst, int batch, hipStream_t s, bool unfused_only = false, const TensorFold* fold = nullptr);
+                   const KsMacDst& dst, int batch, hipStream_t s, bool unfused_only = false, const TensorFold* fold = nullptr,
+                   int extra_tl = -1);
 // out[h][i] = base[h][i] + (acc[h][i] - conv[h][i]) * Pinv_i       (base may be null)
 void launch_moddown_final(Context& c, int level, const u64* acc, long long sacc, int acc_rows_per_poly, const u64* conv,
                           long long sconv, const u64* base, long long sbase, int base_rows_per_poly, int base_polys,
@@ -397,8 +404,20 @@ KeyLayout key_layout(const Context& c, int key_level);
 void key_prepare(Context& c, Key& key, u64* data, int key_level, double* fp, hipStream_t s);
 // second pass of the extension transform + gadget inner product in one launch (see k_ntt_r16_ksmac) for the target limbs that
 // take it (ks_fused_limb); false = shape not covered
+// limbs: which of them one launch covers.  The tail sequence of a merged ModDown + rescale (key_switch.hip, KsTile::mac_rescale)
+// splits the set: KS_FUSED_P, the P limbs, before ModDown's head (it reads the accumulator's P rows); KS_FUSED_Q_TAIL, the Q limbs
+// other than `level`, after it, finishing the rescaled limbs from their running sums (`tail`; FP64-engine limbs, seven- and
+// eight-stage second passes).  Limb `level` takes neither: the head needs its accumulator row whole (launch_ks_mac's extra_tl)
+enum KsFusedLimbs { KS_FUSED_ALL = 0, KS_FUSED_P = 1, KS_FUSED_Q_TAIL = 2 };
+struct KsTailOperands {
+    const u64* conv;   // [2][L][N] per item: pass-one output of the transform of in_j = conv_j * P^-1 + lift_j(t)
+    long long sconv;
+    u64* out;          // [2][level][N] per item: the rescaled ciphertext
+    long long sout;
+};
 bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* ext, long long sext, const Key& key, u64* acc,
-                      long long sacc, int batch, hipStream_t s, const TensorFold* fold = nullptr);
+                      long long sacc, int batch, hipStream_t s, const TensorFold* fold = nullptr, KsFusedLimbs limbs = KS_FUSED_ALL,
+                      const KsTailOperands* tail = nullptr);
 int ks_fused_engines(const Context& c);   // which engines' target limbs take the fused kernel (LSA_KS_FUSED_ENGINES, default FP64 only)
 bool ks_fuse_mac(const Context& c, int level, const Key& key);   // a single-key switch at this level runs k_ntt_r16_ksmac (key_switch.hip)
 bool ks_fused_limb(const Context& c, int L, int tl);   // target limb tl of Q_level u P takes it (by its engine)

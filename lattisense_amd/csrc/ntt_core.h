@@ -342,6 +342,33 @@ LSA_HD double fp_modmul(double v, double w, double q, double qinv) {
 }
 // x mod q into [-q/2-1, q/2+1] for |x| < 2^53
 LSA_HD double fp_reduce(double x, double q, double qinv) { return __builtin_fma(-__builtin_rint(x * qinv), q, x); }
+// The merged ModDown + rescale tail of an FP64-engine limb (fz_epi = 2): the canonical residue of (sum * kd - x + bd) * k2d mod q,
+// x the transformed value NTT(in_j), sum the key MAC's accumulator at the same point, kd = P^-1 mod q, k2d = q_l^-1 mod q,
+// bd the base addend (0 without one).  Every argument is an integer-valued double; 0 <= kd, k2d < q < 2^47, 0 <= bd < q.
+//   wide = false (the store of a stand-alone epilogue pass): x is already reduced, |x| <= q/2 + 1, and sum is the canonical
+//     accumulator word, 0 <= sum < q;
+//   wide = true (the key MAC's own running sums): |x| < 2^53 -- an unreduced forward pass ends below 11 q -- and |sum| < 2^53 --
+//     at most beta + 2 <= 15 products of magnitude < 1.1 q, below 2^51.1; both are first taken to |.| <= q/2 + 1 by fp_reduce,
+//     exact on that range, because fp_modmul wants |v| < 2^51.
+// Then sum * kd is within 1.1 q, the bracket within 1.1 q + q/2 + 1 + q < 2.7 q < 2^49 (in fp_modmul's range), the product
+// within 1.1 q, and one fp_reduce and one conditional add land in [0, q).  The two forms agree residue for residue: they differ
+// only in which representative of sum and of x enters, and every step is exact arithmetic modulo q.
+// Two entry points: fp_merged_tail_product is the arithmetic proper and returns the unreduced product; fp_merged_tail reduces its
+// arguments (wide), calls it and canonicalises.  The register-image epilogue and the key MAC's tail call fp_merged_tail; the
+// staged kernel's ntt_store_fix calls the product alone and goes on into the reduction and conditional add it shares with the
+// unmerged tail (kept that way so that its kernels compile to the instruction sequence they always had).
+LSA_HD double fp_merged_tail_product(double x, double sum, double bd, double kd, double k2d, double q, double qinv) {
+    return fp_modmul(fp_modmul(sum, kd, q, qinv) - x + bd, k2d, q, qinv);   // (the narrow form's arguments; within 1.1 q)
+}
+LSA_HD u64 fp_merged_tail(double x, double sum, double bd, double kd, double k2d, double q, double qinv, bool wide) {
+    if (wide) {
+        x = fp_reduce(x, q, qinv);
+        sum = fp_reduce(sum, q, qinv);
+    }
+    double r = fp_reduce(fp_merged_tail_product(x, sum, bd, kd, k2d, q, qinv), q, qinv);
+    if (r < 0) r += q;
+    return double_to_u52(r);
+}
 
 // phase 0: global -> LDS (2 elements = 16 B per lane per step).  For a full tile (every thread owns exactly
 // LSA_NTT_STAGE_PAIRS pairs) all of a thread's loads are issued before the first one is consumed: a rolled
@@ -604,7 +631,8 @@ LSA_HD u64 ntt_store_fix(const NttStoreFix& f, u64 v, u64 va, u64 vb) {
         if (f.raw) return d_to_bits(r);   // first pass of a two-pass transform: the second pass's butterflies start from this
         if (f.tail) {   // the fused tail of an FP64-engine limb stays on the FP64 engine: exact, 6 operations per product
             const double ad = u52_to_double(va), bd = f.with_base ? u52_to_double(vb) : 0.0;
-            if (f.merged) r = fp_modmul(fp_modmul(ad, f.kd, f.qd, f.qinvd) - r + bd, f.k2d, f.qd, f.qinvd);
+            // (merged: fp_merged_tail's narrow form, its reduction and conditional add shared with the other tail below)
+            if (f.merged) r = fp_merged_tail_product(r, ad, bd, f.kd, f.k2d, f.qd, f.qinvd);
             else r = fp_modmul(ad - r, f.kd, f.qd, f.qinvd) + bd;
             r = fp_reduce(r, f.qd, f.qinvd);
         }

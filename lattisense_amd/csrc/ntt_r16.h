@@ -414,12 +414,9 @@ LSA_HD void r16_store_coalesced(const NttPassArgs& a, const NttBlockCtx& bc, int
         if (f.fp && !f.raw && FZ && f.tail && f.merged) {
 #pragma unroll
             for (int j = 0; j < 2 * LSA_NTT_STORE_CHUNK; j++) {
-                double r = f.skip_reduce ? d_from_bits(v[j]) : fp_reduce(d_from_bits(v[j]), f.qd, f.qinvd);
+                const double r = f.skip_reduce ? d_from_bits(v[j]) : fp_reduce(d_from_bits(v[j]), f.qd, f.qinvd);
                 const double ad = u52_to_double(va[j]), bd = f.with_base ? u52_to_double(vb[j]) : 0.0;
-                r = fp_modmul(fp_modmul(ad, f.kd, f.qd, f.qinvd) - r + bd, f.k2d, f.qd, f.qinvd);
-                r = fp_reduce(r, f.qd, f.qinvd);
-                if (r < 0) r += f.qd;
-                w[j] = double_to_u52(r);
+                w[j] = fp_merged_tail(r, ad, bd, f.kd, f.k2d, f.qd, f.qinvd, false);
             }
         } else if (f.fp && !f.raw && !(FZ && f.tail)) {
 #pragma unroll
@@ -672,6 +669,15 @@ struct KsFusedArgs {
     const u64* fb;
     long long sfa, sfb, pfa, pfb;
     const u64* pf;
+    // the merged rescale tail finished here (the TAIL instantiations; after every other field, so the others see the layout they
+    // always had).  The launch's limbs are FP64-engine Q limbs j < L - 1: after the digits the workgroup runs the second pass of
+    // in_j = conv_j * P^-1 + lift_j(t) for both polynomials (tconv: [batch][2][L][N], pass-one output, raw doubles) and stores
+    // tout[h][j] = (sum_h * P^-1 - NTT(in_j)) * q_l^-1 ([batch][2][L - 1][N]) straight from the running sums: the accumulator's Q
+    // rows are neither written nor read back.  tkd: [2][L - 1] P^-1 and q_l^-1 per limb as plain doubles (Context::tail_fp_vec)
+    const u64* tconv;
+    u64* tout;
+    long long stconv, stout;
+    const double* tkd;
 };
 
 // the MAC of one digit on the pair image: vin = the operand pair values (FP: doubles' bits), acc0/acc1 the two halves' sums
@@ -821,5 +827,31 @@ LSA_HD void r16_mac_store(const KsFusedArgs& g, const NttPassArgs& a, const NttB
         }
         ntt_store_pair(o0 + x, r[0], r[1]);
         ntt_store_pair(o1 + x, r[2], r[3]);
+    }
+}
+// the merged tail of polynomial h on the pair image (FP64 engine): the tile image in LDS is NTT(in_j), unreduced as the plain
+// pass leaves it before its store (|x| < 11 q); sum the polynomial's running sums (fp_merged_tail's wide form)
+template <int MU>
+LSA_HD void r16_mac_tail(const KsFusedArgs& g, const NttPassArgs& a, const NttBlockCtx& bc, const R16Limb& L, int tid, long long b, int tl,
+                         int h, double kd, double k2d, const u64* lds, const u64 (&sum)[16]) {
+    u64* o = g.tout + b * g.stout + (((long long)h * (g.L - 1) + tl) << g.logn);
+    constexpr int CH = 2;   // 16-byte pairs per round: their LDS reads are cheap, and every pair in flight holds two tails' temporaries
+#pragma unroll
+    for (int m0 = 0; m0 < 8; m0 += CH) {
+        u64 v[2 * CH];
+        long long xs[CH];
+#pragma unroll
+        for (int m = 0; m < CH; m++) {
+            int k, i;
+            r16_pair_pos<MU>(tid, m0 + m, k, i);
+            xs[m] = r16_x<1, MU>(a, bc.tile, k, i);
+            v[2 * m] = lds[r16_lds<1, MU>(k, i)];
+            v[2 * m + 1] = lds[r16_lds<1, MU>(k, i + 1)];
+        }
+#pragma unroll
+        for (int m = 0; m < CH; m++)
+            ntt_store_pair(o + xs[m],
+                           fp_merged_tail(d_from_bits(v[2 * m]), d_from_bits(sum[2 * (m0 + m)]), 0.0, kd, k2d, L.q, L.qinv, true),
+                           fp_merged_tail(d_from_bits(v[2 * m + 1]), d_from_bits(sum[2 * (m0 + m) + 1]), 0.0, kd, k2d, L.q, L.qinv, true));
     }
 }

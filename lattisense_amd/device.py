@@ -107,6 +107,11 @@ class DeviceContext:
         """0: single-limb key-switch digits go through the base-conversion kernel like the others (A/B, identical results)"""
         check(lib().lsa_set_modup_lift(self.h, int(enable)))
 
+    def set_ks_tail_in_mac(self, mode):
+        """the merged rescale tail inside the fused key MAC: 0 never, 1 (default) at N = 2^16, 2 wherever the shape allows
+        (identical results)"""
+        check(lib().lsa_set_ks_tail_in_mac(self.h, int(mode)))
+
     def set_bfv_dot_chunk(self, pairs):
         """pairs that bfv_mult_sum / bfv_dot extend per tensor launch (0: the default); the same words for every value"""
         check(lib().lsa_set_bfv_dot_chunk(self.h, int(pairs)))
