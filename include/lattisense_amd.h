@@ -475,7 +475,8 @@ int lsa_bfv_slot_sum(lsa_context ctx, lsa_bfv_slot_sum_handle plan, const uint64
  * plaintexts, the BFV counterpart of lsa_ckks_encode.  The coefficients are oracle/client.py Client.bfv_encode(values): the values
  * placed through Lattigo's batching index matrix, then the inverse negacyclic transform mod t.  The lift to the chain is the
  * pt_mul convention: the coefficient in [0, t) is used as it is at every modulus (t is below every q_j and p_i).
- * form: 0 = ring-t coefficients [N], words in [0, t): the operand of the plaintext add / sub / multiply entry points that lift;
+ * form: 0 = ring-t coefficients [N], words in [0, t): the operand of lsa_bfv_addsub_plain, lsa_bfv_mult_plain and
+ *           lsa_bfv_plain_lift below;
  *       1 = pt_mul [level+1][N]: NTT domain, Montgomery form, the operand of lsa_bfv_mult_plain_mul / _mac_plain_mul /
  *           _rotate_mac_plain_mul;
  *       2 = extended [level+1+k][N] over Q_level u P: NTT domain, plain residues, the operand of lsa_bfv_linear_transform.
@@ -487,6 +488,33 @@ int lsa_bfv_slot_sum(lsa_context ctx, lsa_bfv_slot_sum_handle plan, const uint64
  * t >= 2^32 or t not a prime that is 1 mod 2N, a null pointer, out_dev off the 16-byte grid, a short or odd stride. */
 int lsa_bfv_encode(lsa_context ctx, int level, int form, const uint64_t* values, uint64_t* out_dev, long long sout, int batch,
                    void* stream);
+
+/* ---- BFV ring-t plaintext operands: a ciphertext combined with a plaintext of form 0, the BFV counterparts of
+ * lsa_ckks_addsub_plain / _mult_plain.  ct / out: [2][level+1][N] per batch item, coefficient domain; pt: ring-t coefficients [N]
+ * per item, all on the device; batch strides in words.  spt == 0: one plaintext for the whole batch.  Everything is queued on
+ * `stream`; nothing is allocated per call and nothing waits.  batch <= 0 is a no-op (the other arguments are still checked).
+ * Errors are LSA_ERR_ARG before anything is queued, the message beginning with the entry point's name: a CKKS context, a level out
+ * of range, op outside 0..2 or form outside 1..2, a null pointer, a pointer off the 16-byte grid, an odd stride, a stride below
+ * one item (spt == 0 excepted; never sout), an output that overlaps an input other than "out IS ct" (same pointer, same stride;
+ * lift: no overlap at all), t >= 2^32 (addsub), t not below every modulus written (lift, mult).
+ *
+ * lsa_bfv_addsub_plain: op 0: ct + pt, 1: ct - pt, 2: pt - ct.  The plaintext enters through Lattigo's scaleUp: with
+ * u = ((pt[x] mod t) (Q_level mod t) + floor(t/2)) mod t, limb j of c0 takes +- (u - floor(t/2)) (-t^-1) mod q_j; c1 is copied
+ * (op 2: negated).  Ops 0 and 1 are the words of oracle/pyoracle.py Oracle.plain_ringt(op, level, ct, pt), op 2 the word-wise
+ * negation of op 1 (lsa_poly_addsub op 2 of it).  One launch (k_bfv_addsub_plain); in place, ops 0 and 1 touch c0 only.  A
+ * plaintext word may be any 64-bit value: it is reduced mod t first. */
+int lsa_bfv_addsub_plain(lsa_context ctx, int op, int level, const uint64_t* ct, long long sct, const uint64_t* pt, long long spt,
+                         uint64_t* out, long long sout, int batch, void* stream);
+/* Device ring-t plaintexts -> form 1 (pt_mul, [level+1][N]) or form 2 (extended, [level+1+k][N]): the device half of lsa_bfv_encode
+ * from the coefficient row on, with its words for the same plaintext; no host copy, no synchronise.  Words in [0, t): a word >= t
+ * gives unspecified output words, never an out-of-range access. */
+int lsa_bfv_plain_lift(lsa_context ctx, int level, int form, const uint64_t* pt, long long spt, uint64_t* out, long long sout,
+                       int batch, void* stream);
+/* out = ct x pt slot-wise: the plaintext goes to form 1 in the context workspace (a shared one once per call, per-item ones tile by
+ * tile), then lsa_bfv_mult_plain_mul.  The words of Oracle.plain_ringt(2, level, ct, pt); out may BE ct.  Plaintext words in
+ * [0, t) as for lsa_bfv_plain_lift. */
+int lsa_bfv_mult_plain(lsa_context ctx, int level, const uint64_t* ct, long long sct, const uint64_t* pt, long long spt,
+                       uint64_t* out, long long sout, int batch, void* stream);
 
 /* ---- BFV linear transform: plaintext matrix x encrypted vector in diagonal form, baby-step / giant-step with double hoisting.
  * The matrix acts on both rows of the 2 x N/2 slot matrix at once.  period: a power of two that divides N/2; rotations are column

@@ -161,6 +161,9 @@ SIGNATURES = {
     "lsa_bfv_slot_sum_set_gather": (c_int, [c_vp, c_int]),
     "lsa_bfv_slot_sum": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_int, c_u64p, ctypes.POINTER(c_vp), c_vp]),
     "lsa_bfv_encode": (c_int, [c_vp, c_int, c_int, c_u64p, c_vp, c_ll, c_int, c_vp]),
+    "lsa_bfv_addsub_plain": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
+    "lsa_bfv_plain_lift": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
+    "lsa_bfv_mult_plain": (c_int, [c_vp, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_lt_create": (c_int, [c_vp, c_int, c_int, c_int, ctypes.POINTER(c_int), c_u64p, ctypes.c_double, c_vp, ctypes.POINTER(c_vp)]),
     "lsa_bfv_lt_destroy": (None, [c_vp]),
     "lsa_bfv_lt_info": (c_int, [c_vp] + [ctypes.POINTER(c_int)] * 9),

@@ -33,6 +33,11 @@ const BfvEncodeTables& bfv_encode_tables(Context& c, const char* who);
 // 16-byte aligned).  Queues on s and returns without waiting, but has finished reading `values`.  The one code path of
 // lsa_bfv_encode and of the linear transform's diagonals.
 void bfv_encode_rows(Context& c, int level, int form, const u64* values, u64* out_dev, long long sout, int batch, hipStream_t s);
+// The encoder from the coefficient row on: coef [batch][N] on the device (batch stride scoef, 0: one row for the batch), words in
+// [0, t), t below every modulus written (the caller has checked) -> form BFV_PT_MUL or BFV_PT_EXT in out_dev.  Queues on s, no
+// host copy and no wait: the tail of bfv_encode_rows and the whole of lsa_bfv_plain_lift.
+void bfv_lift_rows(Context& c, int level, int form, const u64* coef, long long scoef, u64* out_dev, long long sout, int batch,
+                   hipStream_t s);
 // the public entry point: every check of include/lattisense_amd.h, then bfv_encode_rows and a wait for s
 void bfv_encode(Context& c, int level, int form, const u64* values, u64* out_dev, long long sout, int batch, hipStream_t s);
 

@@ -163,20 +163,41 @@ const BfvEncodeTables& bfv_encode_tables(Context& c, const char* who) {
     return *c.bfv_enc;
 }
 
+void bfv_lift_rows(Context& c, int level, int form, const u64* coef, long long scoef, u64* out, long long sout, int batch,
+                   hipStream_t s) {
+    if (batch <= 0) return;
+    const long long N = c.n;
+    const int rows = bfv_pt_rows(c, level, form);
+    LSA_REQUIRE((form == BFV_PT_MUL || form == BFV_PT_EXT) && rows <= LSA_MAX_PERIOD, "bfv_lift_rows: internal: form or row count");
+    RowMap rm;
+    rm.period = rows;
+    for (int j = 0; j < rows; j++) rm.mod_of[j] = (unsigned char)c.qp_mod(level + 1, j);
+    NttFusion lf;   // every row of a plaintext reads the one coefficient row (x < t < q: the lift is the identity)
+    lf.pro = 4;
+    lf.limbs = rows;
+    lf.last = coef;
+    lf.last_stride = scoef;
+    lf.last_rpp = 1;
+    lf.ql_mod = 0;
+    launch_ntt(c, out, out, batch, sout, sout, rows, rm, false, s, &lf);
+    if (form == BFV_PT_MUL) {
+        if (sout == (long long)rows * N) {
+            launch_to_mont(c, out, batch * rows, rm, s);
+        } else {
+            for (int b = 0; b < batch; b++) launch_to_mont(c, out + (size_t)b * sout, rows, rm, s);
+        }
+    }
+}
+
 void bfv_encode_rows(Context& c, int level, int form, const u64* values, u64* out, long long sout, int batch, hipStream_t s) {
     if (batch <= 0) return;
     const char* who = "lsa_bfv_encode";
     const BfvEncodeTables& T = bfv_encode_tables(c, who);
     const long long N = c.n;
     const int rows = bfv_pt_rows(c, level, form);
-    RowMap rm;
     LSA_REQUIRE(rows <= LSA_MAX_PERIOD, std::string(who) + ": more rows than a transform launch takes");
-    rm.period = rows;
-    for (int j = 0; j < rows; j++) {
-        rm.mod_of[j] = (unsigned char)c.qp_mod(level + 1, j);
-        // the lift: a coefficient in [0, t) is its own residue
-        LSA_REQUIRE(form == BFV_PT_RINGT || c.t < c.T.mod[rm.mod_of[j]], std::string(who) + ": t must be below every modulus of the chain");
-    }
+    for (int j = 0; j < rows; j++)   // the lift: a coefficient in [0, t) is its own residue
+        LSA_REQUIRE(form == BFV_PT_RINGT || c.t < c.T.mod[c.qp_mod(level + 1, j)], std::string(who) + ": t must be below every modulus of the chain");
     const bool on_device = c.logn <= LSA_BFV_ENC_MAX_LOGN && c.logn >= LSA_BFV_ENC_MIN_LOGN;
     const size_t words = (size_t)batch * N;
     u64* stage = c.workspace(2 * words, s);   // the uploaded words | the coefficient rows (forms 1 and 2, the host transform)
@@ -195,23 +216,7 @@ void bfv_encode_rows(Context& c, int level, int form, const u64* values, u64* ou
             launch_copy_rows(c, coef, N, out, sout, 1, &row0, batch, s);
         }
     }
-    if (form != BFV_PT_RINGT) {
-        NttFusion lf;   // every row of a plaintext reads the one coefficient row (x < t < q: the lift is the identity)
-        lf.pro = 4;
-        lf.limbs = rows;
-        lf.last = coef;
-        lf.last_stride = N;
-        lf.last_rpp = 1;
-        lf.ql_mod = 0;
-        launch_ntt(c, out, out, batch, sout, sout, rows, rm, false, s, &lf);
-        if (form == BFV_PT_MUL) {
-            if (sout == (long long)rows * N) {
-                launch_to_mont(c, out, batch * rows, rm, s);
-            } else {
-                for (int b = 0; b < batch; b++) launch_to_mont(c, out + (size_t)b * sout, rows, rm, s);
-            }
-        }
-    }
+    if (form != BFV_PT_RINGT) bfv_lift_rows(c, level, form, coef, N, out, sout, batch, s);
     LSA_HIP(hipStreamSynchronize(s));   // `values` and `host` have been read; the plaintexts are complete
 }
 

@@ -776,6 +776,28 @@ int lsa_bfv_encode(lsa_context ctx, int level, int form, const uint64_t* values,
         bfv_encode(C(ctx), level, form, values, out_dev, sout, batch, S(stream));
     });
 }
+// ---- BFV ring-t plaintext operands (bfv_plain.hip)
+int lsa_bfv_addsub_plain(lsa_context ctx, int op, int level, const uint64_t* ct, long long sct, const uint64_t* pt, long long spt,
+                         uint64_t* out, long long sout, int batch, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(ctx != nullptr, "lsa_bfv_addsub_plain: null context");
+        bfv_addsub_plain(C(ctx), op, level, ct, sct, pt, spt, out, sout, batch, S(stream));
+    });
+}
+int lsa_bfv_plain_lift(lsa_context ctx, int level, int form, const uint64_t* pt, long long spt, uint64_t* out, long long sout,
+                       int batch, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(ctx != nullptr, "lsa_bfv_plain_lift: null context");
+        bfv_plain_lift(C(ctx), level, form, pt, spt, out, sout, batch, S(stream));
+    });
+}
+int lsa_bfv_mult_plain(lsa_context ctx, int level, const uint64_t* ct, long long sct, const uint64_t* pt, long long spt,
+                       uint64_t* out, long long sout, int batch, void* stream) {
+    return guard([&] {
+        LSA_REQUIRE(ctx != nullptr, "lsa_bfv_mult_plain: null context");
+        bfv_mult_plain(C(ctx), level, ct, sct, pt, spt, out, sout, batch, S(stream));
+    });
+}
 struct lsa_bfv_lt_st : PlanHandle<BfvLinearTransform> {};
 int lsa_bfv_lt_create(lsa_context ctx, int level, int period, int n_diag, const int* diag_index, const uint64_t* values,
                       double bsgs_ratio, void* stream, lsa_bfv_lt* out) {

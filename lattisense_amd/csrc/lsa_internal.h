@@ -620,6 +620,16 @@ void bfv_rescale(Context& c, int level, int polys, const u64* in, u64* out, int 
 // BFV ct x pt_mul (NTT-domain, Montgomery-form plaintexts [L][N]): out = ct . pt per poly; out may be ct
 void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64* out, int batch, long long sct, long long spt,
                         long long sout, hipStream_t s);
+// BFV ct and a ring-t plaintext pt [N] (bfv_plain.hip; semantics: include/lattisense_amd.h).  The launcher serves the task runtime
+// too: polys 2 or 3, out may be ct itself (same pointer and stride), nothing else is checked.
+void launch_bfv_addsub_plain(Context& c, int op, int level, int polys, const u64* ct, long long sct, const u64* pt, long long spt,
+                             u64* out, long long sout, int batch, hipStream_t s);
+void bfv_addsub_plain(Context& c, int op, int level, const u64* ct, long long sct, const u64* pt, long long spt, u64* out,
+                      long long sout, int batch, hipStream_t s);
+void bfv_plain_lift(Context& c, int level, int form, const u64* pt, long long spt, u64* out, long long sout, int batch,
+                    hipStream_t s);
+void bfv_mult_plain(Context& c, int level, const u64* ct, long long sct, const u64* pt, long long spt, u64* out, long long sout,
+                    int batch, hipStream_t s);
 // out = sum_i cts[i] . pts[i] (+ partial), n >= 1 terms, one inverse transform per output; out overlaps no input
 void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
                        const long long* spts, const u64* partial, long long spartial, u64* out, int batch, long long sout,

@@ -252,9 +252,14 @@ void Dispatcher::run_gpu_bucket(Lane& ln, const std::vector<ComputeNode*>& nodes
             const EwOp ew = op == OperationType::ADD ? EW_ADD : EW_SUB;
             if (n0->input_nodes.size() == 1) {
                 launch_elementwise(c, ew, a.ptr, a.ptr, out, m, a.stride, a.stride, so, polys_in * L, rmL, s);
+            } else if (bfv && is_plain_node(n0->input_nodes[1]) && is_ringt_node(n0->input_nodes[1]) && polys_in >= 2 && polys_in <= 3) {
+                // BFV ct +- ring-t pt in one launch: the plaintext is scaled up by Q/t with rounding as c0 is read, the other
+                // polynomials are copied by the same lanes (bfv_plain.hip; the words of lift mode 2 + copy + add)
+                Operand b = gather(ln, nodes, 1, avail, (size_t)N);
+                launch_bfv_addsub_plain(c, ew == EW_ADD ? 0 : 1, lvl, polys_in, a.ptr, a.stride, b.ptr, b.stride, out, so, m, s);
             } else if (is_plain_node(n0->input_nodes[1])) {
-                // CKKS: plaintext limbs in the NTT domain (ring-t: centred lift + NTT); BFV: coefficient domain
-                // (ring-t: scaled up by Q/t with rounding)
+                // CKKS: plaintext limbs in the NTT domain (ring-t: centred lift + NTT); BFV: coefficient domain, a full
+                // plaintext already scaled
                 Operand b = plain_operand(1, bfv ? 2 : 0, !bfv);
                 std::vector<int> rows(polys_in * L);
                 for (size_t i = 0; i < rows.size(); i++) rows[i] = (int)i;

@@ -363,6 +363,36 @@ class DeviceContext:
                                            L * self.n if spt is None else spt, 2 * L * self.n, self.stream))
         return out
 
+    # ---- BFV ring-t plaintext operands (ct / out: [batch][2][level+1][N], pt: [batch][N] ring-t coefficients, lsa_bfv_encode form 0)
+    def bfv_addsub_plain(self, op, level, ct, pt, batch, out=None, spt=None, sct=None, sout=None):
+        """op 0: ct + pt, 1: ct - pt, 2: pt - ct; out=ct works in place; spt: the plaintexts' batch stride in words (0: one
+        plaintext for the whole batch); sct / sout: the ciphertexts' strides (default compact)"""
+        w = 2 * (level + 1) * self.n
+        sct = w if sct is None else sct
+        sout = (sct if out is ct else w) if sout is None else sout
+        if out is None:
+            out = self.alloc(max(batch, 1) * sout)
+        check(lib().lsa_bfv_addsub_plain(self.h, op, level, ct.ptr, sct, pt.ptr, self.n if spt is None else spt, out.ptr, sout, batch,
+                                         self.stream))
+        return out
+
+    def bfv_plain_lift(self, level, form, pt, batch, out=None, spt=None, sout=None):
+        """device ring-t plaintexts -> form 1 (pt_mul) or 2 (extended): [batch][rows][N], the words of bfv_encode; asynchronous"""
+        w = self.bfv_pt_rows(level, form) * self.n
+        sout = w if sout is None else sout
+        if out is None:
+            out = self.alloc(max(batch, 1) * sout)
+        check(lib().lsa_bfv_plain_lift(self.h, level, form, pt.ptr, self.n if spt is None else spt, out.ptr, sout, batch, self.stream))
+        return out
+
+    def bfv_mult_plain(self, level, ct, pt, batch, out=None, spt=None):
+        """ct x pt slot-wise, pt ring-t coefficients; out=ct multiplies in place; spt = 0: one plaintext for the whole batch"""
+        w = 2 * (level + 1) * self.n
+        if out is None:
+            out = self.alloc(max(batch, 1) * w)
+        check(lib().lsa_bfv_mult_plain(self.h, level, ct.ptr, w, pt.ptr, self.n if spt is None else spt, out.ptr, w, batch, self.stream))
+        return out
+
     def bfv_mac_plain_mul(self, level, cts, pts, batch, partial=None):
         """sum_i cts[i] x pts[i] (+ partial): lists of device buffers, [batch][2][L][N] / [batch][L][N]"""
         L = level + 1
