@@ -289,6 +289,13 @@ int lsa_set_modup_lift(lsa_context ctx, int enable);
  * NTT pass has eight stages (N = 2^16, the measured shape); 2: wherever the shape allows (also seven-stage second passes,
  * N = 2^14).  Identical results for every value; another value is refused (LSA_ERR_ARG).  Read by every operator call. */
 int lsa_set_ks_tail_in_mac(lsa_context ctx, int mode);
+/* Merged ModDown + rescale: ModDown's base conversion P -> Q also reads INTT(acc_l) (and INTT(base_l) where the caller has a
+ * base), forms t = (INTT(acc_l) - conv_l) * P^-1 (+ base_l) in registers and stores in_j = conv_j * P^-1 + lift_j(t) itself, so
+ * that the element-wise kernel that wrote t goes away and the forward transform of in_j runs without a load-side prologue.
+ * 0: never; 1 (default): rings with N >= 2^16; 2: every ring.  Needs lsa_set_fuse_tails(ctx, 1) and level >= 1, else the
+ * earlier sequence runs.  Identical results for every value; another value is refused (LSA_ERR_ARG).  Read by every operator
+ * call. */
+int lsa_set_rescale_head_in_conv(lsa_context ctx, int mode);
 /* Two-pass NTTs (N > 2^12) run both passes over a chunk of at most `mib` MiB of limbs before moving on, so that the
  * second pass is served by the 256 MiB Infinity Cache (0, the default = one launch per pass over the whole batch).  Results are
  * identical for every value: the setting only changes how many batch items one launch covers, and the operands of the fused

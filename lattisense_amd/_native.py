@@ -102,6 +102,7 @@ SIGNATURES = {
     "lsa_set_fuse_tails": (c_int, [c_vp, c_int]),
     "lsa_set_modup_lift": (c_int, [c_vp, c_int]),
     "lsa_set_ks_tail_in_mac": (c_int, [c_vp, c_int]),
+    "lsa_set_rescale_head_in_conv": (c_int, [c_vp, c_int]),
     "lsa_set_ntt_chunk_mib": (c_int, [c_vp, c_int]),
     "lsa_debug_set_ntt_stamps": (c_int, [c_vp, c_vp]),
     "lsa_debug_baseconv_plans": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),

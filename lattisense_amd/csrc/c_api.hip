@@ -486,6 +486,12 @@ int lsa_set_ks_tail_in_mac(lsa_context ctx, int mode) {
         C(ctx).ks_tail_in_mac = mode;
     });
 }
+int lsa_set_rescale_head_in_conv(lsa_context ctx, int mode) {
+    return guard([&] {
+        LSA_REQUIRE(mode >= 0 && mode <= 2, "lsa_set_rescale_head_in_conv: mode is 0, 1 or 2");
+        C(ctx).rescale_head_in_conv = mode;
+    });
+}
 int lsa_set_dual_stream(lsa_context ctx, int enable) {
     return guard([&] { C(ctx).dual_stream = enable ? 1 : 0; });
 }

@@ -155,9 +155,11 @@ u64* Context::workspace2(size_t words, hipStream_t s) {
 }
 
 const BaseConvPlan* Context::baseconv(const std::vector<int>& src, const std::vector<int>& dst, bool centered,
-                                      bool pinv_scaled, const BaseConvFold* fold) {
+                                      bool pinv_scaled, const BaseConvFold* fold, bool rescale_head) {
     std::string key = centered ? "c" : "u";
     if (pinv_scaled) key += "s";
+    if (rescale_head) key += "h";
+    LSA_REQUIRE(!rescale_head || (centered && pinv_scaled && !fold && dst.size() >= 2), "base conversion: the rescale-head flavour is a centred, P^-1-scaled ModDown plan");
     if (fold) {
         LSA_REQUIRE(!fold->tag.empty() && (fold->src_pre.empty() || fold->src_pre.size() == src.size()) &&
                         (fold->dst_scale.empty() || fold->dst_scale.size() == dst.size()),
@@ -214,6 +216,9 @@ const BaseConvPlan* Context::baseconv(const std::vector<int>& src, const std::ve
         }
         for (int v = 0; v <= ns; v++) K->vs[j][v] = mul_mod_host(mul_mod_host((u64)v % pj, all, pj), scale, pj);
         K->half_dst[j] = mul_mod_host(mul_mod_host((all + pj - 1 % pj) % pj, (pj + 1) >> 1, pj), scale, pj);
+        // rescale_head: the kernel adds c = t + h mod q_l (q_l the last target) to every other target's sum; h leaves with the
+        // output correction (unscaled: it belongs to lift_j, not to conv_j * P^-1)
+        if (rescale_head && j + 1 < nd) K->half_dst[j] = (K->half_dst[j] + ((T.mod[dst[nd - 1]] - 1) >> 1) % pj) % pj;
     }
     // SPLIT is proved for k_baseconv's up to LSA_BC_NARROW_SRC terms; wider conversions take the 128-bit form
     bool small = !sw::bc_no_split() && ns <= LSA_BC_NARROW_SRC;

@@ -1313,6 +1313,13 @@ struct BaseConvArgs {
     long long ssub;
     int sub_row[LSA_BC_MAX_SRC];
 };
+// the rescale-head form (k_baseconv<.., HEAD>) takes these after the plain arguments, whose layout stays as it is
+struct BaseConvHeadArgs : BaseConvArgs {
+    const u64* head_a;      // INTT(acc[h][l]), one row per batch item
+    const u64* head_b;      // optional: INTT(base[h][l])
+    const u64* head_pinv;   // -> P^-1 mod q_l, Montgomery form (Context::pinv_vec(level) + l)
+    long long s_head_a, s_head_b;
+};
 
 // NSMAX = compile-time bound of the source-limb loops (registers for y[] scale with it; dispatched from ns); EXACT: ns ==
 // NSMAX, so the source loads carry no guard and are all in flight before the first is consumed.  The target loop has a
@@ -1336,8 +1343,23 @@ __device__ __forceinline__ ModDev ld_mod(const LSA_CONST_AS ModDev* t, int i) {
     m.r1 = t[i].r1;
     return m;
 }
-template <int NSMAX, bool EXACT, int TGT, bool SPLIT = false>
-__global__ __launch_bounds__(TPB) void k_baseconv(BaseConvArgs g) {
+// HEAD (the merged ModDown + rescale, key_switch.hip ks_moddown_head): the plan is a pinv_scaled ModDown plan in its rescale-head
+// flavour (Context::baseconv: the output correction of every target but the last also subtracts h = (q_l - 1) / 2), whose last
+// target l = nd - 1 is unscaled.  Every block converts target l for itself first, reads A_l = INTT(acc_l) (and B_l =
+// INTT(base_l)) at its two points and forms t = (A_l - conv_l) * P^-1 (+ B_l) and c = t + h mod q_l in registers (ntt_core.h
+// rescale_head_t, rescale_head_centre).  The centred remainder of t IS the integer c - h, so
+//   in_j = conv_j * P^-1 + lift_j(t) = conv_j * P^-1 + c - h  (mod q_j):
+// c enters every other target's sum as one more term with weight 1 (2^64 mod q_j in the sum's Montgomery form) ahead of the
+// single REDC, the plan's correction takes h off, and the stored word is in_j, canonical -- for any ratio q_l / q_j, without a
+// second conditional subtraction (rescale_head_in states the same residue; tests/test_gpu_rescale_head_conv.py holds the kernel
+// to it through the transform's prologue, word for word).  Nothing is stored for l.  The blocks of blockIdx.z split the nd - 1
+// stored targets; y_i, v and every conv_j are computed exactly as in the plain form.
+// Bounds with the extra term: c < q_l.  128-bit form: the term follows at most 7 products since the last reduction (8 products of
+// < 2^61 * p_j stay below p_j * 2^64).  SPLIT: q_l < 2^58, so c splits like a y_i; the three-product columns take up to 8 terms
+// (NSMAX + 1 <= 8, else the four-product form), whose columns hold 17 terms: 17 * 2 * 2^58 < 2^64, and 17 * 2^58 * p_j plus the
+// correction stays below p_j * 2^64.
+template <int NSMAX, bool EXACT, int TGT, bool SPLIT = false, bool HEAD = false>
+__global__ __launch_bounds__(TPB) void k_baseconv(std::conditional_t<HEAD, BaseConvHeadArgs, BaseConvArgs> g) {
     const LSA_CONST_AS BaseConvConsts& K = *(const LSA_CONST_AS BaseConvConsts*)g.k;
     const LSA_CONST_AS ModDev* const mods_c = (const LSA_CONST_AS ModDev*)g.mods;
     const int x = (blockIdx.x * TPB + threadIdx.x) * 2;
@@ -1349,6 +1371,26 @@ __global__ __launch_bounds__(TPB) void k_baseconv(BaseConvArgs g) {
 #pragma unroll
     for (int i = 0; i < NSMAX; i++)
         if (EXACT || i < ns) xin[i] = ld2(src + ((long long)g.rows.src_row[i] << g.logn));
+    ulonglong2 head_a = {0, 0}, head_b = {0, 0};   // (HEAD: in flight with the source rows)
+    u64 head_c0 = 0, head_c1 = 0;
+    if constexpr (HEAD) {
+        head_a = ld2(g.head_a + b * g.s_head_a + x);
+        if (g.head_b) head_b = ld2(g.head_b + b * g.s_head_b + x);
+    }
+    // HEAD, target l (jj < 0): conv_l -> t -> c, kept in registers
+    auto head_step = [&](const ModDev& m, u64 r0, u64 r1) {
+        if constexpr (HEAD) {
+            const u64 pinv = *(const LSA_CONST_AS u64*)g.head_pinv;
+            u64 t0 = rescale_head_t(head_a.x, r0, pinv, m), t1 = rescale_head_t(head_a.y, r1, pinv, m);
+            if (g.head_b) {
+                t0 = add_mod(t0, head_b.x, m.q);
+                t1 = add_mod(t1, head_b.y, m.q);
+            }
+            const u64 h = (m.q - 1) >> 1;
+            head_c0 = rescale_head_centre(t0, h, m.q);
+            head_c1 = rescale_head_centre(t1, h, m.q);
+        }
+    };
     if (g.sub) {   // block-uniform: a branch around the loop, only the launches that fold a subtraction take it
         const u64* sub = g.sub + b * g.ssub + x;
 #pragma unroll
@@ -1398,8 +1440,8 @@ __global__ __launch_bounds__(TPB) void k_baseconv(BaseConvArgs g) {
             }
     }
 #pragma unroll
-    for (int jj = 0; jj < TGT; jj++) {
-        const int j = min(j0 + jj, nd - 1);
+    for (int jj = HEAD ? -1 : 0; jj < TGT; jj++) {
+        const int j = HEAD ? (jj < 0 ? nd - 1 : min(j0 + jj, nd - 2)) : min(j0 + jj, nd - 1);
         const ModDev m = ld_mod(mods_c, K.dst_mod[j]);
         u64 h0 = 0, l0 = 0, h1 = 0, l1 = 0, r0 = 0, r1 = 0;
 #if defined(LSA_BC_DIAG_NO_MATH)       // diagnostic build: the loads and the stores, no conversion arithmetic
@@ -1411,7 +1453,7 @@ __global__ __launch_bounds__(TPB) void k_baseconv(BaseConvArgs g) {
         if (SPLIT) {
             // columns y0 w0, (y0 + y1)(w0 + w1), y1 w1: three multiply-accumulates per term (the middle column is recovered as
             // cm - c0 - c2); 30-bit factors: up to 8 terms stay below 2^63, more take the four-product form
-            constexpr bool KARA = NSMAX <= 8;
+            constexpr bool KARA = NSMAX + (HEAD ? 1 : 0) <= 8;
             u64 c0[2] = {0, 0}, c1[2] = {0, 0}, c2[2] = {0, 0};
 #pragma unroll
             for (int i = 0; i < NSMAX; i++) {
@@ -1427,6 +1469,22 @@ __global__ __launch_bounds__(TPB) void k_baseconv(BaseConvArgs g) {
                             c1[e] += (u64)ylo[i][e] * w1;
                             c1[e] += (u64)yhi[i][e] * w0;
                         }
+                    }
+                }
+            }
+            if (HEAD && jj >= 0) {   // c as one more term, weight 2^64 mod p_j
+                const u32 w0 = (u32)m.r1 & ((1u << 29) - 1), w1 = (u32)(m.r1 >> 29), ws = w0 + w1;
+                const u64 hc[2] = {head_c0, head_c1};
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    const u32 lo = (u32)hc[e] & ((1u << 29) - 1), hi = (u32)(hc[e] >> 29);
+                    c0[e] += (u64)lo * w0;
+                    c2[e] += (u64)hi * w1;
+                    if (KARA) {
+                        c1[e] += (u64)(lo + hi) * ws;
+                    } else {
+                        c1[e] += (u64)lo * w1;
+                        c1[e] += (u64)hi * w0;
                     }
                 }
             }
@@ -1450,6 +1508,10 @@ __global__ __launch_bounds__(TPB) void k_baseconv(BaseConvArgs g) {
             }
             r0 = csub(mont_redc_lazy(hs[0], ls[0], m.q, m.qinv), m.q);
             r1 = csub(mont_redc_lazy(hs[1], ls[1], m.q, m.qinv), m.q);
+            if (HEAD && jj < 0) {
+                head_step(m, r0, r1);
+                continue;
+            }
 #if defined(LSA_BC_DIAG_NO_STORE)      // diagnostic build: all the arithmetic, (almost) no store traffic
             if (r0 == 0x123456789abcdefull) st2(dst + ((long long)g.rows.dst_row[j] << g.logn), r0, r1);
 #else
@@ -1470,6 +1532,10 @@ __global__ __launch_bounds__(TPB) void k_baseconv(BaseConvArgs g) {
                 }
             }
         }
+        if (HEAD && jj >= 0) {   // c as one more term, weight 2^64 mod p_j
+            mac128(h0, l0, head_c0, m.r1);
+            mac128(h1, l1, head_c1, m.r1);
+        }
         r0 = add_mod(r0, csub(mont_redc_lazy(h0, l0, m.q, m.qinv), m.q), m.q);
         r1 = add_mod(r1, csub(mont_redc_lazy(h1, l1, m.q, m.qinv), m.q), m.q);
         }
@@ -1479,20 +1545,25 @@ __global__ __launch_bounds__(TPB) void k_baseconv(BaseConvArgs g) {
             r0 = sub_mod(r0, K.half_dst[j], m.q);
             r1 = sub_mod(r1, K.half_dst[j], m.q);
         }
+        if (HEAD && jj < 0) {
+            head_step(m, r0, r1);
+            continue;
+        }
         st2(dst + ((long long)g.rows.dst_row[j] << g.logn), r0, r1);
     }
 }
 
-template <int NSMAX, int TGT>
-static void launch_baseconv_nt(int ns, int nd, bool split, dim3 grid, hipStream_t s, const BaseConvArgs& g) {
+// nd: the targets the launch stores (HEAD: without l)
+template <int NSMAX, int TGT, bool HEAD = false, class Args = BaseConvArgs>
+static void launch_baseconv_nt(int ns, int nd, bool split, dim3 grid, hipStream_t s, const Args& g) {
     grid.z = (unsigned)((nd + TGT - 1) / TGT);
     if (split) {
-        if (ns == NSMAX) hipLaunchKernelGGL((k_baseconv<NSMAX, true, TGT, true>), grid, dim3(TPB), 0, s, g);
-        else hipLaunchKernelGGL((k_baseconv<NSMAX, false, TGT, true>), grid, dim3(TPB), 0, s, g);
+        if (ns == NSMAX) hipLaunchKernelGGL((k_baseconv<NSMAX, true, TGT, true, HEAD>), grid, dim3(TPB), 0, s, g);
+        else hipLaunchKernelGGL((k_baseconv<NSMAX, false, TGT, true, HEAD>), grid, dim3(TPB), 0, s, g);
         return;
     }
-    if (ns == NSMAX) hipLaunchKernelGGL((k_baseconv<NSMAX, true, TGT>), grid, dim3(TPB), 0, s, g);
-    else hipLaunchKernelGGL((k_baseconv<NSMAX, false, TGT>), grid, dim3(TPB), 0, s, g);
+    if (ns == NSMAX) hipLaunchKernelGGL((k_baseconv<NSMAX, true, TGT, false, HEAD>), grid, dim3(TPB), 0, s, g);
+    else hipLaunchKernelGGL((k_baseconv<NSMAX, false, TGT, false, HEAD>), grid, dim3(TPB), 0, s, g);
 }
 // targets per block: the candidate with the least total work ceil(nd/T) * (Y + T*C), Y = y/v phase ~ 2.5 target conversions
 static int baseconv_targets_per_block(int nd) {
@@ -1508,12 +1579,12 @@ static int baseconv_targets_per_block(int nd) {
     }
     return best;
 }
-template <int NSMAX>
-static void launch_baseconv_ns(int ns, int nd, bool split, dim3 grid, hipStream_t s, const BaseConvArgs& g) {
+template <int NSMAX, bool HEAD = false, class Args = BaseConvArgs>
+static void launch_baseconv_ns(int ns, int nd, bool split, dim3 grid, hipStream_t s, const Args& g) {
     const int best = baseconv_targets_per_block(nd);
-    if (best == 4) launch_baseconv_nt<NSMAX, 4>(ns, nd, split, grid, s, g);
-    else if (best == 7) launch_baseconv_nt<NSMAX, 7>(ns, nd, split, grid, s, g);
-    else launch_baseconv_nt<NSMAX, 13>(ns, nd, split, grid, s, g);
+    if (best == 4) launch_baseconv_nt<NSMAX, 4, HEAD>(ns, nd, split, grid, s, g);
+    else if (best == 7) launch_baseconv_nt<NSMAX, 7, HEAD>(ns, nd, split, grid, s, g);
+    else launch_baseconv_nt<NSMAX, 13, HEAD>(ns, nd, split, grid, s, g);
 }
 
 // ------------------------------------------------------------------------- wide exact base conversion (17..32 sources)
@@ -1598,9 +1669,10 @@ static void launch_baseconv_wide_ns(int ns, int nd, dim3 grid, hipStream_t s, co
 }
 
 void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows, const u64* src, u64* dst, int batch,
-                     long long ssrc, long long sdst, hipStream_t s, const u64* sub, long long ssub, const int* sub_row) {
+                     long long ssrc, long long sdst, hipStream_t s, const u64* sub, long long ssub, const int* sub_row,
+                     const BaseConvHead* head) {
     if (batch <= 0) return;
-    BaseConvArgs g{};
+    BaseConvHeadArgs g{};
     g.sub = sub;
     g.ssub = ssub;
     LSA_REQUIRE(!sub || sub_row, "base conversion: subtrahend rows missing");
@@ -1614,24 +1686,50 @@ void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows
     g.sdst = sdst;
     g.logn = c.logn;
     g.rows = rows;
-    ProfScope ps(c, PROF_BASECONV, 8.0 * c.n * batch * (double)(k->ns * (sub ? 2 : 1) + k->nd), s);
     const int ns = k->ns, nd = k->nd;
+    if (head) {
+        LSA_REQUIRE(ns <= LSA_BC_NARROW_SRC && nd >= 2 && !sub && head->a && head->pinv, "base conversion: rescale-head form on an unsupported shape");
+        g.head_a = head->a;
+        g.head_b = head->b;
+        g.head_pinv = head->pinv;
+        g.s_head_a = head->sa;
+        g.s_head_b = head->sb;
+    }
+    // algorithmic bytes: the source rows (twice with a subtrahend) and one row per target;
+    // rescale-head form: the source rows, the row A_l (and B_l), one row per target but l, which is not stored
+    ProfScope ps(c, PROF_BASECONV, 8.0 * c.n * batch * (head ? (double)(ns + 1 + (head->b ? 1 : 0) + nd - 1)
+                                                                  : (double)(ns * (sub ? 2 : 1) + nd)), s);
+    if (head) {
+        const dim3 grid((unsigned)(c.n / (2 * TPB)), (unsigned)batch, 1);
+        const int st = nd - 1;   // stored targets
+        if (ns <= 1) launch_baseconv_ns<1, true>(ns, st, k->split29, grid, s, g);
+        else if (ns <= 2) launch_baseconv_ns<2, true>(ns, st, k->split29, grid, s, g);
+        else if (ns <= 3) launch_baseconv_ns<3, true>(ns, st, k->split29, grid, s, g);
+        else if (ns <= 4) launch_baseconv_ns<4, true>(ns, st, k->split29, grid, s, g);
+        else if (ns <= 5) launch_baseconv_ns<5, true>(ns, st, k->split29, grid, s, g);
+        else if (ns <= 8) launch_baseconv_ns<8, true>(ns, st, k->split29, grid, s, g);
+        else if (ns <= 12) launch_baseconv_ns<12, true>(ns, st, k->split29, grid, s, g);
+        else launch_baseconv_ns<LSA_BC_NARROW_SRC, true>(ns, st, k->split29, grid, s, g);
+        LSA_HIP(hipGetLastError());
+        return;
+    }
+    const BaseConvArgs& gp = g;   // the plain forms take the plain arguments
     if (ns > LSA_BC_NARROW_SRC) {
         const dim3 grid((unsigned)(c.n / TPB), (unsigned)batch, 1);   // one point per thread
-        if (ns <= 24) launch_baseconv_wide_ns<24>(ns, nd, grid, s, g);
-        else launch_baseconv_wide_ns<LSA_BC_MAX_SRC>(ns, nd, grid, s, g);
+        if (ns <= 24) launch_baseconv_wide_ns<24>(ns, nd, grid, s, gp);
+        else launch_baseconv_wide_ns<LSA_BC_MAX_SRC>(ns, nd, grid, s, gp);
         LSA_HIP(hipGetLastError());
         return;
     }
     const dim3 grid((unsigned)(c.n / (2 * TPB)), (unsigned)batch, 1);
-    if (ns <= 1) launch_baseconv_ns<1>(ns, nd, k->split29, grid, s, g);
-    else if (ns <= 2) launch_baseconv_ns<2>(ns, nd, k->split29, grid, s, g);
-    else if (ns <= 3) launch_baseconv_ns<3>(ns, nd, k->split29, grid, s, g);
-    else if (ns <= 4) launch_baseconv_ns<4>(ns, nd, k->split29, grid, s, g);
-    else if (ns <= 5) launch_baseconv_ns<5>(ns, nd, k->split29, grid, s, g);
-    else if (ns <= 8) launch_baseconv_ns<8>(ns, nd, k->split29, grid, s, g);
-    else if (ns <= 12) launch_baseconv_ns<12>(ns, nd, k->split29, grid, s, g);
-    else launch_baseconv_ns<LSA_BC_NARROW_SRC>(ns, nd, k->split29, grid, s, g);
+    if (ns <= 1) launch_baseconv_ns<1>(ns, nd, k->split29, grid, s, gp);
+    else if (ns <= 2) launch_baseconv_ns<2>(ns, nd, k->split29, grid, s, gp);
+    else if (ns <= 3) launch_baseconv_ns<3>(ns, nd, k->split29, grid, s, gp);
+    else if (ns <= 4) launch_baseconv_ns<4>(ns, nd, k->split29, grid, s, gp);
+    else if (ns <= 5) launch_baseconv_ns<5>(ns, nd, k->split29, grid, s, gp);
+    else if (ns <= 8) launch_baseconv_ns<8>(ns, nd, k->split29, grid, s, gp);
+    else if (ns <= 12) launch_baseconv_ns<12>(ns, nd, k->split29, grid, s, gp);
+    else launch_baseconv_ns<LSA_BC_NARROW_SRC>(ns, nd, k->split29, grid, s, gp);
     LSA_HIP(hipGetLastError());
 }
 

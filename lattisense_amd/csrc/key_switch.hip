@@ -19,6 +19,27 @@ RowMap rm_seq(int count, int first) {
 // Its head, ks_moddown_head -- the inverse transforms and the conversion -- is the same for every output.  The merged rescale goes
 // on with ks_rescale_head: t, then the fusion of the one forward transform of in_j that finishes it, which ks_moddown launches
 // whole and KsTile::mac_rescale pass by pass around the key MAC's tail variant.
+// The merged rescale with its head formed inside the conversion (Context::rescale_head_in_conv, lsa_set_rescale_head_in_conv):
+// the conversion reads INTT(acc_l) (and INTT(base_l)), keeps t in registers and stores in_j = conv_j * P^-1 + lift_j(t) at
+// conv[h][j], j != l (k_baseconv<.., HEAD>).  No k_sub_mul, conv_l and t are never written, and the forward transform of in_j
+// starts with the plain first pass.  Same residues as the earlier sequence, which mode 0 (and mode 1 below N = 2^16) keeps.
+static bool ks_head_in_conv(const Context& c, int level, const KsOut& o) {
+    return o.form == KsOut::RESCALE && c.fuse_tails && level >= 1 && c.np <= LSA_BC_NARROW_SRC &&
+           (c.rescale_head_in_conv == 2 || (c.rescale_head_in_conv == 1 && c.logn >= 16));
+}
+// the last limbs of base out of the NTT domain, in place.  base is the caller's scratch here (the tensor output): nothing reads
+// these rows in NTT form afterwards.
+static void ks_base_last_intt(Context& c, int level, const KsOut& o, int nb, hipStream_t s) {
+    if (!o.base) return;
+    u64* base_rw = const_cast<u64*>(o.base);
+    RowMap rb;
+    rb.period = 1;
+    rb.mod_of[0] = (unsigned char)level;
+    rb.row0 = level;
+    rb.row_step = o.base_rpp;
+    launch_ntt(c, base_rw, base_rw, nb, o.sbase, o.sbase, 2, rb, true, s);
+}
+
 static void ks_moddown_head(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
     LSA_REQUIRE(!o.scatter || (c.fuse_tails && o.form == KsOut::NTT), "scattered ModDown store: fused tails, NTT-domain output");
     LSA_REQUIRE(!o.rmac || o.scatter, "rotate-and-MAC tail: needs the rotation's index map");
@@ -56,7 +77,19 @@ static void ks_moddown_head(Context& c, int level, u64* acc, long long s_acc, u6
             rows.dst_row[j] = j;
             dst.push_back(j);
         }
-        const BaseConvPlan* k = c.baseconv(src, dst, true, rs);
+        const bool in_conv = ks_head_in_conv(c, level, o);
+        const BaseConvPlan* k = c.baseconv(src, dst, true, rs, nullptr, in_conv);
+        if (in_conv) {
+            // (the plan's last target is l = level, unscaled: the row the head needs)
+            ks_base_last_intt(c, level, o, nb, s);   // before the conversion reads INTT(base_l)
+            for (int h = 0; h < 2; h++) {
+                const BaseConvHead hd{acc + ((size_t)h * T + level) * N, s_acc,
+                                      o.base && h < o.base_polys ? o.base + ((size_t)h * o.base_rpp + level) * N : nullptr, o.sbase,
+                                      c.pinv_vec(level) + level};
+                launch_baseconv(c, k, rows, acc + (size_t)h * T * N, conv + (size_t)h * L * N, nb, s_acc, s_conv, s, nullptr, 0, nullptr, &hd);
+            }
+            return;
+        }
         for (int h = 0; h < 2; h++)
             launch_baseconv(c, k, rows, acc + (size_t)h * T * N, conv + (size_t)h * L * N, nb, s_acc, s_conv, s);
     }
@@ -117,7 +150,8 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
 }
 
 // the merged rescale after the head: t into the last limbs of o.p, then the row map (rmo) and the fusion of the forward transform of
-// in_j over every other limb (prologue: in_j = conv_j * P^-1 + lift_j(t); epilogue: out_j)
+// in_j over every other limb (prologue: in_j = conv_j * P^-1 + lift_j(t); epilogue: out_j).  With the head formed inside the
+// conversion (ks_head_in_conv) conv already holds in_j: no t, no prologue, the epilogue alone.
 static NttFusion ks_rescale_head(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s,
                                  RowMap& rmo) {
     const long long N = c.n;
@@ -128,29 +162,24 @@ static NttFusion ks_rescale_head(Context& c, int level, u64* acc, long long s_ac
     const int l = level;
     // t[h] = (INTT(acc[h][l]) - conv[h][l]) * P^-1 + INTT(base[h][l]) -> p[h][l].  base is the caller's scratch here
     // (the tensor output): its last limbs are transformed in place, nothing reads them in NTT form afterwards.
-    if (o.base) {
-        u64* base_rw = const_cast<u64*>(o.base);
-        RowMap rb;
-        rb.period = 1;
-        rb.mod_of[0] = (unsigned char)l;
-        rb.row0 = l;
-        rb.row_step = o.base_rpp;
-        launch_ntt(c, base_rw, base_rw, nb, o.sbase, o.sbase, 2, rb, true, s);
+    const bool in_conv = ks_head_in_conv(c, level, o);
+    if (!in_conv) {
+        ks_base_last_intt(c, level, o, nb, s);
+        const unsigned char lm[1] = {(unsigned char)l};
+        launch_sub_mul_general(c, 2, 1, lm, c.pinv_vec(level) + l, acc + (long long)l * N, s_acc, T, conv + (long long)l * N,
+                               s_conv, L, o.base ? o.base + (long long)l * N : nullptr, o.sbase, o.base_rpp, o.base_polys,
+                               o.p + (long long)l * N, o.sp, L, nb, s);
     }
-    const unsigned char lm[1] = {(unsigned char)l};
-    launch_sub_mul_general(c, 2, 1, lm, c.pinv_vec(level) + l, acc + (long long)l * N, s_acc, T, conv + (long long)l * N,
-                           s_conv, L, o.base ? o.base + (long long)l * N : nullptr, o.sbase, o.base_rpp, o.base_polys,
-                           o.p + (long long)l * N, o.sp, L, nb, s);
     // every other limb: in = conv_j*P^-1 + lift_j(t), out = (acc_j*P^-1 - NTT(in) + base_j) * q_l^-1
     rmo.period = 2 * L;
     for (int h = 0; h < 2; h++)
         for (int j = 0; j < L; j++) rmo.mod_of[h * L + j] = j == l ? LSA_ROW_SKIP : (unsigned char)j;
     NttFusion fb;
-    fb.pro = 2;
+    fb.pro = in_conv ? 0 : 2;
     fb.epi = 2;
     fb.limbs = L;
     fb.ql_mod = l;
-    fb.last = o.p + (long long)l * N;
+    fb.last = in_conv ? nullptr : o.p + (long long)l * N;
     fb.last_stride = o.sp;
     fb.last_rpp = L;
     fb.a = acc;
@@ -358,9 +387,10 @@ void KsTile::mac_rescale(const Key& k, const KsOut& o) {
     const NttFusion fb = ks_rescale_head(c, level, acc, s_acc, conv, o, nb, s, rmo);
     // 4. the first pass with the prologue alone (the prologue belongs to the first executed pass, the epilogue to the pass that
     //    stores final values: each transform launch here carries only the one its pass runs)
+    //    (head formed inside the conversion: conv holds in_j, the plain first pass)
     NttFusion fp = fb;
     fp.epi = 0;
-    launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rmo, false, s, &fp, 1);
+    launch_ntt(c, conv, conv, nb, s_conv, s_conv, 2 * L, rmo, false, s, fb.pro ? &fp : nullptr, 1);
     // 5. the digits and the tail of the FP64-engine Q limbs
     const KsTailOperands kt{conv, s_conv, o.rs.out, o.rs.sout};
     LSA_REQUIRE(launch_ntt_ksmac(c, level, src.ntt, src.s_ntt, ext, s_ext, k, acc, s_acc, nb, s, fold, KS_FUSED_Q_TAIL, &kt),

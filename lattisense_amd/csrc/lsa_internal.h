@@ -111,6 +111,8 @@ struct Context {
     int fuse_tails = 1;             // ModDown / rescale element-wise tails fused into the NTT load/store phases
     int ks_tail_in_mac = 1;         // merged rescale tail finished inside the fused key MAC (key_switch.h KsTile::plan_tail): 0 never,
                                     // 1 where the second pass has eight stages (the measured shape), 2 wherever the shape allows
+    int rescale_head_in_conv = 1;   // merged rescale head formed inside ModDown's base conversion (key_switch.hip ks_head_in_conv): 0 never,
+                                    // 1 rings with N >= 2^16 (the measured shape), 2 every ring
     int dual_stream = 0;            // 1: overlap alternate tiles of an operator on an auxiliary stream (+5% throughput,
                                     // but per-kernel timings then include the co-running kernel; off for clean accounting)
     hipStream_t aux_stream = nullptr;
@@ -164,6 +166,8 @@ struct Context {
     int qp_mod(int L, int tl) const { return tl < L ? tl : p_mod(tl - L); }   // row tl of Q_level u P (L = level + 1) -> modulus
     bool fp_engine(int mod) const { return fp64_ntt && (T.mod[mod] >> LSA_FP64_MAX_BITS) == 0; }   // FP64 butterflies serve it
     // pinv_scaled: the outputs of every target but the last are multiplied by P^-1 mod p_j (merged ModDown + rescale)
+    // rescale_head (with pinv_scaled, centred): the plan of k_baseconv<.., HEAD> -- those outputs also lose h = (q_l - 1) / 2,
+    // q_l the last target's modulus, which the kernel's extra term c = t + h brings in (launch_baseconv's `head`)
     // fold: element-wise steps on either side of a conversion folded into its constants (both linear, so the residues are the
     // ones the separate steps give): src_pre[i] multiplies source limb i BEFORE the conversion (the centring offset and
     // (S/q_i)^-1 absorb it), dst_scale[j] multiplies target j's output; `tag` names the variant in the plan cache
@@ -172,7 +176,7 @@ struct Context {
         std::vector<u64> src_pre, dst_scale;   // plain residues; empty = none
     };
     const BaseConvPlan* baseconv(const std::vector<int>& src, const std::vector<int>& dst, bool centered,
-                                 bool pinv_scaled = false, const BaseConvFold* fold = nullptr);
+                                 bool pinv_scaled = false, const BaseConvFold* fold = nullptr, bool rescale_head = false);
     const u64* pinv_vec(int level);
     const u64* pmodq_vec(int level);   // [level+1] P mod q_j, Montgomery form (extended ciphertexts: c0 * P)
     // [2][level+1] the P factors of the tensor-fold key MAC (TensorFold): row 0 the Montgomery form of P * 2^64 mod q_j
@@ -323,9 +327,20 @@ struct BaseConvRows {
 };
 // sub (optional): converted is src - sub, limb for limb (rows.src_row indexes both; its own batch stride and row offsets
 // sub_row) -- the subtraction of a preceding element-wise step done on the conversion's source load
+// head (optional, narrow conversions without sub): the rescale-head form of ModDown's conversion.  k is a pinv_scaled plan in its
+// rescale_head flavour, whose last target l is unscaled; a = INTT(acc[h][l]) and b = INTT(base[h][l]) (or null) are single rows with their batch strides,
+// pinv points at P^-1 mod q_l (Montgomery form, device).  Target l is converted but not stored; every other target j gets
+// in_j = conv_j * P^-1 + lift_j(t), t = (a - conv_l) * P^-1 (+ b), canonical (ntt_core.h rescale_head_in).
+struct BaseConvHead {
+    const u64* a;
+    long long sa;
+    const u64* b;
+    long long sb;
+    const u64* pinv;
+};
 void launch_baseconv(Context& c, const BaseConvPlan* k, const BaseConvRows& rows, const u64* src, u64* dst, int batch,
                      long long ssrc, long long sdst, hipStream_t s, const u64* sub = nullptr, long long ssub = 0,
-                     const int* sub_row = nullptr);
+                     const int* sub_row = nullptr, const BaseConvHead* head = nullptr);
 // key-switch inner product: out[h][tl] = sum_d ext(d,tl) * key[d][h][tl];  ext(d,tl) = cx[tl] when tl is in digit d
 // scatter (every target limb only): the result leaves as the ROTATED EXTENDED ciphertext out[h][tl][scatter[x]] = sum(x) + (h == 0, tl < L:
 // P * base[tl][x]) -- gadget product, c0 * P and the automorphism of a baby-step rotation in one pass (base == nullptr: no P * c0);

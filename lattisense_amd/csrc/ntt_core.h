@@ -378,6 +378,23 @@ LSA_HD u64 fp_merged_tail(double x, double sum, double bd, double kd, double k2d
 #ifndef LSA_NTT_HEAD_ROUNDS
 #define LSA_NTT_HEAD_ROUNDS 2   // two-operand prologue: load rounds per tile (1 = all 16 operand pairs in flight at once)
 #endif
+// ---- the merged ModDown + rescale head per coefficient, integer form; every value canonical.  The load-side prologue below
+// (fz_pro = 1 / 2) forms lift_j with these; the rescale-head form of the base conversion (kernels.hip k_baseconv<.., HEAD>) forms
+// t and c with them and reaches the same in_j through its own sum: lift_j is the integer c - h reduced modulo q_j.
+//   t     = (A_l - conv_l) * P^-1 (+ B_l) mod q_l      A_l = INTT(acc_l), pinv_m = P^-1 mod q_l in Montgomery form (k_sub_mul's step)
+//   c     = (t + h) mod q_l, h = (q_l - 1) / 2         the centred remainder of t plus h, in [0, q_l)
+//   lift_j = (c mod q_j) - (h mod q_j) mod q_j         near (q_l <= 2 q_j): c < 2 q_j, one conditional subtraction; else reduce_u64
+//   in_j  = conv_j * P^-1 + lift_j mod q_j             conv_j * P^-1 is what a pinv_scaled conversion plan yields (Context::baseconv)
+LSA_HD u64 rescale_head_t(u64 a_l, u64 conv_l, u64 pinv_m, const ModDev& ml) {
+    return mont_mul(sub_mod(a_l, conv_l, ml.q), pinv_m, ml.q, ml.qinv);
+}
+LSA_HD u64 rescale_head_centre(u64 t, u64 h, u64 ql) { return add_mod(t, h, ql); }
+LSA_HD u64 rescale_head_lift(u64 c, bool near, const ModDev& mj, u64 hq) {
+    return sub_mod(near ? csub(c, mj.q) : reduce_u64(c, mj), hq, mj.q);
+}
+LSA_HD u64 rescale_head_in(u64 conv_j, u64 c, bool near, const ModDev& mj, u64 hq) {
+    return add_mod(conv_j, rescale_head_lift(c, near, mj, hq), mj.q);
+}
 struct NttLoadFix {   // per-block constants of the load-side conversions
     bool head, add, fp, near, raw, fp_lift, lift;
     u64 ql, h, hq;
@@ -428,10 +445,10 @@ LSA_HD u64 ntt_load_fix(const NttLoadFix& f, u64 v, u64 t) {
         return d_to_bits(f.add ? u52_to_double(v) + r : r);
     }
     if (f.head) {
-        const u64 c = add_mod(t, f.h, f.ql);   // centred remainder + h, in [0, q_l)
+        const u64 c = rescale_head_centre(t, f.h, f.ql);   // centred remainder + h, in [0, q_l)
         // chain primes are within a factor two of each other almost always: one conditional subtraction then replaces
         // the general reduction
-        const u64 lift = sub_mod(f.near ? csub(c, f.mi.q) : reduce_u64(c, f.mi), f.hq, f.mi.q);
+        const u64 lift = rescale_head_lift(c, f.near, f.mi, f.hq);
         v = f.add ? add_mod(v, lift, f.mi.q) : lift;
     }
     if (f.fp && !f.raw) v = d_to_bits(u52_to_double(v));  // inputs of an FP64-engine limb are canonical or lazy (< 4q < 2^49): exact

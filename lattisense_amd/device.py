@@ -112,6 +112,11 @@ class DeviceContext:
         (identical results)"""
         check(lib().lsa_set_ks_tail_in_mac(self.h, int(mode)))
 
+    def set_rescale_head_in_conv(self, mode):
+        """the merged rescale head formed inside ModDown's base conversion: 0 never, 1 (default) at N >= 2^16, 2 every ring
+        (identical results)"""
+        check(lib().lsa_set_rescale_head_in_conv(self.h, int(mode)))
+
     def set_bfv_dot_chunk(self, pairs):
         """pairs that bfv_mult_sum / bfv_dot extend per tensor launch (0: the default); the same words for every value"""
         check(lib().lsa_set_bfv_dot_chunk(self.h, int(pairs)))
