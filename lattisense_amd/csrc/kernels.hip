@@ -280,6 +280,14 @@ __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMA
     u64 acc0[16], acc1[16];
 #pragma unroll
     for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = 0;   // (0 is also +0.0)
+    // FP64 engine, eight- and seven-stage passes: the transforms' twiddles come from the workgroup's LDS copy behind the tile image
+    // (ntt_r16.h, "twiddles once per workgroup"); the other instantiations fetch them per transform as they did
+    constexpr bool TWC = ks_fused_twc(MU, FP);
+    double* const twc = reinterpret_cast<double*>(lds + LSA_R16_LDS_WORDS);
+    if constexpr (TWC) {
+        r16_twc_fill<MU>(twc, tid, L, G1, G2);
+        r16_sync<1>();   // (a wave reads only what it wrote)
+    }
     for (int d = 0; d < g.beta; d++) {
         const bool own = d == own_d;
         if (!own) {
@@ -298,6 +306,16 @@ __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMA
                 r8x3_get<2>(k, i, lds, v);
                 r8x3_group<2>(v, a, bc, L, G1, i);
                 r8x3_put<2>(k, i, lds, v);
+            } else if constexpr (TWC) {
+                double w[15];
+                r16_twc_get<MU, 0>(twc, tid, w);
+                r16_group_twc<0, MU>(v, false, L, w);
+                r16_lds_put<1, 0, MU>(tid, lds, v);
+                r16_sync<1>();
+                r16_twc_get<MU, 1>(twc, tid, w);
+                r16_lds_get<1, 1, MU>(tid, lds, v);
+                r16_group_twc<1, MU>(v, false, L, w);
+                r16_lds_put<1, 1, MU>(tid, lds, v);
             } else {
                 r16_group<1, 0, MU>(v, a, bc, L, G1);
                 r16_lds_put<1, 0, MU>(tid, lds, v);
@@ -331,12 +349,24 @@ __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMA
             bc.base_src = tb * g.stconv + ((long long)bc.row << g.logn);
             u64 v[16];
             r16_load_direct<1, false, 0, MU>(a, bc, tt, v);
-            r16_group<1, 0, MU>(v, a, bc, L, T1);
-            r16_lds_put<1, 0, MU>(tt, lds, v);
-            r16_sync<1>();
-            r16_lds_get<1, 1, MU>(tt, lds, v);
-            r16_group<1, 1, MU>(v, a, bc, L, T2);
-            r16_lds_put<1, 1, MU>(tt, lds, v);
+            if constexpr (TWC) {
+                double w[15];
+                r16_twc_get<MU, 0>(twc, tt, w);
+                r16_group_twc<0, MU>(v, false, L, w);
+                r16_lds_put<1, 0, MU>(tt, lds, v);
+                r16_sync<1>();
+                r16_twc_get<MU, 1>(twc, tt, w);
+                r16_lds_get<1, 1, MU>(tt, lds, v);
+                r16_group_twc<1, MU>(v, false, L, w);
+                r16_lds_put<1, 1, MU>(tt, lds, v);
+            } else {
+                r16_group<1, 0, MU>(v, a, bc, L, T1);
+                r16_lds_put<1, 0, MU>(tt, lds, v);
+                r16_sync<1>();
+                r16_lds_get<1, 1, MU>(tt, lds, v);
+                r16_group<1, 1, MU>(v, a, bc, L, T2);
+                r16_lds_put<1, 1, MU>(tt, lds, v);
+            }
             r16_sync<1>();
             r16_mac_tail<MU>(g, a, bc, L, tt, tb, ttl, h, kd, k2d, lds, acc0);
             r16_sync<1>();
@@ -346,6 +376,23 @@ __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMA
         return;
     }
     r16_mac_store<MU, FP>(g, a, bc, L, tid, b, tl, acc0, acc1);
+}
+
+// image + twiddle cache: above 64 KiB of dynamic LDS the kernel instance opts in, once per instance AND device (as ntt_launch_variant)
+template <int MU, bool FP, bool TAIL = false>
+static void ks_fused_launch(dim3 grid, dim3 block, hipStream_t s, const KsFusedArgs& g) {
+    constexpr size_t lds_bytes = ks_fused_lds_bytes(MU, FP);
+    if (lds_bytes > 65536) {
+        static std::atomic<unsigned long long> raised{0};   // bit d: done on device d (the attribute is per device)
+        int dev = 0;
+        LSA_HIP(hipGetDevice(&dev));
+        const unsigned long long bit = 1ull << (dev & 63);
+        if (!(raised.load(std::memory_order_acquire) & bit)) {
+            LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ntt_r16_ksmac<MU, FP, TAIL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+            raised.fetch_or(bit, std::memory_order_release);
+        }
+    }
+    hipLaunchKernelGGL((k_ntt_r16_ksmac<MU, FP, TAIL>), grid, block, lds_bytes, s, g);
 }
 
 bool ks_fused_enabled(const Context& c) {
@@ -411,7 +458,6 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
     }
     const int T = g.L + c.np, mu = c.plan.pass[1].mu;
     LSA_REQUIRE(T <= 64, "fused key MAC: too many target limbs");
-    const size_t lds_bytes = (size_t)LSA_R16_LDS_WORDS * sizeof(u64);
     // one launch per butterfly engine (own register budget each); bytes: one pass of the launch's extension transforms
     // (16 N / 2 per limb) + its share of the gadget inner product as launch_ks_mac counts it
     for (int eng = 0; eng < 2; eng++) {
@@ -441,14 +487,14 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
         const dim3 grid((unsigned)nblocks), block(LSA_R16_THREADS);
         if (tail) {
             LSA_REQUIRE(eng == 1 && (mu == 8 || mu == 7), "fused key MAC: the tail runs on the FP64 engine's eight- and seven-stage passes");
-            if (mu == 8) hipLaunchKernelGGL((k_ntt_r16_ksmac<8, true, true>), grid, block, lds_bytes, s, g);
-            else hipLaunchKernelGGL((k_ntt_r16_ksmac<7, true, true>), grid, block, lds_bytes, s, g);
-        } else if (mu == 9 && eng) hipLaunchKernelGGL((k_ntt_r16_ksmac<9, true>), grid, block, lds_bytes, s, g);
-        else if (mu == 9) hipLaunchKernelGGL((k_ntt_r16_ksmac<9, false>), grid, block, lds_bytes, s, g);
-        else if (mu == 8 && eng) hipLaunchKernelGGL((k_ntt_r16_ksmac<8, true>), grid, block, lds_bytes, s, g);
-        else if (mu == 8) hipLaunchKernelGGL((k_ntt_r16_ksmac<8, false>), grid, block, lds_bytes, s, g);
-        else if (eng) hipLaunchKernelGGL((k_ntt_r16_ksmac<7, true>), grid, block, lds_bytes, s, g);
-        else hipLaunchKernelGGL((k_ntt_r16_ksmac<7, false>), grid, block, lds_bytes, s, g);
+            if (mu == 8) ks_fused_launch<8, true, true>(grid, block, s, g);
+            else ks_fused_launch<7, true, true>(grid, block, s, g);
+        } else if (mu == 9 && eng) ks_fused_launch<9, true>(grid, block, s, g);
+        else if (mu == 9) ks_fused_launch<9, false>(grid, block, s, g);
+        else if (mu == 8 && eng) ks_fused_launch<8, true>(grid, block, s, g);
+        else if (mu == 8) ks_fused_launch<8, false>(grid, block, s, g);
+        else if (eng) ks_fused_launch<7, true>(grid, block, s, g);
+        else ks_fused_launch<7, false>(grid, block, s, g);
     }
     LSA_HIP(hipGetLastError());
     return true;

@@ -1117,9 +1117,11 @@ LSA_HD void ntt_phase_sub(const NttPassArgs& a, const NttBlockCtx& bc, int tid, 
 
 // The same butterfly group on the FP64 engine: integer-valued doubles.  long_pass: a (single-pass) transform of more than 9
 // stages reduces after every forward group; the inverse always does.
-template <int RHO, bool TWU = false>
+// TWC: the group's 2^RHO - 1 twiddles come from the caller (twc[(1 << j) - 1 + k] = the k-th of its j-th stage, the values and
+// the order ntt_load_tw_fp delivers) instead of from the table: a caller that runs the same group many times fetches them once
+template <int RHO, bool TWU = false, bool TWC = false>
 LSA_HD void ntt_group_fp(double (&v)[1 << RHO], bool inverse, const double* tw /* limb's table */, int s_base, unsigned G, double q, double qinv,
-                         bool scale_here, double sc0, double sc1, bool long_pass) {
+                         bool scale_here, double sc0, double sc1, bool long_pass, const double* twc = nullptr) {
     constexpr int E = 1 << RHO;
     if (!inverse) {
 #pragma unroll
@@ -1127,7 +1129,10 @@ LSA_HD void ntt_group_fp(double (&v)[1 << RHO], bool inverse, const double* tw /
             const int half = E >> (j + 1);
             const int s = s_base + j;
             double w[E / 2];   // this stage's 2^j twiddles: one 8-byte (j = 0) or 2^(j-1) 16-byte loads
-            if (TWU) {   // wave-uniform position: scalar loads
+            if (TWC) {
+#pragma unroll
+                for (int k = 0; k < (1 << j); k++) w[k] = twc[(1 << j) - 1 + k];
+            } else if (TWU) {   // wave-uniform position: scalar loads
 #pragma unroll
                 for (int k = 0; k < (1 << j); k++) w[k] = LSA_CONST_PTR(double, tw + (1LL << s))[ntt_tw_pos_fp(s, j, G, k)];
             } else {
@@ -1167,7 +1172,10 @@ LSA_HD void ntt_group_fp(double (&v)[1 << RHO], bool inverse, const double* tw /
                 continue;
             }
             double w[E / 2];
-            if (TWU) {   // wave-uniform position: scalar loads
+            if (TWC) {
+#pragma unroll
+                for (int k = 0; k < (1 << j); k++) w[k] = twc[(1 << j) - 1 + k];
+            } else if (TWU) {   // wave-uniform position: scalar loads
 #pragma unroll
                 for (int k = 0; k < (1 << j); k++) w[k] = LSA_CONST_PTR(double, tw + (1LL << s))[ntt_tw_pos_fp(s, j, G, k)];
             } else {

@@ -680,6 +680,114 @@ struct KsFusedArgs {
     const double* tkd;
 };
 
+// ---- the fused kernel's twiddles, once per workgroup (FP64 engine, eight- and seven-stage passes)
+// (A/B builds only: -DLSA_KSMAC_TWCACHE=0 keeps the loop that fetches them from the table in every transform)
+#ifndef LSA_KSMAC_TWCACHE
+#define LSA_KSMAC_TWCACHE 1
+#endif
+// The twiddles of a workgroup's transforms depend on (limb, tile, lane) only, not on the digit: every wave copies the ones its own
+// lanes use into LDS behind the tile image once, ahead of the digit loop, and every transform (foreign digits and tail) reads them
+// from there.  A wave reads only what it wrote: a wavefront-local ordering point after the fill, no workgroup barrier.
+// Layout in doubles from the cache's first word (MU = 8 | 7; 2^(12-MU) transforms of 2^(MU-4) lanes, 64 / 2^(MU-4) per wave):
+//   shared part, 16 words per transform k: the first group's entry e = 2^j - 1 + k' (k'-th twiddle of stage j) at 16 k + 1 + e --
+//     the two of a 16-byte table load sit on a 16-byte boundary; the transform's lanes read one address (a broadcast);
+//   private part, per wave: the second group(s)' entries of each lane, slot-major and lane-minor -- the stage-0 entry of group g at
+//     64 g + lane, the p-th 16-byte pair of the other stages at 64 NG + 128 p + 2 lane: a wave's 8- and 16-byte reads are
+//     conflict-free.  MU = 8: one radix-16 group, 1 + 7 pairs; MU = 7: two radix-8 groups, 2 x (1 + 3 pairs).
+// 4096 doubles for either split: with the image 67,584 bytes per workgroup, two workgroups per CU in 135,168 of 163,840.
+template <int MU>
+struct R16Twc {
+    static_assert(MU == 8 || MU == 7, "the cached-twiddle loop covers the radix-16 x radix-2^(MU-4) passes");
+    static constexpr int R2 = MU - 4, NG = 16 >> R2, E2 = (1 << R2) - 1;   // second group(s): stages, groups per lane, entries per group
+    static constexpr int PG = (E2 - 1) / 2;                                 // 16-byte pairs per group
+    static constexpr int SHARED = 16 << (12 - MU);
+    static constexpr int WAVE = 64 * NG + 128 * NG * PG;
+    static constexpr int WORDS = SHARED + (LSA_R16_THREADS / 64) * WAVE;
+    static LSA_HD int shared(int k, int e) { return 16 * k + 1 + e; }
+    static LSA_HD int priv(int tid, int g, int e) {
+        const int base = SHARED + (tid >> 6) * WAVE, lane = tid & 63;
+        return e == 0 ? base + 64 * g + lane : base + 64 * NG + 128 * (g * PG + ((e - 1) >> 1)) + 2 * lane + ((e - 1) & 1);
+    }
+};
+// which instantiations of the fused kernel take the cached twiddles (the nine-stage pass and the integer engine keep the loop
+// they had), and the dynamic LDS the launch requests
+constexpr bool ks_fused_twc(int mu, bool fp) { return LSA_KSMAC_TWCACHE != 0 && fp && (mu == 8 || mu == 7); }
+static_assert(R16Twc<8>::WORDS == R16Twc<7>::WORDS, "one cache size for both splits");
+constexpr size_t ks_fused_lds_bytes(int mu, bool fp) {
+    return (size_t)(LSA_R16_LDS_WORDS + (ks_fused_twc(mu, fp) ? R16Twc<8>::WORDS : 0)) * sizeof(u64);
+}
+LSA_HD void r16_twc_ld2(const double* p, double& x, double& y) {   // 16-byte aligned
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double2 v = *reinterpret_cast<const double2*>(p);
+    x = v.x;
+    y = v.y;
+#else
+    x = p[0];
+    y = p[1];
+#endif
+}
+// the fill: exactly the values ntt_load_tw_fp delivers to r16_group<1, HI, MU> (G1, G2 as the kernel forms them)
+template <int MU>
+LSA_HD void r16_twc_fill(double* twc, int tid, const R16Limb& L, unsigned G1, unsigned G2) {
+    typedef R16Twc<MU> C;
+    int k, i;
+    r16_lane<1, MU>(tid, k, i);
+    if (i == 0) {   // one lane per transform
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            double w[8];
+            const int s = L.s_lo + j;
+            ntt_load_tw_fp(L.twd + (1LL << s), s, j, G1, w);
+#pragma unroll
+            for (int kk = 0; kk < (1 << j); kk++) twc[C::shared(k, (1 << j) - 1 + kk)] = w[kk];
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < C::NG; g++) {
+#pragma unroll
+        for (int j = 0; j < C::R2; j++) {
+            double w[8];
+            const int s = L.s_lo + 4 + j;
+            ntt_load_tw_fp(L.twd + (1LL << s), s, j, G2 + (unsigned)g, w);
+#pragma unroll
+            for (int kk = 0; kk < (1 << j); kk++) twc[C::priv(tid, g, (1 << j) - 1 + kk)] = w[kk];
+        }
+    }
+}
+// the twiddles of image HI for this lane, w[g * E + e] with E = 2^R - 1 entries per group, in ntt_group_fp's caller-supplied order
+template <int MU, int HI>
+LSA_HD void r16_twc_get(const double* twc, int tid, double (&w)[15]) {
+    typedef R16Twc<MU> C;
+    if (HI == 0) {
+        int k, i;
+        r16_lane<1, MU>(tid, k, i);
+        w[0] = twc[C::shared(k, 0)];
+#pragma unroll
+        for (int e = 1; e < 15; e += 2) r16_twc_ld2(twc + C::shared(k, e), w[e], w[e + 1]);
+        return;
+    }
+#pragma unroll
+    for (int g = 0; g < C::NG; g++) {
+        w[g * C::E2] = twc[C::priv(tid, g, 0)];
+#pragma unroll
+        for (int e = 1; e < C::E2; e += 2) r16_twc_ld2(twc + C::priv(tid, g, e), w[g * C::E2 + e], w[g * C::E2 + e + 1]);
+    }
+}
+// r16_group<1, HI, MU> on the FP64 engine with the twiddles r16_twc_get delivered: the same butterflies on the same values
+template <int HI, int MU>
+LSA_HD void r16_group_twc(u64 (&v)[16], bool inverse, const R16Limb& L, const double (&w)[15]) {
+    constexpr int R = HI ? MU - 4 : 4, NG = 16 >> R, E = 1 << R;
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+        double d[E];
+#pragma unroll
+        for (int e = 0; e < E; e++) d[e] = d_from_bits(v[g * E + e]);
+        ntt_group_fp<R, false, true>(d, inverse, nullptr, 0, 0u, L.q, L.qinv, false, 0.0, 0.0, false, w + g * (E - 1));
+#pragma unroll
+        for (int e = 0; e < E; e++) v[g * E + e] = d_to_bits(d[e]);
+    }
+}
+
 // the MAC of one digit on the pair image: vin = the operand pair values (FP: doubles' bits), acc0/acc1 the two halves' sums
 template <int MU, bool FP>
 LSA_HD void r16_mac_digit(const KsFusedArgs& g, const NttPassArgs& a, const NttBlockCtx& bc, const R16Limb& L, int tid, int d, int kj,
