@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "build_flags.h"
+#include "ks_mac_groups.h"
 #include "lsa_internal.h"
 #include "ntt_r16.h"
 #include "plain_ops.h"
@@ -2050,10 +2051,10 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
                                              2.0 * g.beta * T), s);
     // enough workgroups to fill the chip, as few key re-reads as possible
     const dim3 grid1 = ew_grid(c, targets, 1);
-    const int groups = std::max(1, std::min(batch, (int)((2048 + grid1.x - 1) / grid1.x)));
+    const KsMacGroups gr = ks_mac_groups(grid1.x, batch);
     g.batch = batch;
-    g.bpt = (batch + groups - 1) / groups;
-    const dim3 grid(grid1.x, (unsigned)((batch + g.bpt - 1) / g.bpt));
+    g.bpt = gr.bpt;
+    const dim3 grid(grid1.x, (unsigned)gr.gy);
     if (scatter && accumulate) launch_ks_mac_kb<true, false, true>(g.beta, grid, s, g);
     else if (scatter) launch_ks_mac_kb<true>(g.beta, grid, s, g);
     else if (fold) launch_ks_mac_kb<false, true>(g.beta, grid, s, g);

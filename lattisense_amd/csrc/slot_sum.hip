@@ -13,6 +13,7 @@
 
 #include "entry_check.h"
 #include "key_switch.h"
+#include "ks_mac_groups.h"
 #include "ks_mac_multi.h"
 
 namespace lsa {
@@ -332,10 +333,10 @@ void launch_ks_mac_multi(Context& c, int level, const u64* cx, long long scx, co
     ProfScope ps(c, PROF_KSMAC, 8.0 * c.n * (batch * ((double)g.beta * T + 2.0 * T * n_keys + g.L) + 2.0 * g.beta * T * n_keys), s);
     // enough workgroups to fill the chip, as few key re-reads as possible (launch_ks_mac's grouping)
     const unsigned gx = (unsigned)(T * (c.n / (2 * TPB)));
-    const int groups = std::max(1, std::min(batch, (int)((2048 + gx - 1) / gx)));
+    const KsMacGroups gr = ks_mac_groups(gx, batch);
     g.batch = batch;
-    g.bpt = (batch + groups - 1) / groups;
-    const dim3 grid(gx, (unsigned)((batch + g.bpt - 1) / g.bpt));
+    g.bpt = gr.bpt;
+    const dim3 grid(gx, (unsigned)gr.gy);
     if (n_keys == 2) launch_ksm_kb<2>(g.beta, grid, s, g);
     else if (n_keys == 3) launch_ksm_kb<3>(g.beta, grid, s, g);
     else launch_ksm_kb<4>(g.beta, grid, s, g);
