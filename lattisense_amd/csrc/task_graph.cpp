@@ -561,6 +561,23 @@ void TaskGraph::fuse_accumulations() {
                     prods.push_back(p);
                 else others.push_back(in);
             }
+        if (algo == ALGO_BFV) {
+            // The backend runs a BFV multiply-accumulate whose plaintexts are all pt_mul or none of them
+            // (bind_gpu_executor).  The flavour with more products joins (a tie: pt_mul); a product of the other flavour
+            // stays as written and is an operand like any other, so exactly one of them can be the partial sum.
+            auto is_ptmul = [](const ComputeNode* p) {
+                const DatumNode::FheProperty& f = *p->input_nodes[1]->fhe_prop;
+                return f.is_ntt && f.is_mform && !(f.p && f.p->is_ringt);
+            };
+            const size_t n_ptmul = (size_t)std::count_if(prods.begin(), prods.end(), is_ptmul);
+            const bool join_ptmul = 2 * n_ptmul >= prods.size();
+            std::vector<ComputeNode*> joined;
+            for (ComputeNode* p : prods) {
+                if (is_ptmul(p) == join_ptmul) joined.push_back(p);
+                else others.push_back(p->output_nodes[0]);
+            }
+            prods.swap(joined);
+        }
         if (prods.size() < 2 || others.size() > 1) continue;   // nothing to gain / more than one partial sum
         std::sort(prods.begin(), prods.end(), [](ComputeNode* a, ComputeNode* b) { return a->index < b->index; });
         DatumNode* final_out = root->output_nodes[0];

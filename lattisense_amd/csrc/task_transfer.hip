@@ -471,7 +471,9 @@ StoreJob stores_enqueue(Lane& ln, const std::vector<ComputeNode*>& nodes, Avail&
     // (no malloc per limb, no second host copy).  The slab returns to the pool when the last struct is released.
     std::shared_ptr<Slab> hslab = total ? ln.pslab(total) : nullptr;
     u64* host = hslab ? hslab->ptr : nullptr;
-    // merge runs that are contiguous on the device into single copies
+    // merge runs that are contiguous on the device into single copies.  Only within one slab: two slabs are two allocations
+    // even where their addresses happen to follow each other (results of two buckets stored in one level), and one copy must
+    // not span them
     for (size_t i = 0; i < items.size();) {
         if (direct[i]) {
             LSA_HIP(hipMemcpyAsync(direct[i], items[i].first->ptr, items[i].first->words(N) * sizeof(u64), hipMemcpyDeviceToHost, ln.s));
@@ -480,7 +482,8 @@ StoreJob stores_enqueue(Lane& ln, const std::vector<ComputeNode*>& nodes, Avail&
             continue;
         }
         size_t j = i, words = 0;
-        while (j < items.size() && !direct[j] && items[j].first->ptr == items[i].first->ptr + words) {
+        while (j < items.size() && !direct[j] && items[j].first->slab == items[i].first->slab &&
+               items[j].first->ptr == items[i].first->ptr + words) {
             words += items[j].first->words(N);
             j++;
         }
