@@ -478,6 +478,50 @@ int lsa_bfv_slot_sum_set_gather(lsa_bfv_slot_sum_handle plan, int enable);
 int lsa_bfv_slot_sum(lsa_context ctx, lsa_bfv_slot_sum_handle plan, const uint64_t* in, uint64_t* out, int batch, long long sin,
                      long long sout, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
 
+/* ---- BFV oblivious expansion (coefficient extraction; the Expand of SealPIR / OnionPIR / Spiral, Lattigo's rlwe.Expand): one
+ * ciphertext of m(X) = sum_i m_i X^i becomes `count` ciphertexts, 1 <= count <= N, k = ceil(log2 count) levels.  State: a list
+ * c[a] of coefficient-domain ciphertexts [2][level+1][N], c[0] = in.  Level j = 0 .. k-1 has the Galois element g_j = N / 2^j + 1
+ * and the shift s = 2^j; for every node a < min(2^j, count):
+ *   sigma   = rotate(c[a], g_j)              the words of lsa_bfv_rotate
+ *   c'[a]   = c[a] + sigma                   the words of lsa_poly_addsub op 0 on both polynomials
+ *   c'[a+s] = X^(-s) * (c[a] - sigma)        only if a + s < count: lsa_poly_addsub op 1, then lsa_bfv_mul_monomial by -s
+ *                                            (coefficient y lands on (y - s) mod N, negated when y < s)
+ * Output i decrypts to 2^k * sum_u m_(i + 2^k u) X^(2^k u); the full expansion count = N leaves 2^k m_i in the constant coefficient.
+ * The plaintext modulus t is odd, so the caller removes the factor by encrypting m * 2^-k mod t.  The key switches number
+ * sum_j min(2^j, count), the keys are the Galois elements N / 2^j + 1, j < k; count == 1 is a copy and needs no key.
+ * The words are those of the composition above (tests/bfv_expand_model.py), whichever tail runs.
+ * Layout: the output is index-major, output i of batch item b at out + i * s_index + b * sout, s_index >= batch * sout; all levels
+ * work inside the output array, nothing is allocated beyond the context workspace.  `in` (batch stride sin) may be output 0 itself
+ * (same pointer, sin == sout) and otherwise overlaps no output.  On the dense layout (s_index == batch * sout) a level runs as one
+ * batched key switch over its nodes x batch items, otherwise one per node.  Keys must be at the plan's level or above, in any
+ * order and possibly more than needed; batch <= 0 is a no-op.
+ * Errors are LSA_ERR_ARG before anything is queued, with a message that begins with the entry point's name and names the
+ * argument: a CKKS context, a level out of range, count < 1 or count > N, a chain without a special prime when count > 1, a null
+ * pointer, a pointer off the 16-byte grid, an odd or short stride, s_index < batch * sout, a forbidden overlap, a missing key (the
+ * element is named), a key below the plan's level, a plan of another context, lsa_bfv_expand_set_gather(plan, 1) on a ring above
+ * 2^14.  A refused call leaves the buffers untouched and the context usable. */
+typedef struct lsa_bfv_expand_st* lsa_bfv_expand_handle;
+/* host only, needs no device and no context: the levels, the key switches and the Galois elements a run needs a key for (ascending,
+ * distinct).  Any output pointer may be null; LSA_ERR_ARG if `galois_elements` is given and capacity is less. */
+int lsa_bfv_expand_plan(int n_ring, int count, int* n_levels, int* n_keyswitch, uint64_t* galois_elements, int capacity, int* n_galois);
+int lsa_bfv_expand_create(lsa_context ctx, int level, int count, lsa_bfv_expand_handle* out);
+void lsa_bfv_expand_destroy(lsa_bfv_expand_handle plan);
+/* gather: the plan's setting (below); any output pointer may be null */
+int lsa_bfv_expand_info(lsa_bfv_expand_handle plan, int* level, int* count, int* n_levels, int* n_keyswitch, int* n_galois, int* gather);
+int lsa_bfv_expand_galois_elements(lsa_bfv_expand_handle plan, uint64_t* out, int capacity);   /* ascending */
+/* 1 (the default where N <= 2^14): the ModDown tail of a level's key switch stages (acc - conv) / P (+ c0) in LDS, gathers the
+ * rotation from there and writes both children (k_bfv_expand_tail).  0 (the only form above 2^14, and what lsa_set_fuse_tails(0)
+ * runs): the key switch leaves (c0 + ks0, ks1) in the workspace and k_bfv_expand_combine gathers the rotation from global memory.
+ * The same words either way. */
+int lsa_bfv_expand_set_gather(lsa_bfv_expand_handle plan, int enable);
+int lsa_bfv_expand(lsa_context ctx, lsa_bfv_expand_handle plan, const uint64_t* in, long long sin, uint64_t* out, long long sout,
+                   long long s_index, int batch, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
+/* out = X^exponent * in on `polys` (1..3) coefficient-domain polynomials [polys][level+1][N] of a BFV context: the negacyclic shift,
+ * coefficient y lands on (y + e) mod N and is negated when (y + e) mod 2N >= N, e = exponent mod 2N (any exponent).  Batch strides in
+ * words, even, pointers 16-byte aligned; the output overlaps nothing; batch <= 0 is a no-op. */
+int lsa_bfv_mul_monomial(lsa_context ctx, int level, int polys, long long exponent, const uint64_t* in, uint64_t* out, int batch,
+                         long long sin, long long sout, void* stream);
+
 /* ---- BFV slot encoder: `batch` host vectors of N integers in [0, t) -- row 0 of the 2 x N/2 slot matrix, then row 1 -- to device
  * plaintexts, the BFV counterpart of lsa_ckks_encode.  The coefficients are oracle/client.py Client.bfv_encode(values): the values
  * placed through Lattigo's batching index matrix, then the inverse negacyclic transform mod t.  The lift to the chain is the

@@ -161,6 +161,14 @@ SIGNATURES = {
     "lsa_bfv_slot_sum_galois_elements": (c_int, [c_vp, c_u64p, c_int]),
     "lsa_bfv_slot_sum_set_gather": (c_int, [c_vp, c_int]),
     "lsa_bfv_slot_sum": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_ll, c_int, c_u64p, ctypes.POINTER(c_vp), c_vp]),
+    "lsa_bfv_expand_plan": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_u64p, c_int, ctypes.POINTER(c_int)]),
+    "lsa_bfv_expand_create": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp)]),
+    "lsa_bfv_expand_destroy": (None, [c_vp]),
+    "lsa_bfv_expand_info": (c_int, [c_vp] + [ctypes.POINTER(c_int)] * 6),
+    "lsa_bfv_expand_galois_elements": (c_int, [c_vp, c_u64p, c_int]),
+    "lsa_bfv_expand_set_gather": (c_int, [c_vp, c_int]),
+    "lsa_bfv_expand": (c_int, [c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, c_ll, c_int, c_int, c_u64p, ctypes.POINTER(c_vp), c_vp]),
+    "lsa_bfv_mul_monomial": (c_int, [c_vp, c_int, c_int, c_ll, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),
     "lsa_bfv_encode": (c_int, [c_vp, c_int, c_int, c_u64p, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_addsub_plain": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_plain_lift": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),

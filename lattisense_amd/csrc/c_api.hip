@@ -52,8 +52,8 @@ static const Key& K(lsa_key k, const char* who = nullptr) {
 }
 static hipStream_t S(void* s) { return (hipStream_t)s; }
 
-// ---- plan handles.  The operators that work through a plan (bootstrap, the two linear transforms, the two slot sums, the two polynomial
-// evaluators) hand out one kind of handle: the plan with its deleter and the context it was made on.  The public header keeps a
+// ---- plan handles.  The operators that work through a plan (bootstrap, the two linear transforms, the two slot sums, the BFV expansion, the two
+// polynomial evaluators) hand out one kind of handle: the plan with its deleter and the context it was made on.  The public header keeps a
 // distinct opaque type per operator; each derives from PlanHandle.  Every entry point keeps its own message texts.
 template <typename T>
 struct PlanHandle {
@@ -966,6 +966,65 @@ int lsa_bfv_slot_sum(lsa_context ctx, lsa_bfv_slot_sum_handle plan, const uint64
         LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "lsa_bfv_slot_sum: null key argument");
         bfv_slot_sum_run(p, in, sin, out, sout, batch, G(n_keys, galois_elements, keys, "lsa_bfv_slot_sum"), S(stream));
     });
+}
+
+// ---- BFV oblivious expansion (bfv_expand.h, bfv_expand.hip bfv_expand_run)
+struct lsa_bfv_expand_st : PlanHandle<BfvExpand> {};
+static void expand_counts(const BfvExpandPlanHost& p, int* count, int* n_levels, int* n_keyswitch, int* n_galois) {
+    if (count) *count = p.count;
+    if (n_levels) *n_levels = (int)p.levels.size();
+    if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
+    if (n_galois) *n_galois = (int)p.galois.size();
+}
+int lsa_bfv_expand_plan(int n_ring, int count, int* n_levels, int* n_keyswitch, uint64_t* galois_elements, int capacity, int* n_galois) {
+    return guard([&] {
+        const BfvExpandPlanHost p = bfv_expand_plan_checked(n_ring, count);
+        expand_counts(p, nullptr, n_levels, n_keyswitch, n_galois);
+        if (galois_elements)
+            copy_out(p.galois, galois_elements, capacity, "lsa_bfv_expand_plan: capacity: buffer too small for the Galois elements");
+    });
+}
+int lsa_bfv_expand_create(lsa_context ctx, int level, int count, lsa_bfv_expand_handle* out) {
+    return guard([&] {
+        LSA_REQUIRE(out != nullptr, "lsa_bfv_expand_create: null argument");
+        Context& c = C(ctx);
+        make_plan(out, c, bfv_expand_create(c, level, count));
+    });
+}
+void lsa_bfv_expand_destroy(lsa_bfv_expand_handle plan) { delete plan; }
+int lsa_bfv_expand_info(lsa_bfv_expand_handle plan, int* level, int* count, int* n_levels, int* n_keyswitch, int* n_galois, int* gather) {
+    return guard([&] {
+        const BfvExpand& p = P(plan, "lsa_bfv_expand_info: null plan handle");
+        if (level) *level = p.level;
+        expand_counts(p.plan, count, n_levels, n_keyswitch, n_galois);
+        if (gather) *gather = p.gather ? 1 : 0;
+    });
+}
+int lsa_bfv_expand_galois_elements(lsa_bfv_expand_handle plan, uint64_t* out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr && out != nullptr, "lsa_bfv_expand_galois_elements: null argument");
+        copy_out(plan->plan->plan.galois, out, capacity, "lsa_bfv_expand_galois_elements: capacity: buffer too small");
+    });
+}
+int lsa_bfv_expand_set_gather(lsa_bfv_expand_handle plan, int enable) {
+    return guard([&] {
+        BfvExpand& p = P(plan, "lsa_bfv_expand_set_gather: null plan handle");
+        LSA_REQUIRE(!enable || p.c.logn <= LSA_PERM_LDS_MAX_LOGN,
+                    "lsa_bfv_expand_set_gather: enable: the gathering tail stages a limb in LDS and needs N <= 2^14");
+        p.gather = enable != 0;
+    });
+}
+int lsa_bfv_expand(lsa_context ctx, lsa_bfv_expand_handle plan, const uint64_t* in, long long sin, uint64_t* out, long long sout,
+                   long long s_index, int batch, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream) {
+    return guard([&] {
+        BfvExpand& p = P(plan, ctx, "lsa_bfv_expand: null plan handle", "lsa_bfv_expand: the plan belongs to another context");
+        LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "lsa_bfv_expand: null key argument");
+        bfv_expand_run(p, in, sin, out, sout, s_index, batch, G(n_keys, galois_elements, keys, "lsa_bfv_expand"), S(stream));
+    });
+}
+int lsa_bfv_mul_monomial(lsa_context ctx, int level, int polys, long long exponent, const uint64_t* in, uint64_t* out, int batch,
+                         long long sin, long long sout, void* stream) {
+    return guard([&] { bfv_mul_monomial(C(ctx), level, polys, exponent, in, out, batch, sin, sout, S(stream)); });
 }
 
 // ---- CKKS polynomial evaluation (poly_eval.hip)

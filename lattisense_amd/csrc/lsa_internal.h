@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/lattisense_amd.h"
+#include "bfv_expand.h"
 #include "galois_keys.h"
 #include "ntt_plan.h"
 #include "ntt_chunk.h"
@@ -595,6 +596,39 @@ struct BfvSlotTail {
 void launch_bfv_slot_tail(Context& c, int level, const BfvSlotTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
                           const u64* conv, long long sconv, const u64* x, long long sx, u64* out, long long sout, int batch,
                           hipStream_t s);
+// ---- BFV oblivious expansion (bfv_expand.hip: kernels and runner, on key_switch(); plan and point arithmetic: bfv_expand.h;
+// semantics: include/lattisense_amd.h).  gather: the tail of a level's key switch forms both children from the rotation staged in LDS
+// (k_bfv_expand_tail, N <= 2^14, fused tails); else the key switch leaves (c0 + ks0, ks1) in the workspace and
+// k_bfv_expand_combine gathers it from there.  The same words.
+struct BfvExpand {
+    Context& c;
+    int level;
+    BfvExpandPlanHost plan;
+    bool gather;
+    BfvExpand(Context& ctx, int level_) : c(ctx), level(level_), gather(ctx.logn <= LSA_PERM_LDS_MAX_LOGN) {}
+};
+BfvExpandPlanHost bfv_expand_plan_checked(int n_ring, int count);   // bfv_expand_plan, refusals as LSA_ERR_ARG
+BfvExpand* bfv_expand_create(Context& c, int level, int count);
+void bfv_expand_run(BfvExpand& p, const u64* in, long long sin, u64* out, long long sout, long long s_index, int batch,
+                    const GaloisKeys& glk, hipStream_t s);
+// one level's tail over the items of a tile, parent and even [2][L][N] per item (even may be parent), sigma = rotate(parent, g):
+//   even[h][j][y] = parent[h][j][y] + sigma[h][j][y]
+//   odd[h][j][(y - shift) mod N] = +-(parent[h][j][y] - sigma[h][j][y]), odd = even + odd_off, negated when y < shift,
+//   for the items whose index coordinate (item0 + i) / batch is below n_odd
+struct BfvExpandTail {
+    const u32* perm;      // Context::coeff_perm(g)
+    long long odd_off;    // words from an item's even child to its odd child
+    int shift;            // s = 2^j
+    int item0, batch, n_odd;
+};
+void launch_bfv_expand_tail(Context& c, int level, const BfvExpandTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
+                            const u64* conv, long long sconv, const u64* parent, long long sparent, u64* even, long long seven, int nb,
+                            hipStream_t s);
+void launch_bfv_expand_combine(Context& c, int level, const BfvExpandTail& t, const u64* sigma, long long ssigma, const u64* parent,
+                               long long sparent, u64* even, long long seven, int nb, hipStream_t s);
+// out = X^exponent * in on `polys` coefficient-domain polynomials (k_mul_monomial); the output overlaps nothing
+void bfv_mul_monomial(Context& c, int level, int polys, long long exponent, const u64* in, u64* out, int batch, long long sin,
+                      long long sout, hipStream_t s);
 // ---- (ops.hip again)
 void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                 hipStream_t s);

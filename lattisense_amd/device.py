@@ -346,6 +346,14 @@ class DeviceContext:
                                    self.stream))
         return out
 
+    def bfv_mul_monomial(self, level, ct, exponent, batch, polys=2, out=None):
+        """X^exponent * ct on `polys` coefficient-domain polynomials (the negacyclic shift); any exponent"""
+        words = polys * (level + 1) * self.n
+        if out is None:
+            out = self.alloc(max(batch, 1) * words)
+        check(lib().lsa_bfv_mul_monomial(self.h, level, polys, int(exponent), ct.ptr, out.ptr, batch, words, words, self.stream))
+        return out
+
     def bfv_rotate_many(self, level, ct, keys, batch):
         """keys: {galois element: key handle}; returns {element: device buffer}, one decomposition for all (hoisted), each
         output bit-identical to bfv_rotate's"""
@@ -847,6 +855,63 @@ class BfvSlotSumPlan(_Plan):
         if out is None:
             out = self.ctx.alloc(max(batch, 1) * words)
         check(lib().lsa_bfv_slot_sum(self.ctx.h, h, in_buf.ptr, out.ptr, batch, words, words, *_key_arrays(glk), self.ctx.stream))
+        return out
+
+
+def bfv_expand_plan(n, count):
+    """{levels, keyswitches, galois_elements} of the BFV oblivious expansion of one ciphertext into `count` -- host only
+    (include/lattisense_amd.h: lsa_bfv_expand_plan); elements ascending."""
+    nl, nk, cnt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    args = (int(n), int(count), ctypes.byref(nl), ctypes.byref(nk))
+    check(lib().lsa_bfv_expand_plan(*args, None, 0, ctypes.byref(cnt)))
+    g = _fetch(ctypes.c_uint64, cnt.value, lambda a, m: lib().lsa_bfv_expand_plan(*args, a, m, None))
+    return {"levels": nl.value, "keyswitches": nk.value, "galois_elements": g}
+
+
+class BfvExpandPlan(_Plan):
+    """One coefficient-domain BFV ciphertext at `level` expanded into `count`: output i holds 2^levels * m_i in its low
+    coefficients (include/lattisense_amd.h: lsa_bfv_expand_*).  Planning needs no GPU (`.galois_elements`, `.levels`,
+    `.keyswitches`); the device plan is made by the first run.  gather: None = the library's default, else the tail to run."""
+    _destroy = "lsa_bfv_expand_destroy"
+
+    def __init__(self, ctx, level, count):
+        self.ctx, self.level, self.count = ctx, int(level), int(count)
+        self.h = None
+        self.gather = None
+        info = bfv_expand_plan(ctx.n, count)
+        self.levels, self.keyswitches, self.galois_elements = info["levels"], info["keyswitches"], info["galois_elements"]
+
+    def _handle(self):
+        if self.h is None:
+            self._adopt(lambda h: lib().lsa_bfv_expand_create(self.ctx.h, self.level, self.count, h))
+            ng = ctypes.c_int()
+            check(lib().lsa_bfv_expand_info(self.h, None, None, None, None, ctypes.byref(ng), None))
+            assert _fetch(ctypes.c_uint64, ng.value, lambda a, n: lib().lsa_bfv_expand_galois_elements(self.h, a, n)) == self.galois_elements
+        return self.h
+
+    def gather_in_force(self):
+        ga = ctypes.c_int()
+        check(lib().lsa_bfv_expand_info(self._handle(), None, None, None, None, None, ctypes.byref(ga)))
+        return bool(ga.value)
+
+    def set_gather(self, enable):
+        check(lib().lsa_bfv_expand_set_gather(self._handle(), int(bool(enable))))
+        self.gather = bool(enable)
+
+    def run(self, in_buf, batch, glk, out=None, s_index=None):
+        """in_buf: device [batch][2][level+1][N], coefficient domain; glk: {galois element: key handle}; returns the device
+        outputs, output i of item b at i * s_index + b * words (s_index: None = dense, batch * words).  out may start with
+        in_buf's words (in is output 0)."""
+        h = self._handle()
+        words = 2 * (self.level + 1) * self.ctx.n
+        if s_index is None:
+            s_index = max(batch, 1) * words
+        if self.gather is not None:
+            check(lib().lsa_bfv_expand_set_gather(h, int(bool(self.gather))))
+        if out is None:
+            out = self.ctx.alloc((self.count - 1) * s_index + max(batch, 1) * words)
+        check(lib().lsa_bfv_expand(self.ctx.h, h, in_buf.ptr, words, out.ptr, words, int(s_index), batch, *_key_arrays(glk),
+                                   self.ctx.stream))
         return out
 
 
