@@ -522,6 +522,56 @@ int lsa_bfv_expand(lsa_context ctx, lsa_bfv_expand_handle plan, const uint64_t* 
 int lsa_bfv_mul_monomial(lsa_context ctx, int level, int polys, long long exponent, const uint64_t* in, uint64_t* out, int batch,
                          long long sin, long long sout, void* stream);
 
+/* ---- BFV coefficient packing (PackLWEs of Chen, Dai, Kim, Song, "Efficient homomorphic conversion between (Ring) LWE
+ * ciphertexts", Alg. 3 plus the field trace; Lattigo's rlwe.Pack), the expansion run backwards: `count` coefficient-domain
+ * ciphertexts c[i], each [2][level+1][N], 1 <= count <= N, become one.  Let k = ceil(log2 count).  Levels run j = k-1 down to 0;
+ * with l = k - j a level has the shift s = N / 2^l and the Galois element g = 2^l + 1; for every node a < 2^j:
+ *   paired (a + 2^j < count):   xb = X^s * c[a + 2^j]           the words of lsa_bfv_mul_monomial by +s
+ *                               u  = c[a] + xb,  v = c[a] - xb   lsa_poly_addsub op 0 / op 1 on both polynomials
+ *   unpaired:                   u  = v = c[a]
+ *   c'[a] = u + rotate(v, g)                                     lsa_bfv_rotate, then lsa_poly_addsub op 0
+ * Only the first level (j = k-1) can have unpaired nodes; its paired nodes are a < count - 2^(k-1).  With trace != 0 the levels
+ * l = k+1 .. log2 N follow on c[0] alone: c[0] <- c[0] + rotate(c[0], 2^l + 1).  The result is c[0].  It decrypts to a polynomial
+ * whose coefficient i * N/2^k is F * (coefficient 0 of input i) for i < count, F = 2^k without the trace and F = N with it.  With
+ * the trace every other coefficient is 0, the positions i * N/2^k with i >= count among them; without it the other coefficients
+ * are unspecified mixtures (zero if the inputs were zero there).  t is odd, so the caller removes F by scaling by F^-1 mod t.  The
+ * key switches number (2^k - 1) + (trace ? log2 N - k : 0), the keys are the Galois elements 2^l + 1 for l = 1 .. k, or
+ * l = 1 .. log2 N with the trace; count == 1 without the trace is a copy and needs no key.
+ * The words are those of the composition above (tests/bfv_pack_model.py), whichever tail runs.
+ * Layout: the inputs are index-major, as the expansion's outputs are: input i of batch item b at in + i * s_index + b * sin,
+ * s_index >= batch * sin.  All levels but the last work inside the input array, so `in` is not const and the inputs count as
+ * consumed; unchanged are the inputs i >= max(1, 2^(k-1)), which are only ever read, and every word of the array that is not part
+ * of an input.  The last level (j = 0, or the last trace level) writes `out` with batch stride sout; `out` may be input 0 itself
+ * (same pointer, sout == sin) and otherwise overlaps no input.  On the dense layout (s_index == batch * sin) a level runs as one
+ * batched key switch over its nodes x batch items, otherwise one per node; nothing is allocated beyond the context workspace.  Keys
+ * must be at the plan's level or above, in any order and possibly more than needed; batch <= 0 is a no-op.
+ * Errors are LSA_ERR_ARG before anything is queued, with a message that begins with the entry point's name and names the
+ * argument: a CKKS context, a level out of range, count < 1 or count > N, a ring below N = 512 when count > 1, a chain without a
+ * special prime when a key switch is needed, a null pointer, a pointer off the 16-byte grid, an odd or short stride,
+ * s_index < batch * sin, a forbidden overlap, a missing key (the element is named), a key below the plan's level, a plan of another
+ * context, lsa_bfv_pack_set_gather(plan, 1) on a ring above 2^14.  A refused call leaves the buffers untouched and the context
+ * usable. */
+typedef struct lsa_bfv_pack_st* lsa_bfv_pack_handle;
+/* host only, needs no device and no context: the tree levels (k), the trace levels, the key switches and the Galois elements a run
+ * needs a key for (ascending, distinct).  Any output pointer may be null; LSA_ERR_ARG if `galois_elements` is given and capacity
+ * is less. */
+int lsa_bfv_pack_plan(int n_ring, int count, int trace, int* n_levels, int* n_trace_levels, int* n_keyswitch, uint64_t* galois_elements,
+                      int capacity, int* n_galois);
+int lsa_bfv_pack_create(lsa_context ctx, int level, int count, int trace, lsa_bfv_pack_handle* out);
+void lsa_bfv_pack_destroy(lsa_bfv_pack_handle plan);
+/* gather: the plan's setting (below); any output pointer may be null */
+int lsa_bfv_pack_info(lsa_bfv_pack_handle plan, int* level, int* count, int* trace, int* n_levels, int* n_trace_levels, int* n_keyswitch,
+                      int* n_galois, int* gather);
+int lsa_bfv_pack_galois_elements(lsa_bfv_pack_handle plan, uint64_t* out, int capacity);   /* ascending */
+/* 1 (the default where N <= 2^14): a paired level's head k_bfv_pack_diff writes v1 = a1 - X^s b1 as the key switch's source, and
+ * the ModDown tail stages (acc - conv) / P (+ a0 - X^s b0) in LDS, gathers the rotation from there and adds u = a + X^s b
+ * (k_bfv_pack_tail).  0 (the only form above 2^14, and what lsa_set_fuse_tails(0) runs): the head writes the whole v, the key
+ * switch leaves (v0 + ks0, ks1) in the workspace and k_bfv_pack_combine gathers the rotation from global memory.  The same words
+ * either way. */
+int lsa_bfv_pack_set_gather(lsa_bfv_pack_handle plan, int enable);
+int lsa_bfv_pack(lsa_context ctx, lsa_bfv_pack_handle plan, uint64_t* in, long long sin, long long s_index, uint64_t* out, long long sout,
+                 int batch, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
+
 /* ---- BFV slot encoder: `batch` host vectors of N integers in [0, t) -- row 0 of the 2 x N/2 slot matrix, then row 1 -- to device
  * plaintexts, the BFV counterpart of lsa_ckks_encode.  The coefficients are oracle/client.py Client.bfv_encode(values): the values
  * placed through Lattigo's batching index matrix, then the inverse negacyclic transform mod t.  The lift to the chain is the

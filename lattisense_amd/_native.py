@@ -169,6 +169,14 @@ SIGNATURES = {
     "lsa_bfv_expand_set_gather": (c_int, [c_vp, c_int]),
     "lsa_bfv_expand": (c_int, [c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, c_ll, c_int, c_int, c_u64p, ctypes.POINTER(c_vp), c_vp]),
     "lsa_bfv_mul_monomial": (c_int, [c_vp, c_int, c_int, c_ll, c_vp, c_vp, c_int, c_ll, c_ll, c_vp]),
+    "lsa_bfv_pack_plan": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_u64p, c_int,
+                                  ctypes.POINTER(c_int)]),
+    "lsa_bfv_pack_create": (c_int, [c_vp, c_int, c_int, c_int, ctypes.POINTER(c_vp)]),
+    "lsa_bfv_pack_destroy": (None, [c_vp]),
+    "lsa_bfv_pack_info": (c_int, [c_vp] + [ctypes.POINTER(c_int)] * 8),
+    "lsa_bfv_pack_galois_elements": (c_int, [c_vp, c_u64p, c_int]),
+    "lsa_bfv_pack_set_gather": (c_int, [c_vp, c_int]),
+    "lsa_bfv_pack": (c_int, [c_vp, c_vp, c_vp, c_ll, c_ll, c_vp, c_ll, c_int, c_int, c_u64p, ctypes.POINTER(c_vp), c_vp]),
     "lsa_bfv_encode": (c_int, [c_vp, c_int, c_int, c_u64p, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_addsub_plain": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_plain_lift": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),

@@ -52,7 +52,7 @@ static const Key& K(lsa_key k, const char* who = nullptr) {
 }
 static hipStream_t S(void* s) { return (hipStream_t)s; }
 
-// ---- plan handles.  The operators that work through a plan (bootstrap, the two linear transforms, the two slot sums, the BFV expansion, the two
+// ---- plan handles.  The operators that work through a plan (bootstrap, the two linear transforms, the two slot sums, the BFV expansion and packing, the two
 // polynomial evaluators) hand out one kind of handle: the plan with its deleter and the context it was made on.  The public header keeps a
 // distinct opaque type per operator; each derives from PlanHandle.  Every entry point keeps its own message texts.
 template <typename T>
@@ -1025,6 +1025,65 @@ int lsa_bfv_expand(lsa_context ctx, lsa_bfv_expand_handle plan, const uint64_t* 
 int lsa_bfv_mul_monomial(lsa_context ctx, int level, int polys, long long exponent, const uint64_t* in, uint64_t* out, int batch,
                          long long sin, long long sout, void* stream) {
     return guard([&] { bfv_mul_monomial(C(ctx), level, polys, exponent, in, out, batch, sin, sout, S(stream)); });
+}
+
+// ---- BFV coefficient packing (bfv_pack.h, bfv_pack.hip bfv_pack_run)
+struct lsa_bfv_pack_st : PlanHandle<BfvPack> {};
+static void pack_counts(const BfvPackPlanHost& p, int* count, int* trace, int* n_levels, int* n_trace_levels, int* n_keyswitch, int* n_galois) {
+    if (count) *count = p.count;
+    if (trace) *trace = p.trace;
+    if (n_levels) *n_levels = (int)p.levels.size();
+    if (n_trace_levels) *n_trace_levels = (int)p.trace_g.size();
+    if (n_keyswitch) *n_keyswitch = p.n_keyswitch;
+    if (n_galois) *n_galois = (int)p.galois.size();
+}
+int lsa_bfv_pack_plan(int n_ring, int count, int trace, int* n_levels, int* n_trace_levels, int* n_keyswitch, uint64_t* galois_elements,
+                      int capacity, int* n_galois) {
+    return guard([&] {
+        const BfvPackPlanHost p = bfv_pack_plan_checked(n_ring, count, trace);
+        pack_counts(p, nullptr, nullptr, n_levels, n_trace_levels, n_keyswitch, n_galois);
+        if (galois_elements)
+            copy_out(p.galois, galois_elements, capacity, "lsa_bfv_pack_plan: capacity: buffer too small for the Galois elements");
+    });
+}
+int lsa_bfv_pack_create(lsa_context ctx, int level, int count, int trace, lsa_bfv_pack_handle* out) {
+    return guard([&] {
+        LSA_REQUIRE(out != nullptr, "lsa_bfv_pack_create: null argument");
+        Context& c = C(ctx);
+        make_plan(out, c, bfv_pack_create(c, level, count, trace));
+    });
+}
+void lsa_bfv_pack_destroy(lsa_bfv_pack_handle plan) { delete plan; }
+int lsa_bfv_pack_info(lsa_bfv_pack_handle plan, int* level, int* count, int* trace, int* n_levels, int* n_trace_levels, int* n_keyswitch,
+                      int* n_galois, int* gather) {
+    return guard([&] {
+        const BfvPack& p = P(plan, "lsa_bfv_pack_info: null plan handle");
+        if (level) *level = p.level;
+        pack_counts(p.plan, count, trace, n_levels, n_trace_levels, n_keyswitch, n_galois);
+        if (gather) *gather = p.gather ? 1 : 0;
+    });
+}
+int lsa_bfv_pack_galois_elements(lsa_bfv_pack_handle plan, uint64_t* out, int capacity) {
+    return guard([&] {
+        LSA_REQUIRE(plan != nullptr && out != nullptr, "lsa_bfv_pack_galois_elements: null argument");
+        copy_out(plan->plan->plan.galois, out, capacity, "lsa_bfv_pack_galois_elements: capacity: buffer too small");
+    });
+}
+int lsa_bfv_pack_set_gather(lsa_bfv_pack_handle plan, int enable) {
+    return guard([&] {
+        BfvPack& p = P(plan, "lsa_bfv_pack_set_gather: null plan handle");
+        LSA_REQUIRE(!enable || p.c.logn <= LSA_PERM_LDS_MAX_LOGN,
+                    "lsa_bfv_pack_set_gather: enable: the gathering tail stages a limb in LDS and needs N <= 2^14");
+        p.gather = enable != 0;
+    });
+}
+int lsa_bfv_pack(lsa_context ctx, lsa_bfv_pack_handle plan, uint64_t* in, long long sin, long long s_index, uint64_t* out, long long sout,
+                 int batch, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream) {
+    return guard([&] {
+        BfvPack& p = P(plan, ctx, "lsa_bfv_pack: null plan handle", "lsa_bfv_pack: the plan belongs to another context");
+        LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "lsa_bfv_pack: null key argument");
+        bfv_pack_run(p, in, sin, s_index, out, sout, batch, G(n_keys, galois_elements, keys, "lsa_bfv_pack"), S(stream));
+    });
 }
 
 // ---- CKKS polynomial evaluation (poly_eval.hip)

@@ -1,7 +1,7 @@
 // key_switch.h — the key switch and what every operator that key-switches shares: the tile (KsTile), its sources and outputs, the
 // rescale that follows a relinearisation, the rotations' index maps and the tiling of a batch (key_switch.hip).
 //   key-switch = per-digit exact ModUp (DecomposeSingleNTT) + gadget MAC + centred ModDown (ModDownQPtoQNTT)
-// Callers: ops.hip (relinearisation, rotations, extended rotations, the BFV forms), slot_sum.hip (both slot sums), bfv_expand.hip.  Nothing outside
+// Callers: ops.hip (relinearisation, rotations, extended rotations, the BFV forms), slot_sum.hip (both slot sums), bfv_expand.hip, bfv_pack.hip.  Nothing outside
 // key_switch.hip launches a key MAC or a ModDown itself.
 #pragma once
 #include <algorithm>
@@ -43,6 +43,8 @@ struct RotMacTerm {   // the pt_mul factor of one rotate-and-MAC term (fz_epi = 
 //            (k_bfv_slot_tail)
 //            expand_tail (base = the parent, polynomial 0): one level of the BFV expansion, the rotation gathered by the tail and
 //            both children written (k_bfv_expand_tail); p is the even child and may be the parent
+//            pack_tail (base = the node a, polynomial 0): one level of the BFV packing, a - X^s b0 joining polynomial 0, the
+//            rotation gathered by the tail and added to a + X^s b (k_bfv_pack_tail); p may be a
 struct KsOut {
     enum Form { NTT, RESCALE, COEFF };
     u64* p;
@@ -57,6 +59,7 @@ struct KsOut {
     const RotMacTerm* rmac = nullptr;
     const BfvSlotTail* slot_tail = nullptr;
     const BfvExpandTail* expand_tail = nullptr;
+    const BfvPackTail* pack_tail = nullptr;
 };
 // the two recurring shapes: the switched polynomial pair added onto c0 of a ciphertext ct [2][L][N] (a rotation, a generic switch),
 // or onto both polynomials of one (a relinearisation's (d0, d1), a slot sum's x).  `o`: the fields beyond p, sp and base

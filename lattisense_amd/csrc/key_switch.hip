@@ -48,6 +48,8 @@ static void ks_moddown_head(Context& c, int level, u64* acc, long long s_acc, u6
                 "slot-sum ModDown tail: coefficient-domain output on a whole ciphertext");
     LSA_REQUIRE(!o.expand_tail || (o.form == KsOut::COEFF && !o.coeff_gather && !o.slot_tail && o.base && o.base_polys == 1 && o.base_rpp == level + 1),
                 "expansion ModDown tail: coefficient-domain output onto c0 of the parent");
+    LSA_REQUIRE(!o.pack_tail || (o.form == KsOut::COEFF && !o.coeff_gather && !o.slot_tail && !o.expand_tail && o.base && o.base_polys == 1 && o.base_rpp == level + 1),
+                "packing ModDown tail: coefficient-domain output onto c0 of the node");
     LSA_REQUIRE(o.form != KsOut::RESCALE || (c.fuse_tails && level >= 1 && ((o.base && o.base_polys == 2) || (!o.base && o.base_polys == 0))),
                 "merged ModDown+rescale: unsupported shape");
     const bool coeff_out = o.form == KsOut::COEFF, rs = o.form == KsOut::RESCALE;
@@ -109,6 +111,8 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
     if (coeff_out) {
         if (o.expand_tail)
             launch_bfv_expand_tail(c, level, *o.expand_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
+        else if (o.pack_tail)
+            launch_bfv_pack_tail(c, level, *o.pack_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
         else if (o.slot_tail)
             launch_bfv_slot_tail(c, level, *o.slot_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
         else if (o.coeff_gather)

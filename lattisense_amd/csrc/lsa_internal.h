@@ -11,6 +11,7 @@
 
 #include "../../include/lattisense_amd.h"
 #include "bfv_expand.h"
+#include "bfv_pack.h"
 #include "galois_keys.h"
 #include "ntt_plan.h"
 #include "ntt_chunk.h"
@@ -629,6 +630,32 @@ void launch_bfv_expand_combine(Context& c, int level, const BfvExpandTail& t, co
 // out = X^exponent * in on `polys` coefficient-domain polynomials (k_mul_monomial); the output overlaps nothing
 void bfv_mul_monomial(Context& c, int level, int polys, long long exponent, const u64* in, u64* out, int batch, long long sin,
                       long long sout, hipStream_t s);
+// ---- BFV coefficient packing (bfv_pack.hip: kernels and runner, on key_switch(); plan and point arithmetic: bfv_pack.h; semantics:
+// include/lattisense_amd.h).  gather: the tail of a level's key switch adds the rotation staged in LDS to u = a + X^s b
+// (k_bfv_pack_tail, N <= 2^14, fused tails); else the key switch leaves (v0 + ks0, ks1) in the workspace and k_bfv_pack_combine
+// gathers it from there.  The same words.
+struct BfvPack {
+    Context& c;
+    int level;
+    BfvPackPlanHost plan;
+    bool gather;
+    BfvPack(Context& ctx, int level_) : c(ctx), level(level_), gather(ctx.logn <= LSA_PERM_LDS_MAX_LOGN) {}
+};
+BfvPackPlanHost bfv_pack_plan_checked(int n_ring, int count, int trace);   // bfv_pack_plan, refusals as LSA_ERR_ARG
+BfvPack* bfv_pack_create(Context& c, int level, int count, int trace);
+void bfv_pack_run(BfvPack& p, u64* in, long long sin, long long s_index, u64* out, long long sout, int batch, const GaloisKeys& glk,
+                  hipStream_t s);
+// one level's tail over the items of a tile, a and out [2][L][N] per item (out may be a), b = a + b_off the partner:
+//   xb[h][j][x] = +-b[h][j][(x - shift) mod N], negated when x < shift (0 where the node has no partner),
+//   out = (a + xb) + rotate(a - xb, g), for the items whose index coordinate (item0 + i) / batch is below n_pair
+struct BfvPackTail {
+    const u32* perm;      // Context::coeff_perm(g)
+    long long b_off;      // words from an item's a to its partner
+    int shift;            // s = N / 2^l
+    int item0, batch, n_pair;
+};
+void launch_bfv_pack_tail(Context& c, int level, const BfvPackTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
+                          const u64* conv, long long sconv, const u64* a, long long sa, u64* out, long long sout, int nb, hipStream_t s);
 // ---- (ops.hip again)
 void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                 hipStream_t s);

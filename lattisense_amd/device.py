@@ -915,6 +915,64 @@ class BfvExpandPlan(_Plan):
         return out
 
 
+def bfv_pack_plan(n, count, trace=False):
+    """{levels, trace_levels, keyswitches, galois_elements} of the BFV coefficient packing of `count` ciphertexts into one -- host
+    only (include/lattisense_amd.h: lsa_bfv_pack_plan); elements ascending."""
+    nl, nt, nk, cnt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    args = (int(n), int(count), int(bool(trace)), ctypes.byref(nl), ctypes.byref(nt), ctypes.byref(nk))
+    check(lib().lsa_bfv_pack_plan(*args, None, 0, ctypes.byref(cnt)))
+    g = _fetch(ctypes.c_uint64, cnt.value, lambda a, m: lib().lsa_bfv_pack_plan(*args, a, m, None))
+    return {"levels": nl.value, "trace_levels": nt.value, "keyswitches": nk.value, "galois_elements": g}
+
+
+class BfvPackPlan(_Plan):
+    """`count` coefficient-domain BFV ciphertexts at `level` packed into one: coefficient i * N / 2^levels of the result holds
+    F * (coefficient 0 of input i), F = 2^levels, or N with the trace, which also clears every other coefficient
+    (include/lattisense_amd.h: lsa_bfv_pack_*).  Planning needs no GPU (`.galois_elements`, `.levels`, `.trace_levels`,
+    `.keyswitches`); the device plan is made by the first run.  gather: None = the library's default, else the tail to run."""
+    _destroy = "lsa_bfv_pack_destroy"
+
+    def __init__(self, ctx, level, count, trace=False):
+        self.ctx, self.level, self.count, self.trace = ctx, int(level), int(count), bool(trace)
+        self.h = None
+        self.gather = None
+        info = bfv_pack_plan(ctx.n, count, trace)
+        self.levels, self.trace_levels = info["levels"], info["trace_levels"]
+        self.keyswitches, self.galois_elements = info["keyswitches"], info["galois_elements"]
+
+    def _handle(self):
+        if self.h is None:
+            self._adopt(lambda h: lib().lsa_bfv_pack_create(self.ctx.h, self.level, self.count, int(self.trace), h))
+            ng = ctypes.c_int()
+            check(lib().lsa_bfv_pack_info(self.h, None, None, None, None, None, None, ctypes.byref(ng), None))
+            assert _fetch(ctypes.c_uint64, ng.value, lambda a, n: lib().lsa_bfv_pack_galois_elements(self.h, a, n)) == self.galois_elements
+        return self.h
+
+    def gather_in_force(self):
+        ga = ctypes.c_int()
+        check(lib().lsa_bfv_pack_info(self._handle(), None, None, None, None, None, None, None, ctypes.byref(ga)))
+        return bool(ga.value)
+
+    def set_gather(self, enable):
+        check(lib().lsa_bfv_pack_set_gather(self._handle(), int(bool(enable))))
+        self.gather = bool(enable)
+
+    def run(self, in_buf, batch, glk, out=None, s_index=None):
+        """in_buf: the device inputs, input i of item b at i * s_index + b * words, each [2][level+1][N] in the coefficient domain
+        (s_index: None = dense, batch * words); they are consumed.  glk: {galois element: key handle}.  Returns the device result
+        [batch][2][level+1][N]; out may be in_buf (the result takes the place of input 0)."""
+        h = self._handle()
+        words = 2 * (self.level + 1) * self.ctx.n
+        if s_index is None:
+            s_index = max(batch, 1) * words
+        if self.gather is not None:
+            check(lib().lsa_bfv_pack_set_gather(h, int(bool(self.gather))))
+        if out is None:
+            out = self.ctx.alloc(max(batch, 1) * words)
+        check(lib().lsa_bfv_pack(self.ctx.h, h, in_buf.ptr, words, int(s_index), out.ptr, words, batch, *_key_arrays(glk), self.ctx.stream))
+        return out
+
+
 BASES = {"chebyshev": 0, "monomial": 1}
 
 
