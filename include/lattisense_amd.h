@@ -572,6 +572,50 @@ int lsa_bfv_pack_set_gather(lsa_bfv_pack_handle plan, int enable);
 int lsa_bfv_pack(lsa_context ctx, lsa_bfv_pack_handle plan, uint64_t* in, long long sin, long long s_index, uint64_t* out, long long sout,
                  int batch, int n_keys, const uint64_t* galois_elements, const lsa_key* keys, void* stream);
 
+/* ---- BFV external product RLWE x RGSW, CMux and select by an encrypted index: the "compute" between lsa_bfv_expand and lsa_bfv_pack
+ * in the schemes they were taken from (OnionPIR, Spiral, RGSW selectors, blind rotation).  Noise growth is additive and there is no
+ * scale-down.
+ *   RGSW ciphertext.  An RGSW ciphertext of a small polynomial m under the secret s is a pair of switching keys (R0, R1) in the layout
+ *     lsa_key_upload takes ([beta][2][klvl+1+np][N], NTT domain) and uploaded with it: R0 is what oracle/client.py
+ *     Client.gen_switching_key(s_in = m, s_out = s, klvl) makes (its rows encrypt P * m on the limbs of digit d), R1 is
+ *     gen_switching_key(s_in = m * s, s_out = s, klvl); m is given as its NTT per modulus of Q u P, as Client.s_ntt is.
+ *   External product.  ct is a coefficient-domain ciphertext [2][level+1][N]:
+ *       acc = gadget_product(NTT(ct[0]), R0) + gadget_product(NTT(ct[1]), R1)     over Q_level u P, limb by limb, canonical
+ *       out = INTT(moddown(acc)) (+ base on both polynomials)
+ *     In oracle/pyoracle.py: Oracle.gadget_product twice, Oracle.vec("add") on every one of the level+1+np rows of both polynomials,
+ *     Oracle.moddown (tests/rgsw_model.py).  ONE ModDown: two key switches and an add would round differently.  out decrypts to
+ *     m * plaintext(ct) (+ plaintext(base)).  The tail reads base only at the points it writes: out may be base, or ct, itself.
+ *   CMux.  lsa_bfv_cmux(c0, c1, R) = c0 + R [.] (c1 - c0): the difference is the words of lsa_poly_addsub op 1 on both polynomials,
+ *     the sum is the ModDown tail's base.  R encrypts 0: c0 (plus noise); 1: c1.  out may be c0 or c1 itself.
+ *   Select.  count >= 1 index-major inputs laid out as for lsa_bfv_pack: input i of item b at in + i * s_index + b * sin.  Let
+ *     k = ceil(log2 count); the selectors R_0 .. R_{k-1} are RGSW ciphertexts, R_j of bit j of the index.  Levels run j = k-1 down to
+ *     0; at level j every node a < 2^j that has a partner (a + 2^j < count) becomes c'[a] = cmux(c[a], c[a + 2^j], R_j); unpaired
+ *     nodes are left alone.  The result is c[0]: it decrypts to input idx for every idx < count.  count == 1 is a copy and takes no
+ *     selector.  count - 1 external products.  All levels but the last work inside the input array (`in` is not const; the inputs
+ *     i >= max(1, 2^(k-1)) are only read); the last level writes `out`, which may be input 0 (same pointer, sout == sin) and otherwise
+ *     overlaps no input.
+ * Errors are LSA_ERR_ARG before anything is queued, with a message that begins with the entry point's name and names the argument: a
+ * CKKS context, a level out of range, a chain without a special prime, N < 512, a null pointer or key, a pointer off the 16-byte
+ * grid, an odd or short stride, s_index < batch * sin, a forbidden overlap (out may equal ct, base, c0 or c1 exactly; partial overlap
+ * is refused), a key below the level, n_sel < k, a plan of another context.  A refused call leaves the buffers untouched and the
+ * context usable.  batch <= 0 is a no-op. */
+/* 1 (default): both gadget products of an external product run as one launch into one accumulator (k_ks_mac_pair); 0: two key MAC
+ * launches, the second adding to the first's output (A/B measurement and parity; identical results).  Read by every call. */
+int lsa_set_rgsw_pair_mac(lsa_context ctx, int enable);
+int lsa_bfv_external_product(lsa_context ctx, int level, const uint64_t* ct, long long sct, lsa_key r0, lsa_key r1,
+                             const uint64_t* base /* may be null */, long long sbase, uint64_t* out, long long sout, int batch, void* stream);
+int lsa_bfv_cmux(lsa_context ctx, int level, const uint64_t* c0, long long s0, const uint64_t* c1, long long s1, lsa_key r0, lsa_key r1,
+                 uint64_t* out, long long sout, int batch, void* stream);
+typedef struct lsa_bfv_select_st* lsa_bfv_select_handle;
+/* host only, needs no device and no context: the levels (k) and the external products (count - 1); any output pointer may be null */
+int lsa_bfv_select_plan(int count, int* n_levels, int* n_products);
+int lsa_bfv_select_create(lsa_context ctx, int level, int count, lsa_bfv_select_handle* out);
+void lsa_bfv_select_destroy(lsa_bfv_select_handle plan);
+int lsa_bfv_select_info(lsa_bfv_select_handle plan, int* level, int* count, int* n_levels, int* n_products);
+/* r0s[j], r1s[j], j < n_sel: the selector of index bit j; n_sel >= k, the entries from k on are not read */
+int lsa_bfv_select(lsa_context ctx, lsa_bfv_select_handle plan, uint64_t* in, long long sin, long long s_index, uint64_t* out, long long sout,
+                   int batch, int n_sel, const lsa_key* r0s, const lsa_key* r1s, void* stream);
+
 /* ---- BFV slot encoder: `batch` host vectors of N integers in [0, t) -- row 0 of the 2 x N/2 slot matrix, then row 1 -- to device
  * plaintexts, the BFV counterpart of lsa_ckks_encode.  The coefficients are oracle/client.py Client.bfv_encode(values): the values
  * placed through Lattigo's batching index matrix, then the inverse negacyclic transform mod t.  The lift to the chain is the

@@ -177,6 +177,14 @@ SIGNATURES = {
     "lsa_bfv_pack_galois_elements": (c_int, [c_vp, c_u64p, c_int]),
     "lsa_bfv_pack_set_gather": (c_int, [c_vp, c_int]),
     "lsa_bfv_pack": (c_int, [c_vp, c_vp, c_vp, c_ll, c_ll, c_vp, c_ll, c_int, c_int, c_u64p, ctypes.POINTER(c_vp), c_vp]),
+    "lsa_set_rgsw_pair_mac": (c_int, [c_vp, c_int]),
+    "lsa_bfv_external_product": (c_int, [c_vp, c_int, c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
+    "lsa_bfv_cmux": (c_int, [c_vp, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_int, c_vp]),
+    "lsa_bfv_select_plan": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "lsa_bfv_select_create": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp)]),
+    "lsa_bfv_select_destroy": (None, [c_vp]),
+    "lsa_bfv_select_info": (c_int, [c_vp] + [ctypes.POINTER(c_int)] * 4),
+    "lsa_bfv_select": (c_int, [c_vp, c_vp, c_vp, c_ll, c_ll, c_vp, c_ll, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "lsa_bfv_encode": (c_int, [c_vp, c_int, c_int, c_u64p, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_addsub_plain": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_plain_lift": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),

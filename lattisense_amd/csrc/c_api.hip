@@ -480,6 +480,9 @@ int lsa_set_fuse_tails(lsa_context ctx, int enable) {
 int lsa_set_modup_lift(lsa_context ctx, int enable) {
     return guard([&] { C(ctx).modup_lift = enable ? 1 : 0; });
 }
+int lsa_set_rgsw_pair_mac(lsa_context ctx, int enable) {
+    return guard([&] { C(ctx).rgsw_pair_mac = enable ? 1 : 0; });
+}
 int lsa_set_ks_tail_in_mac(lsa_context ctx, int mode) {
     return guard([&] {
         LSA_REQUIRE(mode >= 0 && mode <= 2, "lsa_set_ks_tail_in_mac: mode is 0, 1 or 2");
@@ -1083,6 +1086,52 @@ int lsa_bfv_pack(lsa_context ctx, lsa_bfv_pack_handle plan, uint64_t* in, long l
         BfvPack& p = P(plan, ctx, "lsa_bfv_pack: null plan handle", "lsa_bfv_pack: the plan belongs to another context");
         LSA_REQUIRE(n_keys >= 0 && (n_keys == 0 || (galois_elements && keys)), "lsa_bfv_pack: null key argument");
         bfv_pack_run(p, in, sin, s_index, out, sout, batch, G(n_keys, galois_elements, keys, "lsa_bfv_pack"), S(stream));
+    });
+}
+
+// ---- BFV external product, CMux and select by an encrypted index (bfv_select.h, bfv_select.hip)
+struct lsa_bfv_select_st : PlanHandle<BfvSelect> {};
+static const Key* KP(lsa_key k) { return k != nullptr && k->key.data != nullptr ? &k->key : nullptr; }   // null: the runner names the argument
+int lsa_bfv_external_product(lsa_context ctx, int level, const uint64_t* ct, long long sct, lsa_key r0, lsa_key r1, const uint64_t* base,
+                             long long sbase, uint64_t* out, long long sout, int batch, void* stream) {
+    return guard([&] { bfv_external_product(C(ctx), level, ct, sct, KP(r0), KP(r1), base, sbase, out, sout, batch, S(stream)); });
+}
+int lsa_bfv_cmux(lsa_context ctx, int level, const uint64_t* c0, long long s0, const uint64_t* c1, long long s1, lsa_key r0, lsa_key r1,
+                 uint64_t* out, long long sout, int batch, void* stream) {
+    return guard([&] { bfv_cmux(C(ctx), level, c0, s0, c1, s1, KP(r0), KP(r1), out, sout, batch, S(stream)); });
+}
+int lsa_bfv_select_plan(int count, int* n_levels, int* n_products) {
+    return guard([&] {
+        const BfvSelectPlanHost p = bfv_select_plan_checked(count);
+        if (n_levels) *n_levels = (int)p.levels.size();
+        if (n_products) *n_products = p.n_products;
+    });
+}
+int lsa_bfv_select_create(lsa_context ctx, int level, int count, lsa_bfv_select_handle* out) {
+    return guard([&] {
+        LSA_REQUIRE(out != nullptr, "lsa_bfv_select_create: null argument");
+        Context& c = C(ctx);
+        make_plan(out, c, bfv_select_create(c, level, count));
+    });
+}
+void lsa_bfv_select_destroy(lsa_bfv_select_handle plan) { delete plan; }
+int lsa_bfv_select_info(lsa_bfv_select_handle plan, int* level, int* count, int* n_levels, int* n_products) {
+    return guard([&] {
+        const BfvSelect& p = P(plan, "lsa_bfv_select_info: null plan handle");
+        if (level) *level = p.level;
+        if (count) *count = p.plan.count;
+        if (n_levels) *n_levels = (int)p.plan.levels.size();
+        if (n_products) *n_products = p.plan.n_products;
+    });
+}
+int lsa_bfv_select(lsa_context ctx, lsa_bfv_select_handle plan, uint64_t* in, long long sin, long long s_index, uint64_t* out, long long sout,
+                   int batch, int n_sel, const lsa_key* r0s, const lsa_key* r1s, void* stream) {
+    return guard([&] {
+        BfvSelect& p = P(plan, ctx, "lsa_bfv_select: null plan handle", "lsa_bfv_select: the plan belongs to another context");
+        LSA_REQUIRE(n_sel >= 0 && (n_sel == 0 || (r0s && r1s)), "lsa_bfv_select: r0s / r1s is null");
+        std::vector<const Key*> k0(n_sel), k1(n_sel);
+        for (int j = 0; j < n_sel; j++) k0[j] = KP(r0s[j]), k1[j] = KP(r1s[j]);
+        bfv_select_run(p, in, sin, s_index, out, sout, batch, n_sel, k0.data(), k1.data(), S(stream));
     });
 }
 

@@ -1,7 +1,8 @@
 // key_switch.h — the key switch and what every operator that key-switches shares: the tile (KsTile), its sources and outputs, the
 // rescale that follows a relinearisation, the rotations' index maps and the tiling of a batch (key_switch.hip).
 //   key-switch = per-digit exact ModUp (DecomposeSingleNTT) + gadget MAC + centred ModDown (ModDownQPtoQNTT)
-// Callers: ops.hip (relinearisation, rotations, extended rotations, the BFV forms), slot_sum.hip (both slot sums), bfv_expand.hip, bfv_pack.hip.  Nothing outside
+// Callers: ops.hip (relinearisation, rotations, extended rotations, the BFV forms), slot_sum.hip (both slot sums), bfv_expand.hip, bfv_pack.hip,
+// bfv_select.hip (the external product).  Nothing outside
 // key_switch.hip launches a key MAC or a ModDown itself.
 #pragma once
 #include <algorithm>
@@ -148,6 +149,17 @@ struct KsTile {
 
 // a key switch with one key; ws: KsTile::rows(c, level, src.form) rows per item
 void key_switch(Context& c, int level, const KsSource& src, const Key& key, const KsOut& o, int nb, u64* ws, hipStream_t s);
+
+// The external product RLWE x RGSW: ct [2][L][N] in the coefficient domain (batch stride sct), the RGSW ciphertext the key pair (r0, r1):
+//   acc = gadget_product(NTT(ct[0]), r0) + gadget_product(NTT(ct[1]), r1)   over Q_level u P, canonical;   o = ModDown(acc) (+ o.base)
+// Both polynomials are decomposed as COEFF sources -- a dense ct (sct == 2 L N) as the 2 * nb rows of ONE launch sequence, a strided
+// one as two sequences -- the two gadget products go into ONE accumulator and ONE ModDown follows.  The MAC is k_ks_mac_pair, or, with
+// Context::rgsw_pair_mac == 0, launch_ks_mac twice through its extended output (identity index map, no base, the second call
+// accumulating): the same words.  It is never the fused second-pass kernel, which takes one key.  o: KsOut::COEFF without a gathering
+// tail; the tail (launch_moddown_final) reads o.base only at the points it writes, so o.p may be o.base, and ct has been consumed by the
+// decompositions before the tail runs, so o.p may be ct.  ws: 2 * KsTile::rows(c, level, COEFF) rows per item.
+void external_product(Context& c, int level, const u64* ct, long long sct, const Key& r0, const Key& r1, const KsOut& o, int nb, u64* ws,
+                      hipStream_t s);
 
 // the automorphism X -> X^g of a rotation as the SCATTER map of the key switch's last store: out[i] = in[perm_g[i]] is
 // out[perm_{g^-1}[x]] = in[x] (the maps of g and g^-1 are inverse permutations).  rotation_scatter: null when the store cannot

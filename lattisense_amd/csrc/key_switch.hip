@@ -424,6 +424,42 @@ void key_switch(Context& c, int level, const KsSource& src, const Key& key, cons
     t.moddown(o);
 }
 
+void external_product(Context& c, int level, const u64* ct, long long sct, const Key& r0, const Key& r1, const KsOut& o, int nb, u64* ws,
+                      hipStream_t s) {
+    if (nb <= 0) return;
+    LSA_REQUIRE(o.form == KsOut::COEFF && !o.coeff_gather && !o.slot_tail && !o.expand_tail && !o.pack_tail,
+                "external product: a plain coefficient-domain output");
+    const long long N = c.n;
+    const int L = level + 1, T = L + c.np;
+    const long long sL = (long long)L * N, s_acc = 2LL * T * N;
+    const u64 *cx0, *cx1, *ext0, *ext1;
+    long long scx, sext;
+    u64 *acc, *conv;
+    if (sct == 2 * sL) {   // polynomial h of item b is row 2b + h of one decomposition
+        KsTile t(c, level, 2 * nb, ws, s, nullptr, KsSource::COEFF);
+        t.decompose(KsSource::of_coeff(ct, sL));
+        cx0 = t.src.ntt, cx1 = cx0 + t.s_cxi, scx = 2 * t.s_cxi;
+        ext0 = t.ext, ext1 = t.ext + t.s_ext, sext = 2 * t.s_ext;
+        acc = t.acc, conv = t.conv;   // (laid out for 2 * nb items: nb fit)
+    } else {
+        KsTile t0(c, level, nb, ws, s, nullptr, KsSource::COEFF);
+        KsTile t1(c, level, nb, ws + KsTile::rows(c, level, KsSource::COEFF) * (size_t)N * nb, s, nullptr, KsSource::COEFF);
+        t0.decompose(KsSource::of_coeff(ct, sct));
+        t1.decompose(KsSource::of_coeff(ct + sL, sct));
+        cx0 = t0.src.ntt, cx1 = t1.src.ntt, scx = t0.s_cxi;
+        ext0 = t0.ext, ext1 = t1.ext, sext = t0.s_ext;
+        acc = t0.acc, conv = t0.conv;
+    }
+    if (c.rgsw_pair_mac) {
+        launch_ks_mac_pair(c, level, cx0, cx1, scx, ext0, ext1, sext, r0, r1, acc, s_acc, nb, s);
+    } else {
+        const u32* id = c.ntt_perm(1);   // the identity: the extended output as the plain accumulator
+        launch_ks_mac(c, level, cx0, scx, ext0, sext, r0, {acc, s_acc, id}, nb, s);
+        launch_ks_mac(c, level, cx1, scx, ext1, sext, r1, {acc, s_acc, id, nullptr, 0, true}, nb, s);
+    }
+    ks_moddown(c, level, acc, s_acc, conv, o, nb, s);
+}
+
 const u32* inverse_perm(Context& c, u64 g) {
     const u64 mask = 2 * (u64)c.n - 1;
     u64 inv = g;   // Newton iteration for the inverse modulo a power of two: doubles the correct low bits each step

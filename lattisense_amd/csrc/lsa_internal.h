@@ -12,6 +12,7 @@
 #include "../../include/lattisense_amd.h"
 #include "bfv_expand.h"
 #include "bfv_pack.h"
+#include "bfv_select.h"
 #include "galois_keys.h"
 #include "ntt_plan.h"
 #include "ntt_chunk.h"
@@ -109,6 +110,7 @@ struct Context {
     int fp64_ntt = 1;               // use the FP64 butterfly engine for limbs with q < 2^47
     int tile_batch = 0;
     int fp_raw = 1;                 // FP64-engine limbs cross between the two NTT passes as doubles (LSA_NTT_FP_RAW=0: canonical u64)
+    int rgsw_pair_mac = 1;          // external product: both gadget products in ONE k_ks_mac_pair launch (key_switch.hip external_product); 0: two launch_ks_mac
     int modup_lift = 1;             // single-limb key-switch digits lifted by the extension transform's load (key_switch.hip KsTile::decompose)
     int fuse_tails = 1;             // ModDown / rescale element-wise tails fused into the NTT load/store phases
     int ks_tail_in_mac = 1;         // merged rescale tail finished inside the fused key MAC (key_switch.h KsTile::plan_tail): 0 never,
@@ -656,6 +658,29 @@ struct BfvPackTail {
 };
 void launch_bfv_pack_tail(Context& c, int level, const BfvPackTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
                           const u64* conv, long long sconv, const u64* a, long long sa, u64* out, long long sout, int nb, hipStream_t s);
+// ---- BFV external product RLWE x RGSW, CMux and select by an encrypted index (bfv_select.hip: the pair MAC kernel and the runners, on
+// external_product() of key_switch.h; plan: bfv_select.h; semantics: include/lattisense_amd.h).  An RGSW ciphertext is the key pair
+// (r0, r1) in lsa_key_upload's layout.
+// acc[h][tl] = sum_d e0(d,tl) * r0[d][h][tl] + sum_d e1(d,tl) * r1[d][h][tl], e_i(d,tl) = cx_i[tl] when tl is in digit d, else ext_i[d][tl]
+// (k_ks_mac_pair; the fold rule: ks_mac_pair.h).  cx0 / cx1 and ext0 / ext1 share their batch strides.  Called by key_switch.hip alone.
+void launch_ks_mac_pair(Context& c, int level, const u64* cx0, const u64* cx1, long long scx, const u64* ext0, const u64* ext1,
+                        long long sext, const Key& r0, const Key& r1, u64* acc, long long sacc, int batch, hipStream_t s);
+struct BfvSelect {
+    Context& c;
+    int level;
+    BfvSelectPlanHost plan;
+    BfvSelect(Context& ctx, int level_) : c(ctx), level(level_) {}
+};
+BfvSelectPlanHost bfv_select_plan_checked(int count);   // bfv_select_plan, refusals as LSA_ERR_ARG
+BfvSelect* bfv_select_create(Context& c, int level, int count);
+void bfv_select_run(BfvSelect& p, u64* in, long long sin, long long s_index, u64* out, long long sout, int batch, int n_sel,
+                    const Key* const* r0s, const Key* const* r1s, hipStream_t s);
+// out = ct [.] (r0, r1) (+ base); out may be ct or base themselves
+void bfv_external_product(Context& c, int level, const u64* ct, long long sct, const Key* r0, const Key* r1, const u64* base,
+                          long long sbase, u64* out, long long sout, int batch, hipStream_t s);
+// out = c0 + (r0, r1) [.] (c1 - c0); out may be c0 or c1 themselves
+void bfv_cmux(Context& c, int level, const u64* c0, long long s0, const u64* c1, long long s1, const Key* r0, const Key* r1, u64* out,
+              long long sout, int batch, hipStream_t s);
 // ---- (ops.hip again)
 void drop_level(Context& c, int level, int polys, const u64* in, u64* out, int batch, long long sin, long long sout,
                 hipStream_t s);

@@ -354,6 +354,29 @@ class DeviceContext:
         check(lib().lsa_bfv_mul_monomial(self.h, level, polys, int(exponent), ct.ptr, out.ptr, batch, words, words, self.stream))
         return out
 
+    def set_rgsw_pair_mac(self, enable):
+        """0: an external product's two gadget products run as two key MAC launches instead of one k_ks_mac_pair (A/B, identical
+        results)"""
+        check(lib().lsa_set_rgsw_pair_mac(self.h, int(enable)))
+
+    def bfv_external_product(self, level, ct, rgsw, batch, base=None, out=None):
+        """ct [.] rgsw (+ base) on coefficient-domain ciphertexts [batch][2][level+1][N]; rgsw: the key handles (r0, r1) of an RGSW
+        ciphertext (include/lattisense_amd.h: lsa_bfv_external_product).  out may be ct or base."""
+        words = 2 * (level + 1) * self.n
+        if out is None:
+            out = self.alloc(max(batch, 1) * words)
+        check(lib().lsa_bfv_external_product(self.h, level, ct.ptr, words, rgsw[0], rgsw[1], base.ptr if base is not None else None, words,
+                                             out.ptr, words, batch, self.stream))
+        return out
+
+    def bfv_cmux(self, level, c0, c1, rgsw, batch, out=None):
+        """c0 + rgsw [.] (c1 - c0): c1 where rgsw encrypts 1, c0 where it encrypts 0.  out may be c0 or c1."""
+        words = 2 * (level + 1) * self.n
+        if out is None:
+            out = self.alloc(max(batch, 1) * words)
+        check(lib().lsa_bfv_cmux(self.h, level, c0.ptr, words, c1.ptr, words, rgsw[0], rgsw[1], out.ptr, words, batch, self.stream))
+        return out
+
     def bfv_rotate_many(self, level, ct, keys, batch):
         """keys: {galois element: key handle}; returns {element: device buffer}, one decomposition for all (hoisted), each
         output bit-identical to bfv_rotate's"""
@@ -970,6 +993,52 @@ class BfvPackPlan(_Plan):
         if out is None:
             out = self.ctx.alloc(max(batch, 1) * words)
         check(lib().lsa_bfv_pack(self.ctx.h, h, in_buf.ptr, words, int(s_index), out.ptr, words, batch, *_key_arrays(glk), self.ctx.stream))
+        return out
+
+
+def bfv_select_plan(count):
+    """{levels, products} of the select of one of `count` ciphertexts by an encrypted index -- host only
+    (include/lattisense_amd.h: lsa_bfv_select_plan)"""
+    nl, npr = ctypes.c_int(), ctypes.c_int()
+    check(lib().lsa_bfv_select_plan(int(count), ctypes.byref(nl), ctypes.byref(npr)))
+    return {"levels": nl.value, "products": npr.value}
+
+
+class BfvSelectPlan(_Plan):
+    """One of `count` coefficient-domain BFV ciphertexts at `level` selected by an encrypted index: a CMux tree whose selectors are
+    RGSW ciphertexts of the index bits (include/lattisense_amd.h: lsa_bfv_select_*).  Planning needs no GPU (`.levels`, `.products`);
+    the device plan is made by the first run."""
+    _destroy = "lsa_bfv_select_destroy"
+
+    def __init__(self, ctx, level, count):
+        self.ctx, self.level, self.count = ctx, int(level), int(count)
+        self.h = None
+        info = bfv_select_plan(count)
+        self.levels, self.products = info["levels"], info["products"]
+
+    def _handle(self):
+        if self.h is None:
+            self._adopt(lambda h: lib().lsa_bfv_select_create(self.ctx.h, self.level, self.count, h))
+            nl, npr = ctypes.c_int(), ctypes.c_int()
+            check(lib().lsa_bfv_select_info(self.h, None, None, ctypes.byref(nl), ctypes.byref(npr)))
+            assert (nl.value, npr.value) == (self.levels, self.products)
+        return self.h
+
+    def run(self, in_buf, batch, selectors, out=None, s_index=None):
+        """in_buf: the device inputs, input i of item b at i * s_index + b * words, each [2][level+1][N] in the coefficient domain
+        (s_index: None = dense, batch * words); the inputs below max(1, 2^(levels-1)) are consumed.  selectors: [(r0, r1)] key handles,
+        entry j the RGSW ciphertext of index bit j.  Returns the device result [batch][2][level+1][N]; out may be in_buf (the result
+        takes the place of input 0)."""
+        h = self._handle()
+        words = 2 * (self.level + 1) * self.ctx.n
+        if s_index is None:
+            s_index = max(batch, 1) * words
+        if out is None:
+            out = self.ctx.alloc(max(batch, 1) * words)
+        n = len(selectors)
+        r0s = (ctypes.c_void_p * max(n, 1))(*[s[0].value if hasattr(s[0], "value") else s[0] for s in selectors])
+        r1s = (ctypes.c_void_p * max(n, 1))(*[s[1].value if hasattr(s[1], "value") else s[1] for s in selectors])
+        check(lib().lsa_bfv_select(self.ctx.h, h, in_buf.ptr, words, int(s_index), out.ptr, words, batch, n, r0s, r1s, self.ctx.stream))
         return out
 
 
