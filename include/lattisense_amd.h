@@ -616,6 +616,47 @@ int lsa_bfv_select_info(lsa_bfv_select_handle plan, int* level, int* count, int*
 int lsa_bfv_select(lsa_context ctx, lsa_bfv_select_handle plan, uint64_t* in, long long sin, long long s_index, uint64_t* out, long long sout,
                    int batch, int n_sel, const lsa_key* r0s, const lsa_key* r1s, void* stream);
 
+/* ---- BFV plaintext matrix x ciphertext vector, entries whole ring elements: the database scan of a PIR answer, between lsa_bfv_expand
+ * (which makes the `cols` query ciphertexts) and lsa_bfv_select (which folds the `rows` results), and the general product of a resident
+ * table of plaintexts with an encrypted vector.
+ *   out[r] = INTT( sum_{c < cols} NTT(ct[c]) . pt[r][c] . 2^-64 mod q )  (+ partial[r])          r < rows
+ * per polynomial and per limb.  ct[c] and out[r] are coefficient-domain ciphertexts [2][level+1][N]; pt[r][c] is a pt_mul plaintext
+ * [level+1][N], NTT domain, Montgomery form: form 1 of lsa_bfv_encode and lsa_bfv_plain_lift, the operand of lsa_bfv_mult_plain_mul, so
+ * a database is built by those entry points with batch = rows * cols.  partial[r], if given, is added in the coefficient domain after
+ * the inverse transform.  Every output word equals lsa_bfv_mac_plain_mul on row r's terms: both sum canonical residues mod q, so
+ * neither the order of the terms nor where the 128-bit sums are folded matters.  Each ct[c] is transformed once (the composition
+ * transforms it `rows` times) and the sums stay in registers across the columns.  Plaintext words at or above q give unspecified
+ * output words and never an out-of-range access.
+ * Layout, strides in words: input c of item b at cts + c * s_col + b * sct, the index-major layout lsa_bfv_expand writes; output r of
+ * item b at out + r * s_row + b * sout, the one lsa_bfv_select and lsa_bfv_pack read; partial as out with its own strides;
+ * pt[r][c] of item b at pts + r * s_prow + c * s_pcol + b * spt, spt == 0: one database for the whole batch.  s_col >= batch * sct,
+ * s_row >= batch * sout, s_partial_row >= batch * spartial; the database is only read, so s_prow, s_pcol and spt may nest in any order,
+ * each at least one plaintext.  out shares no word with cts or partial and its hull (first to last word) is apart from the
+ * database's; there is no in-place form, every output depends on every input.  On the dense layouts (s_col == batch * sct, s_row ==
+ * batch * sout) the forward and the inverse transforms are one launch each per tile, otherwise one per column / row.
+ * Errors are LSA_ERR_ARG before anything is queued, with a message that begins "lsa_bfv_matvec_plain_mul" and names the argument: a
+ * CKKS context, a level out of range, rows < 1 or cols < 1, N < 512, a null pointer (partial may be null), a pointer off the 16-byte
+ * grid, an odd stride, a stride shorter than what it spans, a forbidden overlap.  A refused call leaves the buffers untouched and the
+ * context usable.  batch <= 0 is a no-op after the checks. */
+int lsa_bfv_matvec_plain_mul(lsa_context ctx, int level, int rows, int cols,
+                             const uint64_t* cts, long long s_col, long long sct,
+                             const uint64_t* pts, long long s_prow, long long s_pcol, long long spt,
+                             const uint64_t* partial /* may be null */, long long s_partial_row, long long spartial,
+                             uint64_t* out, long long s_row, long long sout, int batch, void* stream);
+/* host only, needs no device and no context: the plan of a call on a ring of n_ring coefficients and level_limbs = level + 1 limbs with
+ * `workspace_bytes` of workspace (the runner plans with 8 GiB).  row_block: the output rows one workgroup sums from one read of the
+ * transformed ciphertexts (the last block of a `rows` that is no multiple masks its rows); col_block: the columns transformed and
+ * multiplied per launch, min(cols, what the workspace holds of one item), the blocks after the first adding to the sums in out;
+ * workspace_rows: col_block * 2 * level_limbs rows of N words per batch item; n_launches: the launches of k_bfv_matvec of the call,
+ * ceil(cols / col_block) per batch tile of floor(workspace / item) items (the context's own tile cap and lsa_set_tile_batch can
+ * only make more tiles).  Any output pointer may be null.  LSA_ERR_ARG: a ring that is no power of two in 512 .. 2^20, level_limbs,
+ * rows, cols or batch < 1, a workspace that does not hold one transformed ciphertext. */
+int lsa_bfv_matvec_plan(int n_ring, int level_limbs, int rows, int cols, int batch, size_t workspace_bytes,
+                        int* row_block, int* col_block, int* n_launches, size_t* workspace_rows);
+/* forces the blocks of lsa_bfv_matvec_plain_mul on this context: row_block in {0, 1, 2, 4, 8}, col_block >= 0 (cut to cols and to what
+ * the workspace holds); 0 = the plan's own.  A/B measurement and parity; identical results.  Read by every call. */
+int lsa_set_bfv_matvec_block(lsa_context ctx, int row_block, int col_block);
+
 /* ---- BFV slot encoder: `batch` host vectors of N integers in [0, t) -- row 0 of the 2 x N/2 slot matrix, then row 1 -- to device
  * plaintexts, the BFV counterpart of lsa_ckks_encode.  The coefficients are oracle/client.py Client.bfv_encode(values): the values
  * placed through Lattigo's batching index matrix, then the inverse negacyclic transform mod t.  The lift to the chain is the

@@ -185,7 +185,12 @@ SIGNATURES = {
     "lsa_bfv_select_destroy": (None, [c_vp]),
     "lsa_bfv_select_info": (c_int, [c_vp] + [ctypes.POINTER(c_int)] * 4),
     "lsa_bfv_select": (c_int, [c_vp, c_vp, c_vp, c_ll, c_ll, c_vp, c_ll, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "lsa_bfv_encode": (c_int, [c_vp, c_int, c_int, c_u64p, c_vp, c_ll, c_int, c_vp]),
+    "lsa_bfv_matvec_plain_mul": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_ll, c_ll, c_vp, c_ll, c_ll, c_ll, c_vp, c_ll, c_ll, c_vp, c_ll, c_ll,
+                                         c_int, c_vp]),
+    "lsa_bfv_matvec_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.c_size_t] + [ctypes.POINTER(c_int)] * 3 +
+                            [ctypes.POINTER(ctypes.c_size_t)]),
+    "lsa_set_bfv_matvec_block": (c_int, [c_vp, c_int, c_int]),
+    "lsa_bfv_encode": (c_int,[c_vp, c_int, c_int, c_u64p, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_addsub_plain": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_plain_lift": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),
     "lsa_bfv_mult_plain": (c_int, [c_vp, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_vp]),

@@ -1135,6 +1135,36 @@ int lsa_bfv_select(lsa_context ctx, lsa_bfv_select_handle plan, uint64_t* in, lo
     });
 }
 
+// ---- BFV plaintext matrix x ciphertext vector (bfv_matvec.h, bfv_matvec.hip)
+int lsa_bfv_matvec_plain_mul(lsa_context ctx, int level, int rows, int cols, const uint64_t* cts, long long s_col, long long sct,
+                             const uint64_t* pts, long long s_prow, long long s_pcol, long long spt, const uint64_t* partial,
+                             long long s_partial_row, long long spartial, uint64_t* out, long long s_row, long long sout, int batch,
+                             void* stream) {
+    return guard([&] {
+        const BfvMatvecLayout a{cts, s_col, sct, pts, s_prow, s_pcol, spt, partial, s_partial_row, spartial, out, s_row, sout};
+        bfv_matvec_plain_mul(C(ctx), level, rows, cols, a, batch, S(stream));
+    });
+}
+int lsa_bfv_matvec_plan(int n_ring, int level_limbs, int rows, int cols, int batch, size_t workspace_bytes, int* row_block, int* col_block,
+                        int* n_launches, size_t* workspace_rows) {
+    return guard([&] {
+        const BfvMatvecPlanHost p = bfv_matvec_plan_checked(n_ring, level_limbs, rows, cols, batch, workspace_bytes, 0, 0);
+        if (row_block) *row_block = p.row_block;
+        if (col_block) *col_block = p.col_block;
+        if (n_launches) *n_launches = p.n_launches;
+        if (workspace_rows) *workspace_rows = p.workspace_rows;
+    });
+}
+int lsa_set_bfv_matvec_block(lsa_context ctx, int row_block, int col_block) {
+    return guard([&] {
+        LSA_REQUIRE(bfv_matvec_row_block_legal(row_block), "lsa_set_bfv_matvec_block: row_block must be 0, 1, 2, 4 or 8");
+        LSA_REQUIRE(col_block >= 0, "lsa_set_bfv_matvec_block: col_block must be >= 0");
+        Context& c = C(ctx);
+        c.matvec_row_block = row_block;
+        c.matvec_col_block = col_block;
+    });
+}
+
 // ---- CKKS polynomial evaluation (poly_eval.hip)
 struct lsa_polynomial_st : PlanHandle<Polynomial> {};
 int lsa_poly_plan(int basis, int n_coef, const double* coef, int log_baby, int level_in, int with_interval, int* depth,

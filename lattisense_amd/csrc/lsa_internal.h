@@ -12,6 +12,7 @@
 #include "../../include/lattisense_amd.h"
 #include "bfv_expand.h"
 #include "bfv_pack.h"
+#include "bfv_matvec.h"
 #include "bfv_select.h"
 #include "galois_keys.h"
 #include "ntt_plan.h"
@@ -111,7 +112,8 @@ struct Context {
     int tile_batch = 0;
     int fp_raw = 1;                 // FP64-engine limbs cross between the two NTT passes as doubles (LSA_NTT_FP_RAW=0: canonical u64)
     int rgsw_pair_mac = 1;          // external product: both gadget products in ONE k_ks_mac_pair launch (key_switch.hip external_product); 0: two launch_ks_mac
-    int modup_lift = 1;             // single-limb key-switch digits lifted by the extension transform's load (key_switch.hip KsTile::decompose)
+    int matvec_row_block = 0, matvec_col_block = 0;   // lsa_set_bfv_matvec_block: forced blocks of bfv_matvec_plain_mul, 0 = the plan's own (bfv_matvec.h)
+    int modup_lift = 1;            // single-limb key-switch digits lifted by the extension transform's load (key_switch.hip KsTile::decompose)
     int fuse_tails = 1;             // ModDown / rescale element-wise tails fused into the NTT load/store phases
     int ks_tail_in_mac = 1;         // merged rescale tail finished inside the fused key MAC (key_switch.h KsTile::plan_tail): 0 never,
                                     // 1 where the second pass has eight stages (the measured shape), 2 wherever the shape allows
@@ -740,5 +742,21 @@ void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, cons
 void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const u64* g, const Key* const* glk,
                               const u64* const* pts, const long long* spts, const u64* partial, long long spartial, u64* out,
                               int batch, long long sin, long long sout, hipStream_t s);
+// ---- BFV plaintext matrix x ciphertext vector (bfv_matvec.hip: k_bfv_matvec and the runner; plan: bfv_matvec.h; semantics:
+// include/lattisense_amd.h): out[r] = sum_c cts[c] . pts[r][c] (+ partial[r]), the words of bfv_mac_plain_mul on row r's terms, every
+// ciphertext transformed once.  Index-major cts and out; out overlaps no input.
+struct BfvMatvecLayout {
+    const u64* cts;
+    long long s_col, sct;
+    const u64* pts;
+    long long s_prow, s_pcol, spt;
+    const u64* partial;   // nullable
+    long long s_partial_row, spartial;
+    u64* out;
+    long long s_row, sout;
+};
+BfvMatvecPlanHost bfv_matvec_plan_checked(int n_ring, int level_limbs, int rows, int cols, int batch, size_t workspace_bytes,
+                                          int row_block, int col_block);   // bfv_matvec_plan, refusals as LSA_ERR_ARG
+void bfv_matvec_plain_mul(Context& c, int level, int rows, int cols, const BfvMatvecLayout& a, int batch, hipStream_t s);
 
 }  // namespace lsa

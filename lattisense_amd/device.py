@@ -443,6 +443,27 @@ class DeviceContext:
                                           2 * L * self.n, out.ptr, batch, 2 * L * self.n, self.stream))
         return out
 
+    def set_bfv_matvec_block(self, row_block=0, col_block=0):
+        """forces the blocks of bfv_matvec_plain_mul: row_block in 0 (the default), 1, 2, 4, 8 output rows per workgroup, col_block
+        columns per launch (0: all that fit the workspace).  A/B and parity; identical results"""
+        check(lib().lsa_set_bfv_matvec_block(self.h, int(row_block), int(col_block)))
+
+    def bfv_matvec_plain_mul(self, level, cts, pts, rows, cols, batch, partial=None, out=None, shared=True):
+        """out[r] = sum_c cts[c] x pts[r][c] (+ partial[r]), the words of bfv_mac_plain_mul on row r's terms with every ciphertext
+        transformed once (include/lattisense_amd.h: lsa_bfv_matvec_plain_mul).  cts: one device buffer [cols][batch][2][L][N], what
+        BfvExpandPlan.run returns; pts: one device buffer of pt_mul plaintexts, [rows][cols][L][N] shared by the batch or, with
+        shared=False, [batch][rows][cols][L][N]; partial and the result: [rows][batch][2][L][N], what BfvSelectPlan.run takes."""
+        L = level + 1
+        wct, wpt = 2 * L * self.n, L * self.n
+        nb = max(batch, 1)
+        per_item = not shared
+        if out is None:
+            out = self.alloc(rows * nb * wct)
+        check(lib().lsa_bfv_matvec_plain_mul(self.h, level, rows, cols, cts.ptr, nb * wct, wct, pts.ptr, cols * wpt, wpt,
+                                             rows * cols * wpt if per_item else 0, partial.ptr if partial is not None else None, nb * wct,
+                                             wct, out.ptr, nb * wct, wct, batch, self.stream))
+        return out
+
     def bfv_rotate_mac_plain_mul(self, level, ct, terms, batch, partial=None):
         """sum_i rotate(ct, g_i) x pt_i (+ partial), hoisted, the rotations kept in the NTT domain; terms: a list of
         (galois element, key handle or None for g = 1, pt_mul plaintexts [batch][L][N]); bit-identical to bfv_rotate_many
@@ -1002,6 +1023,15 @@ def bfv_select_plan(count):
     nl, npr = ctypes.c_int(), ctypes.c_int()
     check(lib().lsa_bfv_select_plan(int(count), ctypes.byref(nl), ctypes.byref(npr)))
     return {"levels": nl.value, "products": npr.value}
+
+
+def bfv_matvec_plan(n_ring, level_limbs, rows, cols, batch, workspace_bytes=8 << 30):
+    """{row_block, col_block, launches, workspace_rows} of a plaintext matrix x ciphertext vector product -- host only
+    (include/lattisense_amd.h: lsa_bfv_matvec_plan)"""
+    rb, cb, nl, wr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    check(lib().lsa_bfv_matvec_plan(int(n_ring), int(level_limbs), int(rows), int(cols), int(batch), int(workspace_bytes), ctypes.byref(rb),
+                                    ctypes.byref(cb), ctypes.byref(nl), ctypes.byref(wr)))
+    return {"row_block": rb.value, "col_block": cb.value, "launches": nl.value, "workspace_rows": wr.value}
 
 
 class BfvSelectPlan(_Plan):
