@@ -92,8 +92,10 @@ int lsa_ntt(lsa_context ctx, uint64_t* data, int batch, long long batch_stride, 
  *       lsa_poly_addsub: out may BE a and / or b (same pointer, same stride; element-wise), otherwise it overlaps neither.
  *       lsa_ckks_rotate, lsa_bfv_rotate: out may BE in (same pointer, same stride; the rotation then runs in two steps through the
  *         workspace), otherwise no overlap.
- *       lsa_ckks_rotate_many: outputs overlap each other nowhere; each is apart from the input or IS the input -- so at most one is, and
- *         that rotation is computed last, from the intact input, in two steps.  (lsa_bfv_rotate_many: the same rule.)
+ *       lsa_ckks_rotate_many, lsa_bfv_rotate_many: one rule, checked by one function.  The outputs overlap each other nowhere; each is
+ *         apart from the input or IS the input (same pointer, sout == sin); at most one is, and that rotation is computed last, from the
+ *         intact input, in two steps.  An output that only partly overlaps the input is refused: a tile's store could land on a later
+ *         tile's input.
  *       every other one: the output overlaps no input.  In particular rescale and drop_level store rows at other offsets than they
  *         load them, so an in-place call would corrupt rows still to be read.
  *   Refused with LSA_ERR_ARG before any kernel or copy is queued, the message beginning with the entry point's name: a null pointer
@@ -101,7 +103,19 @@ int lsa_ntt(lsa_context ctx, uint64_t* data, int batch, long long batch_stride, 
  *     off the 16-byte grid; a level out of range (0..max, from 1 for rescale, drop_level, mult_relin_rescale); a key exported below
  *     `level`; polys outside 1..3; a context of the other scheme (lsa_poly_addsub and lsa_drop_level serve both); a forbidden
  *     overlap.  A refused call leaves every buffer untouched and the context usable.
- *   batch <= 0 returns LSA_OK and touches nothing (scheme, level, polys and op are still checked). */
+ *   batch <= 0 returns LSA_OK and touches nothing (scheme, level, polys and op are still checked).
+ *   The operators built on these keep the same contract -- operands, exact overlap, 16-byte bases and even strides, LSA_ERR_ARG before
+ *   anything is queued -- each with its own rule for stride 0 and for the output; tests/test_gpu_operator_layout.py holds them to it:
+ *       lsa_bfv_mult_plain_mul: out may BE ct (same pointer, same stride), otherwise it is apart from ct; always apart from the
+ *         plaintexts.  Stride 0 on pt only.
+ *       lsa_bfv_mac_plain_mul, lsa_bfv_rotate_mac_plain_mul: out overlaps no ciphertext, plaintext or partial sum.  Stride 0 on the
+ *         plaintexts only.  Messages begin with the entry point's name, as for lsa_bfv_rotate_many and lsa_bfv_mult_plain_mul.
+ *       lsa_ckks_slot_sum, lsa_bfv_slot_sum: out may BE in (same pointer, same stride), otherwise no overlap; no stride 0.
+ *       lsa_bfv_affine_const: out may BE ct, otherwise no overlap; no stride 0.
+ *       lsa_ckks_linear_transform, lsa_bfv_linear_transform, lsa_ckks_poly_eval, lsa_bfv_poly_eval: out overlaps no word of in; no
+ *         stride 0.  (Messages begin "linear transform", "lsa_bfv_linear_transform", "poly", "bfv_poly".)
+ *       lsa_ckks_mult_sum / _dot, lsa_bfv_mult_sum / _dot: stride 0 on every as[i], bs[i] and on the addend; as[i] == bs[i] squares;
+ *         the output overlaps no operand.  (Messages begin "dot" / "bfv_dot".) */
 /* ---- K3: limb-wise add / sub / negate over `polys` (1..3) polynomials of level+1 limbs (ct+ct, ct-ct, -ct).
  * op: 0 add, 1 sub, 2 neg (b ignored, may be null).  out may be a and / or b.  Either scheme.
  * Replaces HEArithmeticOperator::add/sub/negate (executors_gpu.cu:79-173). */
@@ -203,12 +217,14 @@ int lsa_bfv_rotate(lsa_context ctx, int level, const uint64_t* in, uint64_t galo
                    uint64_t* out, int batch, long long stride_in, long long stride_out, void* stream);
 /* BFV ciphertext x pt_mul plaintext.  A pt_mul plaintext ([level+1][N] words) is the message lifted to Q, in the NTT domain
  * and in Montgomery form (the frontend's BfvPlaintextMulNode).  Per poly and limb: out = INTT(NTT(ct) . pt . 2^-64 mod q),
- * Lattigo v4's mulPlaintextMul.  ct / out: [2][level+1][N] per batch item; out may be ct.  LSA_PTMUL_FUSED=0 selects the
+ * Lattigo v4's mulPlaintextMul.  ct / out: [2][level+1][N] per batch item; out may BE ct (same pointer, same stride) and otherwise
+ * overlaps neither ct nor pt; spt == 0: one plaintext for the batch ("Layout and aliasing" above).  LSA_PTMUL_FUSED=0 selects the
  * unfused form (when it is read: INTEGRATION.md section 6). */
 int lsa_bfv_mult_plain_mul(lsa_context ctx, int level, const uint64_t* ct, const uint64_t* pt, uint64_t* out, int batch,
                            long long sct, long long spt, long long sout, void* stream);
 /* out = sum_{i<n} cts[i] x pts[i] (+ partial when not null), n >= 1, the same products as lsa_bfv_mult_plain_mul, summed in
- * the NTT domain with one inverse transform per output.  out may overlap no input. */
+ * the NTT domain with one inverse transform per output.  out may overlap no input; spts[i] == 0: one plaintext for the batch; no
+ * other stride may be 0. */
 int lsa_bfv_mac_plain_mul(lsa_context ctx, int level, int n, const uint64_t* const* cts, const long long* scts,
                           const uint64_t* const* pts, const long long* spts, const uint64_t* partial, long long spartial,
                           uint64_t* out, int batch, long long sout, void* stream);
@@ -309,7 +325,9 @@ int lsa_ckks_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_r
                          const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream);
 /* The same for BFV (coefficient-domain ciphertexts): outs[i] = rotate(in, galois_elements[i]), each bit-identical to
  * lsa_bfv_rotate's result.  The input's c1 is transformed and decomposed once; each key then costs its MAC and ModDown only,
- * the automorphism riding on the ModDown tail.  At most one output may overlap the input. */
+ * the automorphism riding on the ModDown tail.  Layout as for lsa_ckks_rotate_many: the outputs overlap each other nowhere, at most
+ * one may BE the input (same pointer, sout == sin), every other one is apart from it; no stride 0; a key exported below `level` is
+ * refused. */
 int lsa_bfv_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_rot, const uint64_t* galois_elements,
                         const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream);
 
@@ -760,7 +778,8 @@ int lsa_poly_info(lsa_polynomial p, int* level_in, int* level_out, double* scale
  * its constant term if non-zero (leaves in the recursion's order, upper half first), then the constant lower halves */
 int lsa_poly_constants(lsa_polynomial p, long long* out, int capacity);
 /* in [batch][2][level_in+1][N] (NTT domain, scale_in) -> out [batch][2][level_out+1][N] at scale_out; batch strides in words;
- * out may not overlap in; batch <= 0 is a no-op.  The only key is the relinearisation key (at level_in or above). */
+ * out may not overlap in, pointers are 16-byte aligned and strides even; batch <= 0 is a no-op.  The only key is the
+ * relinearisation key (at level_in or above). */
 int lsa_ckks_poly_eval(lsa_context ctx, lsa_polynomial p, const uint64_t* in, uint64_t* out, int batch, long long sin,
                        long long sout, lsa_key rlk, void* stream);
 

@@ -540,11 +540,11 @@ int lsa_ckks_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_r
 int lsa_bfv_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_rot, const uint64_t* galois_elements,
                         const lsa_key* glk, uint64_t* const* outs, int batch, long long sin, long long sout, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(in != nullptr && n_rot >= 0 && (n_rot == 0 || (galois_elements && glk && outs)), "null argument");
+        LSA_REQUIRE(in != nullptr && n_rot >= 0 && (n_rot == 0 || (galois_elements && glk && outs)), "lsa_bfv_rotate_many: null argument");
         std::vector<const Key*> keys(n_rot);
         for (int i = 0; i < n_rot; i++) {
-            LSA_REQUIRE(glk[i] != nullptr && outs[i] != nullptr, "null key or output");
-            keys[i] = &K(glk[i]);
+            LSA_REQUIRE(glk[i] != nullptr && outs[i] != nullptr, "lsa_bfv_rotate_many: null key or output");
+            keys[i] = &K(glk[i], "lsa_bfv_rotate_many");
         }
         bfv_rotate_many(C(ctx), level, in, n_rot, galois_elements, keys.data(), outs, batch, sin, sout, S(stream));
     });
@@ -553,7 +553,7 @@ int lsa_bfv_rotate_many(lsa_context ctx, int level, const uint64_t* in, int n_ro
 int lsa_bfv_mult_plain_mul(lsa_context ctx, int level, const uint64_t* ct, const uint64_t* pt, uint64_t* out, int batch,
                            long long sct, long long spt, long long sout, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(ct != nullptr && pt != nullptr && out != nullptr, "null argument");
+        LSA_REQUIRE(ct != nullptr && pt != nullptr && out != nullptr, "lsa_bfv_mult_plain_mul: null argument");
         bfv_mult_plain_mul(C(ctx), level, ct, pt, out, batch, sct, spt, sout, S(stream));
     });
 }
@@ -561,8 +561,9 @@ int lsa_bfv_mac_plain_mul(lsa_context ctx, int level, int n, const uint64_t* con
                           const uint64_t* const* pts, const long long* spts, const uint64_t* partial, long long spartial,
                           uint64_t* out, int batch, long long sout, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(n >= 1 && cts && scts && pts && spts && out, "null argument");
-        for (int i = 0; i < n; i++) LSA_REQUIRE(cts[i] != nullptr && pts[i] != nullptr, "null ciphertext or plaintext");
+        LSA_REQUIRE(n >= 1, "lsa_bfv_mac_plain_mul: needs at least one term");
+        LSA_REQUIRE(cts && scts && pts && spts && out, "lsa_bfv_mac_plain_mul: null argument");
+        for (int i = 0; i < n; i++) LSA_REQUIRE(cts[i] != nullptr && pts[i] != nullptr, "lsa_bfv_mac_plain_mul: null ciphertext or plaintext");
         bfv_mac_plain_mul(C(ctx), level, n, cts, scts, pts, spts, partial, spartial, out, batch, sout, S(stream));
     });
 }
@@ -570,10 +571,10 @@ int lsa_bfv_rotate_mac_plain_mul(lsa_context ctx, int level, const uint64_t* in,
                                  const lsa_key* glk, const uint64_t* const* pts, const long long* spts, const uint64_t* partial,
                                  long long spartial, uint64_t* out, int batch, long long sin, long long sout, void* stream) {
     return guard([&] {
-        LSA_REQUIRE(n >= 1, "bfv_rotate_mac_plain_mul: needs at least one term");
-        LSA_REQUIRE(in && galois_elements && glk && pts && spts && out, "null argument");
+        LSA_REQUIRE(n >= 1, "lsa_bfv_rotate_mac_plain_mul: needs at least one term");
+        LSA_REQUIRE(in && galois_elements && glk && pts && spts && out, "lsa_bfv_rotate_mac_plain_mul: null argument");
         std::vector<const Key*> keys(n, nullptr);
-        for (int i = 0; i < n; i++) keys[i] = glk[i] ? &K(glk[i]) : nullptr;
+        for (int i = 0; i < n; i++) keys[i] = glk[i] ? &K(glk[i], "lsa_bfv_rotate_mac_plain_mul") : nullptr;
         bfv_rotate_mac_plain_mul(C(ctx), level, in, n, galois_elements, keys.data(), pts, spts, partial, spartial, out, batch, sin,
                                  sout, S(stream));
     });
@@ -753,7 +754,7 @@ int lsa_ckks_linear_transform(lsa_context ctx, lsa_linear_transform lt, const ui
     return guard([&] {
         LinearTransform& p = P(lt, ctx, "null linear-transform handle", "linear-transform plan belongs to another context");
         if (batch <= 0) return;
-        LSA_REQUIRE(in != nullptr && out != nullptr && n_glk >= 0 && (n_glk == 0 || (glk_elements && glk)), "null argument");
+        LSA_REQUIRE(in != nullptr && out != nullptr && n_glk >= 0 && (n_glk == 0 || (glk_elements && glk)), "linear transform: null argument");
         lt_run(p, in, sin, out, sout, batch, rescale != 0, G(n_glk, glk_elements, glk), S(stream));
     });
 }
@@ -1206,7 +1207,7 @@ int lsa_ckks_poly_eval(lsa_context ctx, lsa_polynomial p, const uint64_t* in, ui
     return guard([&] {
         Polynomial& poly = P(p, ctx, "null polynomial handle", "poly: the plan belongs to another context");
         if (batch <= 0) return;
-        LSA_REQUIRE(in != nullptr && out != nullptr, "null argument");
+        LSA_REQUIRE(in != nullptr && out != nullptr, "poly: null argument");
         LSA_REQUIRE(rlk != nullptr && rlk->key.data != nullptr, "poly: the relinearisation key is missing");
         poly_run(poly, in, sin, out, sout, batch, K(rlk), S(stream));
     });

@@ -47,6 +47,19 @@ struct EntryCheck {
         LSA_REQUIRE(layout::same_or_apart(out, in, batch),
                     who + ": the output must be " + what + " itself (same pointer, same stride) or not overlap it");
     }
+    // the n outputs of a hoisted rotation (one stride, `words` each) against its input: layout::one_of_outputs_may_be_input.
+    // Returns the output that IS the input, or -1
+    int rotate_many_outputs(const Span& in, u64* const* outs, int n, long long sout, size_t words) const {
+        LSA_REQUIRE(outs != nullptr, who + ": null argument");
+        std::vector<Span> sp(n);
+        for (int i = 0; i < n; i++) sp[i] = output(outs[i], sout, words, "an output");
+        int in_place = -1;
+        const layout::OneOf r = layout::one_of_outputs_may_be_input(in, sp.data(), n, batch, &in_place);
+        LSA_REQUIRE(r != layout::ONE_OF_OUTPUTS_OVERLAP, who + ": two outputs overlap");
+        LSA_REQUIRE(r != layout::ONE_OF_TWO_ARE_INPUT, who + ": at most one output may be the input");
+        LSA_REQUIRE(r == layout::ONE_OF_OK, who + ": an output must be in itself (same pointer, same stride) or not overlap it");
+        return in_place;
+    }
 };
 
 }  // namespace lsa

@@ -81,5 +81,27 @@ inline bool apart(const void* a, long long sa, size_t wa, const void* b, long lo
     return apart(span_of(a, sa, wa), span_of(b, sb, wb), batch);
 }
 
+// the rule of the hoisted rotations (lsa_ckks_rotate_many, lsa_bfv_rotate_many): one input, n outputs.  The outputs are pairwise
+// apart; each one IS the input (same) or is apart from it; at most one is the input -- that rotation is computed last, in two
+// steps, from the intact input.  Returns ONE_OF_OK with *in_place = the output that is the input (-1: none), or the first violation
+// (*in_place is then -1): a partial overlap with the input lets one tile store over what another still reads.
+enum OneOf { ONE_OF_OK = 0, ONE_OF_OUTPUTS_OVERLAP = 1, ONE_OF_PARTLY_INPUT = 2, ONE_OF_TWO_ARE_INPUT = 3 };
+inline OneOf one_of_outputs_may_be_input(const Span& in, const Span* outs, int n, int batch, int* in_place) {
+    int found = -1;
+    *in_place = -1;
+    for (int i = 0; i < n; i++) {
+        if (same(outs[i], in)) {
+            if (found >= 0) return ONE_OF_TWO_ARE_INPUT;
+            found = i;
+        } else if (!apart(outs[i], in, batch)) {
+            return ONE_OF_PARTLY_INPUT;
+        }
+        for (int j = 0; j < i; j++)
+            if (!apart(outs[i], outs[j], batch)) return ONE_OF_OUTPUTS_OVERLAP;
+    }
+    *in_place = found;
+    return ONE_OF_OK;
+}
+
 }  // namespace layout
 }  // namespace lsa

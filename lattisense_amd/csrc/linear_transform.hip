@@ -547,7 +547,11 @@ void lt_run(LinearTransform& lt, const u64* in, long long sin, u64* out, long lo
     const long long N = c.n;
     const int level = lt.m.level, out_level = rescale ? level - 1 : level;
     LSA_REQUIRE(!rescale || level >= 1, "linear transform: a rescale needs level >= 1");
+    LSA_REQUIRE(in && out, "linear transform: null argument");
     LSA_REQUIRE(sin >= 2LL * (level + 1) * N && sout >= 2LL * (out_level + 1) * N, "linear transform: batch stride shorter than a ciphertext");
+    // the row copies that gather `in` and store `out` move 16 bytes per lane at base + item * stride
+    LSA_REQUIRE(layout::aligned16(layout::span_of(in, sin, 0)) && layout::aligned16(layout::span_of(out, sout, 0)),
+                "linear transform: in and out must be 16-byte aligned with even batch strides");
     LSA_REQUIRE(layout::apart(out, sout, 2 * (size_t)(out_level + 1) * N, in, sin, 2 * (size_t)(level + 1) * N, batch),
                 "linear transform: out overlaps in");
     LtEval ev(c, lt.pool, s, batch, glk, "linear transform");

@@ -100,20 +100,15 @@ void ckks_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64
     const size_t ks_rows = KsTile::rows(c, level);
     const long long sp = 2LL * L * N;
     const Span sp_in = ck.operand(in, sin, 2 * (size_t)L * N, "in", false);
-    std::vector<Span> sp_out(n_rot);
     std::vector<const u32*> perms(n_rot), scatters(n_rot);
-    std::vector<int> order;   // the output that IS the input goes last: every other rotation still reads the intact ciphertext
-    int in_place = -1;
     for (int i = 0; i < n_rot; i++) {
         LSA_REQUIRE(glk[i] != nullptr, ck.who + ": a Galois key is null");
         ck.key(*glk[i], "a Galois key");
-        sp_out[i] = ck.output(outs[i], sout, 2 * (size_t)L * N, "an output");
-        ck.same_or_apart(sp_out[i], sp_in, "in");
-        for (int j = 0; j < i; j++) LSA_REQUIRE(layout::apart(sp_out[i], sp_out[j], batch), ck.who + ": two outputs overlap");
-        const bool apart = !layout::same(sp_out[i], sp_in);
-        if (apart) order.push_back(i);
-        else in_place = i;   // (at most one: two of them would overlap each other)
     }
+    const int in_place = ck.rotate_many_outputs(sp_in, outs, n_rot, sout, 2 * (size_t)L * N);
+    std::vector<int> order;   // the output that IS the input goes last: every other rotation still reads the intact ciphertext
+    for (int i = 0; i < n_rot; i++)
+        if (i != in_place) order.push_back(i);
     if (in_place >= 0) order.push_back(in_place);
     for (int i = 0; i < n_rot; i++) {   // (table look-ups upload on first use: only after every argument is accepted)
         scatters[i] = i != in_place ? rotation_scatter(c, g[i]) : nullptr;
@@ -300,11 +295,14 @@ static bool dot_check(const Context& c, int level, const DotTerms& t, bool resca
     const size_t N = (size_t)c.n;
     LSA_REQUIRE(t.as && t.sas && t.bs && t.sbs && out, "dot: null argument");
     LSA_REQUIRE(so >= (long long)wout, "dot: output stride below one result");
+    // the tensor kernel and the tails move 16 bytes per lane at base + item * stride
+    LSA_REQUIRE(layout::aligned16(layout::span_of(out, so, wout)), "dot: the output must be 16-byte aligned with an even batch stride");
     auto operand = [&](const u64* p, long long stride, int rpp, const char* what) {
         LSA_REQUIRE(p != nullptr, std::string("dot: ") + what + " is null");
         LSA_REQUIRE(rpp >= L, std::string("dot: rows per polynomial of ") + what + " below level + 1");
         const size_t words = 2 * (size_t)rpp * N;
         LSA_REQUIRE(stride == 0 || stride >= (long long)words, std::string("dot: batch stride of ") + what + " below one ciphertext");
+        LSA_REQUIRE(layout::aligned16(layout::span_of(p, stride, words)), std::string("dot: ") + what + " must be 16-byte aligned with an even batch stride");
         LSA_REQUIRE(layout::apart(out, so, wout, p, stride, words, batch), std::string("dot: the output overlaps ") + what);
     };
     for (int i = 0; i < t.n; i++) {
@@ -339,6 +337,7 @@ void ckks_mult_sum(Context& c, int level, const DotTerms& t, u64* d3, int batch,
 void ckks_dot(Context& c, int level, const DotTerms& t, const Key& rlk, u64* out, int batch, long long so, bool with_rescale,
               hipStream_t s) {
     if (!dot_check(c, level, t, with_rescale, out, so, 2 * (size_t)(with_rescale ? level : level + 1) * c.n, batch)) return;
+    LSA_REQUIRE(rlk.data != nullptr && rlk.level >= level, "dot: the relinearisation key is missing or was exported at a lower level than the ciphertexts");
     const long long N = c.n;
     const int L = level + 1;
     const size_t r_d3 = 3 * (size_t)L, r_r2 = 2 * (size_t)L;
@@ -680,18 +679,25 @@ void bfv_rotate(Context& c, int level, const u64* in, u64 g, const Key& glk, u64
 // conversions and extension transforms once from the coefficients; then per key the stand-alone MAC (several keys: the
 // fused second pass + MAC does not apply) and the coefficient-domain ModDown, whose tail applies the automorphism by its
 // loads and writes outs[i] directly (k_sub_mul_perm).  Two-step form (tail into the workspace, then k_permute) for an
-// output that overlaps the input, for N > 2^14, with LSA_ROT_SCATTER=0 and with unfused tails.
+// output that is the input, for N > 2^14, with LSA_ROT_SCATTER=0 and with unfused tails.
 void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64* g, const Key* const* glk, u64* const* outs,
                      int batch, long long sin, long long sout, hipStream_t s) {
-    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
-    if (n_rot <= 0) return;
+    const EntryCheck ck(c, "lsa_bfv_rotate_many", LSA_ALGO_BFV, level, 0, batch);
+    if (n_rot <= 0 || batch <= 0) return;
+    LSA_REQUIRE(g && glk && outs, ck.who + ": null argument");
+    const long long N = c.n;
+    const int L = level + 1;
+    const Span sp_in = ck.operand(in, sin, 2 * (size_t)L * N, "in", false);
+    for (int i = 0; i < n_rot; i++) {
+        LSA_REQUIRE(glk[i] != nullptr, ck.who + ": a Galois key is null");
+        ck.key(*glk[i], "a Galois key");
+    }
+    // the rule of lsa_ckks_rotate_many: a partial overlap with the input would let one tile store over what another still reads
+    const int in_place = ck.rotate_many_outputs(sp_in, outs, n_rot, sout, 2 * (size_t)L * N);
     if (n_rot == 1) {
         bfv_rotate(c, level, in, g[0], *glk[0], outs[0], batch, sin, sout, s);
         return;
     }
-    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
-    const long long N = c.n;
-    const int L = level + 1;
     const size_t ks_rows = KsTile::rows(c, level, KsSource::COEFF);
     const long long sp = 2LL * L * N;
     // the one-pass tail stages a limb in LDS (N <= 2^14); larger rings keep the two steps, which measured faster than gathering
@@ -699,20 +705,13 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
     const bool gather_on = sw::rot_scatter() && c.fuse_tails && c.logn <= LSA_PERM_LDS_MAX_LOGN;
     std::vector<const u32*> perms(n_rot);
     std::vector<bool> direct(n_rot);
-    std::vector<int> order;   // an output that overlaps the input goes last: every other rotation still reads the intact c0
-    int overlapping = -1;
-    for (int i = 0; i < n_rot; i++) {
-        const bool apart = layout::apart(outs[i], sout, 2 * (size_t)L * N, in, sin, 2 * (size_t)L * N, batch);
+    std::vector<int> order;   // the output that IS the input goes last: every other rotation still reads the intact c0
+    for (int i = 0; i < n_rot; i++) {   // (table look-ups upload on first use: only after every argument is accepted)
         perms[i] = c.coeff_perm(g[i]);
-        direct[i] = apart && gather_on;
-        if (apart) {
-            order.push_back(i);
-            continue;
-        }
-        LSA_REQUIRE(overlapping < 0, "bfv_rotate_many: at most one output may overlap the input");
-        overlapping = i;
+        direct[i] = i != in_place && gather_on;
+        if (i != in_place) order.push_back(i);
     }
-    if (overlapping >= 0) order.push_back(overlapping);
+    if (in_place >= 0) order.push_back(in_place);
     for_tiles(c, ks_rows + 2 * (size_t)L, batch, s, [&](int nb, int b0, u64* ws, int tb, hipStream_t st) {
         u64* p = ws + ks_rows * N * tb;
         const u64* ct = in + (size_t)b0 * sin;
@@ -766,14 +765,14 @@ static void ptmul_term(Context& c, int L, const u64* ct, long long sct, const u6
 
 void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64* out, int batch, long long sct, long long spt,
                         long long sout, hipStream_t s) {
-    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
-    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
+    const EntryCheck ck(c, "lsa_bfv_mult_plain_mul", LSA_ALGO_BFV, level, 0, batch);
     if (batch <= 0) return;
     const int L = level + 1;
     const size_t wct = 2 * (size_t)L * c.n, wpt = (size_t)L * c.n;
-    LSA_REQUIRE((out == ct && sout == sct) || layout::apart(out, sout, wct, ct, sct, wct, batch),
-                "bfv_mult_plain_mul: out must be ct or not overlap it");
-    LSA_REQUIRE(layout::apart(out, sout, wct, pt, spt, wpt, batch), "bfv_mult_plain_mul: out overlaps the plaintexts");
+    // the transforms load 16-byte pairs at base + item * stride; out == ct item for item is the in-place transform
+    const Span sp_out = ck.output(out, sout, wct);
+    ck.same_or_apart(sp_out, ck.operand(ct, sct, wct, "ct", false), "ct");
+    ck.apart(sp_out, ck.operand(pt, spt, wpt, "pt", true), "the plaintexts");
     ptmul_term(c, L, ct, sct, pt, spt, false, out, sout, out, sout, batch, s);
     launch_ntt(c, out, out, batch, sout, 2 * L, rm_seq(L), true, s);
 }
@@ -781,19 +780,20 @@ void bfv_mult_plain_mul(Context& c, int level, const u64* ct, const u64* pt, u64
 void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, const long long* scts, const u64* const* pts,
                        const long long* spts, const u64* partial, long long spartial, u64* out, int batch, long long sout,
                        hipStream_t s) {
-    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
-    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
-    LSA_REQUIRE(n >= 1, "bfv_mac_plain_mul: needs at least one term");
+    const EntryCheck ck(c, "lsa_bfv_mac_plain_mul", LSA_ALGO_BFV, level, 0, batch);
+    LSA_REQUIRE(n >= 1, ck.who + ": needs at least one term");
     if (batch <= 0) return;
+    LSA_REQUIRE(cts && scts && pts && spts, ck.who + ": null argument");
     const long long N = c.n;
     const int L = level + 1;
     const size_t wct = 2 * (size_t)L * N, wpt = (size_t)L * N;
     // out holds the running sum while the terms are read: it may alias none of them
+    const Span sp_out = ck.output(out, sout, wct);
     for (int i = 0; i < n; i++) {
-        LSA_REQUIRE(layout::apart(out, sout, wct, cts[i], scts[i], wct, batch), "bfv_mac_plain_mul: out overlaps a ciphertext");
-        LSA_REQUIRE(layout::apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_mac_plain_mul: out overlaps a plaintext");
+        ck.apart(sp_out, ck.operand(cts[i], scts[i], wct, "a ciphertext", false), "a ciphertext");
+        ck.apart(sp_out, ck.operand(pts[i], spts[i], wpt, "a plaintext", true), "a plaintext");
     }
-    LSA_REQUIRE(!partial || layout::apart(out, sout, wct, partial, spartial, wct, batch), "bfv_mac_plain_mul: out overlaps the partial sum");
+    if (partial) ck.apart(sp_out, ck.operand(partial, spartial, wct, "the partial sum", false), "the partial sum");
     // workspace: the first pass of terms 1.. (term 0 runs it in out)
     for_tiles(c, n > 1 ? 2 * (size_t)L : 0, batch, s, [&](int nb, int b0, u64* ws, int, hipStream_t st) {
         u64* o = out + (size_t)b0 * sout;
@@ -819,15 +819,15 @@ void bfv_mac_plain_mul(Context& c, int level, int n, const u64* const* cts, cons
 void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const u64* g, const Key* const* glk,
                               const u64* const* pts, const long long* spts, const u64* partial, long long spartial, u64* out,
                               int batch, long long sin, long long sout, hipStream_t s) {
-    LSA_REQUIRE(c.algo == LSA_ALGO_BFV, "context is not BFV");
-    LSA_REQUIRE(level >= 0 && level < c.nq, "level out of range");
-    LSA_REQUIRE(n >= 1, "bfv_rotate_mac_plain_mul: needs at least one term");
+    const EntryCheck ck(c, "lsa_bfv_rotate_mac_plain_mul", LSA_ALGO_BFV, level, 0, batch);
+    LSA_REQUIRE(n >= 1, ck.who + ": needs at least one term");
+    LSA_REQUIRE(g && glk && pts && spts, ck.who + ": null argument");
     bool any_rot = false;
     for (int i = 0; i < n; i++) {
-        LSA_REQUIRE((g[i] & 1) == 1 && g[i] < 2 * (u64)c.n, "bfv_rotate_mac_plain_mul: Galois element must be odd and < 2N");
-        LSA_REQUIRE(pts[i] != nullptr, "bfv_rotate_mac_plain_mul: null plaintext");
+        LSA_REQUIRE((g[i] & 1) == 1 && g[i] < 2 * (u64)c.n, ck.who + ": Galois element must be odd and < 2N");
         if (g[i] == 1) continue;
-        LSA_REQUIRE(glk[i] != nullptr, "bfv_rotate_mac_plain_mul: a rotation term needs its key");
+        LSA_REQUIRE(glk[i] != nullptr, ck.who + ": a rotation term needs its key");
+        ck.key(*glk[i], "a Galois key");
         any_rot = true;
     }
     if (batch <= 0) return;
@@ -835,11 +835,10 @@ void bfv_rotate_mac_plain_mul(Context& c, int level, const u64* in, int n, const
     const int L = level + 1;
     const size_t wct = 2 * (size_t)L * N, wpt = (size_t)L * N;
     // out holds the running sum while the input, the plaintexts and the partial sum are still read: it may alias none of them
-    LSA_REQUIRE(layout::apart(out, sout, wct, in, sin, wct, batch), "bfv_rotate_mac_plain_mul: out overlaps the input");
-    for (int i = 0; i < n; i++)
-        LSA_REQUIRE(layout::apart(out, sout, wct, pts[i], spts[i], wpt, batch), "bfv_rotate_mac_plain_mul: out overlaps a plaintext");
-    LSA_REQUIRE(!partial || layout::apart(out, sout, wct, partial, spartial, wct, batch),
-                "bfv_rotate_mac_plain_mul: out overlaps the partial sum");
+    const Span sp_out = ck.output(out, sout, wct);
+    ck.apart(sp_out, ck.operand(in, sin, wct, "in", false), "the input");
+    for (int i = 0; i < n; i++) ck.apart(sp_out, ck.operand(pts[i], spts[i], wpt, "a plaintext", true), "a plaintext");
+    if (partial) ck.apart(sp_out, ck.operand(partial, spartial, wct, "the partial sum", false), "the partial sum");
     const bool fused = sw::rotmac_fused() && c.fuse_tails && sw::rot_scatter();
     std::vector<const u32*> scatters(n, nullptr), perms(n, nullptr);
     for (int i = 0; i < n; i++) {

@@ -342,7 +342,11 @@ void poly_run(Polynomial& p, const u64* in, long long sin, u64* out, long long s
     const long long N = c.n;
     const PolyStructure& st = p.st;
     LSA_REQUIRE(rlk.level >= p.level_in, "poly: the relinearisation key is below the input level");
+    LSA_REQUIRE(in && out, "poly: null argument");
     LSA_REQUIRE(sin >= 2LL * (p.level_in + 1) * N && sout >= 2LL * (p.level_out + 1) * N, "poly: batch stride shorter than a ciphertext");
+    // the row copies that gather `in` and store `out` move 16 bytes per lane at base + item * stride
+    LSA_REQUIRE(layout::aligned16(layout::span_of(in, sin, 0)) && layout::aligned16(layout::span_of(out, sout, 0)),
+                "poly: in and out must be 16-byte aligned with even batch strides");
     LSA_REQUIRE(layout::apart(out, sout, 2 * (size_t)(p.level_out + 1) * N, in, sin, 2 * (size_t)(p.level_in + 1) * N, batch),
                 "poly: out overlaps in");
     static const GaloisKeys no_glk;

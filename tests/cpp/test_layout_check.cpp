@@ -3,13 +3,37 @@
 //   "base_a stride_a words_a base_b stride_b words_b batch"   (bases in BYTES, strides and sizes in words)
 //     -> "apart same same_or_apart ok_a ok_shared_a aligned_a end_hi end_lo"
 //        ok_a / ok_shared_a: stride_ok(a) without / with shared operands accepted; end: span_end(a) as two 64-bit halves
-// Driven by tests/test_layout_check_host.py, which marks every word of both operands in an array and compares.
+// With the argument "many" the lines are calls of the hoisted rotations' rule (one_of_outputs_may_be_input) instead:
+//   "batch words base_in stride_in stride_out n base_out_0 .. base_out_{n-1}"   (n <= 8)
+//     -> "code in_place"   code: 0 accepted, 1 two outputs overlap, 2 an output partly overlaps the input, 3 two outputs are the input
+// Driven by tests/test_layout_check_host.py, which marks every word of the operands in an array and compares.
 #include <cstdio>
+#include <cstring>
 #include "../../lattisense_amd/csrc/layout_check.h"
 
 using namespace lsa::layout;
 
-int main() {
+static int many() {
+    int batch, n;
+    unsigned long long words, bi;
+    long long si, so;
+    while (std::scanf("%d %llu %llu %lld %lld %d", &batch, &words, &bi, &si, &so, &n) == 6) {
+        if (n < 0 || n > 8) return 4;
+        Span outs[8];
+        for (int i = 0; i < n; i++) {
+            unsigned long long b;
+            if (std::scanf("%llu", &b) != 1) return 5;
+            outs[i] = Span{(uintptr_t)b, so, (size_t)words};
+        }
+        int in_place = -7;
+        const OneOf r = one_of_outputs_may_be_input(Span{(uintptr_t)bi, si, (size_t)words}, outs, n, batch, &in_place);
+        std::printf("%d %d\n", (int)r, in_place);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "many") == 0) return many();
     unsigned long long ba, wa, bb, wb;
     long long sa, sb;
     int batch;

@@ -1,5 +1,5 @@
-"""Helpers of tests/test_gpu_entry_layout.py: operands placed inside larger, sentinel-filled device buffers, and one function
-that turns a dictionary of arguments into the raw C call of a first-generation entry point."""
+"""Helpers of tests/test_gpu_entry_layout.py and tests/test_gpu_operator_layout.py: operands placed inside larger, sentinel-filled
+device buffers, and one function that turns a dictionary of arguments into the raw C call of an entry point."""
 import ctypes
 
 import numpy as np
@@ -57,6 +57,26 @@ def padded_output(ctx, words, batch, inputs, slot=3):
     return Field(ctx, words, batch, BASES[slot], stride)
 
 
+def padded_operands(ctx, arrays, batch, room=0):
+    """padded_inputs for any number of operands (a multiply-accumulate has seven): operand i at its own base, 36 words after the
+    one before, with its own pad -- PADS for the first three, then 22, 26, 30 ..."""
+    out = []
+    for i, a in enumerate(arrays):
+        words = a[0].size
+        base = BASES[i] if i < len(BASES) else BASES[-1] + 36 * (i - len(BASES) + 1)
+        pad = PADS[i] if i < len(PADS) else PADS[-1] + 4 * (i - len(PADS) + 1)
+        out.append(Field(ctx, words, batch, base, words + pad, a, room))
+    return out
+
+
+def padded_outputs(ctx, words, batch, inputs, count=1, room=0):
+    """`count` sentinel-filled outputs with ONE stride, larger than every input's (the hoisted rotations take one stride for all
+    their outputs), each in a buffer of its own at a base no input uses"""
+    stride = max([words] + [f.stride for f in inputs]) + OUT_PAD
+    first = max([BASES[3] - 36] + [f.base for f in inputs]) + 36
+    return [Field(ctx, words, batch, first + 36 * j, stride, room=room) for j in range(count)]
+
+
 def invoke(name, h, a, stream=None):
     """the raw call of entry point `name` from a dictionary: ptrs / strides of the inputs, out / so, batch, level, and op, polys,
     g, key where the entry point has them; returns the C return code"""
@@ -81,6 +101,66 @@ def invoke(name, h, a, stream=None):
         keys = (ctypes.c_void_p * n)(*[k.value if hasattr(k, "value") else k for k in a["key"]])
         outs = (ctypes.c_void_p * n)(*out)
         return L.lsa_ckks_rotate_many(h, lvl, p[0], n, els, keys, outs, batch, s[0], so, stream)
+    return _invoke_operator(name, L, h, a, stream)
+
+
+def _vp(values):
+    return (ctypes.c_void_p * max(len(values), 1))(*[v.value if hasattr(v, "value") else v for v in values])
+
+
+def _ll(values):
+    return (ctypes.c_longlong * max(len(values), 1))(*[int(v) for v in values])
+
+
+def _u64(values):
+    return (ctypes.c_uint64 * max(len(values), 1))(*[int(v) for v in values])
+
+
+def _glk(glk):
+    """{galois element: key handle} -> (count, elements, handles)"""
+    return len(glk), _u64(list(glk)), _vp(list(glk.values()))
+
+
+def _invoke_operator(name, L, h, a, stream):
+    """the second-generation operators.  ptrs / strides list the inputs in the entry point's own order: the ciphertexts, then the
+    plaintexts (or the b side), then the partial sum / addend where a["partial"] / a["addend"] says there is one.  Further keys:
+    n (terms), g and key (lists: Galois elements and their keys), plan (handle), glk ({element: key}), rescale, k and c."""
+    p, s, lvl, out, so, batch = a["ptrs"], a["strides"], a["level"], a["out"], a["so"], a["batch"]
+    if name == "lsa_bfv_rotate_many":                    # g, key, out: lists
+        n = len(a["g"])
+        return L.lsa_bfv_rotate_many(h, lvl, p[0], n, _u64(a["g"]), _vp(a["key"]), _vp(out), batch, s[0], so, stream)
+    if name == "lsa_bfv_mult_plain_mul":
+        return L.lsa_bfv_mult_plain_mul(h, lvl, p[0], p[1], out, batch, s[0], s[1], so, stream)
+    if name == "lsa_bfv_mac_plain_mul":
+        n = a["n"]
+        part = (p[2 * n], s[2 * n]) if a.get("partial") else (None, 0)
+        return L.lsa_bfv_mac_plain_mul(h, lvl, n, _vp(p[:n]), _ll(s[:n]), _vp(p[n:2 * n]), _ll(s[n:2 * n]), part[0], part[1], out, batch, so,
+                                       stream)
+    if name == "lsa_bfv_rotate_mac_plain_mul":
+        n = len(a["g"])
+        part = (p[1 + n], s[1 + n]) if a.get("partial") else (None, 0)
+        return L.lsa_bfv_rotate_mac_plain_mul(h, lvl, p[0], n, _u64(a["g"]), _vp(a["key"]), _vp(p[1:1 + n]), _ll(s[1:1 + n]), part[0], part[1],
+                                              out, batch, s[0], so, stream)
+    if name in ("lsa_ckks_slot_sum", "lsa_bfv_slot_sum", "lsa_bfv_linear_transform"):
+        return getattr(L, name)(h, a["plan"], p[0], out, batch, s[0], so, *_glk(a["glk"]), stream)
+    if name == "lsa_ckks_linear_transform":
+        return L.lsa_ckks_linear_transform(h, a["plan"], p[0], out, batch, s[0], so, int(a["rescale"]), *_glk(a["glk"]), stream)
+    if name in ("lsa_ckks_poly_eval", "lsa_bfv_poly_eval"):
+        return getattr(L, name)(h, a["plan"], p[0], out, batch, s[0], so, a["key"], stream)
+    if name == "lsa_bfv_affine_const":
+        return L.lsa_bfv_affine_const(h, lvl, p[0], s[0], a["k"], a["c"], out, so, batch, stream)
+    if name in ("lsa_ckks_mult_sum", "lsa_ckks_dot", "lsa_bfv_mult_sum", "lsa_bfv_dot"):
+        n = a["n"]
+        add = (p[2 * n], s[2 * n]) if a.get("addend") else (None, 0)
+        terms = (_vp(p[:n]), _ll(s[:n])), (_vp(p[n:2 * n]), _ll(s[n:2 * n]))
+        if name == "lsa_ckks_mult_sum":
+            return L.lsa_ckks_mult_sum(h, lvl, n, *terms[0], None, *terms[1], None, add[0], add[1], out, batch, so, stream)
+        if name == "lsa_ckks_dot":
+            return L.lsa_ckks_dot(h, lvl, n, *terms[0], None, *terms[1], None, add[0], add[1], a["key"], out, batch, so, int(a["rescale"]),
+                                  stream)
+        if name == "lsa_bfv_mult_sum":
+            return L.lsa_bfv_mult_sum(h, lvl, n, *terms[0], *terms[1], add[0], add[1], out, batch, so, stream)
+        return L.lsa_bfv_dot(h, lvl, n, *terms[0], *terms[1], add[0], add[1], a["key"], out, batch, so, stream)
     raise KeyError(name)
 
 

@@ -6,7 +6,11 @@ exact: padding belongs to nobody, operands may interleave.  The model marks, in 
 operand really occupy (and every word of each hull, to see that interleaved cases are reached), and requires
   apart  <=>  the items share no word            (layouts whose own items overlap: the hulls decide)
 over every combination of base offset, stride (0, dense, padded, padded odd) and batch 1..4 of two operands of equal and of
-different item sizes.  Two hand-made cases put strides near 2^40 words, where a 32-bit or a 64-bit intermediate would wrap."""
+different item sizes.  Two hand-made cases put strides near 2^40 words, where a 32-bit or a 64-bit intermediate would wrap.
+
+The rule of the hoisted rotations (one_of_outputs_may_be_input: lsa_ckks_rotate_many and lsa_bfv_rotate_many) gets the same
+treatment: one input and two or three outputs of one stride, every base offset, accepted exactly when no two outputs share a word,
+every output either has the input's base and stride or shares no word with it, and at most one output is the input."""
 import itertools
 import os
 import subprocess
@@ -23,9 +27,9 @@ def _exe(tmp_path):
     return exe
 
 
-def _run(exe, cases):
-    lines = ["%d %d %d %d %d %d %d\n" % c for c in cases]
-    out = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, timeout=600)
+def _run(exe, cases, mode=None):
+    lines = [" ".join("%d" % x for x in c) + "\n" for c in cases]
+    out = subprocess.run([exe] + ([mode] if mode else []), input="".join(lines), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr
     got = [tuple(int(x) for x in line.split()) for line in out.stdout.splitlines()]
     assert len(got) == len(cases)
@@ -119,3 +123,49 @@ def test_strides_near_2_to_40_words(tmp_path):
     assert [g[0] for g in got] == [1, 0, 1, 0, 1, 1, 0, 1, 1]
     assert (got[0][6] << 64) + got[0][7] == end3
     assert (got[6][6] << 64) + got[6][7] == end_big
+
+
+def _many_model(batch, words, base_in, s_in, s_out, outs):
+    """(accepted, in_place, violated rules) from the marked words; bases in words"""
+    inp = _items(base_in, s_in, words, batch)
+    its = [_items(b, s_out, words, batch) for b in outs]
+    is_in = [b == base_in and s_out == s_in for b in outs]
+    broken = set()
+    if any(its[i] & its[j] for i in range(len(outs)) for j in range(i)):
+        broken.add(1)
+    if any((it & inp) and not same for it, same in zip(its, is_in)):
+        broken.add(2)
+    if sum(is_in) > 1:
+        broken.add(3)
+    return not broken, (is_in.index(True) if not broken and any(is_in) else -1), broken
+
+
+def test_rotate_many_rule_against_marked_words(tmp_path):
+    exe = _exe(tmp_path)
+    W, base_in = 4, 24
+    model = []
+    for s_in, s_out in itertools.product((W, W + 2, W + 6), repeat=2):
+        for batch in (1, 2, 3):
+            for b0, b1 in itertools.product(range(0, 64, 2), repeat=2):
+                model.append((batch, W, base_in, s_in, s_out, (b0, b1)))
+    for batch in (2, 3):                                    # three outputs: the input, one interleaved with it, one moving
+        for b2 in range(0, 80, 2):
+            model.append((batch, W, base_in, 3 * W + 4, 3 * W + 4, (base_in, base_in + W + 2, b2)))
+            model.append((batch, W, base_in, 3 * W + 4, 3 * W + 4, (b2, base_in + W + 2, base_in)))
+    cases = [(batch, w, ORIGIN + 8 * bi, si, so, len(outs)) + tuple(ORIGIN + 8 * b for b in outs) for batch, w, bi, si, so, outs in model]
+    got = _run(exe, cases, "many")
+    seen = {"ok": 0, "in_place": 0, "interleaved_in_place": 0, 1: 0, 2: 0, 3: 0}
+    for m, (code, in_place) in zip(model, got):
+        ok, want_in_place, broken = _many_model(*m)
+        assert (code == 0) == ok, (m, code, broken)
+        assert in_place == want_in_place, (m, in_place)
+        if not ok:
+            assert code in broken, (m, code, broken)       # the rule it names is one that the layout breaks
+            seen[code] += 1
+        seen["ok"] += ok
+        seen["in_place"] += ok and in_place >= 0
+        seen["interleaved_in_place"] += ok and in_place >= 0 and len(m[5]) == 3
+    assert all(seen.values()), seen
+    # no output at all, and one output: the rule holds trivially / is same-or-apart
+    assert _run(exe, [(2, W, ORIGIN, W, W, 0), (2, W, ORIGIN, W, W, 1, ORIGIN), (2, W, ORIGIN, W, W, 1, ORIGIN + 8 * W),
+                      (2, W, ORIGIN, 2 * W, 2 * W, 1, ORIGIN + 8 * W)], "many") == [(0, -1), (0, 0), (2, -1), (0, -1)]
