@@ -11,7 +11,7 @@ LIB = os.path.join(HERE, "liblattisense_amd.so")
 HIP_SOURCES = ["kernels.hip", "context.hip", "key_switch.hip", "ops.hip", "linear_transform.hip", "bfv_encode.hip", "bfv_plain.hip", "slot_sum.hip", "bfv_expand.hip", "bfv_pack.hip", "bfv_select.hip", "bfv_matvec.hip", "poly_eval.hip", "bfv_poly.hip", "bootstrap.hip", "c_api.hip", "task_runtime.hip", "task_transfer.hip",
                "task_dispatch.hip", "task_frontend.hip"]
 CXX_SOURCES = ["tables.cpp", "task_graph.cpp"]
-HEADERS = ["build_flags.h", "modarith.h", "ntt_core.h", "ntt_r16.h", "ntt_plan.h", "ntt_chunk.h", "tables.h", "lsa_internal.h", "linear_transform.h", "bfv_encode.h", "poly_eval.h", "bfv_poly.h", "poly_lincomb.h", "tensor_sum.h", "ks_mac_multi.h", "ks_mac_groups.h", "slot_sum.h", "bfv_expand.h", "bfv_pack.h", "bfv_select.h", "bfv_matvec.h", "ks_mac_pair.h", "galois_keys.h", "key_switch.h", "entry_check.h", "plain_ops.h", "bfv_plain.h", "layout_check.h", "task_graph.h", "mini_json.h", "buf_pool.h", "switches.h", "shard_plan.h", "task_pipeline.h", "task_internal.h",
+HEADERS = ["build_flags.h", "modarith.h", "ntt_core.h", "ntt_r16.h", "ntt_plan.h", "ntt_chunk.h", "tables.h", "lsa_internal.h", "linear_transform.h", "bfv_encode.h", "poly_eval.h", "bfv_poly.h", "poly_lincomb.h", "tensor_sum.h", "ks_mac_multi.h", "ks_mac_groups.h", "slot_sum.h", "bfv_expand.h", "bfv_pack.h", "bfv_select.h", "bfv_matvec.h", "ks_mac_pair.h", "galois_keys.h", "key_switch.h", "moddown_gather.h", "entry_check.h", "plain_ops.h", "bfv_plain.h", "layout_check.h", "task_graph.h", "mini_json.h", "buf_pool.h", "switches.h", "shard_plan.h", "task_pipeline.h", "task_internal.h",
            "../../include/lattisense_amd.h", "../../include/lattisense_task.h"]
 
 

@@ -1,7 +1,5 @@
 // bfv_encode.hip — the BFV slot encoder (bfv_encode.h): k_bfv_encode_t, the inverse negacyclic transform mod t of a whole
 // plaintext in LDS, and the host side that lifts its coefficient row into the three plaintext forms.
-#include <atomic>
-
 #include "bfv_encode.h"
 
 namespace lsa {
@@ -132,17 +130,7 @@ static void launch_bfv_encode_t(Context& c, const BfvEncodeTables& T, const u64*
     g.ninv_s = T.ninv_shoup;
     g.logn = c.logn;
     const size_t lds_bytes = ((size_t)c.n + (size_t)c.n / 8) * sizeof(u32);
-    if (lds_bytes > 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in once per device
-        static std::atomic<unsigned long long> raised{0};
-        int dev = 0;
-        LSA_HIP(hipGetDevice(&dev));
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & bit)) {
-            LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bfv_encode_t), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-            raised.fetch_or(bit, std::memory_order_release);
-        }
-    }
+    raise_dynamic_lds<&k_bfv_encode_t>(lds_bytes, 160 * 1024);
     ProfScope ps(c, PROF_ELEMWISE, 16.0 * c.n * batch, s);
     hipLaunchKernelGGL(k_bfv_encode_t, dim3((unsigned)batch), dim3(LSA_BFV_ENC_THREADS), lds_bytes, s, g);
     LSA_HIP(hipGetLastError());

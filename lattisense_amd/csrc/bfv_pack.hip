@@ -1,34 +1,23 @@
 // bfv_pack.hip — the BFV coefficient packing (plan and point arithmetic: bfv_pack.h; semantics: include/lattisense_amd.h):
 //   k_bfv_pack_diff     the head of a paired level: v = a - X^s b into the tile's workspace, the source of the level's key switch
 //                       (polynomial 1 alone in the gather form, both in the two-step form); an unpaired node's rows pass through
-//   k_bfv_pack_tail     the coefficient-domain ModDown tail of one level: (acc - conv) / P (+ a0 - xb0) staged in LDS, the rotation
-//                       gathered from there and added to u = a + X^s b, which the thread kept from the staging loop
+//   k_bfv_pack_tail     the coefficient-domain ModDown tail of one level, the key switch's tail hook (BfvPackTail): the row skeleton
+//                       of moddown_gather.h with PackOp -- (acc - conv) / P (+ a0 - xb0) staged in LDS, the rotation gathered from
+//                       there and added to u = a + X^s b, which the thread kept from the staging loop
 //   k_bfv_pack_combine  the two-step form: the key switch leaves (v0 + ks0, ks1) in the workspace and this kernel gathers the
-//                       rotation from global memory (N > 2^14, unfused tails, the plan's gather switched off)
+//                       rotation from global memory (N > 2^14, unfused tails, the plan's gather switched off) into the same
+//                       PackOp::finish
 // and below them the runner on key_switch() (bfv_pack_run).  Every word equals the composition lsa_bfv_mul_monomial, lsa_poly_addsub
 // (add, sub), lsa_bfv_rotate, lsa_poly_addsub (add): canonical residues, add_mod / sub_mod / neg_mod.
-#include <atomic>
-
 #include "bfv_pack.h"
 #include "entry_check.h"
-#include "key_switch.h"
+#include "moddown_gather.h"
 
 namespace lsa {
 
 namespace {
 
 constexpr int TPB = 256;
-#define LSA_PACK_TAIL_THREADS 1024
-// pairs of points a thread of the tail owns at the largest ring: 2^14 / (2 * 1024)
-constexpr int PACK_TAIL_PAIRS = (1 << LSA_PERM_LDS_MAX_LOGN) / (2 * LSA_PACK_TAIL_THREADS);
-
-__device__ __forceinline__ ulonglong2 ld2(const u64* p) { return *reinterpret_cast<const ulonglong2*>(p); }
-__device__ __forceinline__ void st2(u64* p, u64 x, u64 y) {
-    ulonglong2 v;
-    v.x = x;
-    v.y = y;
-    *reinterpret_cast<ulonglong2*>(p) = v;
-}
 
 // (X^s b)[x], (X^s b)[x + 1], x even, of one row of b.  s even: x - s is even and both points share the sign, one 16-byte load;
 // s = 1: the shifted pair straddles the 16-byte grid (and the row's end at x = 0), so its words are loaded singly.
@@ -46,117 +35,92 @@ __device__ __forceinline__ ulonglong2 shifted_pair(const u64* b, unsigned x, uns
     return v;
 }
 
-struct PackArgs {
+// one level's tail over the items of a tile, a = KsOut::base and out = KsOut::p [2][L][N] per item (out may be a), b = a + b_off the
+// partner:
+//   xb[h][j][x] = +-b[h][j][(x - shift) mod N], negated when x < shift (0 where the node has no partner),
+//   out = (a + xb) + rotate(a - xb, g), for the items whose index coordinate (item0 + i) / batch is below n_pair
+struct BfvPackTail final : KsCoeffTail {
     const u32* perm;      // Context::coeff_perm(g)
-    const u64* acc;       // tail: [2][acc_rpp][N] out of the NTT domain.  combine: the rotation's source (v0 + ks0, ks1), [2][L][N].  diff: unused
-    const u64* conv;      // tail: [2][L][N]
-    const u64* a;         // [2][L][N], coefficient domain (diff: from the first row it takes); the partner b lies b_off words on
-    u64* out;             // tail, combine: [2][L][N], may be a.  diff: v, `limbs`-periodic rows
-    const u64* kvec;      // [L] P^-1 mod q_j, Montgomery form
-    const ModDev* mods;
-    long long sacc, sconv, sa, sout, b_off;
-    int acc_rpp, limbs, logn, shift;
+    long long b_off;      // words from an item's a to its partner
+    int shift;            // s = N / 2^l
+    int item0, batch, n_pair;
+    BfvPackTail(const u32* perm_, long long b_off_, int shift_, int item0_, int batch_, int n_pair_)
+        : KsCoeffTail(1), perm(perm_), b_off(b_off_), shift(shift_), item0(item0_), batch(batch_), n_pair(n_pair_) {}
+    void launch(Context& c, int level, const u64* acc, long long s_acc, int acc_rpp, const u64* conv, long long s_conv, const KsOut& o,
+                int nb, hipStream_t s) const override;
+};
+
+struct PackArgs {
+    RowTailArgs t;   // base: a (diff: from the first row it takes), out may be a (diff: v, `limbs`-periodic rows).  combine: acc is the
+                     // rotation's source (v0 + ks0, ks1), [2][L][N]
+    long long b_off;
+    int shift;
     int item0, batch, n_pair;   // item item0 + blockIdx.y has a partner iff its index coordinate, item / batch, is below n_pair
+};
+
+// the packing's row `row` of item blockIdx.y.  A thread reads a only at the points it writes (u stays in registers across the
+// barrier), so out may lie over a; b belongs to a node no key switch of this level writes.
+struct PackOp {
+    using Keep = ulonglong2;
+    static constexpr bool KEEPS = true;
+    const u64 *a, *b;   // b: the partner's row, or null
+    u64* out;
+    unsigned shift;
+    int logn;
+    u64 q;
+    __device__ __forceinline__ PackOp(const PackArgs& g, int row) : shift((unsigned)g.shift), logn(g.t.logn), q(g.t.mods[row % g.t.limbs].q) {
+        const long long i = blockIdx.y, ro = (long long)row << g.t.logn;
+        a = g.t.base + i * g.t.sbase + ro;
+        b = (g.item0 + (int)blockIdx.y) / g.batch < g.n_pair ? a + g.b_off : nullptr;   // uniform over the workgroup
+        out = g.t.out + i * g.t.sout + ro;
+    }
+    // u = a + X^s b and d = a - X^s b at the points (x, x + 1); both a without a partner
+    __device__ __forceinline__ void sum_diff(int x, ulonglong2& u, ulonglong2& d) const {
+        u = d = ld2(a + x);
+        if (!b) return;
+        const ulonglong2 xb = shifted_pair(b, (unsigned)x, shift, logn, q);
+        d.x = sub_mod(u.x, xb.x, q);
+        d.y = sub_mod(u.y, xb.y, q);
+        u.x = add_mod(u.x, xb.x, q);
+        u.y = add_mod(u.y, xb.y, q);
+    }
+    __device__ __forceinline__ void stage(int x, int poly, ulonglong2& r, Keep& u) const {
+        ulonglong2 d;
+        sum_diff(x, u, d);
+        if (poly == 0) {
+            r.x = add_mod(r.x, d.x, q);
+            r.y = add_mod(r.y, d.y, q);
+        }
+    }
+    // out = u + sigma
+    __device__ __forceinline__ void finish(int y, const Keep& u, ulonglong2 s) const { st2(out + y, add_mod(u.x, s.x, q), add_mod(u.y, s.y, q)); }
 };
 
 // grid: x = rows * (N/2/TPB), y = items.  v[row][x] = a[row][x] - (X^s b)[row][x], or a[row][x] where the node has no partner
 __global__ __launch_bounds__(TPB) void k_bfv_pack_diff(PackArgs g) {
-    const int chunks = (1 << g.logn) / (2 * TPB);
-    const int row = blockIdx.x / chunks;
-    const unsigned x = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
-    const long long b = blockIdx.y;
-    const long long ro = (long long)row << g.logn;
-    const u64 q = g.mods[row % g.limbs].q;
-    const u64* a = g.a + b * g.sa + ro;
-    const bool paired = (g.item0 + (int)blockIdx.y) / g.batch < g.n_pair;
-    ulonglong2 v = ld2(a + x);
-    if (paired) {
-        const ulonglong2 xb = shifted_pair(a + g.b_off, x, (unsigned)g.shift, g.logn, q);
-        v.x = sub_mod(v.x, xb.x, q);
-        v.y = sub_mod(v.y, xb.y, q);
-    }
-    st2(g.out + b * g.sout + ro + x, v.x, v.y);
+    const int chunks = (1 << g.t.logn) / (2 * TPB);
+    const int x = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
+    const PackOp op(g, blockIdx.x / chunks);
+    ulonglong2 u, d;
+    op.sum_diff(x, u, d);
+    st2(op.out + x, d.x, d.y);
 }
 
-// grid: x = 2*limbs, y = items; dynamic LDS 8N bytes.  One workgroup per (row, item).  A thread reads a only at the points it writes
-// (u stays in registers across the barrier), so out may lie over a; b belongs to a node no key switch of this level writes.
-__global__ __launch_bounds__(LSA_PACK_TAIL_THREADS) void k_bfv_pack_tail(PackArgs g) {
-    extern __shared__ __attribute__((aligned(16))) u64 lds[];
-    const int n = 1 << g.logn;
-    const int row = blockIdx.x;
-    const int poly = row / g.limbs, limb = row % g.limbs;
-    const ModDev m = g.mods[limb];
-    const u64 k = g.kvec[limb];
-    const long long b = blockIdx.y;
-    const long long ro = ((long long)poly * g.limbs + limb) << g.logn;
-    const u64* acc = g.acc + b * g.sacc + (((long long)poly * g.acc_rpp + limb) << g.logn);
-    const u64* cv = g.conv + b * g.sconv + ro;
-    const u64* a = g.a + b * g.sa + ro;
-    u64* out = g.out + b * g.sout + ro;
-    const bool paired = (g.item0 + (int)blockIdx.y) / g.batch < g.n_pair;   // uniform over the workgroup
-    ulonglong2 ur[PACK_TAIL_PAIRS];
-#pragma unroll
-    for (int i = 0; i < PACK_TAIL_PAIRS; i++) {
-        const int x = (i * LSA_PACK_TAIL_THREADS + (int)threadIdx.x) * 2;
-        if (x < n) {
-            const ulonglong2 va = ld2(acc + x), vv = ld2(cv + x);
-            ulonglong2 u = ld2(a + x), d = u, r;
-            if (paired) {
-                const ulonglong2 xb = shifted_pair(a + g.b_off, (unsigned)x, (unsigned)g.shift, g.logn, m.q);
-                d.x = sub_mod(u.x, xb.x, m.q);
-                d.y = sub_mod(u.y, xb.y, m.q);
-                u.x = add_mod(u.x, xb.x, m.q);
-                u.y = add_mod(u.y, xb.y, m.q);
-            }
-            r.x = mont_mul(sub_mod(va.x, vv.x, m.q), k, m.q, m.qinv);
-            r.y = mont_mul(sub_mod(va.y, vv.y, m.q), k, m.q, m.qinv);
-            if (poly == 0) {
-                r.x = add_mod(r.x, d.x, m.q);
-                r.y = add_mod(r.y, d.y, m.q);
-            }
-            ur[i] = u;
-            *reinterpret_cast<ulonglong2*>(lds + x) = r;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < PACK_TAIL_PAIRS; i++) {
-        const int y = (i * LSA_PACK_TAIL_THREADS + (int)threadIdx.x) * 2;
-        if (y < n) {
-            const uint2 p = *reinterpret_cast<const uint2*>(g.perm + y);
-            u64 s0 = lds[p.x & 0x7fffffffu], s1 = lds[p.y & 0x7fffffffu];
-            if (p.x >> 31) s0 = neg_mod(s0, m.q);
-            if (p.y >> 31) s1 = neg_mod(s1, m.q);
-            st2(out + y, add_mod(ur[i].x, s0, m.q), add_mod(ur[i].y, s1, m.q));
-        }
-    }
-}
+__global__ __launch_bounds__(LSA_LDS_ROW_THREADS) void k_bfv_pack_tail(PackArgs g) { gathered_tail_row(g.t, PackOp(g, blockIdx.x)); }
 
 // grid: x = 2*limbs * (N/2/TPB), y = items.  acc: the rotation's source in the workspace.  A thread reads only the words of a it
 // writes over.
 __global__ __launch_bounds__(TPB) void k_bfv_pack_combine(PackArgs g) {
-    const int chunks = (1 << g.logn) / (2 * TPB);
+    const int chunks = (1 << g.t.logn) / (2 * TPB);
     const int row = blockIdx.x / chunks;
-    const unsigned y = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
-    const long long b = blockIdx.y;
-    const long long ro = (long long)row << g.logn;
-    const u64 q = g.mods[row % g.limbs].q;
-    const u64* src = g.acc + b * g.sacc + ro;
-    const u64* a = g.a + b * g.sa + ro;
-    const bool paired = (g.item0 + (int)blockIdx.y) / g.batch < g.n_pair;
-    const uint2 p = *reinterpret_cast<const uint2*>(g.perm + y);
-    u64 s0 = src[p.x & 0x7fffffffu], s1 = src[p.y & 0x7fffffffu];
-    if (p.x >> 31) s0 = neg_mod(s0, q);
-    if (p.y >> 31) s1 = neg_mod(s1, q);
-    ulonglong2 u = ld2(a + y);
-    if (paired) {
-        const ulonglong2 xb = shifted_pair(a + g.b_off, y, (unsigned)g.shift, g.logn, q);
-        u.x = add_mod(u.x, xb.x, q);
-        u.y = add_mod(u.y, xb.y, q);
-    }
-    st2(g.out + b * g.sout + ro + y, add_mod(u.x, s0, q), add_mod(u.y, s1, q));
+    const int y = ((blockIdx.x % chunks) * TPB + threadIdx.x) * 2;
+    const PackOp op(g, row);
+    ulonglong2 u, d;
+    op.sum_diff(y, u, d);
+    op.finish(y, u, lds_gather_pair(g.t.acc + blockIdx.y * g.t.sacc + ((long long)row << g.t.logn), g.t.perm, y, op.q));
 }
 
+// the fields of a kernel outside the key switch (head, combine): a and out as the tail hook gets them from KsOut
 PackArgs pack_args(Context& c, int level, const BfvPackTail& t, const u64* a, long long sa, u64* out, long long sout) {
     LSA_REQUIRE(level >= 0 && level < c.nq, "BFV pack: level out of range");
     LSA_REQUIRE(a && out, "BFV pack: null operand");
@@ -164,16 +128,15 @@ PackArgs pack_args(Context& c, int level, const BfvPackTail& t, const u64* a, lo
     LSA_REQUIRE(t.n_pair == 0 || (t.shift >= 1 && t.shift < c.n && t.b_off != 0), "BFV pack: a paired level needs its shift and partner");
     LSA_REQUIRE(((t.b_off | sa | sout) & 1) == 0, "BFV pack: odd stride");
     PackArgs g{};
-    g.perm = t.perm;
-    g.a = a;
-    g.out = out;
-    g.kvec = c.pinv_vec(level);
-    g.mods = c.d_mods;
-    g.sa = sa;
-    g.sout = sout;
+    g.t.perm = t.perm;
+    g.t.base = a;
+    g.t.sbase = sa;
+    g.t.out = out;
+    g.t.sout = sout;
+    g.t.mods = c.d_mods;
+    g.t.limbs = level + 1;
+    g.t.logn = c.logn;
     g.b_off = t.b_off;
-    g.limbs = level + 1;
-    g.logn = c.logn;
     g.shift = t.shift;
     g.item0 = t.item0;
     g.batch = t.batch;
@@ -208,45 +171,25 @@ void launch_bfv_pack_combine(Context& c, int level, const BfvPackTail& t, const 
     LSA_REQUIRE(sigma != nullptr && t.perm != nullptr, "BFV pack combine: null operand");
     LSA_REQUIRE(c.n >= 2 * TPB, "ring degree too small for the BFV pack combine (need N >= 512)");
     PackArgs g = pack_args(c, level, t, a, sa, out, sout);
-    g.acc = sigma;
-    g.sacc = ssigma;
+    g.t.acc = sigma;
+    g.t.sacc = ssigma;
     ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * 2 * L * (3.0 * nb + pack_paired_items(t, nb)) + 4.0 * c.n * 2 * L * nb, s);
     hipLaunchKernelGGL(k_bfv_pack_combine, dim3((unsigned)(2 * L * (c.n / (2 * TPB))), (unsigned)nb), dim3(TPB), 0, s, g);
     LSA_HIP(hipGetLastError());
 }
 
-}  // namespace
-
-void launch_bfv_pack_tail(Context& c, int level, const BfvPackTail& t, const u64* acc, long long sacc, int acc_rpp, const u64* conv,
-                          long long sconv, const u64* a, long long sa, u64* out, long long sout, int nb, hipStream_t s) {
+void BfvPackTail::launch(Context& c, int level, const u64* acc, long long s_acc, int acc_rpp, const u64* conv, long long s_conv,
+                         const KsOut& o, int nb, hipStream_t s) const {
     if (nb <= 0) return;
     const int L = level + 1;
-    LSA_REQUIRE(acc && conv && t.perm && acc_rpp >= L, "BFV pack tail: null or short operand");
-    LSA_REQUIRE(c.logn <= LSA_PERM_LDS_MAX_LOGN, "BFV pack tail: the ring's limbs do not fit in LDS");
-    LSA_REQUIRE(c.n >= 2, "BFV pack tail: ring degree too small");
-    PackArgs g = pack_args(c, level, t, a, sa, out, sout);
-    g.acc = acc;
-    g.conv = conv;
-    g.sacc = sacc;
-    g.sconv = sconv;
-    g.acc_rpp = acc_rpp;
+    LSA_REQUIRE(perm != nullptr, "BFV pack tail: null or short operand");
+    const PackArgs g = pack_args(c, level, *this, o.base, o.sbase, o.p, o.sp);
     // per row: acc, conv and a read, the partner where there is one, the result written, 4 bytes per point of the table
-    ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * 2 * L * (4.0 * nb + pack_paired_items(t, nb)) + 4.0 * c.n * 2 * L * nb, s);
-    const size_t lds_bytes = (size_t)c.n * sizeof(u64);
-    if (lds_bytes > 65536) {   // opt in to more than 64 KiB of dynamic LDS, once per device (the attribute is per device)
-        static std::atomic<unsigned long long> raised{0};
-        int dev = 0;
-        LSA_HIP(hipGetDevice(&dev));
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & bit)) {
-            LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bfv_pack_tail), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-            raised.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    hipLaunchKernelGGL(k_bfv_pack_tail, dim3((unsigned)(2 * L), (unsigned)nb), dim3(LSA_PACK_TAIL_THREADS), lds_bytes, s, g);
-    LSA_HIP(hipGetLastError());
+    launch_lds_row_tail<&k_bfv_pack_tail>(c, level, "BFV pack tail", g, acc, s_acc, acc_rpp, conv, s_conv, o, nb,
+                                          8.0 * c.n * 2 * L * (4.0 * nb + pack_paired_items(*this, nb)) + 4.0 * c.n * 2 * L * nb, s);
 }
+
+}  // namespace
 
 // ------------------------------------------------------------------------------------------------ the operator
 BfvPackPlanHost bfv_pack_plan_checked(int n_ring, int count, int trace) {
@@ -278,27 +221,14 @@ void bfv_pack_run(BfvPack& p, u64* in, long long sin, long long s_index, u64* ou
     Context& c = p.c;
     const int level = p.level, count = p.plan.count;
     const EntryCheck ck(c, "lsa_bfv_pack", LSA_ALGO_BFV, level, 0, batch);
-    const std::vector<const Key*> keys = glk.resolve(p.plan.galois, ck.who, [&](u64, const Key& k) { ck.key(k, "a Galois key"); });
+    glk.resolve(p.plan.galois, ck.who, [&](u64, const Key& k) { ck.key(k, "a Galois key"); });
     if (batch <= 0) return;
     const long long N = c.n;
     const int L = level + 1;
     const size_t w = 2 * (size_t)L * N;
     const layout::Span sp_in0 = ck.operand(in, sin, w, "in", false);
-    const layout::Span sp_out = ck.output(out, sout, w);
-    LSA_REQUIRE((s_index & 1) == 0, ck.who + ": s_index must be even");
-    LSA_REQUIRE(s_index > 0 && (layout::u128)(unsigned long long)s_index >= (layout::u128)(unsigned)batch * (unsigned long long)sin,
-                ck.who + ": s_index below batch * sin");
-    LSA_REQUIRE((long long)count * batch <= 0x7fffffffLL, ck.who + ": count * batch does not fit a batch");
-    {   // `out` is input 0 itself or shares no word with any input
-        const layout::Span hull = layout::span_of(in, s_index, (size_t)(batch - 1) * (size_t)sin + w);
-        const bool out_is_in0 = layout::same(sp_out, sp_in0);
-        if (!out_is_in0 && !layout::apart(hull, layout::span_of(out, 0, (size_t)(batch - 1) * (size_t)sout + w), count)) {
-            ck.same_or_apart(sp_out, sp_in0, "input 0");
-            for (int i = 0; i < count; i++) ck.apart(sp_out, layout::span_of(in + (long long)i * s_index, sin, w), "an input");
-        }
-        if (out_is_in0)
-            for (int i = 1; i < count; i++) ck.apart(sp_out, layout::span_of(in + (long long)i * s_index, sin, w), "an input");
-    }
+    // `out` is input 0 itself or shares no word with any input
+    const auto [in_place, dense] = ck.indexed_array(ck.output(out, sout, w), sp_in0, s_index, count, "sin", "input 0", "an input");
     struct Step {
         int nodes, n_pair, shift;
         u64 g;
@@ -307,18 +237,12 @@ void bfv_pack_run(BfvPack& p, u64* in, long long sin, long long s_index, u64* ou
     for (const BfvPackLevel& lv : p.plan.levels) steps.push_back({lv.nodes, lv.n_pair, lv.shift, lv.g});
     for (u64 g : p.plan.trace_g) steps.push_back({1, 0, 0, g});
     if (steps.empty()) {   // count == 1 without the trace: a copy
-        if (layout::same(sp_out, sp_in0)) return;
-        std::vector<int> rows(2 * L);
-        for (int i = 0; i < 2 * L; i++) rows[i] = i;
-        launch_copy_rows(c, in, sin, out, sout, 2 * L, rows.data(), batch, s);
+        if (!in_place) copy_ciphertexts(c, level, in, sin, out, sout, batch, s);
         return;
     }
     const bool gather = p.gather && c.fuse_tails && c.logn <= LSA_PERM_LDS_MAX_LOGN;
-    std::map<u64, const Key*> key_of;
-    for (size_t i = 0; i < keys.size(); i++) key_of[p.plan.galois[i]] = keys[i];
     const size_t ks_rows = KsTile::rows(c, level, KsSource::COEFF);
     const long long sp = 2LL * L * N, sL = (long long)L * N;
-    const bool dense = (layout::u128)(unsigned long long)s_index == (layout::u128)(unsigned)batch * (unsigned long long)sin;
     // one key switch over `items` nodes a (stride sin) whose results go to dst (stride sdst); the partner lies b_off words after a
     auto run_nodes = [&](const Step& st, const Key& key, const u32* perm, const u64* a, long long b_off, u64* dst, long long sdst,
                          int items, int n_pair) {
@@ -335,7 +259,7 @@ void bfv_pack_run(BfvPack& p, u64* in, long long sin, long long s_index, u64* ou
                     src = v, ssrc = sL;
                 }
                 key_switch(c, level, KsSource::of_coeff(src, ssrc), key,
-                           ks_onto_c0(o, sdst, ai, sin, L, {.form = KsOut::COEFF, .pack_tail = &pt}), nb, ws, str);
+                           ks_onto_c0(o, sdst, ai, sin, L, {.form = KsOut::COEFF, .tail = &pt}), nb, ws, str);
                 return;
             }
             const u64* vv = ai;
@@ -351,7 +275,7 @@ void bfv_pack_run(BfvPack& p, u64* in, long long sin, long long s_index, u64* ou
     };
     for (size_t i = 0; i < steps.size(); i++) {
         const Step& st = steps[i];
-        const Key& key = *key_of.at(st.g);
+        const Key& key = *glk.at(st.g);
         const u32* perm = c.coeff_perm(st.g);
         const bool last = i + 1 == steps.size();   // nodes == 1 there
         u64* dst = last ? out : in;

@@ -277,29 +277,12 @@ void bfv_select_run(BfvSelect& p, u64* in, long long sin, long long s_index, u64
     const int L = level + 1;
     const size_t w = 2 * (size_t)L * N;
     const layout::Span sp_in0 = ck.operand(in, sin, w, "in", false);
-    const layout::Span sp_out = ck.output(out, sout, w);
-    LSA_REQUIRE((s_index & 1) == 0, ck.who + ": s_index must be even");
-    LSA_REQUIRE(s_index > 0 && (layout::u128)(unsigned long long)s_index >= (layout::u128)(unsigned)batch * (unsigned long long)sin,
-                ck.who + ": s_index below batch * sin");
-    LSA_REQUIRE((long long)count * batch <= 0x7fffffffLL, ck.who + ": count * batch does not fit a batch");
-    const bool out_is_in0 = layout::same(sp_out, sp_in0);
-    {   // `out` is input 0 itself or shares no word with any input
-        const layout::Span hull = layout::span_of(in, s_index, (size_t)(batch - 1) * (size_t)sin + w);
-        if (!out_is_in0 && !layout::apart(hull, layout::span_of(out, 0, (size_t)(batch - 1) * (size_t)sout + w), count)) {
-            ck.same_or_apart(sp_out, sp_in0, "input 0");
-            for (int i = 0; i < count; i++) ck.apart(sp_out, layout::span_of(in + (long long)i * s_index, sin, w), "an input");
-        }
-        if (out_is_in0)
-            for (int i = 1; i < count; i++) ck.apart(sp_out, layout::span_of(in + (long long)i * s_index, sin, w), "an input");
-    }
+    // `out` is input 0 itself or shares no word with any input
+    const auto [in_place, dense] = ck.indexed_array(ck.output(out, sout, w), sp_in0, s_index, count, "sin", "input 0", "an input");
     if (k == 0) {   // count == 1: a copy
-        if (out_is_in0) return;
-        std::vector<int> rows(2 * L);
-        for (int i = 0; i < 2 * L; i++) rows[i] = i;
-        launch_copy_rows(c, in, sin, out, sout, 2 * L, rows.data(), batch, s);
+        if (!in_place) copy_ciphertexts(c, level, in, sin, out, sout, batch, s);
         return;
     }
-    const bool dense = (layout::u128)(unsigned long long)s_index == (layout::u128)(unsigned)batch * (unsigned long long)sin;
     for (const BfvSelectLevel& lv : p.plan.levels) {
         const Key &r0 = *r0s[lv.bit], &r1 = *r1s[lv.bit];
         const bool last = lv.bit == 0;   // one node there

@@ -60,6 +60,33 @@ struct EntryCheck {
         LSA_REQUIRE(r == layout::ONE_OF_OK, who + ": an output must be in itself (same pointer, same stride) or not overlap it");
         return in_place;
     }
+    // an array of `count` batched ciphertexts at stride s_index (arr: entry 0; stride_name: what its batch stride is called) against
+    // the one batched operand on the other side of the call: layout::one_against_array.  The OUTPUT side is named in the refusals
+    // whichever it is -- `one` for the packing and the selection, the array for the expansion -- and the input side as in0 where entry
+    // 0 is met in part, as in_any where a later entry is.
+    struct IndexedArray {
+        bool in_place;   // `one` is entry 0 itself
+        bool dense;      // s_index == batch * stride: the array is one strided batch of count * batch items
+    };
+    IndexedArray indexed_array(const Span& one, const Span& arr, long long s_index, int count, const char* stride_name, const char* in0,
+                               const char* in_any) const {
+        LSA_REQUIRE((s_index & 1) == 0, who + ": s_index must be even");
+        LSA_REQUIRE(s_index > 0 && (layout::u128)(unsigned long long)s_index >= (layout::u128)(unsigned)batch * (unsigned long long)arr.stride,
+                    who + ": s_index below batch * " + stride_name);
+        LSA_REQUIRE((long long)count * batch <= 0x7fffffffLL, who + ": count * batch does not fit a batch");
+        const layout::OneVsArray r = layout::one_against_array(one, arr, s_index, count, batch);
+        LSA_REQUIRE(r != layout::ONE_PARTLY_ENTRY0,
+                    who + ": the output must be " + in0 + " itself (same pointer, same stride) or not overlap it");
+        LSA_REQUIRE(r != layout::ONE_OVERLAPS_ENTRY, who + ": the output overlaps " + in_any);
+        return {r == layout::ONE_IS_ENTRY0, layout::dense_array(arr, s_index, batch)};
+    }
 };
+
+// out = in for `batch` ciphertexts at `level` (what an indexed-array operator of count 1 comes to)
+inline void copy_ciphertexts(Context& c, int level, const u64* in, long long sin, u64* out, long long sout, int batch, hipStream_t s) {
+    std::vector<int> rows(2 * (level + 1));
+    for (size_t i = 0; i < rows.size(); i++) rows[i] = (int)i;
+    launch_copy_rows(c, in, sin, out, sout, (int)rows.size(), rows.data(), batch, s);
+}
 
 }  // namespace lsa

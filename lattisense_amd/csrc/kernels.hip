@@ -1,11 +1,11 @@
 // kernels.hip — hand-written gfx950 kernels for the RNS hot path and their launchers.
 // HBM-bound integer work: 16 B/lane coalesced accesses, LDS-staged butterflies, no MFMA (no dense FP contraction here).
-#include <atomic>
 #include <cstdlib>
 
 #include "build_flags.h"
 #include "ks_mac_groups.h"
 #include "lsa_internal.h"
+#include "moddown_gather.h"
 #include "ntt_r16.h"
 #include "plain_ops.h"
 #include "poly_lincomb.h"
@@ -383,16 +383,7 @@ __global__ __launch_bounds__(LSA_R16_THREADS, FP ? LSA_KSMAC_WAVES_FP : LSA_KSMA
 template <int MU, bool FP, bool TAIL = false>
 static void ks_fused_launch(dim3 grid, dim3 block, hipStream_t s, const KsFusedArgs& g) {
     constexpr size_t lds_bytes = ks_fused_lds_bytes(MU, FP);
-    if (lds_bytes > 65536) {
-        static std::atomic<unsigned long long> raised{0};   // bit d: done on device d (the attribute is per device)
-        int dev = 0;
-        LSA_HIP(hipGetDevice(&dev));
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & bit)) {
-            LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ntt_r16_ksmac<MU, FP, TAIL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            raised.fetch_or(bit, std::memory_order_release);
-        }
-    }
+    raise_dynamic_lds<&k_ntt_r16_ksmac<MU, FP, TAIL>>(lds_bytes, (int)lds_bytes);
     hipLaunchKernelGGL((k_ntt_r16_ksmac<MU, FP, TAIL>), grid, block, lds_bytes, s, g);
 }
 
@@ -503,16 +494,7 @@ bool launch_ntt_ksmac(Context& c, int level, const u64* cx, long long scx, u64* 
 
 template <int FZ, int NT>
 static void ntt_launch_variant(const NttPassArgs& a, long long nblocks, size_t lds_bytes, hipStream_t s) {
-    if (lds_bytes > 65536) {   // whole-limb tiles: opt in to more than 64 KiB of dynamic LDS, once per kernel instance AND device
-        static std::atomic<unsigned long long> raised{0};   // bit d: done on device d (the attribute is per device)
-        int dev = 0;
-        LSA_HIP(hipGetDevice(&dev));
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & bit)) {
-            LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ntt_pass<FZ, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            raised.fetch_or(bit, std::memory_order_release);
-        }
-    }
+    raise_dynamic_lds<&k_ntt_pass<FZ, NT>>(lds_bytes, 160 * 1024);   // whole-limb tiles
     hipLaunchKernelGGL((k_ntt_pass<FZ, NT>), dim3((unsigned)nblocks), dim3(NT), lds_bytes, s, a);
     LSA_HIP(hipGetLastError());
 }
@@ -699,14 +681,6 @@ struct EwArgs {
     int rows, logn, op, period;
     unsigned char mod_of[LSA_MAX_PERIOD];
 };
-
-__device__ __forceinline__ ulonglong2 ld2(const u64* p) { return *reinterpret_cast<const ulonglong2*>(p); }
-__device__ __forceinline__ void st2(u64* p, u64 x, u64 y) {
-    ulonglong2 v;
-    v.x = x;
-    v.y = y;
-    *reinterpret_cast<ulonglong2*>(p) = v;
-}
 
 // grid: x = rows * (N/2/TPB), y = batch
 __global__ __launch_bounds__(TPB) void k_elementwise(EwArgs g) {
@@ -2153,102 +2127,52 @@ void launch_moddown_final(Context& c, int level, const u64* acc, long long sacc,
 // The coefficient-domain ModDown tail followed by the automorphism of a rotation, in one pass (hoisted BFV rotations):
 //   out[h][j][i] = s_i * ((acc[h][j][pi_i] - conv[h][j][pi_i]) * P^-1 + (h < base_polys ? base[h][j][pi_i] : 0))
 // pi_i = perm[i] & 0x7fffffff, s_i = -1 where bit 31 is set (Context::coeff_perm, the table of k_permute): residue for residue
-// launch_permute_coeff(launch_moddown_final(...)) without the intermediate.  One workgroup per (row, batch item): the row is
-// computed with coalesced loads into LDS (8N bytes: N <= 2^14, LSA_PERM_LDS_MAX_LOGN), then gathered from LDS and stored
-// coalesced, two words per lane.  Gathering from global memory instead (three gathered 8-byte streams per output through L2)
+// launch_permute_coeff(launch_moddown_final(...)) without the intermediate.  The row skeleton of moddown_gather.h with the plainest
+// policy: one workgroup per (row, batch item), the row computed with coalesced loads into LDS (8N bytes: N <= 2^14,
+// LSA_PERM_LDS_MAX_LOGN), then gathered from LDS and stored coalesced, two words per lane.  The key switch reaches it through its
+// tail hook (KsPermTail, key_switch.h).  Gathering from global memory instead (three gathered 8-byte streams per output through L2)
 // measured slower than the two-step form at N = 2^14 and 2^16: larger rings keep the two steps.
 struct SubMulPermArgs {
-    const u32* perm;
-    const u64* acc;
-    const u64* conv;
-    const u64* base;
-    const u64* kvec;   // [L] P^-1 mod q_j, Montgomery form
-    u64* out;
-    long long sacc, sconv, sbase, so;
-    int acc_rpp, base_rpp, base_polys, limbs, logn;
-    const ModDev* mods;
+    RowTailArgs t;
+    int base_rpp, base_polys;
 };
 
-// grid: x = 2*limbs, y = batch; dynamic LDS 8N bytes
-#define LSA_PERM_LDS_THREADS 1024
-__global__ __launch_bounds__(LSA_PERM_LDS_THREADS) void k_sub_mul_perm(SubMulPermArgs g) {
-    extern __shared__ __attribute__((aligned(16))) u64 lds[];
-    const int n = 1 << g.logn;
-    const int row = blockIdx.x;
-    const int poly = row / g.limbs, limb = row % g.limbs;
-    const ModDev m = g.mods[limb];
-    const u64 k = g.kvec[limb];
+struct SubMulPermOp {   // out = sign * (value + base): the base joins the staged row, nothing crosses the barrier
+    struct Keep {};
+    static constexpr bool KEEPS = false;
+    const u64* c;   // the row of base, or null
+    u64* o;
+    u64 q;
+    __device__ __forceinline__ void stage(int x, int, ulonglong2& r, Keep&) const {
+        if (!c) return;
+        const ulonglong2 vc = ld2(c + x);
+        r.x = add_mod(r.x, vc.x, q);
+        r.y = add_mod(r.y, vc.y, q);
+    }
+    __device__ __forceinline__ void finish(int y, const Keep&, ulonglong2 s) const { st2(o + y, s.x, s.y); }
+};
+
+__global__ __launch_bounds__(LSA_LDS_ROW_THREADS) void k_sub_mul_perm(SubMulPermArgs g) {
+    const int poly = blockIdx.x / g.t.limbs, limb = blockIdx.x % g.t.limbs;
     const long long b = blockIdx.y;
-    const u64* a = g.acc + b * g.sacc + (((long long)poly * g.acc_rpp + limb) << g.logn);
-    const u64* v = g.conv + b * g.sconv + (((long long)poly * g.limbs + limb) << g.logn);
-    const u64* c = g.base && poly < g.base_polys ? g.base + b * g.sbase + (((long long)poly * g.base_rpp + limb) << g.logn) : nullptr;
-    for (int x = threadIdx.x * 2; x < n; x += 2 * LSA_PERM_LDS_THREADS) {
-        const ulonglong2 va = ld2(a + x), vv = ld2(v + x);
-        u64 r0 = mont_mul(sub_mod(va.x, vv.x, m.q), k, m.q, m.qinv);
-        u64 r1 = mont_mul(sub_mod(va.y, vv.y, m.q), k, m.q, m.qinv);
-        if (c) {
-            const ulonglong2 vc = ld2(c + x);
-            r0 = add_mod(r0, vc.x, m.q);
-            r1 = add_mod(r1, vc.y, m.q);
-        }
-        ulonglong2 r;
-        r.x = r0;
-        r.y = r1;
-        *reinterpret_cast<ulonglong2*>(lds + x) = r;
-    }
-    __syncthreads();
-    u64* o = g.out + b * g.so + (((long long)poly * g.limbs + limb) << g.logn);
-    for (int x = threadIdx.x * 2; x < n; x += 2 * LSA_PERM_LDS_THREADS) {
-        const uint2 p = *reinterpret_cast<const uint2*>(g.perm + x);
-        u64 r0 = lds[p.x & 0x7fffffffu], r1 = lds[p.y & 0x7fffffffu];
-        if (p.x >> 31) r0 = neg_mod(r0, m.q);
-        if (p.y >> 31) r1 = neg_mod(r1, m.q);
-        st2(o + x, r0, r1);
-    }
+    const u64* c = g.t.base && poly < g.base_polys ? g.t.base + b * g.t.sbase + (((long long)poly * g.base_rpp + limb) << g.t.logn) : nullptr;
+    u64* o = g.t.out + b * g.t.sout + (((long long)poly * g.t.limbs + limb) << g.t.logn);
+    gathered_tail_row(g.t, SubMulPermOp{c, o, g.t.mods[limb].q});
 }
 
-void launch_moddown_final_perm(Context& c, int level, const u32* perm, const u64* acc, long long sacc, int acc_rpp,
-                               const u64* conv, long long sconv, const u64* base, long long sbase, int base_rpp, int base_polys,
-                               u64* out, long long sout, int batch, hipStream_t s) {
-    if (batch <= 0) return;
+void KsPermTail::launch(Context& c, int level, const u64* acc, long long s_acc, int acc_rpp, const u64* conv, long long s_conv,
+                        const KsOut& o, int nb, hipStream_t s) const {
+    if (nb <= 0) return;
     const int L = level + 1;
     LSA_REQUIRE(perm != nullptr, "gathered ModDown tail: permutation missing");
-    LSA_REQUIRE(L <= c.nq, "gathered ModDown tail: level out of range");
-    LSA_REQUIRE(c.logn <= LSA_PERM_LDS_MAX_LOGN, "gathered ModDown tail: the ring's limbs do not fit in LDS");
-    LSA_REQUIRE(base_polys == 0 || base, "gathered ModDown tail: base polynomial missing");
+    LSA_REQUIRE(o.base_polys == 0 || o.base, "gathered ModDown tail: base polynomial missing");
     SubMulPermArgs g{};
-    g.perm = perm;
-    g.acc = acc;
-    g.conv = conv;
-    g.base = base;
-    g.kvec = c.pinv_vec(level);
-    g.out = out;
-    g.sacc = sacc;
-    g.sconv = sconv;
-    g.sbase = sbase;
-    g.so = sout;
-    g.acc_rpp = acc_rpp;
-    g.base_rpp = base_rpp;
-    g.base_polys = base ? base_polys : 0;
-    g.limbs = L;
-    g.logn = c.logn;
-    g.mods = c.d_mods;
+    g.t.perm = perm;
+    g.base_rpp = o.base_rpp;
+    g.base_polys = o.base ? o.base_polys : 0;
     // acc, conv and out for both polynomials, base for base_polys of them, the permutation table (4 bytes per point) per row
-    ProfScope ps(c, PROF_ELEMWISE, 8.0 * c.n * batch * (3.0 * 2 * L + (double)g.base_polys * L) + 4.0 * c.n * 2 * L * batch, s);
-    const size_t lds_bytes = (size_t)c.n * sizeof(u64);
-    if (lds_bytes > 65536) {   // opt in to more than 64 KiB of dynamic LDS, once per device (the attribute is per device)
-        static std::atomic<unsigned long long> raised{0};
-        int dev = 0;
-        LSA_HIP(hipGetDevice(&dev));
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & bit)) {
-            LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sub_mul_perm), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-            raised.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    hipLaunchKernelGGL(k_sub_mul_perm, dim3((unsigned)(2 * L), (unsigned)batch), dim3(LSA_PERM_LDS_THREADS), lds_bytes, s, g);
-    LSA_HIP(hipGetLastError());
+    launch_lds_row_tail<&k_sub_mul_perm>(c, level, "gathered ModDown tail", g, acc, s_acc, acc_rpp, conv, s_conv, o, nb,
+                                         8.0 * c.n * nb * (3.0 * 2 * L + (double)g.base_polys * L) + 4.0 * c.n * 2 * L * nb, s);
 }
 
 void launch_sub_mul_const(Context& c, const u64* a, long long sa, const u64* b, long long sb, const u64* kvec, u64* out,

@@ -3,7 +3,8 @@
 //   key-switch = per-digit exact ModUp (DecomposeSingleNTT) + gadget MAC + centred ModDown (ModDownQPtoQNTT)
 // Callers: ops.hip (relinearisation, rotations, extended rotations, the BFV forms), slot_sum.hip (both slot sums), bfv_expand.hip, bfv_pack.hip,
 // bfv_select.hip (the external product).  Nothing outside
-// key_switch.hip launches a key MAC or a ModDown itself.
+// key_switch.hip launches a key MAC or a ModDown itself; an operator whose coefficient-domain tail is its own kernel hands it in as
+// the hook KsOut::tail (KsCoeffTail) and stays unknown here.
 #pragma once
 #include <algorithm>
 
@@ -38,14 +39,30 @@ struct RotMacTerm {   // the pt_mul factor of one rotate-and-MAC term (fz_epi = 
 //            kernel afterwards.  rmac (with scatter): the scattered result is multiplied by a pt_mul plaintext and written or
 //            added to p instead (p[row][y] (+)= value * pt[limb][y] * 2^-64, y = scatter[x]): one term of a BFV rotate-and-MAC
 //   RESCALE  NTT domain, fused tails: p is scratch of the same shape and rs.out receives rescale(p)
-//   COEFF    coefficient domain, `base` given there (BFV).  coeff_gather: the coefficient-domain automorphism of a BFV rotation,
-//            Context::coeff_perm(g), applied by the tail's loads (k_sub_mul_perm): p[row][x] = sign_x * value(pi_x).
-//            slot_tail (base = x, both polynomials): one step of the BFV slot sum, the rotated c0 terms gathered by the tail
-//            (k_bfv_slot_tail)
-//            expand_tail (base = the parent, polynomial 0): one level of the BFV expansion, the rotation gathered by the tail and
-//            both children written (k_bfv_expand_tail); p is the even child and may be the parent
-//            pack_tail (base = the node a, polynomial 0): one level of the BFV packing, a - X^s b0 joining polynomial 0, the
-//            rotation gathered by the tail and added to a + X^s b (k_bfv_pack_tail); p may be a
+//   COEFF    coefficient domain, `base` given there (BFV).  tail: the caller's kernel stands in place of launch_moddown_final
+//            (KsCoeffTail below)
+struct KsOut;
+// The hook of a COEFF output: launch() is given the accumulator out of the NTT domain ([2][acc_rpp][N] per item) and the
+// conversion ([2][L][N]) and writes o.p from them -- (acc - conv) * P^-1 combined with o.base as the operator defines, typically
+// through an automorphism gathered from the row staged in LDS (moddown_gather.h).  base_polys: the base the tail needs, o.base a
+// [base_polys][L][N] part of a ciphertext (rows per polynomial L); -1: any base launch_moddown_final takes, none included.
+struct KsCoeffTail {
+    const int base_polys;
+    explicit KsCoeffTail(int base_polys_) : base_polys(base_polys_) {}
+    virtual void launch(Context& c, int level, const u64* acc, long long s_acc, int acc_rpp, const u64* conv, long long s_conv,
+                        const KsOut& o, int nb, hipStream_t s) const = 0;
+
+protected:
+    ~KsCoeffTail() = default;
+};
+// the coefficient-domain automorphism of a BFV rotation, perm = Context::coeff_perm(g), applied by the tail's loads (kernels.hip
+// k_sub_mul_perm): p[row][x] = sign_x * value(pi_x), value = (acc - conv) * P^-1 (+ base)
+struct KsPermTail final : KsCoeffTail {
+    const u32* perm;
+    explicit KsPermTail(const u32* perm_) : KsCoeffTail(-1), perm(perm_) {}
+    void launch(Context& c, int level, const u64* acc, long long s_acc, int acc_rpp, const u64* conv, long long s_conv, const KsOut& o,
+                int nb, hipStream_t s) const override;
+};
 struct KsOut {
     enum Form { NTT, RESCALE, COEFF };
     u64* p;
@@ -56,11 +73,8 @@ struct KsOut {
     Form form = NTT;
     KsRescale rs = {nullptr, 0};
     const u32* scatter = nullptr;
-    const u32* coeff_gather = nullptr;
     const RotMacTerm* rmac = nullptr;
-    const BfvSlotTail* slot_tail = nullptr;
-    const BfvExpandTail* expand_tail = nullptr;
-    const BfvPackTail* pack_tail = nullptr;
+    const KsCoeffTail* tail = nullptr;
 };
 // the two recurring shapes: the switched polynomial pair added onto c0 of a ciphertext ct [2][L][N] (a rotation, a generic switch),
 // or onto both polynomials of one (a relinearisation's (d0, d1), a slot sum's x).  `o`: the fields beyond p, sp and base

@@ -43,13 +43,9 @@ static void ks_base_last_intt(Context& c, int level, const KsOut& o, int nb, hip
 static void ks_moddown_head(Context& c, int level, u64* acc, long long s_acc, u64* conv, const KsOut& o, int nb, hipStream_t s) {
     LSA_REQUIRE(!o.scatter || (c.fuse_tails && o.form == KsOut::NTT), "scattered ModDown store: fused tails, NTT-domain output");
     LSA_REQUIRE(!o.rmac || o.scatter, "rotate-and-MAC tail: needs the rotation's index map");
-    LSA_REQUIRE(!o.coeff_gather || o.form == KsOut::COEFF, "gathered ModDown tail: coefficient-domain output");
-    LSA_REQUIRE(!o.slot_tail || (o.form == KsOut::COEFF && !o.coeff_gather && o.base && o.base_polys == 2 && o.base_rpp == level + 1),
-                "slot-sum ModDown tail: coefficient-domain output on a whole ciphertext");
-    LSA_REQUIRE(!o.expand_tail || (o.form == KsOut::COEFF && !o.coeff_gather && !o.slot_tail && o.base && o.base_polys == 1 && o.base_rpp == level + 1),
-                "expansion ModDown tail: coefficient-domain output onto c0 of the parent");
-    LSA_REQUIRE(!o.pack_tail || (o.form == KsOut::COEFF && !o.coeff_gather && !o.slot_tail && !o.expand_tail && o.base && o.base_polys == 1 && o.base_rpp == level + 1),
-                "packing ModDown tail: coefficient-domain output onto c0 of the node");
+    LSA_REQUIRE(!o.tail || (o.form == KsOut::COEFF &&
+                            (o.tail->base_polys < 0 || (o.base && o.base_polys == o.tail->base_polys && o.base_rpp == level + 1))),
+                "ModDown tail hook: coefficient-domain output onto the base the tail states");
     LSA_REQUIRE(o.form != KsOut::RESCALE || (c.fuse_tails && level >= 1 && ((o.base && o.base_polys == 2) || (!o.base && o.base_polys == 0))),
                 "merged ModDown+rescale: unsupported shape");
     const bool coeff_out = o.form == KsOut::COEFF, rs = o.form == KsOut::RESCALE;
@@ -109,15 +105,8 @@ static void ks_moddown(Context& c, int level, u64* acc, long long s_acc, u64* co
     const long long s_conv = 2LL * L * N;
     ks_moddown_head(c, level, acc, s_acc, conv, o, nb, s);
     if (coeff_out) {
-        if (o.expand_tail)
-            launch_bfv_expand_tail(c, level, *o.expand_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
-        else if (o.pack_tail)
-            launch_bfv_pack_tail(c, level, *o.pack_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
-        else if (o.slot_tail)
-            launch_bfv_slot_tail(c, level, *o.slot_tail, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.p, o.sp, nb, s);
-        else if (o.coeff_gather)
-            launch_moddown_final_perm(c, level, o.coeff_gather, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp,
-                                      o.base_polys, o.p, o.sp, nb, s);
+        if (o.tail)
+            o.tail->launch(c, level, acc, s_acc, T, conv, s_conv, o, nb, s);
         else
             launch_moddown_final(c, level, acc, s_acc, T, conv, s_conv, o.base, o.sbase, o.base_rpp, o.base_polys, o.p, o.sp, nb, s);
         return;
@@ -427,8 +416,7 @@ void key_switch(Context& c, int level, const KsSource& src, const Key& key, cons
 void external_product(Context& c, int level, const u64* ct, long long sct, const Key& r0, const Key& r1, const KsOut& o, int nb, u64* ws,
                       hipStream_t s) {
     if (nb <= 0) return;
-    LSA_REQUIRE(o.form == KsOut::COEFF && !o.coeff_gather && !o.slot_tail && !o.expand_tail && !o.pack_tail,
-                "external product: a plain coefficient-domain output");
+    LSA_REQUIRE(o.form == KsOut::COEFF && !o.tail, "external product: a plain coefficient-domain output");
     const long long N = c.n;
     const int L = level + 1, T = L + c.np;
     const long long sL = (long long)L * N, s_acc = 2LL * T * N;

@@ -103,5 +103,31 @@ inline OneOf one_of_outputs_may_be_input(const Span& in, const Span* outs, int n
     return ONE_OF_OK;
 }
 
+// the rule of the indexed-array operators (lsa_bfv_expand, lsa_bfv_pack, lsa_bfv_select): one batched operand against an array of
+// `count` batched entries, entry i the span `arr` moved on by i * s_index words.  The levels of these operators work inside the
+// array, entry 0 being read and written by the same tile, so `one` IS entry 0 (same) or shares no word with any entry, and being
+// entry 0 it shares none with the others.  Disjoint hulls of the operand and of the whole array settle the usual case in O(1);
+// else the entries are walked.  s_index >= batch * arr.stride is the caller's to check (dense below: equality).
+enum OneVsArray { ONE_APART_FROM_ALL = 0, ONE_IS_ENTRY0 = 1, ONE_PARTLY_ENTRY0 = 2, ONE_OVERLAPS_ENTRY = 3 };
+inline OneVsArray one_against_array(const Span& one, const Span& arr, long long s_index, int count, int batch) {
+    const bool is0 = same(one, arr);
+    const u128 step = s_index > 0 ? 8 * (u128)(unsigned long long)s_index : 0;
+    if (!is0) {
+        const u128 arr_end = span_end(arr, batch) + (u128)(count > 1 ? count - 1 : 0) * step;
+        if (span_end(one, batch) <= (u128)arr.base || arr_end <= (u128)one.base) return ONE_APART_FROM_ALL;
+        if (!apart(one, arr, batch)) return ONE_PARTLY_ENTRY0;
+    }
+    for (int i = 1; i < count; i++) {
+        const u128 at = (u128)arr.base + (u128)i * step;
+        if (at >> 64) break;   // past the address space: no operand has words there
+        if (!apart(one, Span{(uintptr_t)at, arr.stride, arr.words}, batch)) return ONE_OVERLAPS_ENTRY;
+    }
+    return is0 ? ONE_IS_ENTRY0 : ONE_APART_FROM_ALL;
+}
+// the entries follow each other without a gap: the array is ONE batch of count * batch items of stride arr.stride
+inline bool dense_array(const Span& arr, long long s_index, int batch) {
+    return s_index > 0 && (u128)(unsigned long long)s_index == (u128)(unsigned)batch * (u128)(unsigned long long)arr.stride;
+}
+
 }  // namespace layout
 }  // namespace lsa

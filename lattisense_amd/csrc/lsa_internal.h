@@ -1,6 +1,7 @@
 // lsa_internal.h — context, device tables, workspace and launcher declarations (host side, C++).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -39,6 +40,20 @@ void set_last_error(const std::string& m);
     do {                                                         \
         if (!(cond)) throw lsa::Error(LSA_ERR_ARG, (msg));       \
     } while (0)
+
+// A launch with more than 64 KiB of dynamic LDS: the kernel opts in, once per kernel instance (the template argument keeps the
+// flags apart) AND device (the attribute is per device; bit d: done on device d).  limit_bytes: what the instance may ask for
+template <auto Kernel>
+void raise_dynamic_lds(size_t lds_bytes, int limit_bytes) {
+    if (lds_bytes <= 65536) return;
+    static std::atomic<unsigned long long> raised{0};
+    int dev = 0;
+    LSA_HIP(hipGetDevice(&dev));
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (raised.load(std::memory_order_acquire) & bit) return;
+    LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, limit_bytes));
+    raised.fetch_or(bit, std::memory_order_release);
+}
 
 // ---------------------------------------------------------------- exact RNS base conversion plan (device constants)
 // k_baseconv (two points per thread, optional 29-bit SPLIT accumulate) takes up to LSA_BC_NARROW_SRC sources; wider
@@ -368,13 +383,8 @@ void launch_ks_mac(Context& c, int level, const u64* cx, long long scx, const u6
 void launch_moddown_final(Context& c, int level, const u64* acc, long long sacc, int acc_rows_per_poly, const u64* conv,
                           long long sconv, const u64* base, long long sbase, int base_rows_per_poly, int base_polys,
                           u64* out, long long sout, int batch, hipStream_t s);
-// the same tail (coefficient domain) followed by the automorphism of a rotation, in one pass (k_sub_mul_perm, one limb staged
-// in LDS: N <= 2^LSA_PERM_LDS_MAX_LOGN): out[h][i][x] = sign_x * (base[h][i][pi_x] + (acc[h][i][pi_x] - conv[h][i][pi_x]) * Pinv_i),
-// perm = Context::coeff_perm(g)
+// the largest ring whose limb a gathering tail stages in LDS (moddown_gather.h: 8N bytes)
 #define LSA_PERM_LDS_MAX_LOGN 14
-void launch_moddown_final_perm(Context& c, int level, const u32* perm, const u64* acc, long long sacc, int acc_rows_per_poly,
-                               const u64* conv, long long sconv, const u64* base, long long sbase, int base_rows_per_poly,
-                               int base_polys, u64* out, long long sout, int batch, hipStream_t s);
 // out[p][i] = base[p][i] + (a[p][i] - b[p][i]) * kvec[i]; row of operand X = p*X_rpp + i; b/base optional
 void launch_sub_mul_general(Context& c, int polys, int limbs, const unsigned char* limb_mod, const u64* kvec,
                             const u64* a, long long sa, int a_rpp, const u64* b, long long sb, int b_rpp,
@@ -583,24 +593,6 @@ SlotSumPlanHost bfv_slot_sum_plan_checked(int n_ring, long long step, int count,
 BfvSlotSum* bfv_slot_sum_create(Context& c, int level, long long step, int count, int radix, int rows);
 void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, long long sout, int batch,
                       const GaloisKeys& glk, hipStream_t s);
-// the coefficient-domain ModDown tail of one step of the BFV slot sum (k_bfv_slot_tail), x and out [2][L][N]:
-//   out[0][j][y] = x0[j][y] + sum_{r<n_next} sign_r(y) x0[j][pi_r(y)] + (addend ? addend[j][y] : 0) + (acc[0][j][y] - conv[0][j][y]) Pinv_j
-//   out[1][j][y] = x1[j][y] + (acc[1][j][y] - conv[1][j][y]) Pinv_j
-//   tail_c0[j][y] (+)= sign_t(y) x0[j][pi_t(y)]                       when `tail` is given
-// next / tail: Context::coeff_perm tables.  out may be x itself: a row is read and written by one workgroup, reads first.
-struct BfvSlotTail {
-    int n_next = 0;
-    const u32* next[3] = {nullptr, nullptr, nullptr};
-    const u32* tail = nullptr;
-    u64* tail_c0 = nullptr;   // [L][N] per batch item
-    long long s_tail = 0;
-    bool tail_accumulate = false;
-    const u64* addend = nullptr;   // [L][N] per batch item
-    long long s_addend = 0;
-};
-void launch_bfv_slot_tail(Context& c, int level, const BfvSlotTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
-                          const u64* conv, long long sconv, const u64* x, long long sx, u64* out, long long sout, int batch,
-                          hipStream_t s);
 // ---- BFV oblivious expansion (bfv_expand.hip: kernels and runner, on key_switch(); plan and point arithmetic: bfv_expand.h;
 // semantics: include/lattisense_amd.h).  gather: the tail of a level's key switch forms both children from the rotation staged in LDS
 // (k_bfv_expand_tail, N <= 2^14, fused tails); else the key switch leaves (c0 + ks0, ks1) in the workspace and
@@ -616,21 +608,6 @@ BfvExpandPlanHost bfv_expand_plan_checked(int n_ring, int count);   // bfv_expan
 BfvExpand* bfv_expand_create(Context& c, int level, int count);
 void bfv_expand_run(BfvExpand& p, const u64* in, long long sin, u64* out, long long sout, long long s_index, int batch,
                     const GaloisKeys& glk, hipStream_t s);
-// one level's tail over the items of a tile, parent and even [2][L][N] per item (even may be parent), sigma = rotate(parent, g):
-//   even[h][j][y] = parent[h][j][y] + sigma[h][j][y]
-//   odd[h][j][(y - shift) mod N] = +-(parent[h][j][y] - sigma[h][j][y]), odd = even + odd_off, negated when y < shift,
-//   for the items whose index coordinate (item0 + i) / batch is below n_odd
-struct BfvExpandTail {
-    const u32* perm;      // Context::coeff_perm(g)
-    long long odd_off;    // words from an item's even child to its odd child
-    int shift;            // s = 2^j
-    int item0, batch, n_odd;
-};
-void launch_bfv_expand_tail(Context& c, int level, const BfvExpandTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
-                            const u64* conv, long long sconv, const u64* parent, long long sparent, u64* even, long long seven, int nb,
-                            hipStream_t s);
-void launch_bfv_expand_combine(Context& c, int level, const BfvExpandTail& t, const u64* sigma, long long ssigma, const u64* parent,
-                               long long sparent, u64* even, long long seven, int nb, hipStream_t s);
 // out = X^exponent * in on `polys` coefficient-domain polynomials (k_mul_monomial); the output overlaps nothing
 void bfv_mul_monomial(Context& c, int level, int polys, long long exponent, const u64* in, u64* out, int batch, long long sin,
                       long long sout, hipStream_t s);
@@ -649,17 +626,6 @@ BfvPackPlanHost bfv_pack_plan_checked(int n_ring, int count, int trace);   // bf
 BfvPack* bfv_pack_create(Context& c, int level, int count, int trace);
 void bfv_pack_run(BfvPack& p, u64* in, long long sin, long long s_index, u64* out, long long sout, int batch, const GaloisKeys& glk,
                   hipStream_t s);
-// one level's tail over the items of a tile, a and out [2][L][N] per item (out may be a), b = a + b_off the partner:
-//   xb[h][j][x] = +-b[h][j][(x - shift) mod N], negated when x < shift (0 where the node has no partner),
-//   out = (a + xb) + rotate(a - xb, g), for the items whose index coordinate (item0 + i) / batch is below n_pair
-struct BfvPackTail {
-    const u32* perm;      // Context::coeff_perm(g)
-    long long b_off;      // words from an item's a to its partner
-    int shift;            // s = N / 2^l
-    int item0, batch, n_pair;
-};
-void launch_bfv_pack_tail(Context& c, int level, const BfvPackTail& t, const u64* acc, long long sacc, int acc_rows_per_poly,
-                          const u64* conv, long long sconv, const u64* a, long long sa, u64* out, long long sout, int nb, hipStream_t s);
 // ---- BFV external product RLWE x RGSW, CMux and select by an encrypted index (bfv_select.hip: the pair MAC kernel and the runners, on
 // external_product() of key_switch.h; plan: bfv_select.h; semantics: include/lattisense_amd.h).  An RGSW ciphertext is the key pair
 // (r0, r1) in lsa_key_upload's layout.

@@ -721,9 +721,10 @@ void bfv_rotate_many(Context& c, int level, const u64* in, int n_rot, const u64*
             t.mac(*glk[i]);
             KsOut o = ks_onto_c0(p, sp, ct, sin, L, {.form = KsOut::COEFF});
             if (direct[i]) {   // p0 = c0 + ks0 and the automorphism in one tail, straight into the output
+                const KsPermTail gathered(perms[i]);
                 o.p = outs[i] + (size_t)b0 * sout;
                 o.sp = sout;
-                o.coeff_gather = perms[i];
+                o.tail = &gathered;
                 t.moddown(o);
                 continue;
             }

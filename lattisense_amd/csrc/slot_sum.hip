@@ -7,12 +7,11 @@
 // The per-point arithmetic is ks_mac_multi.h's, which the host compiles too (tests/cpp/test_ks_mac_multi.cpp).  k_ks_mac
 // (kernels.hip) stays the single-key kernel: SlotSum::multi_mac = false runs it once per key, each launch adding to its
 // destination, and that form measured faster at every bench shape, so it is the default.  BFV:
-//   k_bfv_slot_tail        the coefficient-domain ModDown tail of one step: x + (acc - conv) / P plus the step's rotated c0 terms,
-//                          gathered from the c0 row staged in LDS.
-#include <atomic>
-
+//   k_bfv_slot_tail        the coefficient-domain ModDown tail of one step, the key switch's tail hook (BfvSlotTail): x + (acc - conv) / P
+//                          plus the step's rotated c0 terms, gathered from the c0 row staged in LDS.  Its own kernel, on
+//                          the helpers of moddown_gather.h.
 #include "entry_check.h"
-#include "key_switch.h"
+#include "moddown_gather.h"
 #include "ks_mac_groups.h"
 #include "ks_mac_multi.h"
 
@@ -21,14 +20,6 @@ namespace lsa {
 namespace {
 
 constexpr int TPB = 256;
-
-__device__ __forceinline__ ulonglong2 ld2(const u64* p) { return *reinterpret_cast<const ulonglong2*>(p); }
-__device__ __forceinline__ void st2(u64* p, u64 x, u64 y) {
-    ulonglong2 v;
-    v.x = x;
-    v.y = y;
-    *reinterpret_cast<ulonglong2*>(p) = v;
-}
 
 struct KsMacMultiArgs {
     const u64* cx;
@@ -214,47 +205,61 @@ __global__ __launch_bounds__(TPB) void k_ext_sum(ExtSumArgs g) {
     st2(po, ext_sum_point(r.x, vx, LSA_KSM_MAX_KEYS - 1, q), ext_sum_point(r.y, vy, LSA_KSM_MAX_KEYS - 1, q));
 }
 
+// the coefficient-domain ModDown tail of one step of the BFV slot sum, the key switch's tail hook (k_bfv_slot_tail), x = KsOut::base
+// and out = KsOut::p [2][L][N]:
+//   out[0][j][y] = x0[j][y] + sum_{r<n_next} sign_r(y) x0[j][pi_r(y)] + (addend ? addend[j][y] : 0) + (acc[0][j][y] - conv[0][j][y]) Pinv_j
+//   out[1][j][y] = x1[j][y] + (acc[1][j][y] - conv[1][j][y]) Pinv_j
+//   tail_c0[j][y] (+)= sign_t(y) x0[j][pi_t(y)]                       when `tail` is given
+// next / tail: Context::coeff_perm tables.  out may be x itself: a row is read and written by one workgroup, reads first.
+struct BfvSlotTail final : KsCoeffTail {
+    int n_next = 0;
+    const u32* next[3] = {nullptr, nullptr, nullptr};
+    const u32* tail = nullptr;
+    u64* tail_c0 = nullptr;   // [L][N] per batch item
+    long long s_tail = 0;
+    bool tail_accumulate = false;
+    const u64* addend = nullptr;   // [L][N] per batch item
+    long long s_addend = 0;
+    BfvSlotTail() : KsCoeffTail(2) {}
+    void launch(Context& c, int level, const u64* acc, long long s_acc, int acc_rpp, const u64* conv, long long s_conv, const KsOut& o,
+                int nb, hipStream_t s) const override;
+};
+
 struct BfvSlotTailArgs {
-    const u64* x;             // [2][L][N], coefficient domain
-    const u64* acc;           // [2][acc_rpp][N], out of the NTT domain
-    const u64* conv;          // [2][L][N]
+    RowTailArgs t;            // base: x, [2][L][N], coefficient domain; out may be x; perm unused
     const u64* addend;        // [L][N] or null: one more addend of polynomial 0
-    u64* out;                 // [2][L][N]; may be x
     u64* tail_c0;             // [L][N] or null
     const u32* next[LSA_KSM_MAX_KEYS - 1];   // coeff_perm tables of the NEXT rotations
     const u32* tail;          // coeff_perm table of the TAIL rotation (with tail_c0)
-    const u64* kvec;          // [L] P^-1 mod q_j, Montgomery form
-    const ModDev* mods;
-    long long sx, sacc, sconv, sadd, so, stail;
-    int n_next, tail_acc, acc_rpp, limbs, logn;
+    long long sadd, stail;
+    int n_next, tail_acc;
 };
 
-#define LSA_SLOT_TAIL_THREADS 1024
 // grid: x = 2*limbs, y = batch; dynamic LDS: 8N bytes when the launch gathers, else none.  One workgroup per row: a c0 row is
 // loaded once (coalesced, into LDS) and serves the row's own term, up to three NEXT gathers and the TAIL gather; every word of x is
 // read before the barrier and every word of out is stored after it by the same workgroup, so out == x is safe.  The c1 rows are
-// plain element-wise work.
-__global__ __launch_bounds__(LSA_SLOT_TAIL_THREADS) void k_bfv_slot_tail(BfvSlotTailArgs g) {
+// plain element-wise work.  (Not the skeleton of moddown_gather.h: it stages x, not the ModDown result, and gathers up to four tables.)
+__global__ __launch_bounds__(LSA_LDS_ROW_THREADS) void k_bfv_slot_tail(BfvSlotTailArgs g) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
-    const int n = 1 << g.logn;
+    const int n = 1 << g.t.logn;
     const int row = blockIdx.x;
-    const int poly = row / g.limbs, limb = row % g.limbs;
-    const ModDev m = g.mods[limb];
-    const u64 k = g.kvec[limb];
+    const int poly = row / g.t.limbs, limb = row % g.t.limbs;
+    const ModDev m = g.t.mods[limb];
+    const u64 k = g.t.kvec[limb];
     const long long b = blockIdx.y;
-    const long long ro = ((long long)poly * g.limbs + limb) << g.logn;
-    const u64* xr = g.x + b * g.sx + ro;
-    const u64* a = g.acc + b * g.sacc + (((long long)poly * g.acc_rpp + limb) << g.logn);
-    const u64* v = g.conv + b * g.sconv + ro;
-    u64* o = g.out + b * g.so + ro;
+    const long long ro = ((long long)poly * g.t.limbs + limb) << g.t.logn;
+    const u64* xr = g.t.base + b * g.t.sbase + ro;
+    const u64* a = g.t.acc + b * g.t.sacc + (((long long)poly * g.t.acc_rpp + limb) << g.t.logn);
+    const u64* v = g.t.conv + b * g.t.sconv + ro;
+    u64* o = g.t.out + b * g.t.sout + ro;
     const bool gather = poly == 0 && (g.n_next > 0 || g.tail != nullptr);   // uniform over the workgroup
     if (gather) {
-        for (int x = threadIdx.x * 2; x < n; x += 2 * LSA_SLOT_TAIL_THREADS) *reinterpret_cast<ulonglong2*>(lds + x) = ld2(xr + x);
+        for (int x = threadIdx.x * 2; x < n; x += 2 * LSA_LDS_ROW_THREADS) *reinterpret_cast<ulonglong2*>(lds + x) = ld2(xr + x);
         __syncthreads();
     }
-    const u64* ad = poly == 0 && g.addend ? g.addend + b * g.sadd + ((long long)limb << g.logn) : nullptr;
-    u64* tc = gather && g.tail ? g.tail_c0 + b * g.stail + ((long long)limb << g.logn) : nullptr;
-    for (int x = threadIdx.x * 2; x < n; x += 2 * LSA_SLOT_TAIL_THREADS) {
+    const u64* ad = poly == 0 && g.addend ? g.addend + b * g.sadd + ((long long)limb << g.t.logn) : nullptr;
+    u64* tc = gather && g.tail ? g.tail_c0 + b * g.stail + ((long long)limb << g.t.logn) : nullptr;
+    for (int x = threadIdx.x * 2; x < n; x += 2 * LSA_LDS_ROW_THREADS) {
         const ulonglong2 va = ld2(a + x), vv = ld2(v + x);
         const ulonglong2 c = gather ? *reinterpret_cast<const ulonglong2*>(lds + x) : ld2(xr + x);
         u64 r0 = add_mod(mont_mul(sub_mod(va.x, vv.x, m.q), k, m.q, m.qinv), c.x, m.q);
@@ -265,30 +270,21 @@ __global__ __launch_bounds__(LSA_SLOT_TAIL_THREADS) void k_bfv_slot_tail(BfvSlot
             r1 = add_mod(r1, w.y, m.q);
         }
         if (gather) {
-            auto rotated = [&](const u32* perm, u64& t0, u64& t1) {
-                const uint2 p = *reinterpret_cast<const uint2*>(perm + x);
-                t0 = lds[p.x & 0x7fffffffu];
-                t1 = lds[p.y & 0x7fffffffu];
-                if (p.x >> 31) t0 = neg_mod(t0, m.q);
-                if (p.y >> 31) t1 = neg_mod(t1, m.q);
-            };
 #pragma unroll
             for (int i = 0; i < LSA_KSM_MAX_KEYS - 1; i++)
                 if (i < g.n_next) {
-                    u64 t0, t1;
-                    rotated(g.next[i], t0, t1);
-                    r0 = add_mod(r0, t0, m.q);
-                    r1 = add_mod(r1, t1, m.q);
+                    const ulonglong2 t = lds_gather_pair(lds, g.next[i], x, m.q);
+                    r0 = add_mod(r0, t.x, m.q);
+                    r1 = add_mod(r1, t.y, m.q);
                 }
             if (tc) {
-                u64 t0, t1;
-                rotated(g.tail, t0, t1);
+                ulonglong2 t = lds_gather_pair(lds, g.tail, x, m.q);
                 if (g.tail_acc) {
                     const ulonglong2 w = ld2(tc + x);
-                    t0 = add_mod(t0, w.x, m.q);
-                    t1 = add_mod(t1, w.y, m.q);
+                    t.x = add_mod(t.x, w.x, m.q);
+                    t.y = add_mod(t.y, w.y, m.q);
                 }
-                st2(tc + x, t0, t1);
+                st2(tc + x, t.x, t.y);
             }
         }
         st2(o + x, r0, r1);
@@ -370,61 +366,29 @@ void launch_ext_sum(Context& c, int level, int n_in, const u64* const* in, long 
     LSA_HIP(hipGetLastError());
 }
 
-void launch_bfv_slot_tail(Context& c, int level, const BfvSlotTail& t, const u64* acc, long long sacc, int acc_rpp, const u64* conv,
-                          long long sconv, const u64* x, long long sx, u64* out, long long sout, int batch, hipStream_t s) {
-    if (batch <= 0) return;
+void BfvSlotTail::launch(Context& c, int level, const u64* acc, long long s_acc, int acc_rpp, const u64* conv, long long s_conv,
+                         const KsOut& o, int nb, hipStream_t s) const {
+    if (nb <= 0) return;
     const int L = level + 1;
-    LSA_REQUIRE(level >= 0 && L <= c.nq, "BFV slot tail: level out of range");
-    LSA_REQUIRE(acc && conv && x && out && acc_rpp >= L, "BFV slot tail: null or short operand");
-    LSA_REQUIRE(t.n_next >= 0 && t.n_next <= LSA_KSM_MAX_KEYS - 1, "BFV slot tail: at most three NEXT rotations");
-    LSA_REQUIRE((t.tail != nullptr) == (t.tail_c0 != nullptr), "BFV slot tail: the TAIL rotation and its accumulator come together");
-    const bool gathers = t.n_next > 0 || t.tail;
-    LSA_REQUIRE(!gathers || c.logn <= LSA_PERM_LDS_MAX_LOGN, "BFV slot tail: the ring's limbs do not fit in LDS");
-    LSA_REQUIRE(c.n >= 2, "BFV slot tail: ring degree too small");
+    LSA_REQUIRE(n_next >= 0 && n_next <= LSA_KSM_MAX_KEYS - 1, "BFV slot tail: at most three NEXT rotations");
+    LSA_REQUIRE((tail != nullptr) == (tail_c0 != nullptr), "BFV slot tail: the TAIL rotation and its accumulator come together");
     BfvSlotTailArgs g{};
-    g.x = x;
-    g.acc = acc;
-    g.conv = conv;
-    g.addend = t.addend;
-    g.out = out;
-    g.tail_c0 = t.tail_c0;
-    for (int i = 0; i < t.n_next; i++) {
-        LSA_REQUIRE(t.next[i] != nullptr, "BFV slot tail: permutation missing");
-        g.next[i] = t.next[i];
+    g.addend = addend;
+    g.tail_c0 = tail_c0;
+    for (int i = 0; i < n_next; i++) {
+        LSA_REQUIRE(next[i] != nullptr, "BFV slot tail: permutation missing");
+        g.next[i] = next[i];
     }
-    g.tail = t.tail;
-    g.kvec = c.pinv_vec(level);
-    g.mods = c.d_mods;
-    g.sx = sx;
-    g.sacc = sacc;
-    g.sconv = sconv;
-    g.sadd = t.s_addend;
-    g.so = sout;
-    g.stail = t.s_tail;
-    g.n_next = t.n_next;
-    g.tail_acc = t.tail_accumulate ? 1 : 0;
-    g.acc_rpp = acc_rpp;
-    g.limbs = L;
-    g.logn = c.logn;
+    g.tail = tail;
+    g.sadd = s_addend;
+    g.stail = s_tail;
+    g.n_next = n_next;
+    g.tail_acc = tail_accumulate ? 1 : 0;
     // x, acc, conv and out for both polynomials; per c0 row the addend, the tail (read if it accumulates) and 4 bytes per point and table
-    ProfScope ps(c, PROF_ELEMWISE,
-                 8.0 * c.n * batch * L * (8.0 + (t.addend ? 1 : 0) + (t.tail ? (t.tail_accumulate ? 2 : 1) : 0)) +
-                     4.0 * c.n * batch * L * (t.n_next + (t.tail ? 1 : 0)),
-                 s);
-    const size_t lds_bytes = gathers ? (size_t)c.n * sizeof(u64) : 0;
-    if (lds_bytes > 65536) {   // opt in to more than 64 KiB of dynamic LDS, once per device (the attribute is per device)
-        static std::atomic<unsigned long long> raised{0};
-        int dev = 0;
-        LSA_HIP(hipGetDevice(&dev));
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & bit)) {
-            LSA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bfv_slot_tail), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-            raised.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    hipLaunchKernelGGL(k_bfv_slot_tail, dim3((unsigned)(2 * L), (unsigned)batch), dim3(LSA_SLOT_TAIL_THREADS), lds_bytes, s, g);
-    LSA_HIP(hipGetLastError());
+    launch_lds_row_tail<&k_bfv_slot_tail>(c, level, "BFV slot tail", g, acc, s_acc, acc_rpp, conv, s_conv, o, nb,
+                                          8.0 * c.n * nb * L * (8.0 + (addend ? 1 : 0) + (tail ? (tail_accumulate ? 2 : 1) : 0)) +
+                                              4.0 * c.n * nb * L * (n_next + (tail ? 1 : 0)),
+                                          s, n_next > 0 || tail);
 }
 
 // ------------------------------------------------------------------------------------------------ CKKS slot sum
@@ -646,7 +610,7 @@ void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, lon
                     next_live = true;
                 }
             }
-            t.moddown(ks_onto_ct(o, sout, x, sx, L, {.form = KsOut::COEFF, .slot_tail = gather ? &bt : nullptr}));
+            t.moddown(ks_onto_ct(o, sout, x, sx, L, {.form = KsOut::COEFF, .tail = gather ? &bt : nullptr}));
             x = o;
             sx = sout;
         }
@@ -654,7 +618,7 @@ void bfv_slot_sum_run(BfvSlotSum& p, const u64* in, long long sin, u64* out, lon
             BfvSlotTail bt;
             bt.addend = last;
             bt.s_addend = sL;
-            t.moddown_of(tail, s_ext2, ks_onto_ct(o, sout, x, sx, L, {.form = KsOut::COEFF, .slot_tail = gather ? &bt : nullptr}));
+            t.moddown_of(tail, s_ext2, ks_onto_ct(o, sout, x, sx, L, {.form = KsOut::COEFF, .tail = gather ? &bt : nullptr}));
         }
     });
 }

@@ -6,6 +6,10 @@
 // With the argument "many" the lines are calls of the hoisted rotations' rule (one_of_outputs_may_be_input) instead:
 //   "batch words base_in stride_in stride_out n base_out_0 .. base_out_{n-1}"   (n <= 8)
 //     -> "code in_place"   code: 0 accepted, 1 two outputs overlap, 2 an output partly overlaps the input, 3 two outputs are the input
+// With the argument "array" the lines are calls of the indexed-array operators' rule (one_against_array, dense_array):
+//   "batch words base_one stride_one base_arr stride_arr s_index count"
+//     -> "code dense"   code: 0 apart from every entry, 1 `one` is entry 0, 2 it shares words with entry 0 without being it, 3 it shares
+//                       words with a later entry
 // Driven by tests/test_layout_check_host.py, which marks every word of the operands in an array and compares.
 #include <cstdio>
 #include <cstring>
@@ -32,8 +36,20 @@ static int many() {
     return 0;
 }
 
+static int array() {
+    int batch, count;
+    unsigned long long words, bo, ba;
+    long long so, sa, s_index;
+    while (std::scanf("%d %llu %llu %lld %llu %lld %lld %d", &batch, &words, &bo, &so, &ba, &sa, &s_index, &count) == 8) {
+        const Span one{(uintptr_t)bo, so, (size_t)words}, arr{(uintptr_t)ba, sa, (size_t)words};
+        std::printf("%d %d\n", (int)one_against_array(one, arr, s_index, count, batch), dense_array(arr, s_index, batch) ? 1 : 0);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && std::strcmp(argv[1], "many") == 0) return many();
+    if (argc > 1 && std::strcmp(argv[1], "array") == 0) return array();
     unsigned long long ba, wa, bb, wb;
     long long sa, sb;
     int batch;

@@ -1,5 +1,5 @@
 """CPU-only: the span arithmetic behind every operator's argument checks (lattisense_amd/csrc/layout_check.h, compiled for the
-host by tests/cpp/test_layout_check.cpp with g++ -fsanitize=undefined) against a word-by-word model.
+host by tests/cpp/test_layout_check.cpp with g++ -fsanitize=address,undefined) against a word-by-word model.
 
 An operand is `batch` items of `words` words, item b at base + b * stride; stride 0 is one item shared by the batch.  Overlap is
 exact: padding belongs to nobody, operands may interleave.  The model marks, in a small array, every word the items of each
@@ -10,7 +10,12 @@ different item sizes.  Two hand-made cases put strides near 2^40 words, where a 
 
 The rule of the hoisted rotations (one_of_outputs_may_be_input: lsa_ckks_rotate_many and lsa_bfv_rotate_many) gets the same
 treatment: one input and two or three outputs of one stride, every base offset, accepted exactly when no two outputs share a word,
-every output either has the input's base and stride or shares no word with it, and at most one output is the input."""
+every output either has the input's base and stride or shares no word with it, and at most one output is the input.
+
+The rule of the indexed-array operators (one_against_array, dense_array: lsa_bfv_expand, lsa_bfv_pack, lsa_bfv_select) likewise:
+one batched operand against `count` batched entries at stride s_index, accepted exactly when the operand is entry 0 itself (and
+then shares no word with a later entry) or shares no word with any entry; the refusal names entry 0 or a later entry as the
+marked words do."""
 import itertools
 import os
 import subprocess
@@ -22,7 +27,7 @@ ORIGIN = 1 << 20  # byte address of word 0 (16-byte aligned)
 
 def _exe(tmp_path):
     exe = str(tmp_path / "test_layout_check")
-    subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-fsanitize=undefined", "-fno-sanitize-recover=undefined",
+    subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            os.path.join(ROOT, "tests", "cpp", "test_layout_check.cpp"), "-o", exe])
     return exe
 
@@ -169,3 +174,99 @@ def test_rotate_many_rule_against_marked_words(tmp_path):
     # no output at all, and one output: the rule holds trivially / is same-or-apart
     assert _run(exe, [(2, W, ORIGIN, W, W, 0), (2, W, ORIGIN, W, W, 1, ORIGIN), (2, W, ORIGIN, W, W, 1, ORIGIN + 8 * W),
                       (2, W, ORIGIN, 2 * W, 2 * W, 1, ORIGIN + 8 * W)], "many") == [(0, -1), (0, 0), (2, -1), (0, -1)]
+
+
+def _array_model(batch, words, base_one, s_one, base_arr, s_arr, s_index, count):
+    """the code one_against_array owes, from the marked words of every entry; bases in words"""
+    one = _items(base_one, s_one, words, batch)
+    entries = [_items(base_arr + i * s_index, s_arr, words, batch) for i in range(count)]
+    is0 = base_one == base_arr and s_one == s_arr
+    if not is0 and one & entries[0]:
+        return 2
+    if any(one & e for e in entries[1:]):
+        return 3
+    return 1 if is0 else 0
+
+
+def test_indexed_array_rule_against_marked_words(tmp_path):
+    """lsa_bfv_expand / lsa_bfv_pack / lsa_bfv_select: one batched operand against `count` batched entries at stride s_index.  Every
+    word of every entry is marked; the operand is moved word by word from before the array to behind it, at the array's own stride,
+    at a wider one (its items then interleave with the items of an entry) and at a narrower one."""
+    exe = _exe(tmp_path)
+    base_arr = 16
+    model = []
+    for words in (2, 4, 6):
+        for batch in (1, 2, 3):
+            for s_arr in (words, words + 2, 2 * words + 2):
+                for gap in (0, 2, batch * s_arr + words):               # dense; a small gap; room for a whole operand
+                    s_index = batch * s_arr + gap
+                    for count in (1, 2, 3, 4):
+                        end = base_arr + (count - 1) * s_index + (batch - 1) * s_arr + words
+                        for s_one in {s_arr, words, 2 * words + 2}:
+                            for base_one in range(0, end + 3):
+                                model.append((batch, words, base_one, s_one, base_arr, s_arr, s_index, count))
+    cases = [(b, w, ORIGIN + 8 * bo, so, ORIGIN + 8 * ba, sa, si, n) for b, w, bo, so, ba, sa, si, n in model]
+    got = _run(exe, cases, "array")
+    seen = {0: 0, 1: 0, 2: 0, 3: 0, "in_padding": 0, "between_items": 0, "one_word_of_later_entry": 0, "dense": 0, "not_dense": 0}
+    for m, (code, dense) in zip(model, got):
+        batch, words, base_one, s_one, base_arr, s_arr, s_index, count = m
+        assert code == _array_model(*m), (m, code)
+        assert bool(dense) == (s_index == batch * s_arr), m
+        seen[code] += 1
+        seen["dense" if dense else "not_dense"] += 1
+        one = _items(base_one, s_one, words, batch)
+        hulls = [_hull(base_arr + i * s_index, s_arr, words, batch) for i in range(count)]
+        whole = set(range(base_arr, max(hulls[-1]) + 1))
+        if code == 0 and one <= whole:
+            seen["in_padding"] += not any(one & h for h in hulls)            # wholly in the padding between two entries
+            seen["between_items"] += any(one & h for h in hulls)            # between the items of an entry
+        if code == 3:
+            entries = [_items(base_arr + i * s_index, s_arr, words, batch) for i in range(1, count)]
+            seen["one_word_of_later_entry"] += sum(len(one & e) for e in entries) == 1
+    assert all(seen.values()), seen     # the sweep reached every kind of case
+
+
+def test_indexed_array_dense_and_one_word_below(tmp_path):
+    """s_index == batch * stride exactly, and one word below (which the entry points refuse: the entries then run into each other):
+    `dense` holds at equality alone, and the answer still follows the marked words"""
+    exe = _exe(tmp_path)
+    batch, words, s_arr, count, base_arr = 3, 4, 6, 3, 16
+    for s_index, want_dense in ((batch * s_arr, 1), (batch * s_arr - 1, 0), (batch * s_arr + 1, 0)):
+        model = [(batch, words, base_one, s_arr, base_arr, s_arr, s_index, count) for base_one in range(0, base_arr + count * s_index + 8)]
+        got = _run(exe, [(b, w, ORIGIN + 8 * bo, so, ORIGIN + 8 * ba, sa, si, n) for b, w, bo, so, ba, sa, si, n in model], "array")
+        for m, (code, dense) in zip(model, got):
+            assert dense == want_dense, m
+            assert code == _array_model(*m), (m, code)
+
+
+def test_indexed_array_strides_near_2_to_40_words(tmp_path):
+    exe = _exe(tmp_path)
+    W, S = 1 << 12, (1 << 40) + 6
+    base_arr = 1 << 30
+    # a batch near 2^31: the entries' batch stride A keeps s_index = batch * A (+ padding) below 2^63 words and the array below 2^64
+    # bytes; the operand's own stride is S, so ITS hull passes 2^64 bytes -- a 64-bit end would wrap to a small address
+    big, A = (1 << 31) - 1, (1 << 28) + 2
+    s_index, count = big * A + 2 * W, 3
+    entry_words = (big - 1) * A + W
+    arr_end = base_arr + 8 * ((count - 1) * s_index + entry_words)
+    assert arr_end < (1 << 64) and base_arr + 8 * ((big - 1) * S + W) >= (1 << 64)
+    e1 = base_arr + 8 * s_index
+    cases = [(big, W, arr_end, S, base_arr, A, s_index, count),                     # starts where the array ends: disjoint hulls
+             (big, W, arr_end, 0, base_arr, A, s_index, count),                     # one shared item there
+             (big, W, arr_end - 8, 0, base_arr, A, s_index, count),                 # ... one word earlier: the last word of the last entry
+             (big, W, base_arr - 8 * W, 0, base_arr, A, s_index, count),            # just before the array
+             (big, W, base_arr - 8 * (W - 1), 0, base_arr, A, s_index, count),      # ... on the first word of entry 0
+             (big, W, base_arr + 8 * entry_words, 0, base_arr, A, s_index, count),  # in the padding behind entry 0
+             (big, W, e1 - 8 * (W - 1), 0, base_arr, A, s_index, count),            # ... reaching the first word of entry 1
+             (big, W, base_arr, A, base_arr, A, s_index, count),                    # entry 0 itself
+             (big, W, base_arr, A, base_arr, A, big * A, count)]                    # ... of a dense array
+    got = _run(exe, cases, "array")
+    assert got == [(0, 0), (0, 0), (3, 0), (0, 0), (2, 0), (0, 0), (3, 0), (1, 0), (1, 1)]
+    # batch 3 at stride S: the operand's items lie in the paddings between the items of entry 0 / one word into an item of entry 2
+    s_index, count = 4 * S, 4
+    e2 = base_arr + 8 * 2 * s_index
+    cases = [(3, W, base_arr + 8 * W, S, base_arr, S, s_index, count),
+             (3, W, base_arr + 8 * (W - 1), S, base_arr, S, s_index, count),
+             (3, W, e2 + 8 * (S + W - 1), S, base_arr, S, s_index, count),
+             (3, W, e2 + 8 * (S + W), S, base_arr, S, s_index, count)]
+    assert [g[0] for g in _run(exe, cases, "array")] == [0, 2, 3, 0]
